@@ -21,9 +21,22 @@ Workloads (config.workload):
   wg     one merged index over --chroms (default 8) independent synthetic chromosomes, --haps 32 haplotypes each: n = 4.35e9 > 2^32, the
          64-bit (WIDE) images and kernels; built by pgx_build_index_from_texts (per-chromosome suffix arrays + k-way merge).
 
-Prints ONE JSON line on rank 0.  The CPU oracle is used here only for the `cpu_baseline` legs.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline figure
+(value, ms_per_step, the per-stage HIP-event times and the roofline of the last timed step).  Everything else the bench can
+measure or check -- the CPU baseline, the oracle parity sample, the fresh-batch rates, the nested x measurement and the
+opt-in --overlap / --batch-sweep / --pcie legs -- runs only under --full.  The CPU oracle is used here only for the
+`cpu_baseline` and `parity_sample` legs.
+
+--dump-outputs DIR writes what the last timed step computed (a fixed, seeded sample of the reads: their MEMs, tag run counts
+and positions, float64) as DIR/<name>.npy, so that two builds can be compared output for output; the inputs depend only on
+the arguments.
+
+The indexes of the synthetic workloads are kept in a cache directory ($PGX_BENCH_CACHE, else pgx_bench/<recipe key> under
+$XDG_CACHE_HOME or ~/.cache; --workdir overrides it).  `python bench.py --prepare` fills it for the default workload without a
+GPU; __graft_entry__.build() does that on a machine with a GPU, so that a plain run does not spend minutes building the index.
 """
 import argparse
+import hashlib
 import json
 import os
 import subprocess
@@ -85,7 +98,17 @@ def parse(argv=None):
     ap.add_argument("--one-device", action="store_true", help="every rank uses device 0 (rehearsal only)")
     ap.add_argument("--stub-workload", action="store_true",
                     help="launcher self-test: no GPU work, every rank contributes a constant (tests/test_bench_launch.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: cpu_baseline, parity_sample, fresh_batch, secondary (each with its --no-* switch) "
+                         "and the opt-in --overlap / --batch-sweep / --pcie legs; a plain run only sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (a fixed, seeded sample of the reads) as DIR/<name>.npy, float64")
+    ap.add_argument("--prepare", action="store_true",
+                    help="build the index files of --workload into the cache directory and exit (host only, no GPU)")
     args = ap.parse_args(argv)
+    for flag, on in (("--overlap", args.overlap), ("--batch-sweep", args.batch_sweep), ("--pcie", args.pcie)):
+        if on and not args.full:
+            ap.error("%s is a --full measurement" % flag)
     d = DEFAULTS[args.workload]
     if args.reads is None:
         args.reads = d[0]
@@ -98,6 +121,54 @@ def parse(argv=None):
     if args.chroms is None:
         args.chroms = 8 if args.workload == "wg" else 6
     return args
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# where the synthetic indexes live between runs
+RECIPE_SOURCES = ("pangenome-index_amd/pgx_workload.py", "pangenome-index_amd/csrc/pgx_build.cpp", "pangenome-index_amd/csrc/pgx_sdsl.cpp", "include/pgx.h")
+
+
+def cache_dir():
+    """$PGX_BENCH_CACHE, else <XDG cache>/pgx_bench/<key>: the key hashes the sources that decide the bytes of the index files
+    (text synthesis, index writers), so an index built by other sources is never picked up"""
+    if os.environ.get("PGX_BENCH_CACHE"):
+        return os.environ["PGX_BENCH_CACHE"]
+    h = hashlib.sha256()
+    for rel in RECIPE_SOURCES:
+        with open(os.path.join(ROOT, rel), "rb") as f:
+            h.update(f.read())
+    base = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    return os.path.join(base, "pgx_bench", h.hexdigest()[:16])
+
+
+class DirLock:
+    """exclusive flock on <dir>/.lock: one process at a time builds into a shared work directory"""
+
+    def __init__(self, d):
+        self.path = os.path.join(d, ".lock")
+        self.f = None
+
+    def __enter__(self):
+        import fcntl
+
+        self.f = open(self.path, "a")
+        fcntl.flock(self.f, fcntl.LOCK_EX)
+        return self
+
+    def __exit__(self, *exc):
+        self.f.close()  # (releases the lock)
+        return False
+
+
+def prepare(args):
+    """--prepare: the index files and the reads of args.workload in the cache directory, made on the host if they are not there yet"""
+    wd = args.workdir or cache_dir()
+    os.makedirs(wd, exist_ok=True)
+    if args.workload not in ("chr22", "synth", "wg"):
+        raise SystemExit("--prepare: only the chr22, synth and wg workloads keep files worth caching")
+    with DirLock(wd):
+        make_workload(args, args.workload, 0, wd, lambda: None, args.reads, args.base_len)  # index files + the reads of rank 0
+    print(json.dumps({"prepared": args.workload, "workdir": wd}), flush=True)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -146,6 +217,8 @@ def synth_index(W, wd, base_len, haps, rank, barrier):
 
 
 def make_workload(args, workload, rank, wd, barrier, n_reads, base_len):
+    import numpy as np
+
     import pgx_workload as W
 
     golden = os.path.join(ROOT, "tests", "golden")
@@ -156,7 +229,7 @@ def make_workload(args, workload, rank, wd, barrier, n_reads, base_len):
             W.build_index_from_rlbwt(os.path.join(golden, "x.rl_bwt"), wd, name)
         barrier()
         ri, tags = os.path.join(wd, name + ".ri"), os.path.join(wd, name + ".compact.tags")
-        seqs = W.load_sequences(os.path.join(golden, "x.newline_separated"))
+        load = lambda: W.load_sequences(os.path.join(golden, "x.newline_separated"))  # noqa: E731
         seed = 42 + 2
         desc = "x.rl_bwt index (n=3012, sigma=5), BASELINE configs[1]"
     elif workload == "wg":
@@ -174,14 +247,12 @@ def make_workload(args, workload, rank, wd, barrier, n_reads, base_len):
             sys.stderr.write("[bench] %d chromosome texts in %.1f s, merged index built in %.1f s (host: SA-IS per chromosome + k-way merge)\n" % (args.chroms, t1 - t0, time.time() - t1))
         barrier()
         ri, tags = os.path.join(wd, name + ".ri"), os.path.join(wd, name + ".compact.tags")
-        seqs = []
-        for t in texts:
-            seqs += W.load_sequences(t)
+        load = lambda: [s for t in texts for s in W.load_sequences(t)]  # noqa: E731
         seed = 42 + 5
         desc = "synthetic whole-genome-scale pangenome: %d chromosomes x %d bp base x %d haplotypes x 2 strands in one index, sigma=6" % (args.chroms, base_len, args.haps)
     else:
         ri, tags, text, build_s = synth_index(W, wd, base_len, args.haps, rank, barrier)
-        seqs = W.load_sequences(text)
+        load = lambda: W.load_sequences(text)  # noqa: E731
         seed = 42 + 3
         desc = "synthetic pangenome: %d bp base x %d haplotypes x 2 strands, sigma=6" % (base_len, args.haps)
         if workload == "chr22":
@@ -191,12 +262,24 @@ def make_workload(args, workload, rank, wd, barrier, n_reads, base_len):
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # weak: every rank samples its own n_reads; strong (BASELINE configs[3] as worded): ONE batch of n_reads, the same on every rank, cut into
     # contiguous slices (make_slice below)
-    cat, offs = W.sample_reads(seqs, n_reads, args.read_len, seed=seed + (0 if strong else 1000 * rank), n_frac=nf)
+    rseed = seed + (0 if strong else 1000 * rank)
+    # the sampled reads are kept next to the index (sampling 10 M reads takes longer than loading them); not for x, whose text is a file of the
+    # repository that the cache key does not cover
+    rfile = None if workload == "x" else os.path.join(wd, "%s.reads_%d_%d_%d_%r.npy" % (os.path.splitext(os.path.basename(ri))[0], n_reads, args.read_len, rseed, nf))
+    if rfile and os.path.exists(rfile):
+        cat = np.load(rfile)
+        offs = np.arange(n_reads + 1, dtype=np.uint64) * np.uint64(args.read_len)  # (what sample_reads returns with them)
+    else:
+        cat, offs = W.sample_reads(load(), n_reads, args.read_len, seed=rseed, n_frac=nf)
+        if rfile:
+            tmp = "%s.%d.tmp.npy" % (rfile[:-4], os.getpid())
+            np.save(tmp, cat)
+            os.replace(tmp, rfile)
     if strong and world > 1:
         cat, offs = strong_slice(cat, offs, rank, world)
 
     def resample(k):  # further batches of the same shape (fresh_batch rotates over three)
-        return W.sample_reads(seqs, len(offs) - 1, args.read_len, seed=seed + 1000 * rank + 7919 * k, n_frac=nf)
+        return W.sample_reads(load(), len(offs) - 1, args.read_len, seed=seed + 1000 * rank + 7919 * k, n_frac=nf)
 
     make_workload.resample = resample
     return ri, tags, cat, offs, desc, build_s
@@ -519,6 +602,53 @@ def oracle_objects(ri, tags):
     return _ORACLE[key]
 
 
+DUMP_BYTES = 64 << 20  # everything --dump-outputs writes, at most
+DUMP_SEED = 20240607
+DUMP_READS = 1 << 16
+
+
+def dump_outputs(out_dir, res, prefix=""):
+    """What a caller of pgx_batch_result receives from the last timed step, for a fixed, seeded sample of the reads (sorted read ids,
+    the same for every run with the same arguments), every array as float64 (all values stay below 2^53):
+      <prefix>reads           ids of the sampled reads
+      <prefix>mem_counts      MEMs of every sampled read
+      <prefix>mems            [MEMs of the sampled reads, 4]: start, end, bwt_start, size
+      <prefix>tag_run_counts  tag runs of every such MEM          (with tags)
+      <prefix>pos_counts      positions of every such MEM          (with tags)
+      <prefix>positions       the positions themselves, in order   (with tags)
+      <prefix>totals          whole batch: reads, MEMs, positions, extensions
+    The sample halves until the arrays fit DUMP_BYTES."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    mo = res["mem_offsets"].astype(np.int64)
+    n = len(mo) - 1
+    tags = "positions" in res
+    po = res["pos_offsets"].astype(np.int64) if tags else None
+    order = np.random.default_rng(DUMP_SEED).permutation(n)
+    k = min(n, DUMP_READS)
+    while True:
+        reads = np.sort(order[:k])
+        counts = mo[reads + 1] - mo[reads]
+        mem_ids = np.repeat(mo[reads], counts) + (np.arange(int(counts.sum())) - np.repeat(np.cumsum(counts) - counts, counts))
+        arrays = {"reads": reads, "mem_counts": counts}
+        m = res["mems"][mem_ids]
+        arrays["mems"] = np.stack([m["start"], m["end"], m["bwt_start"], m["size"]], axis=1) if len(m) else np.zeros((0, 4))
+        if tags:
+            pc = po[mem_ids + 1] - po[mem_ids]
+            pos_ids = np.repeat(po[mem_ids], pc) + (np.arange(int(pc.sum())) - np.repeat(np.cumsum(pc) - pc, pc))
+            arrays["tag_run_counts"] = res["tag_run_counts"][mem_ids]
+            arrays["pos_counts"] = pc
+            arrays["positions"] = res["positions"][pos_ids]
+        arrays["totals"] = np.array([n, int(mo[-1]), int(po[-1]) if tags else 0, int(res["n_extensions"])])
+        if sum(8 * a.size for a in arrays.values()) <= DUMP_BYTES or k <= 1:
+            break
+        k //= 2
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "reads_sampled": int(k), "files": sorted(prefix + name + ".npy" for name in arrays)}
+
+
 def parity_sample(args, ri, tags, cat, offs, min_len, res, sample, idx=None, local=0):
     """The oracle on the first `sample` reads of the batch against the prefix of the device result of the SAME batch run (one chunk of
     n reads, the measured configuration): MEM offsets, MEM bytes, tag run counts, positions.  The oracle is the checker here, nothing else."""
@@ -555,6 +685,8 @@ def parity_sample(args, ri, tags, cat, offs, min_len, res, sample, idx=None, loc
 
 def main():
     args = parse()
+    if args.prepare:
+        return prepare(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(fan_out(args.gpus, sys.argv[1:]))
     rank = int(os.environ.get("RANK", "0"))
@@ -625,15 +757,28 @@ def main():
         wd = args.workdir
         os.makedirs(wd, exist_ok=True)
     else:
-        # all ranks of one node share the directory rank 0 fills
-        wd = os.path.join(tempfile.gettempdir(), "pgx_bench_%s" % os.environ.get("MASTER_PORT", str(os.getpid())))
-        os.makedirs(wd, exist_ok=True)
-        own_tmp = wd
+        wd = None
+        # the cache holds the indexes worth keeping (x takes a moment to build; chrom names its shard files by chromosome number alone)
+        if args.workload in ("chr22", "synth", "wg"):
+            try:
+                wd = cache_dir()
+                os.makedirs(wd, exist_ok=True)
+            except OSError:
+                wd = None
+        if wd is None:
+            # all ranks of one node share the directory rank 0 fills
+            wd = os.path.join(tempfile.gettempdir(), "pgx_bench_%s" % os.environ.get("MASTER_PORT", str(os.getpid())))
+            os.makedirs(wd, exist_ok=True)
+            own_tmp = wd
 
     if args.workload == "chrom":
         return run_chrom(args, rank, world, local, wd, barrier, dist, red_dev)
     t_prep = time.time()
-    ri, tags, cat, offs, desc, build_s = make_workload(args, args.workload, rank, wd, barrier, args.reads, args.base_len)
+    if rank == 0:
+        with DirLock(wd):
+            ri, tags, cat, offs, desc, build_s = make_workload(args, args.workload, rank, wd, barrier, args.reads, args.base_len)
+    else:
+        ri, tags, cat, offs, desc, build_s = make_workload(args, args.workload, rank, wd, barrier, args.reads, args.base_len)
     mode = P.MODE_COMPAT if args.mode == "compat" else P.MODE_STRICT
     idx = P.Index(ri, None if args.no_tags else tags, mode=mode)
     info = idx.info()
@@ -702,12 +847,17 @@ def main():
             "pairs_kernel": {"used": bool(batch.timing().pairs_reads), "extensions_through_the_dense2_image": int(batch.timing().pairs_other_steps)},
             "roofline": roofline_record(info, len(cat), n, counts, k_ms, batch.timing(), args.workload, args.min_len, not args.no_tags),
         }
-        if args.pcie:
+        resident_result = None
+        if args.dump_outputs:  # the last timed step's result, before any --full leg runs anything else on the device
+            resident_result = batch.result()
+            d = dump_outputs(args.dump_outputs, resident_result)
+            sys.stderr.write("[bench] outputs of the last timed step (%d sampled reads) written to %s\n" % (d["reads_sampled"], d["dir"]))
+        if args.full and args.pcie:
             line["pcie_inclusive_reads_per_s"] = pcie_rate(idx, cat, offs, args, local)
             line["pcie_inclusive_note"] = "long-lived batch: pgx_batch_upload (H2D of reads + offsets), pgx_batch_run, pgx_batch_result (D2H of MEMs / positions into host arrays)"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args, ri, None if args.no_tags else tags, cat, offs, args.min_len)
-        if world == 1 and args.overlap and not args.no_overlap and args.steps >= 2:
+        if args.full and world == 1 and args.overlap and not args.no_overlap and args.steps >= 2:
             dt2, c2 = measure_two_in_flight(idx, cat, offs, local, args.min_len, args.min_occ, flags, args.steps, torch.cuda.synchronize)
             line["two_batches_in_flight"] = {
                 "value": n * args.steps / dt2, "unit": "reads/s", "ms_per_step": 1e3 * dt2 / args.steps, "steps": args.steps,
@@ -715,14 +865,14 @@ def main():
                 "note": "not the bench value: K steps over two resident batches of the same reads, each on its own stream with its own host thread (what "
                         "the CLI's device workers do with consecutive batches): one batch's compaction and tag stage run under the other's find_mems kernel",
             }
-        resident_result = None
-        if world == 1 and not args.no_parity:
+        if args.full and world == 1 and not args.no_parity:
             # the measured configuration itself under the oracle: the result of the last timed step, downloaded, against the oracle on a prefix
             sample = min(n, args.parity_reads)
-            resident_result = batch.result()
+            if resident_result is None:
+                resident_result = batch.result()
             line["parity_sample"] = parity_sample(args, ri, None if args.no_tags else tags, cat, offs, args.min_len, resident_result, sample, idx, local)
             parity_failed = parity_failed or not line["parity_sample"]["identical"]
-        if world == 1 and not args.no_fresh and args.steps >= 3:
+        if args.full and world == 1 and not args.no_fresh and args.steps >= 3:
             # what a caller that brings a NEW batch every step gets (the bench value re-runs reads already resident in HBM)
             hbs = [HostBatch(P, cat, offs)] + [HostBatch(P, *make_workload.resample(k)) for k in (1, 2)]
             line["fresh_batch"] = fresh_record(P, idx, hbs, local, args, flags, torch.cuda.synchronize, resident_result, counts)
@@ -731,13 +881,13 @@ def main():
                     parity_failed = True
             del hbs
         resident_result = None
-        if world == 1 and args.batch_sweep:
+        if args.full and world == 1 and args.batch_sweep:
             line["batch_size_sweep"] = batch_size_sweep(P, idx, cat, offs, local, args, flags, stream, torch.cuda.synchronize)
     batch.free()
     idx.close()
     del cat, offs
     if rank == 0:
-        if args.workload == "chr22" and world == 1 and not args.no_secondary:
+        if args.full and args.workload == "chr22" and world == 1 and not args.no_secondary:
             line["secondary"] = secondary_x(args, P, wd, local, stream, torch)
             parity_failed = parity_failed or not line["secondary"].get("parity_sample", {}).get("identical", True)
         print(json.dumps(line), flush=True)
@@ -773,7 +923,8 @@ def pcie_rate(idx, cat, offs, args, local, min_len=None, reps=5):
 def secondary_x(args, P, wd, local, stream, torch):
     """BASELINE configs[1] (x index, 1 M reads, min_len 10: where the >= 10x CPU target is stated) measured in the same run"""
     n, min_len = DEFAULTS["x"][0], DEFAULTS["x"][1]
-    ri, tags, cat, offs, desc, _ = make_workload(args, "x", 0, wd, lambda: None, n, None)
+    with DirLock(wd):
+        ri, tags, cat, offs, desc, _ = make_workload(args, "x", 0, wd, lambda: None, n, None)
     idx = P.Index(ri, None if args.no_tags else tags, mode=P.MODE_COMPAT if args.mode == "compat" else P.MODE_STRICT)
     info = idx.info()
     flags = P.RUN_TIMING | (0 if args.no_tags else P.RUN_TAGS)
@@ -873,6 +1024,9 @@ def run_chrom(args, rank, world, local, wd, barrier, dist, red_dev):
                                     if comm is not None else "torch.distributed all_gather (%s), host-staged records" % args.dist_backend)},
             "mems_per_step": int(mo[-1]), "mems_per_s": float(mo[-1]) * args.steps / dt,
         }), flush=True)
+    if rank == 0 and args.dump_outputs:  # every shard this rank searched, as its batch holds it after the last timed step
+        for c in owners[rank]:
+            dump_outputs(args.dump_outputs, batches[c].result(), prefix="shard%d_" % c)
     for b in batches.values():
         b.free()
     barrier()

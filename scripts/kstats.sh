@@ -3,7 +3,7 @@
 tag=$1; shift
 export TMPDIR=/tmp
 R=$PWD/gpurun_out/kstats_$tag; mkdir -p $R
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/out -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --workdir /tmp/wd "$@" > $R/bench.json 2> $R/err.txt || echo FAIL
+rocprofv3 --kernel-trace --stats --output-format csv -d $R/out -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --workdir /tmp/wd "$@" > $R/bench.json 2> $R/err.txt || echo FAIL
 python3 - $R <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/out/*/*kernel_stats.csv"):

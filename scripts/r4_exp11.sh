@@ -11,7 +11,7 @@ k=d["kernel_ms_per_step"]; r=d["roofline"]
 print("$1: %.1f M reads/s, step %.2f ms, main %.2f ms, lines %.1f M, parity %s" % (d["value"]/1e6, d["ms_per_step"], k["find_mems_main"], r["probes_issued"]/1e6, d["parity_sample"]["identical"]))
 PY
 }
-B="python bench.py --workdir $W --no-cpu-baseline --no-secondary --no-fresh --parity-reads 30000 --steps 10"
+B="python bench.py --full --workdir $W --no-cpu-baseline --no-secondary --no-fresh --parity-reads 30000 --steps 10"
 $B > gpurun_out/r4_x11_base.json 2> gpurun_out/r4_x11_base.err; show base
 for v in 4 8 20 32; do PGX_FM_REFILL_MIN=$v $B > gpurun_out/r4_x11_refill$v.json 2> gpurun_out/r4_x11_refill$v.err; show refill$v; done
 PGX_FM_LCE_MAX=8 $B > gpurun_out/r4_x11_lcemax8.json 2> gpurun_out/r4_x11_lcemax8.err; show lcemax8

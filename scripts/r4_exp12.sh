@@ -14,11 +14,11 @@ k=d["kernel_ms_per_step"]; r=d["roofline"]
 print("$1: %.1f M reads/s, step %.2f ms, main %.2f ms, post %.2f ms, lines %.1f M, seeds %.1f M, parity %s" % (d["value"]/1e6, d["ms_per_step"], k["find_mems_main"], k["total"]-k["find_mems"], r["probes_issued"]/1e6, r["seed_loads"]/1e6, d["parity_sample"]["identical"]))
 PY
 }
-B="python bench.py --workdir $W --no-cpu-baseline --no-secondary --no-fresh --parity-reads 30000 --steps 10"
+B="python bench.py --full --workdir $W --no-cpu-baseline --no-secondary --no-fresh --parity-reads 30000 --steps 10"
 $B > gpurun_out/r4_x12_base.json 2> gpurun_out/r4_x12_base.err; show base
 for h in 32 64; do
   WH=/tmp/pgxwd_h$h; mkdir -p $WH
-  BH="python bench.py --workdir $WH --haps $h --base-len $((320000000 / h)) --no-cpu-baseline --no-secondary --no-fresh --parity-reads 30000 --steps 10"
+  BH="python bench.py --full --workdir $WH --haps $h --base-len $((320000000 / h)) --no-cpu-baseline --no-secondary --no-fresh --parity-reads 30000 --steps 10"
   $BH > gpurun_out/r4_x12_h$h.json 2> gpurun_out/r4_x12_h$h.err; show h$h
   PGX_FM_LCE_MAX=16 $BH > gpurun_out/r4_x12_h${h}_max16.json 2> gpurun_out/r4_x12_h${h}_max16.err; show h${h}_max16
 done

@@ -14,7 +14,7 @@ k=d["kernel_ms_per_step"]; r=d["roofline"]
 print("$1: %.1f M reads/s, step %.2f ms, main %.2f ms, lines %.1f M, seeds %.1f M, parity %s" % (d["value"]/1e6, d["ms_per_step"], k["find_mems_main"], r["probes_issued"]/1e6, r["seed_loads"]/1e6, d["parity_sample"]["identical"]))
 PY
 }
-B="python bench.py --workdir $W --no-cpu-baseline --no-secondary --no-fresh --parity-reads 30000 --steps 10"
+B="python bench.py --full --workdir $W --no-cpu-baseline --no-secondary --no-fresh --parity-reads 30000 --steps 10"
 $B > gpurun_out/r4_x13_two.json 2> gpurun_out/r4_x13_two.err; show two
 D=/tmp/pgx_one; rm -rf $D; mkdir -p $D
 cp -r pangenome-index_amd include oracle bench.py __graft_entry__.py tests $D/

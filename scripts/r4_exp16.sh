@@ -3,7 +3,7 @@
 set -e
 mkdir -p gpurun_out
 W=/tmp/pgxwd; mkdir -p $W
-B="python bench.py --workdir $W --no-cpu-baseline --no-secondary --no-fresh --parity-reads 30000 --steps 10"
+B="python bench.py --full --workdir $W --no-cpu-baseline --no-secondary --no-fresh --parity-reads 30000 --steps 10"
 run() {
   env $2 $B $3 > gpurun_out/r4_x16_$1.json 2> gpurun_out/r4_x16_$1.err
   python - <<PY
