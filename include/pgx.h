@@ -205,6 +205,38 @@ pgx_status pgx_merge_tags_gbz(const char *gbz_path, const char *ri_path, const c
 pgx_status pgx_merge_tags_gbz_ex(const char *gbz_path, const char *ri_path, const char *const *tag_paths, uint32_t n_files, int device,
                                  const char *out_path, uint32_t flags); /* flags as pgx_merge_tags_ex */
 
+/* build_tags equivalent (src/build_tags.cpp): graph + BWT -> tag array in the "algorithm format" merge_tags and convert_tags
+ * read (int_vector<8> header holding the body length in bits; body = gbwt ByteCodes of offset:10 | rev:1 | len:9 | node << 20,
+ * one per run piece of at most 511 rows; zero padding to 8 bytes).  The tag of BWT row i >= n_seq is Position::encode of text
+ * position SA[i] = (sequence s, offset off): node_id << 11 | rev << 10 | offset within the oriented node of path s that
+ * covers off; the endmarker rows [0, n_seq) have none.  Equal neighbouring tags form maximal runs.
+ *
+ * Not the reference's method (unique k-mers, a B+-tree, a BFS and one psi walk per sequence): the suffix array of the whole
+ * BWT on `device` (the locate kernels), then one lookup per row and a run-length encoding, all HIP kernels; no CPU fallback.
+ * Index sequence s is path s of the graph (GBWT sequence s), or GBWT sequence 2s with PGX_BUILD_TAGS_FORWARD_ONLY (a text of
+ * one orientation per path, e.g. gbz_extract without -b).  PGX_ERR_FORMAT names the first offending sequence when the
+ * index's sequence count differs from the number of paths used, a path's length differs from its sequence's length in the
+ * index, a path visits a node without a sequence or one longer than 1024 bp (the offset field has 10 bits).  No output file
+ * is left behind after an error. */
+#define PGX_BUILD_TAGS_REFERENCE_RUNS 0x1u /* run lengths mod 65 536 as the reference's uint16_t counter leaves them
+                                              (algorithm.hpp traverse_sequences_parallel); a run that becomes 0 is dropped.
+                                              Without it lengths are exact; the bytes agree whenever no run reaches 65 536 */
+#define PGX_BUILD_TAGS_FORWARD_ONLY 0x2u   /* index sequence s = GBWT sequence 2s; pgx_gbz_extract: even sequences only */
+#define PGX_BUILD_TAGS_INPUT_RLBWT 0x4u    /* ri_path names a grlBWT .rl_bwt; its r-index is built in memory */
+pgx_status pgx_build_tags(const char *gbz_path, const char *ri_path, int device, const char *out_path, uint32_t flags);
+/* pgx_build_tags with the graph stated by the caller: n_seq paths, path s = path_nodes[path_offsets[s], path_offsets[s + 1])
+ * with nodes as id << 1 | rev; node_length[id - first_node_id] for n_node_ids ids (0: the id has no sequence). */
+pgx_status pgx_build_tags_paths(const char *ri_path, uint64_t n_seq, const uint64_t *path_offsets, const uint64_t *path_nodes,
+                                const uint32_t *node_length, uint64_t first_node_id, uint64_t n_node_ids, int device,
+                                const char *out_path, uint32_t flags);
+/* stage times (ms) of this thread's last pgx_build_tags[_paths] call, up to n of: [0] graph (GBZ parse + path extraction; 0 for
+ * _paths) [1] index (read or built, locate image upload) [2] suffix array [3] tag of every row incl. the length checks [4] run
+ * encoding incl. the body download [5] file write */
+pgx_status pgx_build_tags_timing(double *ms, uint32_t n);
+/* gbz_extract: the newline-separated text of every GBWT sequence of the graph spelled from its node sequences (reverse
+ * complemented where the orientation bit is set), or of the even ones with PGX_BUILD_TAGS_FORWARD_ONLY. */
+pgx_status pgx_gbz_extract(const char *gbz_path, const char *out_text_path, uint32_t flags);
+
 /* ---- primitives (tests; mirror the public FastLocate / TagArray query API) ----------------- */
 /* FastLocate::rank_at_cached_encoded (src/r-index.cpp:619-641): out[i*6 .. i*6+sigma) per position;
  * entries >= sigma are zero.  true_codes!=0 returns the six true code ranks instead. */

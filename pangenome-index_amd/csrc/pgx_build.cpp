@@ -450,7 +450,7 @@ static std::vector<std::pair<uint8_t, uint64_t>> read_rlbwt(const std::string &p
 // every sequence, src/r-index.cpp:993-1130) or, when the caller still holds the suffix array the BWT was made from (`tb`),
 // straight from it: the sample of BWT position p is the (sequence, offset) of suffix SA[p] -- the same values, without
 // n binary searches over the run starts.
-static void build_rindex_core(const std::vector<std::pair<uint8_t, uint64_t>> &file_runs, const TextBwt *tb, const char *out_ri_path, int encoded) {
+static std::vector<uint8_t> build_rindex_core(const std::vector<std::pair<uint8_t, uint64_t>> &file_runs, const TextBwt *tb, int encoded) {
     BuildTimer bt;
     // calculate_C, r-index.hpp:440-482: sym_map = rank among present byte values; C = exclusive sums
     uint64_t freq[256] = {0}, n = 0;
@@ -672,9 +672,19 @@ static void build_rindex_core(const std::vector<std::pair<uint8_t, uint64_t>> &f
         }
     }
     bt.lap(".ri: blocks stream");
+    return out;
+}
+
+static void build_rindex_core(const std::vector<std::pair<uint8_t, uint64_t>> &file_runs, const TextBwt *tb, const char *out_ri_path, int encoded) {
+    BuildTimer bt;
+    const std::vector<uint8_t> out = build_rindex_core(file_runs, tb, encoded);
     write_whole_file(out_ri_path, out);
     bt.lap(".ri: file written");
 }
+
+namespace pgx {
+std::vector<uint8_t> build_rindex_bytes(const char *rlbwt_path, int encoded) { return build_rindex_core(read_rlbwt(rlbwt_path), nullptr, encoded); }
+} // namespace pgx
 
 extern "C" pgx_status pgx_build_rindex(const char *rlbwt_path, const char *out_ri_path, int encoded) {
     PGX_GUARD_BEGIN

@@ -252,5 +252,15 @@ __global__ void pgx_mt_flags_kernel(const uint64_t *tags, uint64_t n, uint64_t n
 __global__ void pgx_mt_compact_kernel(const uint64_t *tags, const uint8_t *flags, const uint64_t *idx, uint64_t n, uint64_t n_seq,
                                       uint64_t *out_val, uint64_t *out_start);
 
+// build_tags passes (pgx_build_tags_kernels.hip)
+__global__ void pgx_bt_endmarker_kernel(const uint64_t *sa, uint64_t n_seq, uint64_t max_length, uint64_t *idx_len);
+__global__ void pgx_bt_tag_kernel(uint64_t *sa, uint64_t n, uint64_t n_seq, uint64_t max_length, const uint64_t *seq_len, const uint64_t *dir_off,
+                                  const uint64_t *dir, const uint64_t *node_start, const uint64_t *path_nodes, unsigned long long *bad);
+__global__ void pgx_bt_heads_kernel(const uint64_t *tags, uint64_t n, uint64_t n_seq, uint8_t *head);
+__global__ void pgx_bt_compact_kernel(const uint64_t *tags, const uint8_t *head, const uint64_t *idx, uint64_t n, uint64_t *run_val, uint64_t *run_start);
+__global__ void pgx_bt_length_kernel(const uint64_t *run_start, uint64_t n_runs, uint64_t n, uint32_t reference_runs, uint64_t *run_len);
+__global__ void pgx_bt_size_kernel(const uint64_t *run_val, const uint64_t *run_len, uint64_t n_runs, uint64_t *bytes);
+__global__ void pgx_bt_write_kernel(const uint64_t *run_val, const uint64_t *run_len, const uint64_t *byte_off, uint64_t n_runs, uint8_t *body);
+
 #define PGX_SCAN_BLOCK_ITEMS 2048 // 256 threads x 8 items (pgx_kernels.hip PGX_SCAN_ITEMS)
 #define PGX_SCAN1_TILE_ITEMS 4096 // 256 threads x 16 rounds (pgx_scan_onepass_kernel)

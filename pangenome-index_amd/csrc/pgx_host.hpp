@@ -114,6 +114,18 @@ struct GbzPaths {
     uint64_t max_node_id = 0;
 };
 void parse_gbz_paths(const std::string &path, GbzPaths &g);
+
+// what build_tags takes from the graph (pgx_gbz.cpp): node lengths and the paths used, as pgx_build_tags_paths takes them
+struct GbzGraph {
+    uint64_t n_gbwt_seq = 0, first_node_id = 0;
+    std::vector<uint32_t> node_length;              // by id - first_node_id; 0 for ids that do not occur
+    std::vector<uint64_t> path_offsets, path_nodes; // path u = GBWT sequence u (all) or 2u (forward_only); nodes id << 1 | rev
+    std::vector<uint64_t> seq_start;                // with_sequences: node id - first_node_id -> [seq_start[x], seq_start[x + 1]) of chars
+    std::vector<uint8_t> chars;
+};
+void parse_gbz_graph(const std::string &path, bool forward_only, bool with_sequences, GbzGraph &g);
+// the r-index of a grlBWT .rl_bwt as the bytes pgx_build_rindex writes (pgx_build.cpp)
+std::vector<uint8_t> build_rindex_bytes(const char *rlbwt_path, int encoded);
 void write_compact_tags(const char *out_path, const uint64_t *values, const uint64_t *lengths, uint64_t n_runs, uint64_t max_node_floor);
 
 std::vector<uint8_t> read_whole_file(const std::string &path);

@@ -121,6 +121,10 @@ def lib():
     L.pgx_merge_tags_gbz.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u32, C.c_int, C.c_char_p]
     L.pgx_merge_tags_ex.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), u32, p, u64, C.c_int, C.c_char_p, u32]
     L.pgx_merge_tags_gbz_ex.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u32, C.c_int, C.c_char_p, u32]
+    L.pgx_build_tags.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, u32]
+    L.pgx_build_tags_paths.argtypes = [C.c_char_p, u64, p, p, p, u64, u64, C.c_int, C.c_char_p, u32]
+    L.pgx_build_tags_timing.argtypes = [p, u32]
+    L.pgx_gbz_extract.argtypes = [C.c_char_p, C.c_char_p, u32]
     L.pgx_rank_batch.argtypes = [p, C.c_int, p, u64, C.c_int, p]
     L.pgx_extend_batch.argtypes = [p, C.c_int, p, p, p, u64, p]
     L.pgx_count_batch.argtypes = [p, C.c_int, p, p, u64, p]
@@ -274,6 +278,41 @@ def merge_tags_gbz(gbz_path, ri_path, tag_paths, out_path, device=0, flags=0):
     """merge_tags with the reference's inputs: the sequence -> tag file map comes from the graph"""
     arr = (C.c_char_p * len(tag_paths))(*[t.encode() for t in tag_paths])
     _check(lib().pgx_merge_tags_gbz_ex(gbz_path.encode(), ri_path.encode(), arr, len(tag_paths), device, out_path.encode(), flags))
+
+
+BUILD_TAGS_REFERENCE_RUNS, BUILD_TAGS_FORWARD_ONLY, BUILD_TAGS_INPUT_RLBWT = 0x1, 0x2, 0x4
+BUILD_TAGS_STAGES = ("graph", "index", "suffix_array", "tags", "runs", "write")
+
+
+def build_tags(gbz_path, ri_path, out_path, device=0, flags=0):
+    """build_tags: graph + r-index (or .rl_bwt with BUILD_TAGS_INPUT_RLBWT) -> tag array in build_tags' format.  flags:
+    BUILD_TAGS_REFERENCE_RUNS (lengths mod 65 536 as the reference writes them), BUILD_TAGS_FORWARD_ONLY (index sequence s =
+    GBWT sequence 2s).  Returns the stage times in ms (BUILD_TAGS_STAGES)."""
+    _check(lib().pgx_build_tags(gbz_path.encode(), ri_path.encode(), device, out_path.encode(), flags))
+    return build_tags_timing()
+
+
+def build_tags_paths(ri_path, path_offsets, path_nodes, node_length, first_node_id, out_path, device=0, flags=0):
+    """build_tags with the graph stated directly: path s = path_nodes[path_offsets[s]:path_offsets[s + 1]] (id << 1 | rev),
+    node_length[id - first_node_id] (0: no such node).  Returns the stage times in ms."""
+    po = np.ascontiguousarray(path_offsets, dtype=np.uint64)
+    pn = np.ascontiguousarray(path_nodes, dtype=np.uint64)
+    nl = np.ascontiguousarray(node_length, dtype=np.uint32)
+    assert len(po) >= 1 and int(po[-1]) == len(pn)
+    _check(lib().pgx_build_tags_paths(ri_path.encode(), len(po) - 1, po.ctypes.data, pn.ctypes.data if len(pn) else None,
+                                      nl.ctypes.data if len(nl) else None, first_node_id, len(nl), device, out_path.encode(), flags))
+    return build_tags_timing()
+
+
+def build_tags_timing():
+    ms = (C.c_double * len(BUILD_TAGS_STAGES))()
+    _check(lib().pgx_build_tags_timing(C.cast(ms, C.c_void_p), len(BUILD_TAGS_STAGES)))
+    return dict(zip(BUILD_TAGS_STAGES, list(ms)))
+
+
+def gbz_extract(gbz_path, out_text_path, both=True):
+    """newline-separated text of the graph's GBWT sequences (both=False: the even ones, the forward orientation)"""
+    _check(lib().pgx_gbz_extract(gbz_path.encode(), out_text_path.encode(), 0 if both else BUILD_TAGS_FORWARD_ONLY))
 
 
 class Index:
