@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PGX_ABI_VERSION 4 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed */
+#define PGX_ABI_VERSION 5 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_* */
 
 typedef enum {
     PGX_OK = 0,
@@ -359,6 +359,31 @@ pgx_status pgx_batch_upload_packed(pgx_batch *b, const uint32_t *packed, const u
  * are always what the batch needs; PGX_ERR_NOMEM when that exceeds side_ids_cap / side_bytes_cap (upload such a batch as bytes). */
 pgx_status pgx_pack_reads(const uint8_t *reads, const uint64_t *offsets, uint64_t n_reads, uint32_t threads, uint32_t *packed, uint64_t *side_ids,
                           uint64_t side_ids_cap, uint8_t *side_bytes, uint64_t side_bytes_cap, uint64_t *n_side, uint64_t *n_side_bytes);
+/* ---- reads as text, parsed on the device ----------------------------------------------------
+ * Record rules (tests/fastx_emu.py states the same in Python).  A line is the text up to a '\n' (not included); a last line without
+ * its newline counts; nothing follows a final newline.
+ *   LINES  the find_mems contract (src/find_mems.cpp:94-98, std::getline): every non-empty line is a read, '\r' kept.
+ *   FASTQ  strict 4-line records: '@' line, sequence, '+' line, quality.  A trailing '\r' is stripped from each line; the quality
+ *          length must equal the sequence length; multi-line records and a text that ends inside a record are PGX_ERR_FORMAT.
+ *   FASTA  a '>' line plus every following line up to the next '>' line; the sequence is those lines concatenated, a trailing '\r'
+ *          stripped from each; blank lines add nothing; a non-blank line before the first '>' is PGX_ERR_FORMAT.
+ * In FASTA and FASTQ every record is a read, one with an empty sequence included (it has no MEMs), so read i is the i-th record of
+ * the text.  Sequence bytes pass as they are (lower case, N, IUPAC codes).  Error texts name the format, the record (1-based, as
+ * find_mems numbers its "Seq:" lines) and the byte offset of the offending line in `text`. */
+#define PGX_READS_LINES 0u /* the reference's contract: a line is a read, empty lines skipped, '\r' kept (std::getline) */
+#define PGX_READS_FASTA 1u
+#define PGX_READS_FASTQ 2u
+/* Replace the reads of a batch with the records of `text` (whole records; the last may lack its final newline), parsed on the device.
+ * *n_reads = records taken.  A refused upload (PGX_ERR_FORMAT / _ARG) leaves the batch exactly as it was.  Device memory per batch:
+ * the text, 29 bytes per line (line table, byte and record scans) and the CSR reads.  Pinned `text` uploads at link speed. */
+pgx_status pgx_batch_upload_text(pgx_batch *b, const uint8_t *text, uint64_t n_bytes, uint32_t format, uint64_t *n_reads);
+/* Host only, no device: the first record start at or after `want` (n_bytes if none); what a caller that cuts a file into batches needs.
+ *   LINES  the start of the next non-empty line.
+ *   FASTQ  the next line start L with byte L '@' and line L+2 starting with '+' (a quality line that starts with '@' fails: its line
+ *          L+2 is a sequence line); fewer than 4 lines left from L means n_bytes.
+ *   FASTA  the next line that starts with '>'.
+ * PGX_ERR_ARG for an unknown format. */
+pgx_status pgx_fastx_cut(const uint8_t *text, uint64_t n_bytes, uint32_t format, uint64_t want, uint64_t *cut);
 /* Run find_all_mems (+ tag queries) for every read of the batch; results stay on the device.
  * (A run whose predecessor on this batch had the same shape is enqueued whole, with buffer sizes taken from that run and the
  * counts kept on the device, and synchronises once at the end: pgx_batch_spec_stats.)

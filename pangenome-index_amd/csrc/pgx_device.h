@@ -262,5 +262,24 @@ __global__ void pgx_bt_length_kernel(const uint64_t *run_start, uint64_t n_runs,
 __global__ void pgx_bt_size_kernel(const uint64_t *run_val, const uint64_t *run_len, uint64_t n_runs, uint64_t *bytes);
 __global__ void pgx_bt_write_kernel(const uint64_t *run_val, const uint64_t *run_len, const uint64_t *byte_off, uint64_t n_runs, uint8_t *body);
 
+// reads as text -> CSR reads (pgx_fastx_kernels.hip, pgx_batch_upload_text)
+#define PGX_FASTX_ROUNDS 4                        // 16-byte loads per thread and tile
+#define PGX_FASTX_TILE (256 * 16 * PGX_FASTX_ROUNDS) // bytes of text per block of the newline passes
+// error word: first bad line << 8 | code (atomicMin)
+#define PGX_FASTX_ERR_NO_AT 1u        // FASTQ header line without '@'
+#define PGX_FASTX_ERR_NO_PLUS 2u      // FASTQ third line without '+'
+#define PGX_FASTX_ERR_QUAL_LEN 3u     // FASTQ quality length != sequence length
+#define PGX_FASTX_ERR_TRUNCATED 4u    // FASTQ text ends inside a record (line: its header)
+#define PGX_FASTX_ERR_BEFORE_FIRST 5u // FASTA text before the first '>'
+#define PGX_FASTX_ERR_LONG_LINE 6u    // a line of 2^31 bytes or more
+__global__ void pgx_fastx_count_kernel(const uint8_t *text, uint64_t n, uint32_t *tile_count);
+__global__ void pgx_fastx_lines_kernel(const uint8_t *text, uint64_t n, const uint64_t *tile_base, uint64_t *ls, uint64_t n_lines, uint32_t tail);
+__global__ void pgx_fastx_role_kernel(const uint8_t *text, const uint64_t *ls, uint64_t n_lines, uint32_t format, uint32_t *contrib, uint8_t *rec,
+                                      unsigned long long *err);
+__global__ void pgx_fastx_records_kernel(uint64_t n_lines, uint32_t format, const uint32_t *contrib, const uint8_t *rec, const uint64_t *out_off,
+                                         const uint64_t *rec_idx, uint64_t *offs, unsigned long long *err);
+__global__ void pgx_fastx_longest_kernel(const uint64_t *offs, const uint64_t *n_reads, unsigned long long *longest);
+__global__ void pgx_fastx_copy_kernel(const uint8_t *text, const uint64_t *ls, const uint64_t *out_off, uint64_t n_lines, uint64_t total, uint8_t *out);
+
 #define PGX_SCAN_BLOCK_ITEMS 2048 // 256 threads x 8 items (pgx_kernels.hip PGX_SCAN_ITEMS)
 #define PGX_SCAN1_TILE_ITEMS 4096 // 256 threads x 16 rounds (pgx_scan_onepass_kernel)

@@ -1166,6 +1166,34 @@ inline uint32_t pack8(uint64_t x, uint64_t &bad) {
 }
 } // namespace
 
+// the first record start at or after `want` (pgx.h): line starts only, tested by the rules of the format
+extern "C" pgx_status pgx_fastx_cut(const uint8_t *text, uint64_t n_bytes, uint32_t format, uint64_t want, uint64_t *cut) {
+    PGX_GUARD_BEGIN
+    if (!cut || (!text && n_bytes)) throw Error(PGX_ERR_ARG, "pgx_fastx_cut: null argument");
+    if (format > PGX_READS_FASTQ) throw Error(PGX_ERR_ARG, "pgx_fastx_cut: unknown format " + std::to_string(format));
+    // start of the line after the one holding byte p (n_bytes if none)
+    auto next_line = [&](uint64_t p) -> uint64_t {
+        const void *nl = p < n_bytes ? std::memchr(text + p, '\n', n_bytes - p) : nullptr;
+        return nl ? (uint64_t)(static_cast<const uint8_t *>(nl) - text) + 1 : n_bytes;
+    };
+    uint64_t L = want == 0 ? 0 : want > n_bytes ? n_bytes : text[want - 1] == '\n' ? want : next_line(want);
+    for (; L < n_bytes; L = next_line(L)) {
+        const uint8_t c = text[L];
+        if (format == PGX_READS_LINES) { if (c != '\n') break; }
+        else if (format == PGX_READS_FASTA) { if (c == '>') break; }
+        else if (c == '@') {
+            const uint64_t l1 = next_line(L), l2 = next_line(l1), l3 = l2 < n_bytes ? next_line(l2) : n_bytes;
+            if (l2 < n_bytes && text[l2] == '+') {
+                if (l3 >= n_bytes) L = n_bytes; // (fewer than 4 lines left)
+                break;
+            }
+        }
+    }
+    *cut = L < n_bytes ? L : n_bytes;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
 extern "C" pgx_status pgx_pack_reads(const uint8_t *reads, const uint64_t *offsets, uint64_t n_reads, uint32_t threads, uint32_t *packed,
                                      uint64_t *side_ids, uint64_t side_ids_cap, uint8_t *side_bytes, uint64_t side_bytes_cap, uint64_t *n_side,
                                      uint64_t *n_side_bytes) {

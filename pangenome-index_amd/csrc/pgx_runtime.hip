@@ -1270,6 +1270,7 @@ struct pgx_batch {
     // run state
     DevBuf slot_off, slots, mem_count, mem_off, mems, scan_tmp, counters, heavy_list, heavy_scratch, read_flags, side_list, side_count, packed, ovf_base;
     DevBuf up_side_ids, up_side_off, up_side_bytes; // pgx_batch_upload_packed: the listed reads as they arrive
+    DevBuf fx_text, fx_tiles, fx_tile_base, fx_lines, fx_contrib, fx_rec, fx_out_off, fx_rec_idx, fx_offs, fx_scal, fx_scan_tmp; // pgx_batch_upload_text
     std::vector<uint64_t> h_side_off;
     hipEvent_t ev_up[2] = {nullptr, nullptr};        // around the device passes of an upload
     float ms_upload_passes = 0;                      // device time of the passes this upload needed before its first find_mems launch (pgx_timing.ms_per_upload adds the run's own)
@@ -1296,7 +1297,8 @@ static void batch_release(pgx_batch *b) {
     if (hipSetDevice(b->device) == hipSuccess) {
         DevBuf *all[] = {&b->reads, &b->offsets, &b->slot_off, &b->slots, &b->mem_count, &b->mem_off, &b->mems, &b->scan_tmp,
                          &b->counters, &b->heavy_list, &b->heavy_scratch, &b->read_flags, &b->side_list, &b->side_count, &b->packed, &b->ovf_base,
-                         &b->up_side_ids, &b->up_side_off, &b->up_side_bytes};
+                         &b->up_side_ids, &b->up_side_off, &b->up_side_bytes, &b->fx_text, &b->fx_tiles, &b->fx_tile_base, &b->fx_lines,
+                         &b->fx_contrib, &b->fx_rec, &b->fx_out_off, &b->fx_rec_idx, &b->fx_offs, &b->fx_scal, &b->fx_scan_tmp};
         for (DevBuf *d : all) d->release();
         b->tw.release();
         HostBuf *hb[] = {&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]};
@@ -1434,6 +1436,108 @@ static void batch_upload_packed(pgx_batch *b, const uint32_t *packed, const uint
     b->side_reads_est = n_side;
 }
 
+// reads as text (pgx.h, PGX_READS_*), parsed by the passes of pgx_fastx_kernels.hip on the batch's own stream.  Everything up to the
+// validation goes into buffers of its own (text, line table, scans, the new offsets): a refused upload leaves the batch as it was.
+// Two small read-backs: the newline count (sizes the line arrays), then error word / reads / bytes / longest read in one copy.
+static void batch_upload_text(pgx_batch *b, const uint8_t *text, uint64_t n_bytes, uint32_t format, uint64_t *n_reads_out) {
+    static const char *const fmt_name[3] = {"LINES", "FASTA", "FASTQ"};
+    if (n_bytes >= (1ull << 40)) throw Error(PGX_ERR_UNSUPPORTED, "pgx_batch_upload_text: text of 2^40 bytes or more");
+    if (n_bytes == 0) {
+        static const uint64_t none[1] = {0};
+        batch_upload(b, nullptr, none, 0);
+        *n_reads_out = 0;
+        return;
+    }
+    hipStream_t s = b->own;
+    const uint64_t n_tiles = (n_bytes + PGX_FASTX_TILE - 1) / PGX_FASTX_TILE;
+    b->fx_text.ensure(n_bytes + 64); // (a 16-byte load that starts before n_bytes stays inside)
+    b->fx_tiles.ensure(n_tiles * 4);
+    b->fx_tile_base.ensure((n_tiles + 1) * 8);
+    b->fx_scal.ensure(64);
+    unsigned long long *scal = b->fx_scal.as<unsigned long long>(); // [0] first error (line << 8 | code), [1] reads, [2] sequence bytes, [3] longest read
+    HIPCHECK(hipMemcpyAsync(b->fx_text.p, text, n_bytes, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(scal, 0, 64, s));
+    HIPCHECK(hipMemsetAsync(scal, 0xFF, 8, s));
+    const uint8_t *dt = b->fx_text.as<uint8_t>();
+    hipLaunchKernelGGL(pgx_fastx_count_kernel, dim3(grid_for(n_tiles, 1)), dim3(256), 0, s, dt, n_bytes, b->fx_tiles.as<uint32_t>());
+    HIPCHECK(hipGetLastError());
+    scan_excl(0, b->fx_tiles.p, n_tiles, 0, b->fx_tile_base.as<uint64_t>(), b->fx_scan_tmp, s);
+    const uint64_t n_nl = read_u64(b->fx_tile_base.as<uint64_t>() + n_tiles, s);
+    const uint32_t tail = text[n_bytes - 1] != '\n';
+    const uint64_t n_lines = n_nl + tail;
+    b->fx_lines.ensure((n_lines + 1) * 8);
+    b->fx_contrib.ensure(n_lines * 4);
+    b->fx_rec.ensure(n_lines);
+    b->fx_out_off.ensure((n_lines + 1) * 8);
+    b->fx_rec_idx.ensure((n_lines + 1) * 8);
+    b->fx_offs.ensure((n_lines + 1) * 8); // (reads <= lines)
+    uint64_t *ls = b->fx_lines.as<uint64_t>(), *out_off = b->fx_out_off.as<uint64_t>(), *rec_idx = b->fx_rec_idx.as<uint64_t>(), *offs = b->fx_offs.as<uint64_t>();
+    hipLaunchKernelGGL(pgx_fastx_lines_kernel, dim3(grid_for(n_tiles, 1)), dim3(256), 0, s, dt, n_bytes, b->fx_tile_base.as<uint64_t>(), ls, n_lines, tail);
+    hipLaunchKernelGGL(pgx_fastx_role_kernel, dim3(grid_for(n_lines, 256)), dim3(256), 0, s, dt, (const uint64_t *)ls, n_lines, format, b->fx_contrib.as<uint32_t>(),
+                       b->fx_rec.as<uint8_t>(), scal);
+    HIPCHECK(hipGetLastError());
+    scan_excl(0, b->fx_contrib.p, n_lines, 0, out_off, b->fx_scan_tmp, s, reinterpret_cast<uint64_t *>(scal + 2));
+    scan_excl(4, b->fx_rec.p, n_lines, 0, rec_idx, b->fx_scan_tmp, s, reinterpret_cast<uint64_t *>(scal + 1));
+    hipLaunchKernelGGL(pgx_fastx_records_kernel, dim3(grid_for(n_lines, 256)), dim3(256), 0, s, n_lines, format, (const uint32_t *)b->fx_contrib.as<uint32_t>(),
+                       (const uint8_t *)b->fx_rec.as<uint8_t>(), (const uint64_t *)out_off, (const uint64_t *)rec_idx, offs, scal);
+    hipLaunchKernelGGL(pgx_fastx_longest_kernel, dim3(std::min<unsigned>(grid_for(n_lines, 256), 2048u)), dim3(256), 0, s, (const uint64_t *)offs, (const uint64_t *)(rec_idx + n_lines), scal + 3);
+    HIPCHECK(hipGetLastError());
+    uint64_t sc[4];
+    read_scalars(sc, scal, 32, s);
+    if (sc[0] != ~0ull) { // the first bad line: its start (and the neighbours the message needs) from the line table
+        const uint64_t line = sc[0] >> 8, code = sc[0] & 0xFF, w0 = line >= 2 ? line - 2 : 0;
+        uint64_t win[4] = {0, 0, 0, 0}, ri = 0;
+        read_scalars(win, ls + w0, (line + 2 - w0) * 8, s);
+        ri = read_u64(rec_idx + line, s);
+        const uint64_t at = win[line - w0], len = win[line - w0 + 1] - 1 - at;
+        const unsigned long long rec = format == PGX_READS_FASTQ ? line / 4 + 1 : format == PGX_READS_FASTA ? std::max<uint64_t>(ri, 1) : ri + 1;
+        char msg[256];
+        const char *f = fmt_name[format];
+        auto stripped = [&](uint64_t a, uint64_t l) { return l - ((l && text[a + l - 1] == '\r') ? 1 : 0); };
+        switch (code) {
+        case PGX_FASTX_ERR_NO_AT: std::snprintf(msg, sizeof msg, "%s record %llu (byte %llu): header line does not start with '@'", f, rec, (unsigned long long)at); break;
+        case PGX_FASTX_ERR_NO_PLUS: std::snprintf(msg, sizeof msg, "%s record %llu (byte %llu): third line does not start with '+'", f, rec, (unsigned long long)at); break;
+        case PGX_FASTX_ERR_QUAL_LEN: {
+            const uint64_t sa = win[line - 2 - w0], sl = win[line - 1 - w0] - 1 - sa;
+            std::snprintf(msg, sizeof msg, "%s record %llu (byte %llu): quality length %llu != sequence length %llu", f, rec, (unsigned long long)at,
+                          (unsigned long long)stripped(at, len), (unsigned long long)stripped(sa, sl));
+            break;
+        }
+        case PGX_FASTX_ERR_TRUNCATED:
+            std::snprintf(msg, sizeof msg, "%s record %llu (byte %llu): truncated record (%llu of 4 lines)", f, rec, (unsigned long long)at, (unsigned long long)(n_lines - line));
+            break;
+        case PGX_FASTX_ERR_BEFORE_FIRST: std::snprintf(msg, sizeof msg, "%s record 1 (byte %llu): text before the first '>'", f, (unsigned long long)at); break;
+        default: std::snprintf(msg, sizeof msg, "%s record %llu (byte %llu): line of 2^31 bytes or more", f, rec, (unsigned long long)at); break;
+        }
+        throw Error(code == PGX_FASTX_ERR_LONG_LINE ? PGX_ERR_UNSUPPORTED : PGX_ERR_FORMAT, std::string("pgx_batch_upload_text: ") + msg);
+    }
+    const uint64_t n_reads = sc[1], total = sc[2], longest = sc[3];
+    if (longest >= (1ull << 31)) throw Error(PGX_ERR_UNSUPPORTED, "read longer than 2^31 bytes");
+    // valid: from here on the batch changes (what batch_take_offsets sets for the other uploads)
+    HostBuf &hb = b->h_off[b->h_off_cur ^ 1];
+    hb.ensure((n_reads + 1) * 8);
+    b->reads.ensure(total + 32);
+    if (total) {
+        hipLaunchKernelGGL(pgx_fastx_copy_kernel, dim3(grid_for(total, 4096)), dim3(256), 0, s, dt, (const uint64_t *)ls, (const uint64_t *)out_off, n_lines, total,
+                           b->reads.as<uint8_t>());
+        HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipMemsetAsync((uint8_t *)b->reads.p + total, 0, 32, s));
+    std::swap(b->offsets, b->fx_offs);
+    HIPCHECK(hipMemcpyAsync(hb.p, b->offsets.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    b->h_off_cur ^= 1;
+    b->n_reads = n_reads;
+    b->ran = b->ran_tags = false;
+    b->plan_valid = false;
+    b->slot_off_valid = false;
+    b->class_valid = false;
+    b->ms_upload_passes = 0;
+    b->max_read_len = longest;
+    b->read_bytes = total;
+    *n_reads_out = n_reads;
+}
+
 // LCE image (pgx_image.h): suffix array in text coordinates + the text at two bits per symbol, for the pairs kernel's forward stages over narrow intervals.
 // Built once per device image, on the device: the suffix array by the locate kernels (every BWT run is an independent chain from its sample), the text from
 // it (the first symbol of suffix i is the one whose C-bucket holds i).  Only next to a narrow PAIRS image (textbook tables, n < 2^32); PGX_FM_LCE=0: never.
@@ -1564,6 +1668,17 @@ extern "C" pgx_status pgx_batch_upload_packed(pgx_batch *b, const uint32_t *pack
         throw Error(PGX_ERR_ARG, "pgx_batch_upload_packed: null argument");
     use_device(b->device);
     batch_upload_packed(b, packed, offsets, n_reads, side_ids, side_bytes, n_side);
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_batch_upload_text(pgx_batch *b, const uint8_t *text, uint64_t n_bytes, uint32_t format, uint64_t *n_reads) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_upload_text");
+    if (!b || !n_reads || (!text && n_bytes)) throw Error(PGX_ERR_ARG, "pgx_batch_upload_text: null argument");
+    if (format > PGX_READS_FASTQ) throw Error(PGX_ERR_ARG, "pgx_batch_upload_text: unknown format " + std::to_string(format));
+    use_device(b->device);
+    batch_upload_text(b, text, n_bytes, format, n_reads);
     return PGX_OK;
     PGX_GUARD_END
 }

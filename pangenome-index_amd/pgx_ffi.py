@@ -20,6 +20,7 @@ MODE_IMAGE_WIDE = 0x1000  # modifier: the 64-bit form of dense2 / pairs
 IMAGE_RL, IMAGE_DENSE, IMAGE_DENSE2 = 0, 1, 2
 TAGS_AUTO, TAGS_BYTECODE, TAGS_COMPACT = 0, 1, 2
 RUN_TAGS, RUN_TIMING = 1, 2
+READS_LINES, READS_FASTA, READS_FASTQ = 0, 1, 2  # pgx_batch_upload_text / pgx_fastx_cut: record rules in include/pgx.h
 
 MEM_DTYPE = np.dtype([("start", "<u8"), ("end", "<u8"), ("bwt_start", "<u8"), ("size", "<i8")])
 BIINT_DTYPE = np.dtype([("forward", "<u8"), ("reverse", "<u8"), ("size", "<i8")])
@@ -137,6 +138,8 @@ def lib():
     L.pgx_batch_create.argtypes = [p, C.c_int, p, p, u64, C.POINTER(p)]
     L.pgx_batch_upload.argtypes = [p, p, p, u64]
     L.pgx_batch_upload_packed.argtypes = [p, p, p, u64, p, p, u64]
+    L.pgx_batch_upload_text.argtypes = [p, p, u64, u32, C.POINTER(u64)]
+    L.pgx_fastx_cut.argtypes = [p, u64, u32, u64, C.POINTER(u64)]
     L.pgx_pack_reads.argtypes = [p, p, u64, u32, p, p, u64, p, u64, C.POINTER(u64), C.POINTER(u64)]
     L.pgx_host_alloc.argtypes = [C.c_size_t, C.POINTER(p)]
     L.pgx_host_free.argtypes = [p]
@@ -213,6 +216,21 @@ def pack_reads(reads_cat, offsets, packed_out, side_ids_out, side_bytes_out, thr
     _check(lib().pgx_pack_reads(reads_cat.ctypes.data if len(reads_cat) else None, offsets.ctypes.data, len(offsets) - 1, threads, packed_out.ctypes.data,
                                 side_ids_out.ctypes.data, len(side_ids_out), side_bytes_out.ctypes.data, len(side_bytes_out), C.byref(ns), C.byref(nb)))
     return ns.value, nb.value
+
+
+def _text_bytes(buf):
+    """bytes / bytearray / uint8 array -> a contiguous uint8 array (no copy where there is one already)"""
+    if isinstance(buf, np.ndarray):
+        return np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+    return np.frombuffer(buf, dtype=np.uint8)
+
+
+def fastx_cut(buf, fmt, want):
+    """pgx_fastx_cut: the first record start at or after `want` (len(buf) if none).  Host only."""
+    t = _text_bytes(buf)
+    out = u64(0)
+    _check(lib().pgx_fastx_cut(t.ctypes.data if len(t) else None, len(t), fmt, want, C.byref(out)))
+    return out.value
 
 
 def build_rindex(rlbwt_path, out_path, encoded=True):
@@ -460,6 +478,16 @@ class Index:
         finally:
             b.free()
 
+    def find_mems_text(self, buf, fmt, min_len, min_occ, tags=False, device=0):
+        """find_mems over the records of a text (READS_LINES / READS_FASTA / READS_FASTQ), parsed on the device"""
+        b = self.batch_empty(device)
+        try:
+            b.upload_text(buf, fmt)
+            b.run(min_len, min_occ, RUN_TAGS if tags else 0)
+            return b.result()
+        finally:
+            b.free()
+
 
 def _result_dict(r):
     n, m = int(r.n_reads), int(r.n_mems)
@@ -587,6 +615,14 @@ class Batch:
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         self.n = len(offsets) - 1
         _check(self.L.pgx_batch_upload(self.b, reads_cat.ctypes.data if len(reads_cat) else None, offsets.ctypes.data, self.n))
+
+    def upload_text(self, buf, fmt):
+        """pgx_batch_upload_text: the records of `buf` become the reads; returns their number"""
+        t = _text_bytes(buf)
+        n = u64(0)
+        _check(self.L.pgx_batch_upload_text(self.b, t.ctypes.data if len(t) else None, len(t), fmt, C.byref(n)))
+        self.n = n.value
+        return n.value
 
     def run(self, min_len, min_occ, flags=0, stream=None):
         _check(self.L.pgx_batch_run(self.b, min_len, min_occ, flags, stream))

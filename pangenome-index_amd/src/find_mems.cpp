@@ -6,7 +6,8 @@
 // tag_arrays.cpp:885-889); reads are processed in device batches but printed in file order.
 // Options (ours): --device N | --gpus N (devices 0 .. N-1) | --devices a,b,.. ; --streams W (batches in flight per device);
 //                 --mode compat|strict, --batch N (reads per device batch), --tags-format auto|bytecode|compact,
-//                 --quiet (no per-read stderr line)
+//                 --quiet (no per-read stderr line), --reads-format lines|fasta|fastq|auto (default lines; auto: by the first byte,
+//                 '>' FASTA, '@' FASTQ, otherwise lines), --device-parse (line files parsed on the device too; FASTA / FASTQ always are)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -14,6 +15,9 @@
 // upload, run, download and format the text of whole batches -- so on one device the upload of batch k + 1, the kernels of
 // batch k and the download / formatting of batch k - 1 overlap, and N devices take batches in turn with the index replicated
 // (reads shard, no collective); the main thread writes the finished texts in file order.
+// Device-parsed input (FASTA, FASTQ, --device-parse): the ranges end at record starts (pgx_fastx_cut), the parse threads only copy the raw
+// bytes into pinned buffers and the workers hand them to pgx_batch_upload_text; a range's read count -- and so the numbers of the reads
+// after it -- is known once it has been uploaded, and a worker formats its batch when every range before it has been counted.
 #include <condition_variable>
 #include <deque>
 #include <map>
@@ -140,7 +144,7 @@ int main(int argc, char **argv) {
     if (argc < 6) {
         std::cerr << "usage: find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ>"
                      " [--device N | --gpus N | --devices a,b,..] [--streams W] [--mode compat|strict] [--batch N]"
-                     " [--tags-format auto|bytecode|compact] [--quiet]" << std::endl;
+                     " [--tags-format auto|bytecode|compact] [--quiet] [--reads-format lines|fasta|fastq|auto] [--device-parse]" << std::endl;
         return EXIT_FAILURE;
     }
     const std::string r_index_file = argv[1], tag_array_index = argv[2], reads_file = argv[3];
@@ -150,7 +154,8 @@ int main(int argc, char **argv) {
     uint32_t mode = PGX_MODE_COMPAT, tfmt = PGX_TAGS_AUTO;
     size_t batch_reads = 1u << 18; // (reads per batch.  The device alone would like 2^20 -- fresh batches 177 M reads/s at 2^18, 278 M at 2^20, profiles/r04_batch_size_sweep.txt --, but this program is bound by its own host stages: 16 M reads take 0.5-0.7 s with 2^18 and 2.7-2.9 s with 2^20, pinned buffers of 150 MB per job and the formatting of the first and last batch: profiles/r04_cli_e2e.txt)
     unsigned streams = 3;
-    bool quiet = false;
+    bool quiet = false, device_parse = false;
+    std::string reads_format = "lines";
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -170,6 +175,14 @@ int main(int argc, char **argv) {
         else if (a == "--batch") batch_reads = (size_t)std::stoull(next());
         else if (a == "--tags-format") { const std::string f = next(); tfmt = f == "bytecode" ? PGX_TAGS_BYTECODE : f == "compact" ? PGX_TAGS_COMPACT : PGX_TAGS_AUTO; }
         else if (a == "--quiet") quiet = true;
+        else if (a == "--reads-format") {
+            reads_format = next();
+            if (reads_format != "lines" && reads_format != "fasta" && reads_format != "fastq" && reads_format != "auto") {
+                std::cerr << "--reads-format: lines, fasta, fastq or auto" << std::endl;
+                return EXIT_FAILURE;
+            }
+        }
+        else if (a == "--device-parse") device_parse = true;
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
     if (batch_reads == 0) batch_reads = 1;
@@ -225,6 +238,14 @@ int main(int argc, char **argv) {
         }
     }
 
+    // the format of the reads: FASTA and FASTQ are parsed on the device, line files there too with --device-parse
+    uint32_t rfmt = PGX_READS_LINES;
+    if (reads_format == "fasta") rfmt = PGX_READS_FASTA;
+    else if (reads_format == "fastq") rfmt = PGX_READS_FASTQ;
+    else if (reads_format == "auto" && mf.n) rfmt = mf.p[0] == '>' ? PGX_READS_FASTA : mf.p[0] == '@' ? PGX_READS_FASTQ : PGX_READS_LINES;
+    const bool dev_parse = device_parse || rfmt != PGX_READS_LINES;
+    static const char *const rfmt_name[3] = {"LINES", "FASTA", "FASTQ"};
+
     // ---- queues ----
     const unsigned n_workers = (unsigned)devices.size() * streams;
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
@@ -238,19 +259,25 @@ int main(int argc, char **argv) {
     bool reader_done = false, failed = false;
     uint64_t n_jobs = 0, next_write = 0, next_take = 0, next_seq_id = 0, seq_so_far = 0;
     std::map<uint64_t, uint64_t> counts;                  // reads of parsed ranges whose first_seq is not known yet
+    std::map<uint64_t, uint64_t> first_seq_of;            // device-parsed ranges: first_seq, once every range before them has been counted
     const size_t max_ahead = 2 * n_workers + n_parse + 2; // ranges parsed or finished but not yet written (bounds memory)
 
-    // ranges: about batch_reads reads each, by the length of the first lines
+    // ranges: about batch_reads reads each, by the length of the first lines (records: four lines of FASTQ, the '>' lines of FASTA)
     std::vector<std::pair<size_t, size_t>> ranges;
     {
         size_t probe = std::min<size_t>(mf.n, 1u << 16), lines = 0;
-        for (size_t i = 0; i < probe; i++) lines += mf.p[i] == '\n';
-        const double per_line = lines ? (double)probe / (double)lines : 152.0;
+        for (size_t i = 0; i < probe; i++) lines += rfmt == PGX_READS_FASTA ? (mf.p[i] == '>' && (i == 0 || mf.p[i - 1] == '\n')) : mf.p[i] == '\n';
+        if (rfmt == PGX_READS_FASTQ) lines /= 4;
+        const double per_line = lines ? (double)probe / (double)lines : rfmt == PGX_READS_LINES ? 152.0 : (double)std::max<size_t>(probe, 1);
         const size_t want = (size_t)std::max(1.0, per_line * (double)batch_reads);
         size_t at = 0;
         while (at < mf.n) {
             size_t end = std::min(mf.n, at + want);
-            if (end < mf.n) {
+            if (end < mf.n && dev_parse) {
+                uint64_t cut = mf.n;
+                if (pgx_fastx_cut(reinterpret_cast<const uint8_t *>(mf.p), mf.n, rfmt, end, &cut) != PGX_OK) { std::cerr << pgx_last_error() << std::endl; return EXIT_FAILURE; }
+                end = (size_t)cut;
+            } else if (end < mf.n) {
                 const char *nl = static_cast<const char *>(std::memchr(mf.p + end, '\n', mf.n - end));
                 end = nl ? (size_t)(nl - mf.p) + 1 : mf.n;
             }
@@ -273,6 +300,11 @@ int main(int argc, char **argv) {
         const char *q = mf.p + ranges[id].first, *end = mf.p + ranges[id].second;
         j->id = id;
         j->cat = pool.get((size_t)(end - q) + 1);
+        if (dev_parse) { // the raw bytes, pinned: the device parses them (pgx_batch_upload_text)
+            std::memcpy(j->cat.p, q, (size_t)(end - q));
+            j->cat.len = (size_t)(end - q);
+            return j;
+        }
         j->offs.reserve((size_t)(end - q) / 100 + 16);
         j->offs.push_back(0);
         char *dst = j->cat.p;
@@ -317,6 +349,7 @@ int main(int argc, char **argv) {
                 std::unique_ptr<Job> j = parse_range(id);
                 ns_parse += now_ns() - tp0;
                 std::lock_guard<std::mutex> lk(mu);
+                if (dev_parse) { parsed[id] = std::move(j); cv_jobs.notify_all(); continue; } // (counted by the worker that uploads it)
                 counts[id] = j->offs.size() - 1;
                 parsed[id] = std::move(j);
                 // sequence numbers: a range knows its first read's number once every range before it has been parsed
@@ -338,7 +371,7 @@ int main(int argc, char **argv) {
             {
                 std::unique_lock<std::mutex> lk(mu);
                 // the next range in file order, once it is parsed and numbered
-                cv_jobs.wait(lk, [&]() { return failed || next_take >= n_jobs || (parsed.count(next_take) && next_take < next_seq_id); });
+                cv_jobs.wait(lk, [&]() { return failed || next_take >= n_jobs || (parsed.count(next_take) && (dev_parse || next_take < next_seq_id)); });
                 if (failed || next_take >= n_jobs) break;
                 j = std::move(parsed[next_take]);
                 parsed.erase(next_take);
@@ -346,7 +379,47 @@ int main(int argc, char **argv) {
                 if (next_take >= n_jobs) { reader_done = true; cv_jobs.notify_all(); cv_done.notify_all(); }
             }
             std::unique_ptr<Done> d(new Done());
-            const size_t n = j->offs.size() - 1;
+            size_t n = j->offs.size() - 1;
+            pgx_status st = PGX_OK;
+            uint64_t t0 = now_ns();
+            if (dev_parse) { // upload + parse on the device; then this range's count numbers the ranges behind it
+                static const uint64_t no_offsets[1] = {0};
+                if (!b) st = pgx_batch_create(h, device, nullptr, no_offsets, 0, &b);
+                uint64_t nr = 0;
+                if (st == PGX_OK) st = pgx_batch_upload_text(b, reinterpret_cast<const uint8_t *>(j->cat.p), j->cat.len, rfmt, &nr);
+                n = (size_t)nr;
+                std::unique_lock<std::mutex> lk(mu);
+                if (st == PGX_OK) {
+                    counts[j->id] = nr;
+                    while (counts.count(next_seq_id)) {
+                        first_seq_of[next_seq_id] = seq_so_far;
+                        seq_so_far += counts[next_seq_id];
+                        counts.erase(next_seq_id);
+                        next_seq_id++;
+                    }
+                    cv_jobs.notify_all();
+                } else { // the library's message, with the record and byte counted from the start of the file once the ranges before are counted
+                    std::string msg = pgx_last_error();
+                    // (this range is never counted: the chain stops at it, next_seq_id == j->id and seq_so_far is its first_seq)
+                    cv_jobs.wait(lk, [&]() { return failed || next_seq_id == j->id; });
+                    const size_t at = msg.find(" record ");
+                    unsigned long long rec = 0, byte = 0;
+                    int used = 0;
+                    if (next_seq_id == j->id && at != std::string::npos &&
+                        std::sscanf(msg.c_str() + at, " record %llu (byte %llu):%n", &rec, &byte, &used) == 2 && used > 0)
+                        msg = reads_file + ": " + rfmt_name[rfmt] + " record " + std::to_string(seq_so_far + rec) + " (byte " +
+                              std::to_string(ranges[j->id].first + byte) + "):" + msg.substr(at + (size_t)used);
+                    d->error = msg;
+                    pool.put(j->cat);
+                    j->cat = ReadBuf();
+                    failed = true;
+                    finished[j->id] = std::move(d);
+                    cv_done.notify_all();
+                    cv_jobs.notify_all();
+                    cv_space.notify_all();
+                    continue;
+                }
+            }
             if (n == 0) { // a range of empty lines only
                 pool.put(j->cat);
                 std::lock_guard<std::mutex> lk(mu);
@@ -356,15 +429,13 @@ int main(int argc, char **argv) {
             }
             pgx_result r;
             const uint8_t *rp = reinterpret_cast<const uint8_t *>(j->cat.p);
-            uint64_t t0 = now_ns();
-            pgx_status st = PGX_OK;
-            if (j->packed) {
+            if (j->packed) { // (never with dev_parse: those ranges are uploaded above)
                 static const uint64_t no_offsets[1] = {0};
                 if (!b) st = pgx_batch_create(h, device, nullptr, no_offsets, 0, &b);
                 if (st == PGX_OK)
                     st = pgx_batch_upload_packed(b, reinterpret_cast<const uint32_t *>(j->pk.p), j->offs.data(), n, j->side_ids.data(),
                                                  reinterpret_cast<const uint8_t *>(j->pk.p) + j->side_at, j->n_side);
-            } else st = b ? pgx_batch_upload(b, rp, j->offs.data(), n) : pgx_batch_create(h, device, rp, j->offs.data(), n, &b);
+            } else if (!dev_parse) st = b ? pgx_batch_upload(b, rp, j->offs.data(), n) : pgx_batch_create(h, device, rp, j->offs.data(), n, &b);
             uint64_t t1 = now_ns();
             if (st == PGX_OK) st = pgx_batch_run(b, mem_length, min_occ, PGX_RUN_TAGS | PGX_RUN_TIMING, nullptr);
             uint64_t t2 = now_ns();
@@ -375,7 +446,13 @@ int main(int argc, char **argv) {
             j->cat = ReadBuf();
             pool.put(j->pk);
             j->pk = ReadBuf();
-            if (st != PGX_OK) d->error = pgx_last_error();
+            if (st == PGX_OK && dev_parse) { // its number: every range before it counted
+                std::unique_lock<std::mutex> lk(mu);
+                cv_jobs.wait(lk, [&]() { return failed || j->id < next_seq_id; });
+                if (j->id < next_seq_id) j->first_seq = first_seq_of[j->id], first_seq_of.erase(j->id);
+                else { st = PGX_ERR_ARG; d->error = "find_mems: a batch before this one failed"; }
+            }
+            if (st != PGX_OK) { if (d->error.empty()) d->error = pgx_last_error(); }
             else {
                 pgx_timing t;
                 if (pgx_batch_timing(b, &t) == PGX_OK) {
