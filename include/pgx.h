@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PGX_ABI_VERSION 5 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_* */
+#define PGX_ABI_VERSION 6 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS */
 
 typedef enum {
     PGX_OK = 0,
@@ -414,6 +414,40 @@ pgx_status pgx_batch_timing(pgx_batch *b, pgx_timing *out);
  * sizes because a capacity was too small.  Results never depend on it; PGX_SPEC=0 in the environment switches it off. */
 pgx_status pgx_batch_spec_stats(pgx_batch *b, uint32_t *speculative_runs, uint32_t *fallbacks);
 void pgx_batch_free(pgx_batch *b);
+/* ---- locate the MEMs of the last run, on the device --------------------------------------------------------------
+ * For MEM m of the last pgx_batch_run (mems[m] of pgx_batch_result, same order) the occurrences are the suffix-array values of BWT
+ * rows [bwt_start, bwt_start + size - 1], in exactly the forms pgx_locate_batch defines: flags = 0 packed positions
+ * seq * max_length + offset in BWT order; PGX_LOCATE_SEQ_IDS sequence ids in BWT order; PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE sorted
+ * unique sequence ids (PGX_LOCATE_UNIQUE alone: sorted unique packed positions).  MEM m's values equal
+ * pgx_locate_batch(first = bwt_start, last = bwt_start + size - 1, flags); there is no other definition of correctness.
+ *   max_occ (0 = no cap): a MEM with size > max_occ gets no values and counts as not located (its loc_offsets entry stays empty, its
+ *     size stays in mems[m].size).
+ *   size <= 0, or a range that would end at or beyond bwt_size: no values, counted as not located, never read.
+ *   Support is pgx_locate_batch's: PGX_ERR_UNSUPPORTED in COMPAT mode on an encoded index without N.  A failed or refused call
+ *     leaves the batch's find_mems results as they were (and no locate result).
+ * Runs on the device-resident MEMs (no re-run of the search) on `stream` (as pgx_batch_run: NULL = the batch's own stream) and is
+ * complete when it returns.  Where the index keeps its whole suffix array on the device (the LCE image of narrow bidirectional
+ * indexes) the values are a gather from it; elsewhere the sample chains of pgx_locate_batch are walked.  PGX_LOCATE_CHAINS (tests)
+ * forces the chains.  The values of a batch are produced in passes over consecutive MEMs whose intermediate buffer stays within
+ * PGX_LOCATE_BUDGET_MB (environment; default a quarter of free device memory); results never depend on it.
+ * PGX_ERR_ARG without a completed run. */
+#define PGX_LOCATE_CHAINS 4u
+typedef struct {
+    uint64_t n_mems;
+    uint64_t n_values;
+    uint64_t n_not_located;       /* MEMs skipped by max_occ or an invalid range */
+    uint32_t flags;               /* what the locate ran with (PGX_LOCATE_CHAINS dropped) */
+    uint32_t resident;            /* 1: gathered from the resident suffix array, 0: sample chains */
+    const uint64_t *loc_offsets;  /* n_mems + 1; values of MEM m = values[loc_offsets[m] .. [m + 1]) */
+    const uint64_t *values;       /* n_values */
+    float ms_locate;              /* device time of the call when the last run had PGX_RUN_TIMING, else 0 */
+    float reserved;
+} pgx_locations;
+pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t max_occ, void *stream);
+/* Host copy of the last locate (buffers owned by the batch) / the same as device pointers.  Valid until the next run, upload, locate or
+ * free of the batch; PGX_ERR_ARG when there is none. */
+pgx_status pgx_batch_locations(pgx_batch *b, pgx_locations *out);
+pgx_status pgx_batch_device_locations(pgx_batch *b, pgx_locations *out);
 
 /* Convenience: create + run + result in one call (what the find_mems CLI uses). */
 pgx_status pgx_find_mems_batch(pgx_index *h, int device, const uint8_t *reads, const uint64_t *offsets,

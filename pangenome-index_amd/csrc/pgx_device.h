@@ -227,7 +227,19 @@ __global__ void pgx_locate_plan_kernel(PgxLocImage loc, const uint64_t *qs, cons
                                        uint64_t *n_pieces);
 __global__ void pgx_locate_walk_kernel(PgxLocImage loc, const uint64_t *qs, const uint64_t *qe, uint64_t n_queries,
                                        const uint64_t *run0, const uint64_t *piece_off, uint64_t n_pieces, const uint64_t *val_off,
-                                       int seq_ids, uint64_t *out);
+                                       uint64_t val_base, int seq_ids, uint64_t *out);
+
+// MEM occurrences (pgx_mem_locate_kernels.hip, pgx_batch_locate)
+#define PGX_ML_SPAN 4096 // values per block of the resident gather
+#define PGX_ML_WIN 1024  // value offsets / sequence starts a block of it stages in LDS
+__global__ void pgx_ml_plan_kernel(const pgx_mem *mems, uint64_t n, uint64_t bwt_n, uint64_t max_occ, uint64_t *cnt, uint64_t *qs, uint64_t *qe,
+                                   unsigned long long *n_not_located);
+__global__ void pgx_ml_cut_kernel(const uint64_t *off, uint64_t n, uint64_t m0, uint64_t budget, uint64_t *out);
+__global__ void pgx_ml_gather_kernel(const pgx_mem *mems, const uint64_t *off, uint64_t m0, uint64_t m1, uint64_t o_first, uint64_t nv,
+                                     const uint32_t *sa32, uint64_t bwt_n, const uint64_t *seq_start, uint64_t n_seq, uint64_t max_length,
+                                     int seq_ids, uint64_t *out);
+__global__ void pgx_ml_classify_kernel(const uint64_t *cnt, const uint64_t *off, uint64_t np, uint64_t *seg, uint64_t *wave_list,
+                                       uint64_t *wg_list, uint64_t *need, uint64_t *ucount, unsigned long long *ctr);
 
 // literal count image: COMPAT count_encoded / LF_encoded on an encoded index without N, block by block as the
 // reference's rankAt_encoded (src/r-index.cpp:570-590) sees it -- true cumulative counts, run scan one varint late

@@ -59,7 +59,7 @@ pgx_locate_plan_kernel(PgxLocImage loc, const uint64_t *__restrict__ qs, const u
 __global__ void __launch_bounds__(256)
 pgx_locate_walk_kernel(PgxLocImage loc, const uint64_t *__restrict__ qs, const uint64_t *__restrict__ qe, uint64_t n_queries,
                        const uint64_t *__restrict__ run0, const uint64_t *__restrict__ piece_off, uint64_t n_pieces,
-                       const uint64_t *__restrict__ val_off, int seq_ids, uint64_t *__restrict__ out) {
+                       const uint64_t *__restrict__ val_off, uint64_t val_base, int seq_ids, uint64_t *__restrict__ out) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_pieces) return;
     // query owning piece t: last q with piece_off[q] <= t (piece_off has n_queries + 1 entries)
@@ -75,7 +75,7 @@ pgx_locate_walk_kernel(PgxLocImage loc, const uint64_t *__restrict__ qs, const u
     const uint64_t b = qe[q] < re - 1 ? qe[q] : re - 1;
     uint64_t v = loc.rsamp[run];
     for (uint64_t p = rs; p < a; p++) v = pgx_locate_next(loc, v); // :1280-1283
-    uint64_t *dst = out + val_off[q] + (a - qs[q]);
+    uint64_t *dst = out + (val_off[q] - val_base) + (a - qs[q]); // (val_base: the first value `out` holds)
     for (uint64_t p = a;; p++) {
         *dst++ = (seq_ids && v != PGX_NO_POSITION) ? v / loc.max_length : v;
         if (p == b) break;

@@ -86,6 +86,8 @@ struct pgx_device_image {
     DevBuf blocks, dir, blow, consts, tstart, tvals, tdir, tpair, tbucket, seed, seed_small, seed_end, exc, pairs, first_ext, sbase2, pbase;
     DevBuf rstart, rsamp, rdir, lpos, lnext, ldir; // locate image, uploaded on first use
     DevBuf lce_sa, lce_text, lce_flags, lce_lcp;   // LCE image (ensure_lce), built on the first batch
+    DevBuf lce_seq_start;                          // with it: n_seq + 1 text positions, sequence q at [start[q], start[q + 1]) (pgx_batch_locate)
+    uint64_t lce_n_seq = 0;
     int lce_state = 0;                             // 0 not tried, 1 built, 2 not available for this index / device
     DevBuf lit_bstart, lit_cum, lit_runs, lit_roff, lit_tabs; // literal count image (quirk 3), uploaded on first use
     PgxLitImage lit{};
@@ -103,7 +105,7 @@ void pgx_release_device_images(pgx_index *h) {
             d->tstart.release(); d->tvals.release(); d->tdir.release(); d->tpair.release(); d->tbucket.release(); d->seed.release(); d->seed_small.release(); d->seed_end.release(); d->exc.release(); d->pairs.release(); d->first_ext.release(); d->sbase2.release(); d->pbase.release();
             d->lit_bstart.release(); d->lit_cum.release(); d->lit_runs.release(); d->lit_roff.release(); d->lit_tabs.release();
             d->rstart.release(); d->rsamp.release(); d->rdir.release(); d->lpos.release(); d->lnext.release(); d->ldir.release();
-            d->lce_sa.release(); d->lce_text.release(); d->lce_flags.release(); d->lce_lcp.release();
+            d->lce_sa.release(); d->lce_text.release(); d->lce_flags.release(); d->lce_lcp.release(); d->lce_seq_start.release();
         }
         delete d;
     }
@@ -445,6 +447,26 @@ struct TagWork {
     }
 };
 
+// pgx_batch_locate's buffers (grow-only, kept with the batch like its other result buffers) and its result
+struct LocWork {
+    DevBuf cnt, qs, qe, voff, uoff, vals, gbuf, run0, npieces, poff, seg, lists, need, soff, scratch, ucount, uloc, ctr, scan_tmp;
+    HostBuf h_off, h_vals;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool valid = false, resident = false;
+    uint32_t flags = 0;
+    uint64_t n_mems = 0, n_values = 0, n_not_located = 0;
+    const uint64_t *d_off = nullptr; // voff, or uoff with PGX_LOCATE_UNIQUE
+    float ms = 0;
+    void release() {
+        DevBuf *all[] = {&cnt, &qs, &qe, &voff, &uoff, &vals, &gbuf, &run0, &npieces, &poff, &seg, &lists, &need, &soff, &scratch, &ucount, &uloc, &ctr, &scan_tmp};
+        for (DevBuf *d : all) d->release();
+        h_off.release(); h_vals.release();
+        for (auto &e : ev)
+            if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        valid = false;
+    }
+};
+
 static inline uint64_t with_slack(uint64_t v) { return v + v / 4 + 64; }
 
 // Device scalars of the stage, sc[] (zeroed by the caller): [0] big-list length [1] large-list length [2] largest run count on the
@@ -691,7 +713,7 @@ static void locate_core(pgx_index *h, pgx_device_image *d, const uint64_t *first
         gbuf.ensure((V ? V : 1) * 8);
         if (n_pieces) {
             hipLaunchKernelGGL(pgx_locate_walk_kernel, dim3(grid_for(n_pieces, 256)), dim3(256), 0, s, d->loc, dqs.as<uint64_t>(),
-                               dqe.as<uint64_t>(), n, drun0.as<uint64_t>(), dpoff.as<uint64_t>(), n_pieces, dvoff.as<uint64_t>(),
+                               dqe.as<uint64_t>(), n, drun0.as<uint64_t>(), dpoff.as<uint64_t>(), n_pieces, dvoff.as<uint64_t>(), (uint64_t)0,
                                (flags & PGX_LOCATE_SEQ_IDS) ? 1 : 0, gbuf.as<uint64_t>());
             HIPCHECK(hipGetLastError());
         }
@@ -1277,6 +1299,7 @@ struct pgx_batch {
     uint64_t last_ovf_used = 0; // arena slots the last run handed out (sizes the next arena)
     uint64_t max_read_len = 0; // longest read of the upload (sizes the LDS columns of the packed pairs kernel)
     TagWork tw;
+    LocWork lw; // pgx_batch_locate
     uint64_t n_mems = 0, n_positions = 0, n_ext = 0, n_tag_overflow = 0;
     bool ran = false, ran_tags = false;
     // speculative sizing (pgx_batch_run): what the last run with these parameters produced
@@ -1301,6 +1324,7 @@ static void batch_release(pgx_batch *b) {
                          &b->fx_contrib, &b->fx_rec, &b->fx_out_off, &b->fx_rec_idx, &b->fx_offs, &b->fx_scal, &b->fx_scan_tmp};
         for (DevBuf *d : all) d->release();
         b->tw.release();
+        b->lw.release();
         HostBuf *hb[] = {&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]};
         for (HostBuf *x : hb) x->release();
         for (auto &e : b->ev)
@@ -1359,6 +1383,7 @@ static void batch_take_offsets(pgx_batch *b, const uint64_t *offsets, uint64_t n
     b->h_off_cur ^= 1;
     b->n_reads = n_reads;
     b->ran = b->ran_tags = false;
+    b->lw.valid = false;
     b->plan_valid = false;
     b->slot_off_valid = false;
     b->class_valid = false;
@@ -1529,6 +1554,7 @@ static void batch_upload_text(pgx_batch *b, const uint8_t *text, uint64_t n_byte
     b->h_off_cur ^= 1;
     b->n_reads = n_reads;
     b->ran = b->ran_tags = false;
+    b->lw.valid = false;
     b->plan_valid = false;
     b->slot_off_valid = false;
     b->class_valid = false;
@@ -1619,12 +1645,15 @@ static void ensure_lce(pgx_index *h, pgx_device_image *d) {
         d->img.lce_flags = d->lce_flags.as<uint32_t>();
         d->img.lce_max = with_lcp ? PGX_LCE_MAX_OCC : 16; // (without the table of common prefixes every occurrence costs a trip)
         if (const char *e = std::getenv("PGX_FM_LCE_MAX")) d->img.lce_max = (uint32_t)std::min<unsigned long>(std::strtoul(e, nullptr, 10), (unsigned long)PGX_LCE_MAX_OCC);
+        d->lce_seq_start = seq_start; seq_start = DevBuf(); // (kept: text position -> sequence for pgx_batch_locate, 8 bytes per sequence)
+        d->lce_n_seq = n_seq;
         d->img.refill_min = 12; // (chr22 scale, 1 / 3 / 6 / 10 / 16 / 24: main kernel 10.76 / 10.44 / 10.24 / 10.15 / 10.10 / 10.08 ms, step 13.16 / 12.87 / 12.62 / 12.59 / 12.56 / 12.65)
         if (const char *e = std::getenv("PGX_FM_REFILL_MIN")) d->img.refill_min = (uint32_t)std::max<unsigned long>(1ul, std::min<unsigned long>(std::strtoul(e, nullptr, 10), 64ul));
         d->lce_state = 1;
     } catch (...) { // (no LCE image: the search runs on the PAIRS image alone, as before)
         (void)hipGetLastError();
-        d->lce_sa.release(); d->lce_text.release(); d->lce_flags.release(); d->lce_lcp.release();
+        d->lce_sa.release(); d->lce_text.release(); d->lce_flags.release(); d->lce_lcp.release(); d->lce_seq_start.release();
+        d->lce_n_seq = 0;
         d->img.lce_sa = nullptr; d->img.lce_text = nullptr; d->img.lce_flags = nullptr; d->img.lce_lcp = nullptr;
     }
     vals.release(); seq_len.release(); seq_start.release(); text8.release(); bad.release();
@@ -1708,6 +1737,7 @@ extern "C" pgx_status pgx_batch_run(pgx_batch *b, uint64_t min_len, uint64_t min
     b->timed = (flags & PGX_RUN_TIMING) != 0;
     b->ran = false;
     b->ran_tags = false;
+    b->lw.valid = false; // (the locate result belongs to the run before)
     b->n_mems = b->n_positions = b->n_ext = b->n_tag_overflow = 0;
     std::memset(&b->timing, 0, sizeof b->timing);
 
@@ -2207,6 +2237,187 @@ extern "C" pgx_status pgx_batch_result(pgx_batch *b, pgx_result *out) {
         out->n_tag_overflow = b->n_tag_overflow;
     }
     HIPCHECK(hipStreamSynchronize(b->own)); // (the run itself completed inside pgx_batch_run, on whatever stream it used)
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// pgx_batch_locate (pgx_mem_locate_kernels.hip): the occurrences of the last run's MEMs, on the device
+// values one pass of the intermediate buffer may hold: PGX_LOCATE_BUDGET_MB (fractions allowed), default a quarter of free device memory
+static uint64_t locate_budget_values() {
+    uint64_t bytes = 0;
+    if (const char *e = std::getenv("PGX_LOCATE_BUDGET_MB")) {
+        const double mb = std::strtod(e, nullptr);
+        if (mb > 0) bytes = (uint64_t)(mb * 1048576.0);
+    }
+    if (!bytes) {
+        size_t mem_free = 0, mem_total = 0;
+        if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); mem_free = 1ull << 30; }
+        bytes = mem_free / 4;
+    }
+    return std::max<uint64_t>(bytes / 8, 1);
+}
+
+extern "C" pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t max_occ, void *stream) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_locate");
+    checked_device_count();
+    if (!b) throw Error(PGX_ERR_ARG, "pgx_batch_locate: null batch");
+    if (flags & ~(PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE | PGX_LOCATE_CHAINS)) throw Error(PGX_ERR_ARG, "pgx_batch_locate: unknown flag");
+    if (!b->ran) throw Error(PGX_ERR_ARG, "pgx_batch_locate: batch has not been run");
+    LocWork &w = b->lw;
+    w.valid = false;
+    locate_check_supported(b->h, "pgx_batch_locate");
+    use_device(b->device);
+    pgx_device_image *d = locate_image(b->h, b->device);
+    hipStream_t s = stream ? (hipStream_t)stream : b->own;
+    const uint64_t n = b->n_mems, bwt_n = d->loc.n;
+    const bool seq_ids = (flags & PGX_LOCATE_SEQ_IDS) != 0, uniq = (flags & PGX_LOCATE_UNIQUE) != 0;
+    // the resident suffix array: the LCE image in text coordinates and its sequence starts (built from this very locate image's chains)
+    const bool resident = !(flags & PGX_LOCATE_CHAINS) && d->lce_state == 1 && d->img.lce_sa && d->lce_seq_start.p && d->lce_n_seq && d->img.n == bwt_n;
+    const bool timed = b->timed;
+    if (timed) {
+        for (auto &e : w.ev)
+            if (!e) HIPCHECK(hipEventCreate(&e));
+        HIPCHECK(hipEventRecord(w.ev[0], s));
+    }
+    // 1. plan: counts (cap, range checks), ranges, not-located total; value offsets
+    //    ctr: [0] wave list [1] workgroup list [2] scratch total [3] unique values of a pass [4] not located [5] values [6..7] cut
+    w.cnt.ensure((n ? n : 1) * 8); w.qs.ensure((n ? n : 1) * 8); w.qe.ensure((n ? n : 1) * 8); w.voff.ensure((n + 1) * 8); w.ctr.ensure(64);
+    unsigned long long *ctr = w.ctr.as<unsigned long long>();
+    HIPCHECK(hipMemsetAsync(w.ctr.p, 0, 64, s));
+    if (n) {
+        hipLaunchKernelGGL(pgx_ml_plan_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const pgx_mem *)b->mems.as<pgx_mem>(), n, bwt_n, max_occ,
+                           w.cnt.as<uint64_t>(), w.qs.as<uint64_t>(), w.qe.as<uint64_t>(), ctr + 4);
+        HIPCHECK(hipGetLastError());
+    }
+    scan_excl(1, w.cnt.p, n, 0, w.voff.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 5));
+    uint64_t tot[2];
+    read_scalars(tot, ctr + 4, 16, s);
+    const uint64_t n_not = tot[0], V = tot[1];
+    const uint64_t *voff = w.voff.as<uint64_t>();
+    // 2. passes over consecutive MEMs whose values fit the budget (one pass unless the batch exceeds it)
+    const uint64_t budget = locate_budget_values();
+    if (!uniq) w.vals.ensure((V ? V : 1) * 8); // (the values are written in place: no intermediate buffer)
+    else { w.ucount.ensure((n ? n : 1) * 8); w.uoff.ensure((n + 1) * 8); }
+    uint64_t U = 0; // unique values of the passes so far
+    for (uint64_t m0 = 0, o0 = 0; m0 < n;) {
+        uint64_t m1 = n, o1 = V;
+        if (V - o0 > budget) {
+            hipLaunchKernelGGL(pgx_ml_cut_kernel, dim3(1), dim3(64), 0, s, voff, n, m0, budget, reinterpret_cast<uint64_t *>(ctr + 6));
+            HIPCHECK(hipGetLastError());
+            uint64_t c[2];
+            read_scalars(c, ctr + 6, 16, s);
+            m1 = c[0]; o1 = c[1];
+        }
+        const uint64_t np = m1 - m0, nv = o1 - o0;
+        if (uniq) w.gbuf.ensure((nv ? nv : 1) * 8);
+        uint64_t *dst = uniq ? w.gbuf.as<uint64_t>() : w.vals.as<uint64_t>() + o0; // value o of the batch goes to dst[o - o0]
+        if (nv && resident) {
+            hipLaunchKernelGGL(pgx_ml_gather_kernel, dim3(grid_for(nv, PGX_ML_SPAN)), dim3(256), 0, s, (const pgx_mem *)b->mems.as<pgx_mem>(), voff, m0, m1, o0, nv,
+                               (const uint32_t *)d->img.lce_sa, bwt_n, (const uint64_t *)d->lce_seq_start.as<uint64_t>(), d->lce_n_seq, d->loc.max_length,
+                               seq_ids ? 1 : 0, dst);
+            HIPCHECK(hipGetLastError());
+        } else if (nv) { // the sample chains of pgx_locate_batch, from the device ranges
+            w.run0.ensure(np * 8); w.npieces.ensure(np * 8); w.poff.ensure((np + 1) * 8);
+            const uint64_t *qs = w.qs.as<uint64_t>() + m0, *qe = w.qe.as<uint64_t>() + m0;
+            hipLaunchKernelGGL(pgx_locate_plan_kernel, dim3(grid_for(np, 256)), dim3(256), 0, s, d->loc, qs, qe, np, w.run0.as<uint64_t>(), w.npieces.as<uint64_t>());
+            HIPCHECK(hipGetLastError());
+            scan_excl(1, w.npieces.p, np, 0, w.poff.as<uint64_t>(), w.scan_tmp, s);
+            const uint64_t n_pieces = read_u64(w.poff.as<uint64_t>() + np, s);
+            if (n_pieces) {
+                hipLaunchKernelGGL(pgx_locate_walk_kernel, dim3(grid_for(n_pieces, 256)), dim3(256), 0, s, d->loc, qs, qe, np, (const uint64_t *)w.run0.as<uint64_t>(),
+                                   (const uint64_t *)w.poff.as<uint64_t>(), n_pieces, voff + m0, o0, seq_ids ? 1 : 0, dst);
+                HIPCHECK(hipGetLastError());
+            }
+        }
+        if (uniq) { // segmented sort-unique with the tag stage's kernels, size-class lists built on the device, then compaction behind the passes before
+            w.seg.ensure((np + 1) * 8); w.lists.ensure(2 * np * 8); w.need.ensure(np * 8); w.soff.ensure((np + 1) * 8); w.uloc.ensure((np + 1) * 8);
+            uint64_t *seg = w.seg.as<uint64_t>(), *wave_list = w.lists.as<uint64_t>(), *wg_list = wave_list + np, *ucount = w.ucount.as<uint64_t>() + m0;
+            const uint64_t *cnt = w.cnt.as<uint64_t>() + m0;
+            HIPCHECK(hipMemsetAsync(w.ctr.p, 0, 32, s));
+            hipLaunchKernelGGL(pgx_ml_classify_kernel, dim3(grid_for(np + 1, 256)), dim3(256), 0, s, cnt, voff + m0, np, seg, wave_list, wg_list,
+                               w.need.as<uint64_t>(), ucount, ctr);
+            HIPCHECK(hipGetLastError());
+            scan_excl(1, w.need.p, np, 0, w.soff.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 2));
+            uint64_t c[3];
+            read_scalars(c, ctr, 24, s);
+            const uint64_t n_wave = c[0], n_wg = c[1], S = c[2];
+            if (n_wave)
+                hipLaunchKernelGGL(pgx_tag_sort_unique_kernel, dim3(grid_for(n_wave, 4)), dim3(256), 0, s, (const uint64_t *)wave_list, n_wave, (const uint64_t *)nullptr,
+                                   (const uint64_t *)nullptr, cnt, (const uint64_t *)seg, w.gbuf.as<uint64_t>(), ucount);
+            if (n_wg) {
+                w.scratch.ensure((S ? S : 1) * 8);
+                HIPCHECK(hipFuncSetAttribute((const void *)pgx_tag_sort_large_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PGX_SORT_WG_LDS_CAP * 8)));
+                hipLaunchKernelGGL(pgx_tag_sort_large_kernel, dim3(grid_for(n_wg, 1)), dim3(1024), (size_t)PGX_SORT_WG_LDS_CAP * 8, s, (const uint64_t *)wg_list, n_wg,
+                                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, cnt, (const uint64_t *)seg, w.gbuf.as<uint64_t>(), w.scratch.as<uint64_t>(),
+                                   (const uint64_t *)w.soff.as<uint64_t>(), ucount);
+            }
+            HIPCHECK(hipGetLastError());
+            scan_excl(1, ucount, np, 0, w.uloc.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 3));
+            const uint64_t Up = read_u64(reinterpret_cast<const uint64_t *>(ctr + 3), s);
+            w.vals.ensure_keep((U + Up ? U + Up : 1) * 8, U * 8); // (the stream is idle here: the read-back above synchronised it)
+            if (Up) {
+                hipLaunchKernelGGL(pgx_tag_compact_kernel, dim3(grid_for(np, 16)), dim3(256), 0, s, (const uint64_t *)nullptr, np, (const uint64_t *)nullptr,
+                                   (const uint64_t *)nullptr, (const uint64_t *)ucount, (const uint64_t *)seg, (const uint64_t *)w.gbuf.as<uint64_t>(),
+                                   (const uint64_t *)w.uloc.as<uint64_t>(), w.vals.as<uint64_t>() + U, ~0ull);
+                HIPCHECK(hipGetLastError());
+            }
+            U += Up;
+        }
+        m0 = m1; o0 = o1;
+    }
+    if (uniq) scan_excl(1, w.ucount.p, n, 0, w.uoff.as<uint64_t>(), w.scan_tmp, s);
+    w.vals.ensure(8);
+    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
+    HIPCHECK(hipStreamSynchronize(s));
+    w.ms = 0;
+    if (timed) HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
+    w.d_off = uniq ? w.uoff.as<uint64_t>() : voff;
+    w.n_mems = n;
+    w.n_values = uniq ? U : V;
+    w.n_not_located = n_not;
+    w.flags = flags & (PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE);
+    w.resident = resident;
+    w.valid = true;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+static void locations_header(const pgx_batch *b, pgx_locations *out) {
+    const LocWork &w = b->lw;
+    std::memset(out, 0, sizeof *out);
+    out->n_mems = w.n_mems;
+    out->n_values = w.n_values;
+    out->n_not_located = w.n_not_located;
+    out->flags = w.flags;
+    out->resident = w.resident ? 1u : 0u;
+    out->ms_locate = w.ms;
+}
+
+extern "C" pgx_status pgx_batch_device_locations(pgx_batch *b, pgx_locations *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->lw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_locations: batch has no locate result");
+    locations_header(b, out);
+    out->loc_offsets = b->lw.d_off;
+    out->values = b->lw.vals.as<uint64_t>();
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_batch_locations(pgx_batch *b, pgx_locations *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->lw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_locations: batch has no locate result");
+    use_device(b->device);
+    LocWork &w = b->lw;
+    w.h_off.ensure((w.n_mems + 1) * 8);
+    w.h_vals.ensure((w.n_values ? w.n_values : 1) * 8);
+    HIPCHECK(hipMemcpyAsync(w.h_off.p, w.d_off, (w.n_mems + 1) * 8, hipMemcpyDeviceToHost, b->own));
+    if (w.n_values) HIPCHECK(hipMemcpyAsync(w.h_vals.p, w.vals.p, w.n_values * 8, hipMemcpyDeviceToHost, b->own));
+    HIPCHECK(hipStreamSynchronize(b->own)); // (the locate itself completed inside pgx_batch_locate, on whatever stream it used)
+    locations_header(b, out);
+    out->loc_offsets = w.h_off.as<uint64_t>();
+    out->values = w.h_vals.as<uint64_t>();
     return PGX_OK;
     PGX_GUARD_END
 }

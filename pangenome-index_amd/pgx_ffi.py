@@ -52,6 +52,11 @@ class DeviceResult(C.Structure):
                 ("tag_run_counts", p), ("pos_offsets", p), ("positions", p)]
 
 
+class Locations(C.Structure):  # pgx_locations: host pointers (pgx_batch_locations) or device pointers (pgx_batch_device_locations)
+    _fields_ = [("n_mems", u64), ("n_values", u64), ("n_not_located", u64), ("flags", u32), ("resident", u32), ("loc_offsets", p),
+                ("values", p), ("ms_locate", C.c_float), ("reserved", C.c_float)]
+
+
 class DeviceArray:
     """a device buffer owned by a batch, exposed through __cuda_array_interface__ (zero copy: torch.as_tensor(a, device="cuda"));
     64-bit unsigned values are presented as int64"""
@@ -150,6 +155,9 @@ def lib():
     L.pgx_batch_device_result.argtypes = [p, C.POINTER(DeviceResult)]
     L.pgx_batch_timing.argtypes = [p, C.POINTER(Timing)]
     L.pgx_batch_spec_stats.argtypes = [p, C.POINTER(u32), C.POINTER(u32)]
+    L.pgx_batch_locate.argtypes = [p, u32, u64, p]
+    L.pgx_batch_locations.argtypes = [p, C.POINTER(Locations)]
+    L.pgx_batch_device_locations.argtypes = [p, C.POINTER(Locations)]
     L.pgx_batch_free.argtypes = [p]
     L.pgx_batch_free.restype = None
     L.pgx_find_mems_batch.argtypes = [p, C.c_int, p, p, u64, u64, u64, u32, C.POINTER(p), C.POINTER(Result)]
@@ -267,6 +275,7 @@ _VIEW_DTYPES = {0: np.uint8, 1: np.uint64, 2: np.uint64, 3: np.uint64, 4: np.uin
                 8: np.uint64, 9: np.uint64, 10: np.uint32, 11: np.uint64, 12: np.uint64, 13: np.uint32, 14: np.uint8, 15: np.uint32,
                 16: np.uint64, 17: np.uint64, 18: np.uint64, 19: np.uint32, 20: np.uint32, 21: np.uint32, 22: np.uint64, 23: np.uint64}
 LOCATE_SEQ_IDS, LOCATE_UNIQUE = 1, 2
+LOCATE_CHAINS = 4  # pgx_batch_locate: the sample chains even where the suffix array is resident (tests)
 NO_POSITION = 0xFFFFFFFFFFFFFFFF
 
 
@@ -675,6 +684,32 @@ class Batch:
             out["tag_run_counts"] = DeviceArray(r.tag_run_counts, (m,), self)
             out["pos_offsets"] = DeviceArray(r.pos_offsets, (m + 1,), self)
             out["positions"] = DeviceArray(r.positions, (int(r.n_positions),), self)
+        return out
+
+    def locate(self, flags=0, max_occ=0, stream=None):
+        """pgx_batch_locate: the occurrences of the last run's MEMs, left on the device (locations() / device_locations())"""
+        _check(self.L.pgx_batch_locate(self.b, flags, max_occ, stream))
+
+    def _locations(self, fn):
+        r = Locations()
+        _check(fn(self.b, C.byref(r)))
+        return r, dict(n_mems=int(r.n_mems), n_values=int(r.n_values), n_not_located=int(r.n_not_located), flags=int(r.flags),
+                       resident=bool(r.resident), ms_locate=float(r.ms_locate))
+
+    def locations(self):
+        """the last locate as numpy arrays: loc_offsets uint64[n_mems + 1] (MEM m's values = values[loc_offsets[m] .. [m + 1])), values,
+        with n_values, n_not_located, flags, resident (1: gathered from the resident suffix array), ms_locate"""
+        r, out = self._locations(self.L.pgx_batch_locations)
+        out["loc_offsets"] = _u64_array(C.cast(r.loc_offsets, C.POINTER(u64)), out["n_mems"] + 1)
+        out["values"] = _u64_array(C.cast(r.values, C.POINTER(u64)), out["n_values"])
+        return out
+
+    def device_locations(self):
+        """the same as device arrays (valid until the next run / upload / locate / free)"""
+        r, out = self._locations(self.L.pgx_batch_device_locations)
+        out["device"] = True
+        out["loc_offsets"] = DeviceArray(r.loc_offsets, (out["n_mems"] + 1,), self)
+        out["values"] = DeviceArray(r.values, (out["n_values"],), self)
         return out
 
     def free(self):

@@ -7,7 +7,8 @@
 // Options (ours): --device N | --gpus N (devices 0 .. N-1) | --devices a,b,.. ; --streams W (batches in flight per device);
 //                 --mode compat|strict, --batch N (reads per device batch), --tags-format auto|bytecode|compact,
 //                 --quiet (no per-read stderr line), --reads-format lines|fasta|fastq|auto (default lines; auto: by the first byte,
-//                 '>' FASTA, '@' FASTQ, otherwise lines), --device-parse (line files parsed on the device too; FASTA / FASTQ always are)
+//                 '>' FASTA, '@' FASTQ, otherwise lines), --device-parse (line files parsed on the device too; FASTA / FASTQ always are),
+//                 --locate positions|seqs (the occurrences of every MEM, pgx_batch_locate), --locate-max K (MEMs with more occurrences: not located)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -26,6 +27,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
+#include <cerrno>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -111,13 +113,30 @@ struct Done {
 };
 
 // text of reads [lo, hi) of a finished batch (stdout piece + the per-read stderr lines of find_all_mems, algorithm.hpp:754)
-static void format_range(const pgx_result &r, size_t lo, size_t hi, uint64_t first_seq, bool quiet, std::string &out, std::string &err) {
+// --locate: two more lines per MEM block (the reference's list style, every item followed by ", "):
+//   positions  "Occurrences: <size>" and "<seq>:<offset>, " per occurrence in BWT order
+//   seqs       "Sequences: <count>" and "<seq>, " per sorted unique sequence id
+//   a MEM without values (over --locate-max): "Occurrences: <size> (not located)" and an empty line
+enum { LOCATE_NONE = 0, LOCATE_POSITIONS = 1, LOCATE_SEQS = 2 };
+struct LocateOut {
+    int mode = LOCATE_NONE;
+    uint64_t max_length = 1;
+    const pgx_locations *loc = nullptr;
+};
+static inline char *put_i64(char *p, int64_t v) {
+    if (v < 0) { *p++ = '-'; return put_u64(p, (uint64_t)(-(v + 1)) + 1u); }
+    return put_u64(p, (uint64_t)v);
+}
+
+static void format_range(const pgx_result &r, size_t lo, size_t hi, uint64_t first_seq, bool quiet, const LocateOut &lo_, std::string &out, std::string &err) {
     out.clear();
     err.clear();
     // exact upper bound of the text of this range: 20 digits per number
     const uint64_t m_lo = r.mem_offsets[lo], m_hi = r.mem_offsets[hi];
     const uint64_t p_cnt = r.pos_offsets[m_hi] - r.pos_offsets[m_lo];
-    out.resize((hi - lo) * 32 + (m_hi - m_lo) * 192 + p_cnt * 22 + 64);
+    const uint64_t *lof = lo_.mode ? lo_.loc->loc_offsets : nullptr;
+    const uint64_t v_cnt = lo_.mode ? lof[m_hi] - lof[m_lo] : 0;
+    out.resize((hi - lo) * 32 + (m_hi - m_lo) * (lo_.mode ? 256 : 192) + p_cnt * 22 + v_cnt * 44 + 64);
     char *p = &out[0];
     for (size_t i = lo; i < hi; i++) {
         const size_t seq = first_seq + i + 1;
@@ -134,6 +153,20 @@ static void format_range(const pgx_result &r, size_t lo, size_t hi, uint64_t fir
             p = put_str(p, "Number of unique positions: "); p = put_u64(p, r.pos_offsets[m + 1] - r.pos_offsets[m]); *p++ = '\n'; // tag_arrays.cpp:885
             for (uint64_t q = r.pos_offsets[m]; q < r.pos_offsets[m + 1]; q++) { p = put_u64(p, r.positions[q]); *p++ = ','; *p++ = ' '; }
             *p++ = '\n';
+            if (lo_.mode) {
+                const uint64_t *v = lo_.loc->values;
+                if (lof[m + 1] == lof[m]) { p = put_str(p, "Occurrences: "); p = put_i64(p, mm.size); p = put_str(p, " (not located)\n"); }
+                else if (lo_.mode == LOCATE_POSITIONS) {
+                    p = put_str(p, "Occurrences: "); p = put_i64(p, mm.size); *p++ = '\n';
+                    for (uint64_t q = lof[m]; q < lof[m + 1]; q++) {
+                        p = put_u64(p, v[q] / lo_.max_length); *p++ = ':'; p = put_u64(p, v[q] % lo_.max_length); *p++ = ','; *p++ = ' ';
+                    }
+                } else {
+                    p = put_str(p, "Sequences: "); p = put_u64(p, lof[m + 1] - lof[m]); *p++ = '\n';
+                    for (uint64_t q = lof[m]; q < lof[m + 1]; q++) { p = put_u64(p, v[q]); *p++ = ','; *p++ = ' '; }
+                }
+                *p++ = '\n';
+            }
         }
         *p++ = '\n'; // :138
     }
@@ -144,7 +177,8 @@ int main(int argc, char **argv) {
     if (argc < 6) {
         std::cerr << "usage: find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ>"
                      " [--device N | --gpus N | --devices a,b,..] [--streams W] [--mode compat|strict] [--batch N]"
-                     " [--tags-format auto|bytecode|compact] [--quiet] [--reads-format lines|fasta|fastq|auto] [--device-parse]" << std::endl;
+                     " [--tags-format auto|bytecode|compact] [--quiet] [--reads-format lines|fasta|fastq|auto] [--device-parse]"
+                     " [--locate positions|seqs] [--locate-max K]" << std::endl;
         return EXIT_FAILURE;
     }
     const std::string r_index_file = argv[1], tag_array_index = argv[2], reads_file = argv[3];
@@ -156,6 +190,8 @@ int main(int argc, char **argv) {
     unsigned streams = 3;
     bool quiet = false, device_parse = false;
     std::string reads_format = "lines";
+    int locate_mode = LOCATE_NONE;
+    uint64_t locate_max = 0;
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -183,9 +219,24 @@ int main(int argc, char **argv) {
             }
         }
         else if (a == "--device-parse") device_parse = true;
+        else if (a == "--locate") {
+            const std::string f = next();
+            if (f == "positions") locate_mode = LOCATE_POSITIONS;
+            else if (f == "seqs") locate_mode = LOCATE_SEQS;
+            else { std::cerr << "--locate: positions or seqs" << std::endl; return EXIT_FAILURE; }
+        }
+        else if (a == "--locate-max") {
+            const std::string f = next();
+            errno = 0;
+            char *endp = nullptr;
+            const unsigned long long k = f.empty() || f.size() > 19 || f.find_first_not_of("0123456789") != std::string::npos ? 0 : std::strtoull(f.c_str(), &endp, 10);
+            if (!endp || *endp || errno) { std::cerr << "--locate-max: a number of occurrences >= 0 (0: no cap)" << std::endl; return EXIT_FAILURE; }
+            locate_max = k;
+        }
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
     if (batch_reads == 0) batch_reads = 1;
+    if (locate_max && !locate_mode) { std::cerr << "--locate-max needs --locate" << std::endl; return EXIT_FAILURE; }
 
     auto time1 = std::chrono::high_resolution_clock::now();
     double total_mem_time = 0.0, total_tag_time = 0.0;
@@ -204,6 +255,14 @@ int main(int argc, char **argv) {
         std::cerr << pgx_last_error() << std::endl; // reference: uncaught sdsl::simple_sds::InvalidData
         return EXIT_FAILURE;
     }
+    LocateOut locate_out;
+    locate_out.mode = locate_mode;
+    if (locate_mode) {
+        pgx_index_info info;
+        if (pgx_index_info_get(h, &info) != PGX_OK) { std::cerr << pgx_last_error() << std::endl; return EXIT_FAILURE; }
+        locate_out.max_length = info.max_length ? info.max_length : 1;
+    }
+    const uint32_t locate_flags = locate_mode == LOCATE_SEQS ? (PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE) : 0u;
     auto time2 = std::chrono::high_resolution_clock::now();
     std::cerr << "Loading r-index into memory took " << std::chrono::duration<double>(time2 - time1).count() << " seconds" << std::endl;
     std::cerr << "Reading the tag array index" << std::endl;
@@ -440,6 +499,14 @@ int main(int argc, char **argv) {
             if (st == PGX_OK) st = pgx_batch_run(b, mem_length, min_occ, PGX_RUN_TAGS | PGX_RUN_TIMING, nullptr);
             uint64_t t2 = now_ns();
             if (st == PGX_OK) st = pgx_batch_result(b, &r);
+            pgx_locations loc;
+            LocateOut lout = locate_out;
+            if (st == PGX_OK && locate_mode) {
+                st = pgx_batch_locate(b, locate_flags, locate_max, nullptr);
+                if (st == PGX_OK) st = pgx_batch_locations(b, &loc);
+                if (st == PGX_ERR_UNSUPPORTED) d->error = std::string(pgx_last_error()) + " (find_mems: run with --mode strict)";
+                lout.loc = &loc;
+            }
             uint64_t t3 = now_ns();
             ns_upload += t1 - t0; ns_run += t2 - t1; ns_download += t3 - t2;
             pool.put(j->cat); // (the upload has completed: pgx_batch_upload synchronises its copies)
@@ -462,11 +529,11 @@ int main(int argc, char **argv) {
                 const unsigned parts = n < 4096 ? 1u : n_fmt;
                 d->outs.resize(parts);
                 d->errs.resize(parts);
-                if (parts == 1) format_range(r, 0, n, j->first_seq, quiet, d->outs[0], d->errs[0]);
+                if (parts == 1) format_range(r, 0, n, j->first_seq, quiet, lout, d->outs[0], d->errs[0]);
                 else {
                     std::vector<std::thread> pool;
                     for (unsigned w = 0; w < parts; w++)
-                        pool.emplace_back([&, w]() { format_range(r, n * w / parts, n * (w + 1) / parts, j->first_seq, quiet, d->outs[w], d->errs[w]); });
+                        pool.emplace_back([&, w]() { format_range(r, n * w / parts, n * (w + 1) / parts, j->first_seq, quiet, lout, d->outs[w], d->errs[w]); });
                     for (auto &th : pool) th.join();
                 }
                 ns_format += now_ns() - t3;
