@@ -99,7 +99,7 @@
  * (Round 3 also tried blocks of 64 positions read as three 16-byte pieces instead of five: fewer requests per line changed nothing, the extra
  * lines of the shorter blocks did -- profiles/r03_pairs64_layout.json -- and the layout was dropped.) */
 #define PGX_PAIRS_STRIDE64 64u
-/* LCE image (round 4; device only, built on the device next to a narrow PAIRS image: pgx_runtime.hip ensure_lce):
+/* LCE image (round 4; device only, built on the device next to a narrow PAIRS image: pgx_images.hip ensure_lce):
  *   lce_sa[i]     u32: where suffix i of the BWT order starts in lce_text (the r-index's samples expanded to the whole suffix array by the locate
  *                 kernels, sequence * max_length + offset -> start of the sequence + offset)
  *   lce_text      the collection itself, two bits per symbol, 16 symbols per u32, A C T G = 0 1 2 3 (the order of the packed reads: XOR compares

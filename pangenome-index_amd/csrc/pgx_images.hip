@@ -1,0 +1,391 @@
+// pgx_images.hip -- the device images of an index: the rank image with its seed tables, tag runs and PAIRS blocks (device_image), and what is
+// added on first use: the locate image (locate_image), the LCE image (ensure_lce) and the literal count image (literal_image).
+#include <memory>
+#include <mutex>
+
+#include "pgx_runtime_internal.hpp"
+
+// The environment variables that shape an image, read in one place when the image is built (device_image: the seed tables and the tag runs;
+// ensure_lce: the LCE image) -- never later: an image keeps the shape it was built with.  What a run consults is in pgx_batch.hip (RunKnobs).
+struct ImageKnobs {
+    bool has_seed_k;     // PGX_SEED_K is set, and
+    int seed_k;          //   its value (atoi): depth of the k-mer seed table, below 2 = no table
+    bool has_seed_end_k; // PGX_SEED_END_K is set, and
+    int seed_end_k;      //   its value (atoi, held to [0, 12]): depth of the end table
+    bool tpair;          // PGX_NO_TPAIR set at all clears it: no (start, value) pairs of the tag runs
+    bool tbucket;        // PGX_NO_TBUCKET set at all clears it: no bucket lines of the tag runs
+    bool lce;            // PGX_FM_LCE=0 clears it: no LCE image
+    bool lcp;            // PGX_FM_LCP=0 clears it: no table of common prefixes next to the LCE image (every occurrence is compared with the text)
+    bool has_lce_max;    // PGX_FM_LCE_MAX is set, and
+    uint32_t lce_max;    //   its value (strtoul, at most PGX_LCE_MAX_OCC): widest interval that takes the text path
+    bool has_refill_min; // PGX_FM_REFILL_MIN is set, and
+    uint32_t refill_min; //   its value (strtoul, held to [1, 64]): idle lanes a wave of the LCE kernel gathers before it fetches new reads
+};
+
+static ImageKnobs read_image_knobs() {
+    auto not_zero = [](const char *name) { const char *e = std::getenv(name); return !(e && e[0] == '0'); };
+    ImageKnobs k{};
+    if (const char *e = std::getenv("PGX_SEED_K")) { k.has_seed_k = true; k.seed_k = std::atoi(e); }
+    if (const char *e = std::getenv("PGX_SEED_END_K")) { k.has_seed_end_k = true; k.seed_end_k = std::max(0, std::min(std::atoi(e), 12)); }
+    k.tpair = !std::getenv("PGX_NO_TPAIR");
+    k.tbucket = !std::getenv("PGX_NO_TBUCKET");
+    k.lce = not_zero("PGX_FM_LCE");
+    k.lcp = not_zero("PGX_FM_LCP");
+    if (const char *e = std::getenv("PGX_FM_LCE_MAX")) { k.has_lce_max = true; k.lce_max = (uint32_t)std::min<unsigned long>(std::strtoul(e, nullptr, 10), (unsigned long)PGX_LCE_MAX_OCC); }
+    if (const char *e = std::getenv("PGX_FM_REFILL_MIN")) { k.has_refill_min = true; k.refill_min = (uint32_t)std::max<unsigned long>(1ul, std::min<unsigned long>(std::strtoul(e, nullptr, 10), 64ul)); }
+    return k;
+}
+
+void pgx_release_device_images(pgx_index *h) {
+    for (auto *d : h->dev) {
+        if (!d) continue;
+        if (hipSetDevice(d->device) == hipSuccess) {
+            d->blocks.release(); d->dir.release(); d->blow.release(); d->consts.release();
+            d->tstart.release(); d->tvals.release(); d->tdir.release(); d->tpair.release(); d->tbucket.release(); d->seed.release(); d->seed_small.release(); d->seed_end.release(); d->exc.release(); d->pairs.release(); d->first_ext.release(); d->sbase2.release(); d->pbase.release();
+            d->lit_bstart.release(); d->lit_cum.release(); d->lit_runs.release(); d->lit_roff.release(); d->lit_tabs.release();
+            d->rstart.release(); d->rsamp.release(); d->rdir.release(); d->lpos.release(); d->lnext.release(); d->ldir.release();
+            d->lce_sa.release(); d->lce_text.release(); d->lce_flags.release(); d->lce_lcp.release(); d->lce_seq_start.release();
+        }
+        delete d;
+    }
+    h->dev.clear();
+}
+
+// k-mer seed table of a dense image (pgx_kernels.hip "k-mer seeds"): built level by level on the device,
+// 4^L entries at level L, each one pgx_extend of its parent.  K = floor(log4 n), at most 14 (4 GiB of table; chr22 scale, 10 M
+// reads, K = 11 / 12 / 13 / 14: 41.2 / 39.1 / 37.2 / 36.4 ms with the 64-byte dense image; n = 64 M, 1 M reads, K = 0 / 9 / 11 / 12: 3.64 / 3.44 /
+// 3.14 / 3.07 ms), PGX_SEED_K overrides (0 = no table).
+static void build_seed_table(pgx_device_image *d, const ImageKnobs &knobs) {
+    PgxDevImage &g = d->img;
+    // depth: one more than the first at which a random window is expected in the index less than once (4^K >= n), at most 15 (16 GiB): a seed that dies
+    // inside the table ends a stage without another trip (n = 640 M: K = 14 / 15 / 16: 20.8 / 19.4-20.5 / 20.1 ms; n = 64 M: K = 12 / 13 / 14: 2.47 / 2.43 / 2.37 ms)
+    // Round 4: at most 16 (64 GiB) and three tenths of the device's memory -- with the forward stages through the text a read is ~28 lane trips and the
+    // two-step trips behind the seed are a third of them: depth 16 leaves 4 symbols = 2 trips of a 20-symbol step 1 instead of 5 = 3
+    // (n = 640 M, K = 15 / 16: main kernel 10.26 / 9.44 ms, 791 / 830 M reads/s, 3.6 s more to build)
+    int K = 0;
+    while (K < 16 && (K == 0 || (1ull << (2 * (K - 1))) < g.n)) K++;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); mem_free = mem_total = (size_t)16 << 30; }
+        while (K > 2 && (((size_t)1 << (2 * K)) * sizeof(uint4)) * 5 / 4 > std::min(mem_total * 3 / 10, mem_free / 2)) K--; // table + the level below it while building
+    }
+    // an image small enough for LDS leaves the loop bound by instruction issue, and every extension a seed replaces is a gain: depth 10
+    // (16 MiB of table, hot in L2) whatever n is (x index, 1 M reads, min_len 10, K = 0 / 4 / 6 / 8 / 10: 1.22 / 1.03 / 0.81 / 0.72 / 0.59 ms)
+    if (d->lds_bytes) K = 10;
+    if (knobs.has_seed_k) K = knobs.seed_k;
+    if (K > PGX_SEED_MAX_K) K = PGX_SEED_MAX_K;
+    if (K < 2) return;
+    const uint64_t limit = g.n < (1ull << 30) ? (1ull << 32) : (1ull << 40); // what an entry (and the 32-bit kernels) can hold
+    DevBuf tmp;
+    // end table (stages that start at j = len, i.e. with the extension by 0): depth 8, 1 MiB -- such a stage almost always dies within a few
+    // extensions (a read rarely ends where a sequence ends), which the entry's death depth answers at once
+    int Ke = std::min(K, 8);
+    if (knobs.has_seed_end_k) Ke = knobs.seed_end_k;
+    auto build = [&](DevBuf &out, int depth, int end_table) {
+        out.ensure(((size_t)1 << (2 * depth)) * sizeof(uint4));
+        tmp.ensure(((size_t)1 << (2 * (depth - 1))) * sizeof(uint4));
+        for (int L = 0; L < depth; L++) { // level L -> L + 1; level `depth` ends in out
+            uint4 *dst = ((depth - (L + 1)) % 2 == 0) ? out.as<uint4>() : tmp.as<uint4>();
+            const uint4 *src = ((depth - L) % 2 == 0) ? out.as<uint4>() : tmp.as<uint4>();
+            const uint64_t n_dst = 1ull << (2 * (L + 1));
+            hipLaunchKernelGGL(pgx_seed_build_kernel, dim3((unsigned)std::min<uint64_t>((n_dst + 255) / 256, 1u << 22)), dim3(256), 0, nullptr, g, src, dst, (uint32_t)L, n_dst, limit, end_table);
+            HIPCHECK(hipGetLastError());
+        }
+        HIPCHECK(hipDeviceSynchronize());
+    };
+    const int Ks = K > PGX_SEED_SMALL_K ? PGX_SEED_SMALL_K : 0; // second, shallower table for searches with min_len < K
+    try {
+        build(d->seed, K, 0);
+        if (Ks) build(d->seed_small, Ks, 0);
+        if (Ke >= 2) build(d->seed_end, Ke, 1);
+    } catch (...) { tmp.release(); d->seed.release(); d->seed_small.release(); d->seed_end.release(); throw; }
+    tmp.release();
+    if (Ke >= 2) { g.seed_end = d->seed_end.as<uint4>(); g.seed_end_k = (uint32_t)Ke; }
+    g.seed = d->seed.as<uint4>();
+    g.seed_k = (uint32_t)K;
+    g.seed_main = g.seed; g.seed_k_main = g.seed_k;
+    if (Ks) { g.seed_small = d->seed_small.as<uint4>(); g.seed_k_small = (uint32_t)Ks; }
+}
+
+// one device image per (index, device), created on first use; concurrent first calls from several host threads are serialised
+static std::mutex g_image_mutex;
+
+pgx_device_image *device_image(pgx_index *h, int device) {
+    use_device(device);
+    std::lock_guard<std::mutex> lock(g_image_mutex);
+    if ((int)h->dev.size() <= device) h->dev.resize(device + 1, nullptr);
+    if (h->dev[device]) return h->dev[device];
+    std::unique_ptr<pgx_device_image> d(new pgx_device_image());
+    d->device = device;
+    const HostImage &m = h->img;
+    const ImageKnobs knobs = read_image_knobs();
+    upload(d->blocks, m.blocks.data(), m.blocks.size());
+    upload(d->dir, m.dir.data(), m.dir.size() * 8);
+    upload(d->blow, m.blow.data(), m.blow.size() * 2);
+    upload(d->exc, m.exc.data(), m.exc.size() * 4);
+    upload(d->consts, &m.consts, sizeof(PgxConsts));
+    upload(d->tstart, m.tstart.data(), m.tstart.size() * 8);
+    upload(d->tvals, m.tvals.data(), m.tvals.size() * 8);
+    upload(d->tdir, m.tdir.data(), m.tdir.size() * 4);
+    PgxDevImage &g = d->img;
+    g.blocks = d->blocks.as<uint4>();
+    g.dir = d->dir.as<uint64_t>();
+    g.blow = d->blow.as<uint16_t>();
+    g.consts = d->consts.as<PgxConsts>();
+    g.tstart = d->tstart.as<uint64_t>();
+    g.tvals = d->tvals.as<uint64_t>();
+    g.tdir = d->tdir.as<uint32_t>();
+    g.tpair = nullptr;
+    if (!m.tstart.empty() && !m.tvals.empty() && knobs.tpair) { // tag runs as (start, value) pairs for the locate kernel (built on the device)
+        const uint64_t np = std::max<uint64_t>(m.tstart.size(), m.tvals.size());
+        d->tpair.ensure(np * sizeof(ulonglong2));
+        hipLaunchKernelGGL(pgx_tag_pair_kernel, dim3((unsigned)std::min<uint64_t>((np + 255) / 256, 65536)), dim3(256), 0, nullptr, d->tstart.as<uint64_t>(),
+                           d->tvals.as<uint64_t>(), (uint64_t)m.tstart.size(), (uint64_t)m.tvals.size(), d->tpair.as<ulonglong2>());
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipDeviceSynchronize());
+        g.tpair = d->tpair.as<ulonglong2>();
+    }
+    g.tbucket = nullptr; g.n_tbuckets = 0; g.tbucket_shift = 0;
+    if (!m.tstart.empty() && !m.tvals.empty() && knobs.tbucket) { // tag runs by bucket, one line each (pgx_tag_bucket_kernel): about four runs per bucket
+        const uint64_t nr = m.tstart.size(), span = m.tstart.back() + 1;
+        uint32_t sh = 0;
+        while (sh < 16 && (span >> (sh + 1)) >= nr / 4 + 1) sh++;
+        const uint64_t nbk = (span >> sh) + 1;
+        if (nbk * 128 <= (16ull << 30)) {
+            d->tbucket.ensure(nbk * 128);
+            hipLaunchKernelGGL(pgx_tag_bucket_kernel, dim3((unsigned)std::min<uint64_t>((nbk + 255) / 256, 1u << 20)), dim3(256), 0, nullptr, d->tstart.as<uint64_t>(),
+                               d->tvals.as<uint64_t>(), nr, (uint64_t)m.tvals.size(), sh, nbk, d->tbucket.as<uint4>());
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipDeviceSynchronize());
+            g.tbucket = d->tbucket.as<uint4>(); g.n_tbuckets = nbk; g.tbucket_shift = sh;
+        }
+    }
+    g.n = m.consts.n;
+    g.dir_entries = m.consts.dir_entries;
+    g.n_tag_runs = m.consts.n_tag_runs;
+    g.n_tag_items = m.tvals.size();
+    g.tag_dir_entries = m.consts.tag_dir_entries;
+    g.n_blocks = m.consts.n_blocks;
+    g.dir_shift = m.consts.dir_shift;
+    g.excl_mask = m.consts.excl_mask;
+    g.tag_dir_shift = m.consts.tag_dir_shift;
+    g.dense = m.consts.image_kind; // PGX_IMAGE_RL / _DENSE / _DENSE2
+    g.wide = m.consts.wide;
+    if (g.dense == PGX_IMAGE_DENSE2 && g.wide) g.dense = 3; // dense2 blocks with delta counts: the 64-bit kernels (pgx_image.h "WIDE")
+    upload(d->sbase2, m.sbase2.data(), m.sbase2.size() * 8);
+    g.sbase2 = d->sbase2.as<uint64_t>();
+    g.d2_sb_shift = m.consts.d2_sb_shift; g.n_sb2 = m.consts.n_sb2;
+    g.pbase = nullptr; g.pairs_sb_shift = 0; g.n_sbp = 0; g.pairs_stride = 0;
+    g.exc = d->exc.as<uint32_t>();
+    size_t img_bytes = m.blocks.size() + m.dir.size() * 8 + m.blow.size() * 2;
+    if (g.dense == 1) img_bytes = (size_t)m.consts.n_blocks * 16 * PGX_DENSE_LDS_U4 + 16; // padded blocks, no directory (pgx_dense_load)
+    d->lds_bytes = (g.dense < 2 && img_bytes <= 48 * 1024) ? ((img_bytes + 15) & ~(size_t)15) : 0; // the dense2 image is never staged in LDS
+    g.seed_k = 0;
+    g.seed = nullptr;
+    g.seed_end_k = 0;
+    g.seed_end = nullptr;
+    g.seed_k_main = g.seed_k_small = 0;
+    g.seed_main = g.seed_small = nullptr;
+    g.pairs = nullptr; g.first_ext = nullptr; g.pair_runs = 0;
+    g.lce_sa = nullptr; g.lce_text = nullptr; g.lce_flags = nullptr; g.lce_lcp = nullptr; g.lce_max = 0; g.refill_min = 1;
+    if (g.dense && h->has_rank) build_seed_table(d.get(), knobs);
+    if (m.consts.has_pairs && !m.pairs.empty() && h->has_rank) { // the two-step image next to dense2 (pgx_image.h)
+        upload(d->pairs, m.pairs.data(), m.pairs.size());
+        upload(d->pbase, m.pbase.data(), m.pbase.size() * 8);
+        g.pbase = d->pbase.as<uint64_t>();
+        g.pairs_sb_shift = m.consts.pairs_sb_shift; g.n_sbp = m.consts.n_sbp;
+        g.pairs_stride = m.consts.pairs_stride;
+        d->first_ext.ensure(512 * sizeof(uint4));
+        hipLaunchKernelGGL(pgx_first_ext_kernel, dim3(1), dim3(256), 0, nullptr, g, d->first_ext.as<uint4>());
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipDeviceSynchronize());
+        g.pairs = d->pairs.as<uint4>();
+        g.first_ext = d->first_ext.as<uint4>();
+        g.pair_runs = m.consts.pair_runs;
+    }
+    h->dev[device] = d.release();
+    return h->dev[device];
+}
+
+extern "C" pgx_status pgx_index_to_device(pgx_index *h, int device) {
+    PGX_GUARD_BEGIN
+    if (!h) throw Error(PGX_ERR_ARG, "pgx_index_to_device: null index");
+    (void)device_image(h, device);
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_index_device_view(pgx_index *h, int device, int which, void *out, uint64_t bytes) {
+    PGX_GUARD_BEGIN
+    if (!h || !out) throw Error(PGX_ERR_ARG, "pgx_index_device_view: null argument");
+    pgx_device_image *d = device_image(h, device);
+    const HostImage &m = h->img;
+    const void *src = nullptr;
+    uint64_t have = 0;
+    switch (which) {
+    case 0: src = d->blocks.p; have = m.blocks.size(); break;
+    case 15: src = d->exc.p; have = m.exc.size() * 4; break;
+    case 20: src = d->pairs.p; have = m.pairs.size(); break;
+    case 22: src = d->sbase2.p; have = m.sbase2.size() * 8; break;
+    case 23: src = d->pbase.p; have = m.pbase.size() * 8; break;
+    case 30: case 31: case 32: case 33: { // the LCE image (device only; nothing where it does not exist for this index)
+        if (h->has_rank) ensure_lce(h, d);
+        if (d->img.lce_sa) {
+            const uint64_t n = d->img.n, n_words = (n + 15) / 16 + 64;
+            if (which == 30) { src = d->lce_sa.p; have = n * 4; }
+            else if (which == 31) { src = d->lce_text.p; have = n_words * 4; }
+            else if (which == 32) { src = d->lce_flags.p; have = (n_words / 1024 + 2) * 4; }
+            else if (d->img.lce_lcp) { src = d->lce_lcp.p; have = n; }
+        }
+        break;
+    }
+    default: throw Error(PGX_ERR_ARG, "pgx_index_device_view: unknown view");
+    }
+    const uint64_t k = std::min(bytes, have);
+    if (k && src) HIPCHECK(hipMemcpy(out, src, k, hipMemcpyDeviceToHost));
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// locate path (pgx_locate_kernels.hip)
+pgx_device_image *locate_image(pgx_index *h, int device) {
+    if (!h->has_rank) throw Error(PGX_ERR_ARG, "locate: index opened without an r-index");
+    pgx_device_image *d = device_image(h, device);
+    std::lock_guard<std::mutex> lock(g_image_mutex);
+    if (d->has_loc) return d;
+    build_locate_image(h->ri, h->loc);
+    const LocHostImage &m = h->loc;
+    upload(d->rstart, m.rstart.data(), m.rstart.size() * 8);
+    upload(d->rsamp, m.rsamp.data(), m.rsamp.size() * 8);
+    upload(d->rdir, m.rdir.data(), m.rdir.size() * 4);
+    upload(d->lpos, m.lpos.data(), m.lpos.size() * 8);
+    upload(d->lnext, m.lnext.data(), m.lnext.size() * 8);
+    upload(d->ldir, m.ldir.data(), m.ldir.size() * 4);
+    PgxLocImage &g = d->loc;
+    g.rstart = d->rstart.as<uint64_t>(); g.rsamp = d->rsamp.as<uint64_t>(); g.rdir = d->rdir.as<uint32_t>();
+    g.lpos = d->lpos.as<uint64_t>(); g.lnext = d->lnext.as<uint64_t>(); g.ldir = d->ldir.as<uint32_t>();
+    g.n = m.consts.n; g.n_runs = m.consts.n_runs; g.n_last = m.consts.n_last; g.max_length = m.consts.max_length;
+    g.rdir_entries = m.consts.rdir_entries; g.ldir_entries = m.consts.ldir_entries;
+    g.rdir_shift = m.consts.rdir_shift; g.ldir_shift = m.consts.ldir_shift;
+    d->has_loc = true;
+    return d;
+}
+
+// LCE image (pgx_image.h): suffix array in text coordinates + the text at two bits per symbol, for the pairs kernel's forward stages over narrow intervals.
+// Built once per device image, on the device: the suffix array by the locate kernels (every BWT run is an independent chain from its sample), the text from
+// it (the first symbol of suffix i is the one whose C-bucket holds i).  Only next to a narrow PAIRS image (textbook tables, n < 2^32); PGX_FM_LCE=0: never.
+static std::mutex g_lce_mutex;
+void ensure_lce(pgx_index *h, pgx_device_image *d) {
+    std::lock_guard<std::mutex> lock(g_lce_mutex);
+    if (d->lce_state) return;
+    d->lce_state = 2;
+    const ImageKnobs knobs = read_image_knobs();
+    const uint64_t n = d->img.n;
+    if (!knobs.lce || !d->img.pairs || d->img.wide || n < 4096 || n >= (1ull << 32) - (1ull << 20) || h->ri.max_length == 0) return;
+    uint64_t tot[6] = {0, 0, 0, 0, 0, 0}; // symbol counts of the BWT = bucket bounds of the first column
+    for (const auto &blk : h->ri.blocks)
+        for (const auto &ru : blk.runs) if (ru.first < 6) tot[ru.first] += ru.second;
+    const uint64_t n_seq = tot[0];
+    if (tot[0] + tot[1] + tot[2] + tot[3] + tot[4] + tot[5] != n || n_seq == 0 || n_seq > (1ull << 24)) return;
+    {
+        size_t mem_free = 0, mem_total = 0;
+        if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); return; }
+        if ((double)mem_free < 16.0 * (double)n + (double)(2ull << 30)) return; // 8 n (suffix array as the locate kernels write it) + n (text bytes) + 5.25 n (the image) + room
+    }
+    DevBuf vals, seq_len, seq_start, text8, bad;
+    try {
+        pgx_device_image *dl = locate_image(h, d->device);
+        if (!dl->loc.n || dl->loc.n != n) throw Error(PGX_ERR_UNSUPPORTED, "no locate image");
+        const uint64_t first = 0, last = n - 1;
+        std::vector<uint64_t> off;
+        uint64_t nv = 0;
+        locate_core(h, dl, &first, &last, 1, 0, off, vals, nv);
+        if (nv != n) throw Error(PGX_ERR_UNSUPPORTED, "suffix array incomplete");
+        const uint64_t ml = h->ri.max_length;
+        seq_len.ensure(n_seq * 8); seq_start.ensure((n_seq + 1) * 8); bad.ensure(16);
+        HIPCHECK(hipMemset(seq_len.p, 0, n_seq * 8));
+        HIPCHECK(hipMemset(bad.p, 0, 16));
+        hipLaunchKernelGGL(pgx_lce_seqlen_kernel, dim3(grid_for(n_seq, 256)), dim3(256), 0, nullptr, vals.as<uint64_t>(), n_seq, ml, seq_len.as<unsigned long long>());
+        HIPCHECK(hipGetLastError());
+        std::vector<uint64_t> hl(n_seq), hs(n_seq + 1, 0);
+        HIPCHECK(hipMemcpy(hl.data(), seq_len.p, n_seq * 8, hipMemcpyDeviceToHost));
+        for (uint64_t q = 0; q < n_seq; q++) { if (hl[q] == 0) throw Error(PGX_ERR_UNSUPPORTED, "a sequence without an endmarker suffix"); hs[q + 1] = hs[q] + hl[q]; }
+        if (hs[n_seq] != n) throw Error(PGX_ERR_UNSUPPORTED, "sequence lengths do not add up to the BWT size");
+        HIPCHECK(hipMemcpy(seq_start.p, hs.data(), (n_seq + 1) * 8, hipMemcpyHostToDevice));
+        const uint64_t n_words = (n + 15) / 16 + 64, n_flag_words = n_words / 1024 + 2; // (64 words = two lines of padding behind the text, flagged)
+        text8.ensure(n);
+        d->lce_sa.ensure(n * 4 + 128); // (the kernel reads aligned windows of up to 20 entries from an interval's first entry on)
+        d->lce_text.ensure(n_words * 4);
+        d->lce_flags.ensure(n_flag_words * 4);
+        HIPCHECK(hipMemset(d->lce_flags.p, 0, n_flag_words * 4));
+        const uint64_t c1 = tot[0], c2 = c1 + tot[1], c3 = c2 + tot[2], c4 = c3 + tot[3], c5 = c4 + tot[4];
+        hipLaunchKernelGGL(pgx_lce_scatter_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 20)), dim3(256), 0, nullptr, vals.as<uint64_t>(), n, ml,
+                           seq_start.as<uint64_t>(), n_seq, c1, c2, c3, c4, c5, d->lce_sa.as<uint32_t>(), text8.as<uint8_t>(), bad.as<unsigned long long>());
+        HIPCHECK(hipGetLastError());
+        unsigned long long n_bad = 0;
+        HIPCHECK(hipMemcpy(&n_bad, bad.p, 8, hipMemcpyDeviceToHost));
+        if (n_bad) throw Error(PGX_ERR_UNSUPPORTED, "suffix array values outside the collection");
+        vals.release();
+        // both orientations of every sequence (pgx_lce_rc_check_kernel): a forward-only collection is searched stepwise, as the reference's arithmetic has it
+        if (n_seq & 1) throw Error(PGX_ERR_UNSUPPORTED, "odd number of sequences");
+        hipLaunchKernelGGL(pgx_lce_rc_check_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 20)), dim3(256), 0, nullptr, text8.as<uint8_t>(),
+                           seq_start.as<uint64_t>(), n_seq, n, bad.as<unsigned long long>());
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpy(&n_bad, bad.p, 8, hipMemcpyDeviceToHost));
+        if (n_bad) throw Error(PGX_ERR_UNSUPPORTED, "the collection does not hold every sequence next to its reverse complement");
+        hipLaunchKernelGGL(pgx_lce_pack_kernel, dim3((unsigned)std::min<uint64_t>((n_words + 255) / 256, 1u << 20)), dim3(256), 0, nullptr, text8.as<uint8_t>(), n, n_words,
+                           d->lce_text.as<uint32_t>(), d->lce_flags.as<uint32_t>());
+        HIPCHECK(hipGetLastError());
+        text8.release();
+        const bool with_lcp = knobs.lcp; // (PGX_FM_LCP=0: every occurrence is compared with the text, as before the table existed)
+        if (with_lcp) {
+            d->lce_lcp.ensure(n + 64); // (the kernel reads aligned windows of up to 20 entries)
+            hipLaunchKernelGGL(pgx_lce_lcp_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 20)), dim3(256), 0, nullptr, d->lce_sa.as<uint32_t>(),
+                               d->lce_text.as<uint32_t>(), d->lce_flags.as<uint32_t>(), n, d->lce_lcp.as<uint8_t>());
+            HIPCHECK(hipGetLastError());
+        }
+        HIPCHECK(hipDeviceSynchronize());
+        d->img.lce_lcp = with_lcp ? d->lce_lcp.as<uint8_t>() : nullptr;
+        d->img.lce_sa = d->lce_sa.as<uint32_t>();
+        d->img.lce_text = d->lce_text.as<uint32_t>();
+        d->img.lce_flags = d->lce_flags.as<uint32_t>();
+        d->img.lce_max = with_lcp ? PGX_LCE_MAX_OCC : 16; // (without the table of common prefixes every occurrence costs a trip)
+        if (knobs.has_lce_max) d->img.lce_max = knobs.lce_max;
+        d->lce_seq_start = seq_start; seq_start = DevBuf(); // (kept: text position -> sequence for pgx_batch_locate, 8 bytes per sequence)
+        d->lce_n_seq = n_seq;
+        d->img.refill_min = 12; // (chr22 scale, 1 / 3 / 6 / 10 / 16 / 24: main kernel 10.76 / 10.44 / 10.24 / 10.15 / 10.10 / 10.08 ms, step 13.16 / 12.87 / 12.62 / 12.59 / 12.56 / 12.65)
+        if (knobs.has_refill_min) d->img.refill_min = knobs.refill_min;
+        d->lce_state = 1;
+    } catch (...) { // (no LCE image: the search runs on the PAIRS image alone, as before)
+        (void)hipGetLastError();
+        d->lce_sa.release(); d->lce_text.release(); d->lce_flags.release(); d->lce_lcp.release(); d->lce_seq_start.release();
+        d->lce_n_seq = 0;
+        d->img.lce_sa = nullptr; d->img.lce_text = nullptr; d->img.lce_flags = nullptr; d->img.lce_lcp = nullptr;
+    }
+    vals.release(); seq_len.release(); seq_start.release(); text8.release(); bad.release();
+}
+
+// COMPAT count_encoded / LF_encoded on an encoded index without N: the reference mis-parses every block (quirk 3); the literal
+// image reproduces what it computes (pgx_runtime.hip literal_count says when)
+pgx_device_image *literal_image(pgx_index *h, int device) {
+    pgx_device_image *d = device_image(h, device);
+    std::lock_guard<std::mutex> lock(g_image_mutex);
+    if (d->has_lit) return d;
+    build_literal_image(h->ri, h->lit);
+    LitHostImage &m = h->lit;
+    upload(d->lit_bstart, m.bstart.data(), m.bstart.size() * 8);
+    upload(d->lit_cum, m.cum.data(), m.cum.size() * 8);
+    upload(d->lit_runs, m.runs.data(), m.runs.size() * 8);
+    upload(d->lit_roff, m.roff.data(), m.roff.size() * 4);
+    d->lit_tabs.ensure(512 * 4);
+    HIPCHECK(hipMemcpy(d->lit_tabs.p, m.code_of, 1024, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(d->lit_tabs.as<uint32_t>() + 256, m.cslot_of, 1024, hipMemcpyHostToDevice));
+    PgxLitImage &g = d->lit;
+    g.bstart = d->lit_bstart.as<uint64_t>(); g.cum = d->lit_cum.as<uint64_t>(); g.runs = d->lit_runs.as<uint64_t>();
+    g.roff = d->lit_roff.as<uint32_t>(); g.code_of = d->lit_tabs.as<uint32_t>(); g.cslot_of = d->lit_tabs.as<uint32_t>() + 256;
+    for (int i = 0; i < 8; i++) g.C[i] = m.C[i];
+    g.n = h->ri.sequence_size; g.n_blocks = m.bstart.size();
+    d->has_lit = true;
+    return d;
+}

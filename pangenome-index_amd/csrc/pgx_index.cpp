@@ -764,7 +764,7 @@ static uint32_t choose_image(const RiFile &ri, uint32_t mode_bits, const PgxCons
         return (force & PGX_MODE_IMAGE_DENSE) ? PGX_IMAGE_DENSE : PGX_IMAGE_DENSE2;
     }
     if ((force & PGX_MODE_IMAGE_RL) || !can) return PGX_IMAGE_RL;
-    // tiny BWTs: the 64-byte layout, staged in LDS by the kernels (cheapest decode; pgx_runtime.hip: 80 padded bytes per block)
+    // tiny BWTs: the 64-byte layout, staged in LDS by the kernels (cheapest decode; pgx_images.hip: 80 padded bytes per block)
     const uint64_t dense_blocks = (c.n >> 6) + 1;
     if (dense_blocks * 80 + 16 <= 48 * 1024) return PGX_IMAGE_DENSE;
     // the 64-byte layout while it stays resident in the 256 MB memory-side cache (cheapest decode: n = 64 M, 1 M reads: 3.1 ms
@@ -999,7 +999,7 @@ extern "C" int pgx_abi_version(void) { return PGX_ABI_VERSION; }
     catch (const std::bad_alloc &) { pgx::set_last_error("out of host memory"); return PGX_ERR_NOMEM; } \
     catch (const std::exception &e) { pgx::set_last_error(e.what()); return PGX_ERR_FORMAT; }
 
-void pgx_release_device_images(pgx_index *h); // pgx_runtime.hip
+void pgx_release_device_images(pgx_index *h); // pgx_images.hip
 
 static pgx_index *open_impl(const uint8_t *ri, uint64_t ri_n, const uint8_t *tags, uint64_t tags_n, uint32_t tags_format, uint32_t mode) {
     if ((mode & PGX_MODE_MASK) > PGX_MODE_STRICT || (mode & ~(PGX_MODE_MASK | PGX_MODE_IMAGE_RL | PGX_MODE_IMAGE_DENSE | PGX_MODE_IMAGE_DENSE2 | PGX_MODE_IMAGE_PAIRS | PGX_MODE_IMAGE_WIDE)))

@@ -92,7 +92,7 @@ __device__ __forceinline__ uint32_t pgx_tbucket_le(const uint4 &h0, const uint4 
 // Counts that live on the device: every kernel of the tag stage takes its element count as a value (an upper bound: the
 // capacity its buffers were sized for) AND, optionally, a device pointer to the actual count, loops over its elements with a
 // grid stride, and returns at once when the stage's abort flag is set -- so the whole stage can be enqueued without the host
-// knowing any count (pgx_runtime.hip "speculative sizing"); with a NULL pointer and an exact value it is the plain launch.
+// knowing any count (pgx_batch.hip "speculative sizing"); with a NULL pointer and an exact value it is the plain launch.
 #define PGX_DEV_COUNT(n, n_dev) ((n_dev) ? ((*(n_dev)) < (n) ? (*(n_dev)) : (n)) : (n))
 #define PGX_ABORTED(abort) ((abort) && *(abort))
 

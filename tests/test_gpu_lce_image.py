@@ -1,4 +1,4 @@
-"""The LCE image as the device builds it (pgx_runtime.hip ensure_lce: pgx_lce_scatter / pack / lcp kernels; pgx_image.h "LCE image") against the same arrays made
+"""The LCE image as the device builds it (pgx_images.hip ensure_lce: pgx_lce_scatter / pack / lcp kernels; pgx_image.h "LCE image") against the same arrays made
 on the CPU from the oracle's suffix array and the text file: suffix array in text coordinates, text at two bits per symbol, line flags, common prefixes of
 neighbouring suffixes -- bit for bit (what find_all_mems' forward stages, algorithm.hpp:676-700, are answered from on the text path)."""
 import os

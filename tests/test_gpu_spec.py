@@ -1,4 +1,4 @@
-"""Speculative sizing of pgx_batch_run (pgx_runtime.hip): a run whose predecessor on the same batch had the same shape takes its
+"""Speculative sizing of pgx_batch_run (pgx_batch.hip): a run whose predecessor on the same batch had the same shape takes its
 buffer sizes from that run, keeps every count on the device and synchronises once at the end; when a capacity turns out too
 small the run is repeated with exact sizes.  Either way the results are those of the oracle."""
 import os
