@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PGX_ABI_VERSION 6 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS */
+#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants */
 
 typedef enum {
     PGX_OK = 0,
@@ -313,7 +313,7 @@ typedef struct {
     float ms_total;       /* first launch -> last launch, device time */
     uint32_t find_mems_launches;
     uint32_t heavy_reads; /* reads whose rest went through the heavy-read kernel (filled by every run, timed or not) */
-    uint32_t pairs_reads; /* != 0: the run used the two-step PAIRS kernel (2: with the reads packed in LDS; 3: and cooperative line fetches) */
+    uint32_t pairs_reads; /* != 0: the run used the two-step PAIRS kernel (2: with the reads packed in LDS; 3: and cooperative line fetches; 4: packed reads and the LCE image; `kernels` names the instance) */
     uint32_t pairs_other_steps; /* extensions the PAIRS kernel took through the image it accompanies: its own block held \n or N, or the interval was wider
                                  * than two blocks (until ABI 3's last revision: redo_reads, reads handed on to the dense2 kernel) */
     /* the first launch of the find_mems stage alone (the PAIRS kernel when pairs_reads, else pgx_find_mems_kernel): ms_find_mems
@@ -332,7 +332,32 @@ typedef struct {
      * event to the first find_mems launch); with pgx_batch_upload_packed the unpack pass and the listed reads' bytes (inside the upload) plus
      * that scan.  0 for a run that found everything in place. */
     float ms_per_upload;
+    /* which kernels of the find_mems stage the run launched (PGX_KERNELS_*; filled by every run, timed or not) */
+    uint32_t kernels;
 } pgx_timing;
+
+/* pgx_timing.kernels.  pgx_find_mems_kernel is instantiated per (image staged in LDS, image kind, 32-bit interval state, seeded),
+ * pgx_find_mems_pairs_kernel per (64-bit form, reads packed in LDS, cooperative line fetches, blocks every 64 positions, forward stages
+ * through the LCE image); a run reports the instance of each it launched. */
+#define PGX_KERNELS_FM 0x1u              /* pgx_find_mems_kernel was launched (over every read, or over the reads the pairs kernel skips); its instance: */
+#define PGX_KERNELS_FM_SEEDED 0x2u
+#define PGX_KERNELS_FM_NARROW 0x4u       /*   32-bit interval state */
+#define PGX_KERNELS_FM_KIND_SHIFT 3      /*   two bits: 0 run-length image, 1 dense, 2 dense2, 3 dense2 in its 64-bit form */
+#define PGX_KERNELS_FM_LDS 0x20u         /*   image staged in LDS */
+#define PGX_KERNELS_FM_REDO 0x40u        /* a chunk was repeated with the 64-bit instance of the same kernel (PGX_KERNELS_FM_NARROW cleared) */
+#define PGX_KERNELS_PAIRS 0x100u         /* pgx_find_mems_pairs_kernel was launched; its instance: */
+#define PGX_KERNELS_PAIRS_S64 0x200u     /*   PAIRS blocks every 64 positions (else every 96) */
+#define PGX_KERNELS_PAIRS_COOP 0x400u
+#define PGX_KERNELS_PAIRS_PACKED 0x800u
+#define PGX_KERNELS_PAIRS_WIDE 0x1000u
+#define PGX_KERNELS_PAIRS_LCE 0x2000u
+#define PGX_KERNELS_SIDE 0x10000u        /* the pgx_find_mems_kernel launch on the second stream, next to the pairs kernel */
+#define PGX_KERNELS_HEAVY 0x20000u       /* pgx_find_mems_heavy_kernel was launched (pgx_timing.heavy_reads: over how many reads) */
+#define PGX_KERNELS_FM_MASK 0x3Fu
+#define PGX_KERNELS_PAIRS_MASK 0x3F00u
+/* Every instance the runtime can launch, in the encoding above (PGX_KERNELS_FM | ... or PGX_KERNELS_PAIRS | ...): up to `cap` of them
+ * into out (may be NULL), returns their number.  Host only. */
+uint32_t pgx_kernel_variants(uint32_t *out, uint32_t cap);
 
 /* Upload reads (read i = reads[offsets[i] .. offsets[i+1]); the `std::getline` lines of
  * find_mems.cpp:96-98, empty lines already skipped by the caller) to `device`. */

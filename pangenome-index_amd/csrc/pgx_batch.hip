@@ -417,8 +417,10 @@ static RunKnobs read_run_knobs() {
 }
 
 // The variants of pgx_find_mems_kernel the runtime launches (instantiated in pgx_kernels.hip), each named here and nowhere else.
-// Only the 64-byte dense image is ever staged in LDS, the run-length image has neither a 32-bit form nor seeds, the wide dense2 image (kind 3) no 32-bit form.
-static const void *find_mems_variant(bool in_lds, uint32_t kind, bool narrow, bool seeded) {
+// Only images of up to 48 KiB are staged in LDS, and only the run-length and the 64-byte dense image are (pgx_images.hip device_image); the run-length image has
+// neither a 32-bit form nor seeds, the wide dense2 image (kind 3) no 32-bit form.
+// (nullptr: no such instance)
+static const void *find_mems_entry(bool in_lds, uint32_t kind, bool narrow, bool seeded) {
     using K = const void *;
     static const K tab[2][4][2][2] = { // [image in LDS][image kind][32-bit state][seeded]
         {{{(K)pgx_find_mems_kernel<false, 0, false, false>, nullptr}, {nullptr, nullptr}},
@@ -432,15 +434,26 @@ static const void *find_mems_variant(bool in_lds, uint32_t kind, bool narrow, bo
           {(K)pgx_find_mems_kernel<true, 1, true, false>, (K)pgx_find_mems_kernel<true, 1, true, true>}},
          {{nullptr, nullptr}, {nullptr, nullptr}},
          {{nullptr, nullptr}, {nullptr, nullptr}}}};
+    return kind < 4 ? tab[in_lds][kind][narrow][seeded] : nullptr;
+}
+
+// pgx_timing.kernels: the coordinates of an instance in the table above
+static uint32_t find_mems_bits(bool in_lds, uint32_t kind, bool narrow, bool seeded) {
+    return PGX_KERNELS_FM | (seeded ? PGX_KERNELS_FM_SEEDED : 0u) | (narrow ? PGX_KERNELS_FM_NARROW : 0u) | (kind << PGX_KERNELS_FM_KIND_SHIFT) | (in_lds ? PGX_KERNELS_FM_LDS : 0u);
+}
+
+static const void *find_mems_variant(bool in_lds, uint32_t kind, bool narrow, bool seeded, uint32_t &bits) {
     if (kind == 0) seeded = false; // (no stage of the run-length kernel looks at a seed table)
-    const K f = kind < 4 ? tab[in_lds][kind][narrow][seeded] : nullptr;
+    const void *f = find_mems_entry(in_lds, kind, narrow, seeded);
     if (!f) throw Error(PGX_ERR_UNSUPPORTED, "pgx_batch_run: no find_mems kernel for this image");
+    bits = find_mems_bits(in_lds, kind, narrow, seeded);
     return f;
 }
 
 // The same for pgx_find_mems_pairs_kernel (always seeded).  The cooperative line fetches and the LCE path exist only with the packed reads,
 // the LCE path only for narrow images without the cooperative fetches.
-static const void *find_mems_pairs_variant(bool wide, bool packed, bool coop, bool s64, bool lce) {
+// (nullptr: no such instance)
+static const void *find_mems_pairs_entry(bool wide, bool packed, bool coop, bool s64, bool lce) {
     using K = const void *;
     static const K plain[2][2] = { // [wide][stride 64]
         {(K)pgx_find_mems_pairs_kernel<true, false, false, false, false, false>, (K)pgx_find_mems_pairs_kernel<true, false, false, false, true, false>},
@@ -451,15 +464,38 @@ static const void *find_mems_pairs_variant(bool wide, bool packed, bool coop, bo
         {{(K)pgx_find_mems_pairs_kernel<true, true, true, false, false, false>, (K)pgx_find_mems_pairs_kernel<true, true, true, false, true, false>},
          {(K)pgx_find_mems_pairs_kernel<true, true, true, true, false, false>, (K)pgx_find_mems_pairs_kernel<true, true, true, true, true, false>}}};
     static const K with_lce[2] = {(K)pgx_find_mems_pairs_kernel<true, false, true, false, false, true>, (K)pgx_find_mems_pairs_kernel<true, false, true, false, true, true>}; // [stride 64]
-    if (lce) {
-        if (wide || !packed || coop) throw Error(PGX_ERR_UNSUPPORTED, "pgx_batch_run: no LCE pairs kernel for this image");
-        return with_lce[s64];
-    }
-    if (!packed) {
-        if (coop) throw Error(PGX_ERR_UNSUPPORTED, "pgx_batch_run: no cooperative pairs kernel without the packed reads");
-        return plain[wide][s64];
-    }
+    if (lce) return (wide || !packed || coop) ? nullptr : with_lce[s64];
+    if (!packed) return coop ? nullptr : plain[wide][s64];
     return pack[wide][coop][s64];
+}
+
+static uint32_t find_mems_pairs_bits(bool wide, bool packed, bool coop, bool s64, bool lce) {
+    return PGX_KERNELS_PAIRS | (s64 ? PGX_KERNELS_PAIRS_S64 : 0u) | (coop ? PGX_KERNELS_PAIRS_COOP : 0u) | (packed ? PGX_KERNELS_PAIRS_PACKED : 0u) |
+           (wide ? PGX_KERNELS_PAIRS_WIDE : 0u) | (lce ? PGX_KERNELS_PAIRS_LCE : 0u);
+}
+
+static const void *find_mems_pairs_variant(bool wide, bool packed, bool coop, bool s64, bool lce, uint32_t &bits) {
+    const void *f = find_mems_pairs_entry(wide, packed, coop, s64, lce);
+    if (!f && lce) throw Error(PGX_ERR_UNSUPPORTED, "pgx_batch_run: no LCE pairs kernel for this image");
+    if (!f) throw Error(PGX_ERR_UNSUPPORTED, "pgx_batch_run: no cooperative pairs kernel without the packed reads");
+    bits = find_mems_pairs_bits(wide, packed, coop, s64, lce);
+    return f;
+}
+
+// every instance of the two tables, as pgx_timing.kernels names it (tests: what "all variants" means comes from here)
+extern "C" uint32_t pgx_kernel_variants(uint32_t *out, uint32_t cap) {
+    uint32_t n = 0;
+    auto put = [&](uint32_t bits) { if (out && n < cap) out[n] = bits; n++; };
+    for (int c = 0; c < 32; c++) {
+        const bool in_lds = c & 16, narrow = c & 2, seeded = c & 1;
+        const uint32_t kind = (c >> 2) & 3;
+        if (find_mems_entry(in_lds, kind, narrow, seeded)) put(find_mems_bits(in_lds, kind, narrow, seeded));
+    }
+    for (int c = 0; c < 32; c++) {
+        const bool wide = c & 16, packed = c & 8, coop = c & 4, s64 = c & 2, lce = c & 1;
+        if (find_mems_pairs_entry(wide, packed, coop, s64, lce)) put(find_mems_pairs_bits(wide, packed, coop, s64, lce));
+    }
+    return n;
 }
 
 // what a run carries from stage to stage
@@ -475,6 +511,7 @@ struct RunCtx {
     bool spec = false, arena_on = false;
     uint64_t cm_cap = 0; // capacity of the MEM array of a speculative pass
     const void *kfn = nullptr, *kfn_wide = nullptr, *kfn_pairs = nullptr; // the kernel of the first attempt, its 64-bit form, the pairs kernel (or none)
+    uint32_t kfn_bits = 0, kfn_pairs_bits = 0; // their instances, as pgx_timing.kernels names them
     size_t pairs_lds = 0;
     int cus = 0;
     // gathered over the pass
@@ -574,16 +611,16 @@ static void choose_kernels(RunCtx &r) {
     const PgxDevImage &img = r.img;
     const bool in_lds = b->dimg->lds_bytes != 0;
     const bool seeded = img.seed_k != 0 && r.min_len >= img.seed_k; // (no stage of a shorter search has room for a seed)
-    r.kfn = r.kfn_wide = find_mems_variant(in_lds, img.dense, false, seeded);
+    r.kfn = r.kfn_wide = find_mems_variant(in_lds, img.dense, false, seeded, r.kfn_bits);
     // 32-bit interval state for dense images of BWTs shorter than 2^30 (PGX_FM_NARROW=0 switches it off)
     bool c_fits = true; // C[] comes straight from the file: a (corrupt) value beyond 2^32 must not be truncated by the 32-bit state
     for (int i = 0; i < 8; i++) c_fits = c_fits && !(b->h->img.consts.C[i] >> 32);
-    if (img.dense && img.dense != 3 && img.n < (1ull << 30) && c_fits && r.k.narrow) r.kfn = find_mems_variant(in_lds, img.dense, true, seeded);
+    if (img.dense && img.dense != 3 && img.n < (1ull << 30) && c_fits && r.k.narrow) r.kfn = find_mems_variant(in_lds, img.dense, true, seeded, r.kfn_bits);
     // two extensions per cache line where the index has a PAIRS image (PGX_FM_PAIRS=0: the dense2 kernel alone)
     // (only behind the seed table: the wide intervals at the start of an unseeded stage always have special positions between their ends)
     r.kfn_pairs = nullptr;
     if (img.pairs && seeded && !(r.n >> 32) && b->read_bytes < (1ull << 35) && r.k.pairs)
-        r.kfn_pairs = find_mems_pairs_variant(img.wide != 0, false, false, img.pairs_stride == PGX_PAIRS_STRIDE64, false);
+        r.kfn_pairs = find_mems_pairs_variant(img.wide != 0, false, false, img.pairs_stride == PGX_PAIRS_STRIDE64, false, r.kfn_pairs_bits);
     r.pairs_lds = img.wide ? (size_t)img.n_sbp * 192 : 0; // (superblock bases of the wide form, behind the other dynamic LDS)
     HIPCHECK(hipDeviceGetAttribute(&r.cus, hipDeviceAttributeMultiprocessorCount, b->device));
 }
@@ -640,6 +677,7 @@ static void launch_side(RunCtx &r, FmArgs &a, const void *kf, unsigned grid) {
     const uint64_t cus = (uint64_t)r.cus;
     const unsigned side_wgs = (unsigned)std::min<uint64_t>(4 * cus, std::max<uint64_t>(cus, b->side_reads_est / (2ull * PGX_FM_THREADS) + 1));
     HIPCHECK(hipLaunchKernel(kf, dim3(std::min<unsigned>(grid, side_wgs)), dim3(PGX_FM_THREADS), sargs, b->dimg->lds_bytes, b->side));
+    b->timing.kernels |= r.kfn_bits | PGX_KERNELS_SIDE | (kf != r.kfn ? PGX_KERNELS_FM_REDO : 0u);
     HIPCHECK(hipEventRecord(b->ev_side[1], b->side));
 }
 
@@ -649,6 +687,7 @@ static void launch_pairs(RunCtx &r, FmArgs &a, const uint8_t *skip, uint64_t cn,
     pgx_batch *b = r.b;
     const PgxDevImage &img = r.img;
     const void *kp = r.kfn_pairs;
+    uint32_t kp_bits = r.kfn_pairs_bits;
     size_t plds = r.pairs_lds;
     const uint32_t *a_packed = nullptr;
     uint32_t a_pkw = 0;
@@ -659,7 +698,7 @@ static void launch_pairs(RunCtx &r, FmArgs &a, const uint8_t *skip, uint64_t cn,
         const bool coop = r.k.coop >= 0 ? r.k.coop != 0 : b->h->img.pairs.size() > (3ull << 30);
         // forward stages over narrow intervals through the suffix array and the text (pgx_image.h "LCE image"; min_occ <= 1: the longest match decides)
         const bool lce = img.lce_sa && !coop && !img.wide && r.min_occ <= 1 && r.k.lce;
-        kp = find_mems_pairs_variant(img.wide != 0, true, coop, img.pairs_stride == PGX_PAIRS_STRIDE64, lce);
+        kp = find_mems_pairs_variant(img.wide != 0, true, coop, img.pairs_stride == PGX_PAIRS_STRIDE64, lce, kp_bits);
         // per thread of the LCE kernel: a seed entry, a suffix array entry, sixteen common prefixes from any byte on (five dwords)
         const size_t lce_lds = lce ? (size_t)PGX_FM_THREADS * (16 + 4 + 20) : 0;
         a_packed = b->packed.as<uint32_t>();
@@ -671,6 +710,7 @@ static void launch_pairs(RunCtx &r, FmArgs &a, const uint8_t *skip, uint64_t cn,
     void *pargs[] = {&a.img, &a.reads, &a.off, &a.n, &a.min_len, &a.min_occ, &a.slot_off, &a.slots, &a.cnt, &a.next, &a.cur, &a.first, &a.base,
                      &a.hext, &a.hcap, &a.hlist, &a.hcount, &skip, &a_packed, &a_pkw, &a.ovf, &a.ovf_cap};
     HIPCHECK(hipLaunchKernel(kp, dim3(grid), dim3(PGX_FM_THREADS), pargs, plds, r.s));
+    b->timing.kernels |= kp_bits;
 }
 
 // arena for the fifth and later MEMs of a chunk's reads, in slots (0 = worst-case layout): sized from the last run of this batch, or eight slots per read
@@ -744,10 +784,12 @@ static uint64_t find_mems_chunk(RunCtx &r, size_t ci, uint64_t &ovf_cap) {
                             &a.hext, &a.hcap, &a.hlist, &a.hcount, &a_rlist, &a_rcount, &a.ovf, &a.ovf_cap};
             if (ci == 0 && attempt == 0) { record(b, 9, s); r.fresh_mark = true; }
             HIPCHECK(hipLaunchKernel(kf, dim3(grid), dim3(PGX_FM_THREADS), args, b->dimg->lds_bytes, s)); // one of the variants
+            b->timing.kernels |= r.kfn_bits | (kf != r.kfn ? PGX_KERNELS_FM_REDO : 0u);
         }
         record(b, 8, s);
         if (side_running) HIPCHECK(hipStreamWaitEvent(s, b->ev_side[1], 0)); // the other stream's reads are done (they may have queued heavy reads)
         if (heavy_ext) { // the rest of reads that spent heavy_ext extensions (usually none: the launch then costs a few microseconds)
+            b->timing.kernels |= PGX_KERNELS_HEAVY;
             if (b->dimg->lds_bytes)
                 hipLaunchKernelGGL(pgx_find_mems_heavy_kernel<true>, dim3(PGX_FM_HEAVY_GRID), dim3(256), b->dimg->lds_bytes, s, r.img, a.reads, a.off,
                                    r.min_len, r.min_occ, a.slot_off, c.slot_base, a.slots, a.cnt, r.ctr, (const pgx_heavy_item *)a.hlist,

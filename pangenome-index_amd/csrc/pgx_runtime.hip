@@ -94,6 +94,8 @@ void scan_excl(int mode, const void *in, uint64_t n, uint64_t min_len, uint64_t 
         if (tmp.scan_epoch == 0 || tmp.scan_epoch >= 0x3FFFFu) {
             HIPCHECK(hipMemsetAsync(tmp.p, 0, tmp.cap, s));
             tmp.scan_epoch = 0;
+            // tests: PGX_SCAN_EPOCH0 = the epoch a cleared buffer starts from (below the last one), so that a few scans reach the wrap
+            if (const char *e = std::getenv("PGX_SCAN_EPOCH0")) tmp.scan_epoch = (uint32_t)std::min<unsigned long>(std::strtoul(e, nullptr, 0), 0x3FFFEul);
         }
         tmp.scan_epoch++;
         unsigned long long *st = tmp.as<unsigned long long>();

@@ -77,8 +77,23 @@ class Timing(C.Structure):
         ("find_mems_launches", u32), ("heavy_reads", u32), ("pairs_reads", u32), ("pairs_other_steps", u32),
         ("ms_find_mems_main", C.c_float), ("seed_depth", u32),
         ("main_lines", u64), ("main_seed_loads", u64), ("other_lines", u64), ("other_seed_loads", u64), ("two_step_trips", u64),
-        ("ms_per_upload", C.c_float),
+        ("ms_per_upload", C.c_float), ("kernels", u32),
     ]
+
+
+# pgx_timing.kernels (include/pgx.h PGX_KERNELS_*): the instances of pgx_find_mems_kernel / pgx_find_mems_pairs_kernel a run launched
+KERNELS_FM, KERNELS_FM_SEEDED, KERNELS_FM_NARROW, KERNELS_FM_KIND_SHIFT, KERNELS_FM_LDS, KERNELS_FM_REDO = 0x1, 0x2, 0x4, 3, 0x20, 0x40
+KERNELS_PAIRS, KERNELS_PAIRS_S64, KERNELS_PAIRS_COOP, KERNELS_PAIRS_PACKED, KERNELS_PAIRS_WIDE, KERNELS_PAIRS_LCE = 0x100, 0x200, 0x400, 0x800, 0x1000, 0x2000
+KERNELS_SIDE, KERNELS_HEAVY = 0x10000, 0x20000
+KERNELS_FM_MASK, KERNELS_PAIRS_MASK = 0x3F, 0x3F00
+
+
+def kernel_variants():
+    """pgx_kernel_variants: every instance of the two kernels the runtime can launch, in the encoding of pgx_timing.kernels (host only)"""
+    n = lib().pgx_kernel_variants(None, 0)
+    out = np.zeros(n, dtype=np.uint32)
+    assert lib().pgx_kernel_variants(out.ctypes.data, n) == n
+    return [int(v) for v in out]
 
 
 def _u64_array(ptr, n):
@@ -111,6 +126,8 @@ def lib():
     L = C.CDLL(LIB_PATH)
     L.pgx_last_error.restype = C.c_char_p
     L.pgx_abi_version.restype = C.c_int
+    L.pgx_kernel_variants.argtypes = [p, u32]
+    L.pgx_kernel_variants.restype = u32
     L.pgx_index_open.argtypes = [C.c_char_p, C.c_char_p, u32, u32, C.POINTER(p)]
     L.pgx_index_info_get.argtypes = [p, C.POINTER(IndexInfo)]
     L.pgx_index_close.argtypes = [p]

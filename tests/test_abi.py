@@ -31,6 +31,20 @@ def test_header_symbols_exported(built):
     assert L.pgx_abi_version() == G.header_abi_version()
 
 
+def test_kernel_variants_are_listed(built):
+    """pgx_kernel_variants (host only; tests/test_gpu_variants.py takes "every instance" from it): distinct words, one kernel each, inside the
+    masks pgx_timing.kernels uses, and the constants of the binding are the header's"""
+    src = open(os.path.join(ROOT, "include", "pgx.h")).read()
+    for name, value in re.findall(r"^#define\s+PGX_(KERNELS_[A-Z0-9_]+)\s+(0x[0-9A-Fa-f]+|\d+)u?\b", src, re.M):
+        assert getattr(P, name) == int(value, 0), name
+    v = P.kernel_variants()
+    assert len(set(v)) == len(v) > 0
+    for w in v:
+        assert bool(w & P.KERNELS_FM) != bool(w & P.KERNELS_PAIRS)
+        assert not (w & ~((P.KERNELS_FM_MASK & ~P.KERNELS_FM_REDO) if w & P.KERNELS_FM else P.KERNELS_PAIRS_MASK)), hex(w)
+    assert ctypes.sizeof(P.Timing) == 96 and P.Timing.kernels.offset == 92  # appended behind ms_per_upload: the fields before it stay where they were
+
+
 def test_driver_entry_build(built):
     """__graft_entry__.build() is what the driver runs on the CPU box every round: it must
     succeed at HEAD (a header bump once left a stale literal in it)."""

@@ -18,7 +18,7 @@ def test_symbols_and_abi_version(built):
     L = ctypes.CDLL(P.LIB_PATH)
     for n in ("pgx_batch_locate", "pgx_batch_locations", "pgx_batch_device_locations"):
         assert hasattr(L, n), n
-    assert P.lib().pgx_abi_version() == 6
+    assert P.lib().pgx_abi_version() == 7
     assert ctypes.sizeof(P.Locations) == 56  # pgx_locations: 3 x u64, 2 x u32, 2 pointers, 2 floats
 
 
