@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants */
+#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset) */
 
 typedef enum {
     PGX_OK = 0,
@@ -455,8 +455,21 @@ void pgx_batch_free(pgx_batch *b);
  * indexes) the values are a gather from it; elsewhere the sample chains of pgx_locate_batch are walked.  PGX_LOCATE_CHAINS (tests)
  * forces the chains.  The values of a batch are produced in passes over consecutive MEMs whose intermediate buffer stays within
  * PGX_LOCATE_BUDGET_MB (environment; default a quarter of free device memory); results never depend on it.
- * PGX_ERR_ARG without a completed run. */
+ * PGX_ERR_ARG without a completed run.
+ *
+ * PGX_LOCATE_SEQ_SETS (alone or with PGX_LOCATE_CHAINS; with PGX_LOCATE_SEQ_IDS or PGX_LOCATE_UNIQUE: PGX_ERR_ARG): the sequences that hold
+ * each MEM as a bitmap, the input of set AND / OR across the MEMs of a read.  With n_seq = pgx_index_info.n_sequences and
+ * W = ceil(n_seq / 64), values holds n_mems x W words, MEM m's set is values[m * W .. (m + 1) * W), loc_offsets[m] = m * W and
+ * n_values = n_mems * W.  Bit s & 63 of word s >> 6 is set iff s is among the values of
+ * pgx_locate_batch(first = bwt_start, last = bwt_start + size - 1, PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE) for that MEM; bits at or beyond
+ * n_seq are zero.  A MEM that is not located (the rules above) has an all-zero set and counts in n_not_located.  Built without writing or
+ * sorting the occurrences: every occurrence sets its bit.  PGX_ERR_UNSUPPORTED where W > 64 (more than 4096 sequences: a bitmap per MEM
+ * then costs more than the ids it replaces).  pgx_locate_batch does not take the flag.
+ * Where W <= 64, PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE is served from the same sets (built in passes within the budget, expanded to
+ * ascending ids) in place of the segmented sort: the result is the same byte for byte, and set_words tells that it happened.
+ * PGX_LOCATE_SETS=0 (environment, read per call) forces the sort.  PGX_LOCATE_UNIQUE alone always sorts. */
 #define PGX_LOCATE_CHAINS 4u
+#define PGX_LOCATE_SEQ_SETS 8u
 typedef struct {
     uint64_t n_mems;
     uint64_t n_values;
@@ -466,7 +479,7 @@ typedef struct {
     const uint64_t *loc_offsets;  /* n_mems + 1; values of MEM m = values[loc_offsets[m] .. [m + 1]) */
     const uint64_t *values;       /* n_values */
     float ms_locate;              /* device time of the call when the last run had PGX_RUN_TIMING, else 0 */
-    float reserved;
+    uint32_t set_words;           /* W when the call built sequence sets (PGX_LOCATE_SEQ_SETS, or unique sequence ids served from them), else 0 */
 } pgx_locations;
 pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t max_occ, void *stream);
 /* Host copy of the last locate (buffers owned by the batch) / the same as device pointers.  Valid until the next run, upload, locate or

@@ -1097,12 +1097,20 @@ static uint64_t locate_budget_values() {
     return std::max<uint64_t>(bytes / 8, 1);
 }
 
+// PGX_LOCATE_SETS=0 (read per call): PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE by the segmented sort even where the sequence sets would serve it
+static bool locate_sets_enabled() {
+    const char *e = std::getenv("PGX_LOCATE_SETS");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+
 extern "C" pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t max_occ, void *stream) {
     PGX_GUARD_BEGIN
     RoctxRange range("pgx_batch_locate");
+    if ((flags & PGX_LOCATE_SEQ_SETS) && (flags & (PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE))) // (a contradiction in the call itself: said with or without a device)
+        throw Error(PGX_ERR_ARG, "pgx_batch_locate: PGX_LOCATE_SEQ_SETS goes with PGX_LOCATE_CHAINS alone");
     checked_device_count();
     if (!b) throw Error(PGX_ERR_ARG, "pgx_batch_locate: null batch");
-    if (flags & ~(PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE | PGX_LOCATE_CHAINS)) throw Error(PGX_ERR_ARG, "pgx_batch_locate: unknown flag");
+    if (flags & ~(PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE | PGX_LOCATE_CHAINS | PGX_LOCATE_SEQ_SETS)) throw Error(PGX_ERR_ARG, "pgx_batch_locate: unknown flag");
     if (!b->ran) throw Error(PGX_ERR_ARG, "pgx_batch_locate: batch has not been run");
     LocWork &w = b->lw;
     w.valid = false;
@@ -1111,7 +1119,17 @@ extern "C" pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t ma
     pgx_device_image *d = locate_image(b->h, b->device);
     hipStream_t s = stream ? (hipStream_t)stream : b->own;
     const uint64_t n = b->n_mems, bwt_n = d->loc.n;
-    const bool seq_ids = (flags & PGX_LOCATE_SEQ_IDS) != 0, uniq = (flags & PGX_LOCATE_UNIQUE) != 0;
+    const bool sets_form = (flags & PGX_LOCATE_SEQ_SETS) != 0;
+    const bool seq_ids = sets_form || (flags & PGX_LOCATE_SEQ_IDS) != 0, uniq = (flags & PGX_LOCATE_UNIQUE) != 0;
+    // sequence sets: the result itself (PGX_LOCATE_SEQ_SETS), or what the sorted unique sequence ids are expanded from (routed) in place of the sort
+    const uint64_t n_seq = b->h->ri.C.size() > 1 ? b->h->ri.C[1] - b->h->ri.C[0] : 0;
+    const uint64_t W = (n_seq + 63) / 64;
+    const bool sets_fit = W >= 1 && W <= PGX_ML_SET_WORDS_MAX;
+    if (sets_form && !sets_fit)
+        throw Error(PGX_ERR_UNSUPPORTED, "pgx_batch_locate: PGX_LOCATE_SEQ_SETS serves at most " + std::to_string(64 * PGX_ML_SET_WORDS_MAX) + " sequences, the index has " +
+                                             std::to_string(n_seq));
+    const bool routed = !sets_form && seq_ids && uniq && sets_fit && locate_sets_enabled();
+    const bool build_sets = sets_form || routed, sort_uniq = uniq && !routed;
     // the resident suffix array: the LCE image in text coordinates and its sequence starts (built from this very locate image's chains)
     const bool resident = !(flags & PGX_LOCATE_CHAINS) && d->lce_state == 1 && d->img.lce_sa && d->lce_seq_start.p && d->lce_n_seq && d->img.n == bwt_n;
     const bool timed = b->timed;
@@ -1137,22 +1155,43 @@ extern "C" pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t ma
     const uint64_t *voff = w.voff.as<uint64_t>();
     // 2. passes over consecutive MEMs whose values fit the budget (one pass unless the batch exceeds it)
     const uint64_t budget = locate_budget_values();
-    if (!uniq) w.vals.ensure((V ? V : 1) * 8); // (the values are written in place: no intermediate buffer)
+    if (sets_form) { // the result: n x W words, cleared once; loc_offsets[m] = m * W
+        w.vals.ensure((n ? n * W : 1) * 8); w.uoff.ensure((n + 1) * 8);
+        if (n) HIPCHECK(hipMemsetAsync(w.vals.p, 0, n * W * 8, s));
+        hipLaunchKernelGGL(pgx_ml_stride_kernel, dim3(grid_for(n + 1, 256)), dim3(256), 0, s, w.uoff.as<uint64_t>(), n + 1, W);
+        HIPCHECK(hipGetLastError());
+    } else if (!uniq) w.vals.ensure((V ? V : 1) * 8); // (the values are written in place: no intermediate buffer)
     else { w.ucount.ensure((n ? n : 1) * 8); w.uoff.ensure((n + 1) * 8); }
+    // the values of a pass need a buffer unless they are written in place or go straight from the resident suffix array into the sets
+    const bool value_buffer = sort_uniq || (build_sets && !resident);
+    const uint64_t set_mems = std::max<uint64_t>(budget / (W ? W : 1), 1); // MEMs whose sets fit the budget (routed: the set array is intermediate too)
     uint64_t U = 0; // unique values of the passes so far
     for (uint64_t m0 = 0, o0 = 0; m0 < n;) {
         uint64_t m1 = n, o1 = V;
-        if (V - o0 > budget) {
-            hipLaunchKernelGGL(pgx_ml_cut_kernel, dim3(1), dim3(64), 0, s, voff, n, m0, budget, reinterpret_cast<uint64_t *>(ctr + 6));
+        const bool by_values = !(build_sets && resident) && V - o0 > budget;
+        const uint64_t m_lim = routed && n - m0 > set_mems ? m0 + set_mems : n;
+        if (by_values || m_lim < n) {
+            hipLaunchKernelGGL(pgx_ml_cut_kernel, dim3(1), dim3(64), 0, s, voff, m_lim, m0, by_values ? budget : V, reinterpret_cast<uint64_t *>(ctr + 6));
             HIPCHECK(hipGetLastError());
             uint64_t c[2];
             read_scalars(c, ctr + 6, 16, s);
             m1 = c[0]; o1 = c[1];
         }
         const uint64_t np = m1 - m0, nv = o1 - o0;
-        if (uniq) w.gbuf.ensure((nv ? nv : 1) * 8);
-        uint64_t *dst = uniq ? w.gbuf.as<uint64_t>() : w.vals.as<uint64_t>() + o0; // value o of the batch goes to dst[o - o0]
-        if (nv && resident) {
+        if (value_buffer) w.gbuf.ensure((nv ? nv : 1) * 8);
+        uint64_t *dst = value_buffer ? w.gbuf.as<uint64_t>() : w.vals.as<uint64_t>() + o0; // value o of the batch goes to dst[o - o0]
+        unsigned long long *sets = nullptr; // the pass's sets: MEM m at sets[(m - m0) * W ..)
+        if (sets_form) sets = w.vals.as<unsigned long long>() + m0 * W;
+        else if (routed) {
+            w.sets.ensure(np * W * 8);
+            sets = w.sets.as<unsigned long long>();
+            HIPCHECK(hipMemsetAsync(sets, 0, np * W * 8, s));
+        }
+        if (nv && resident && build_sets) {
+            hipLaunchKernelGGL(pgx_ml_sets_kernel, dim3(grid_for(nv, PGX_ML_SPAN)), dim3(256), 0, s, (const pgx_mem *)b->mems.as<pgx_mem>(), voff, m0, m1, o0, nv,
+                               (const uint32_t *)d->img.lce_sa, bwt_n, (const uint64_t *)d->lce_seq_start.as<uint64_t>(), d->lce_n_seq, (uint32_t)W, sets);
+            HIPCHECK(hipGetLastError());
+        } else if (nv && resident) {
             hipLaunchKernelGGL(pgx_ml_gather_kernel, dim3(grid_for(nv, PGX_ML_SPAN)), dim3(256), 0, s, (const pgx_mem *)b->mems.as<pgx_mem>(), voff, m0, m1, o0, nv,
                                (const uint32_t *)d->img.lce_sa, bwt_n, (const uint64_t *)d->lce_seq_start.as<uint64_t>(), d->lce_n_seq, d->loc.max_length,
                                seq_ids ? 1 : 0, dst);
@@ -1168,9 +1207,31 @@ extern "C" pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t ma
                 hipLaunchKernelGGL(pgx_locate_walk_kernel, dim3(grid_for(n_pieces, 256)), dim3(256), 0, s, d->loc, qs, qe, np, (const uint64_t *)w.run0.as<uint64_t>(),
                                    (const uint64_t *)w.poff.as<uint64_t>(), n_pieces, voff + m0, o0, seq_ids ? 1 : 0, dst);
                 HIPCHECK(hipGetLastError());
+                if (build_sets) { // the pass's sequence ids -> bits
+                    hipLaunchKernelGGL(pgx_ml_sets_ids_kernel, dim3(grid_for(nv, PGX_ML_SPAN)), dim3(256), 0, s, voff, m0, m1, o0, nv, (const uint64_t *)dst, (uint32_t)W,
+                                       sets);
+                    HIPCHECK(hipGetLastError());
+                }
             }
         }
-        if (uniq) { // segmented sort-unique with the tag stage's kernels, size-class lists built on the device, then compaction behind the passes before
+        if (routed) { // the sets as ascending ids behind the passes before: sorted and unique by construction
+            uint32_t Wp = 1;
+            while (Wp < W) Wp <<= 1;
+            uint64_t *ucount = w.ucount.as<uint64_t>() + m0;
+            w.uloc.ensure((np + 1) * 8);
+            hipLaunchKernelGGL(pgx_ml_set_count_kernel, dim3(grid_for(np * Wp, 256)), dim3(256), 0, s, (const unsigned long long *)sets, np, (uint32_t)W, Wp, ucount);
+            HIPCHECK(hipGetLastError());
+            scan_excl(1, ucount, np, 0, w.uloc.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 3));
+            const uint64_t Up = read_u64(reinterpret_cast<const uint64_t *>(ctr + 3), s);
+            w.vals.ensure_keep((U + Up ? U + Up : 1) * 8, U * 8); // (the stream is idle here: the read-back above synchronised it)
+            if (Up) {
+                hipLaunchKernelGGL(pgx_ml_set_expand_kernel, dim3(grid_for(np, 4)), dim3(256), 0, s, (const unsigned long long *)sets, np, (uint32_t)W,
+                                   (const uint64_t *)w.uloc.as<uint64_t>(), w.vals.as<uint64_t>() + U);
+                HIPCHECK(hipGetLastError());
+            }
+            U += Up;
+        }
+        if (sort_uniq) { // segmented sort-unique with the tag stage's kernels, size-class lists built on the device, then compaction behind the passes before
             w.seg.ensure((np + 1) * 8); w.lists.ensure(2 * np * 8); w.need.ensure(np * 8); w.soff.ensure((np + 1) * 8); w.uloc.ensure((np + 1) * 8);
             uint64_t *seg = w.seg.as<uint64_t>(), *wave_list = w.lists.as<uint64_t>(), *wg_list = wave_list + np, *ucount = w.ucount.as<uint64_t>() + m0;
             const uint64_t *cnt = w.cnt.as<uint64_t>() + m0;
@@ -1212,11 +1273,12 @@ extern "C" pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t ma
     HIPCHECK(hipStreamSynchronize(s));
     w.ms = 0;
     if (timed) HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
-    w.d_off = uniq ? w.uoff.as<uint64_t>() : voff;
+    w.d_off = uniq || sets_form ? w.uoff.as<uint64_t>() : voff;
     w.n_mems = n;
-    w.n_values = uniq ? U : V;
+    w.n_values = sets_form ? n * W : uniq ? U : V;
     w.n_not_located = n_not;
-    w.flags = flags & (PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE);
+    w.flags = flags & (PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE | PGX_LOCATE_SEQ_SETS);
+    w.set_words = build_sets ? (uint32_t)W : 0;
     w.resident = resident;
     w.valid = true;
     return PGX_OK;
@@ -1232,6 +1294,7 @@ static void locations_header(const pgx_batch *b, pgx_locations *out) {
     out->flags = w.flags;
     out->resident = w.resident ? 1u : 0u;
     out->ms_locate = w.ms;
+    out->set_words = w.set_words;
 }
 
 extern "C" pgx_status pgx_batch_device_locations(pgx_batch *b, pgx_locations *out) {

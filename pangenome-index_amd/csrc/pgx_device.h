@@ -240,6 +240,19 @@ __global__ void pgx_ml_gather_kernel(const pgx_mem *mems, const uint64_t *off, u
                                      int seq_ids, uint64_t *out);
 __global__ void pgx_ml_classify_kernel(const uint64_t *cnt, const uint64_t *off, uint64_t np, uint64_t *seg, uint64_t *wave_list,
                                        uint64_t *wg_list, uint64_t *need, uint64_t *ucount, unsigned long long *ctr);
+// sequence sets: W = ceil(n_seq / 64) words a MEM.  The cap is one word per lane of a wave (pgx_ml_set_expand_kernel); beyond it a bitmap per
+// MEM costs more than the ids it replaces.
+#define PGX_ML_SET_WORDS_MAX 64
+#define PGX_ML_SET_BATCH 8  // values a thread of the set kernel loads before it merges them
+#define PGX_ML_SET_WIN 2048 // set words a block accumulates in LDS at a time (16 KiB next to the 16 KiB of offsets and sequence starts: five blocks a CU)
+__global__ void pgx_ml_sets_kernel(const pgx_mem *mems, const uint64_t *off, uint64_t m0, uint64_t m1, uint64_t o_first, uint64_t nv,
+                                   const uint32_t *sa32, uint64_t bwt_n, const uint64_t *seq_start, uint64_t n_seq, uint32_t W,
+                                   unsigned long long *sets);
+__global__ void pgx_ml_sets_ids_kernel(const uint64_t *off, uint64_t m0, uint64_t m1, uint64_t o_first, uint64_t nv, const uint64_t *ids, uint32_t W,
+                                       unsigned long long *sets);
+__global__ void pgx_ml_set_count_kernel(const unsigned long long *sets, uint64_t np, uint32_t W, uint32_t Wp, uint64_t *ucount);
+__global__ void pgx_ml_set_expand_kernel(const unsigned long long *sets, uint64_t np, uint32_t W, const uint64_t *uloc, uint64_t *out);
+__global__ void pgx_ml_stride_kernel(uint64_t *out, uint64_t n, uint64_t stride);
 
 // literal count image: COMPAT count_encoded / LF_encoded on an encoded index without N, block by block as the
 // reference's rankAt_encoded (src/r-index.cpp:570-590) sees it -- true cumulative counts, run scan one varint late

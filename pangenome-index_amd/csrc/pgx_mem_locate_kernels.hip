@@ -9,6 +9,13 @@
 //   (chains) pgx_locate_plan_kernel / pgx_locate_walk_kernel (pgx_locate_kernels.hip) on the ranges of the plan
 //   classify PGX_LOCATE_UNIQUE: pass-local segment offsets and the size-class lists of the tag stage's sort kernels, built by compaction
 //            (wave-aggregated appends; every segment is sorted on its own, so the list order does not matter)
+//   sets     PGX_LOCATE_SEQ_SETS, and PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE over few sequences: one bit per sequence per MEM, W words a MEM.
+//            The block shape of the gather, but no value is written: a block ORs the bits of its PGX_ML_SPAN values into an LDS window of
+//            its MEMs' words and writes every non-zero word once -- a plain store where the MEM lies inside the block, a global atomicOr
+//            where neighbouring blocks share it.  From the resident suffix array, or from the sequence ids the chain walk left in the pass
+//            buffer.  OR does not depend on the order: the bytes are the same from run to run.
+//   count / expand   the routed unique form: popcount per MEM -> ucount, (scan), then a wave per MEM writes the set bits as ascending ids
+//   stride   loc_offsets of the set form: m * W
 // Every index is 64-bit; no kernel reads outside its arrays whatever the pgx_mem contents.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -124,4 +131,150 @@ pgx_ml_classify_kernel(const uint64_t *__restrict__ cnt, const uint64_t *__restr
     if (wave) wave_list[a] = i;
     const uint64_t b = pgx_ml_append(wg, ctr + 1);
     if (wg) wg_list[b] = i;
+}
+
+// ---- sequence sets ---------------------------------------------------------------------------------------------------------------
+// Values [o_first, o_first + nv) of the batch as in pgx_ml_gather_kernel, ORed into sets[(m - m0) * W + (q >> 6)], bit q & 63, for the
+// sequence q of each value of MEM m (sets: (m1 - m0) * W words, cleared by the caller).  FROM_IDS: q = ids[o - o_first], what
+// pgx_locate_walk_kernel wrote for the pass; else q = the sequence of lce_sa[row] as in the gather.  A block walks its MEMs [ma, mb) in
+// windows of at most PGX_ML_WIN - 1 MEMs and PGX_ML_SET_WIN words; a window's values are one contiguous range.  Each thread merges the
+// bits of consecutive values of one word in a register before it touches LDS (a MEM of thousands of occurrences costs a block one LDS
+// atomic per thread, not one per value).  1 <= W <= PGX_ML_SET_WORDS_MAX; a q at or beyond 64 W (never, for the index the caller sized W
+// from) is dropped.
+template <bool FROM_IDS>
+__device__ __forceinline__ void pgx_ml_sets_body(const pgx_mem *__restrict__ mems, const uint64_t *__restrict__ off, uint64_t m0, uint64_t m1, uint64_t o_first,
+                                                 uint64_t nv, const uint32_t *__restrict__ sa32, const uint64_t *__restrict__ ids, uint64_t bwt_n,
+                                                 const uint64_t *__restrict__ seq_start, uint64_t n_seq, uint32_t W, unsigned long long *__restrict__ sets) {
+    __shared__ uint64_t s_off[PGX_ML_WIN];
+    __shared__ uint64_t s_seq[FROM_IDS ? 1 : PGX_ML_WIN];
+    __shared__ unsigned long long s_set[PGX_ML_SET_WIN];
+    __shared__ uint64_t s_ab[2];
+    const uint64_t o_begin = o_first + (uint64_t)blockIdx.x * PGX_ML_SPAN;
+    if (o_begin >= o_first + nv || W == 0 || W > PGX_ML_SET_WORDS_MAX) return;
+    const uint64_t o_end = o_begin + PGX_ML_SPAN < o_first + nv ? o_begin + PGX_ML_SPAN : o_first + nv;
+    if (threadIdx.x == 0) s_ab[0] = pgx_ml_last_le(off, m0, m1, o_begin);
+    if (threadIdx.x == 64) s_ab[1] = pgx_ml_last_le(off, m0, m1, o_end - 1);
+    const bool seq_lds = !FROM_IDS && n_seq + 1 <= PGX_ML_WIN;
+    if (seq_lds)
+        for (uint64_t t = threadIdx.x; t <= n_seq; t += blockDim.x) s_seq[t] = seq_start[t];
+    __syncthreads();
+    const uint64_t ma = s_ab[0], mb = s_ab[1] + 1; // the block's MEMs: [ma, mb), mb <= m1
+    const uint64_t n_bits = (uint64_t)W * 64;
+    const uint64_t win = (PGX_ML_SET_WIN / W) < (PGX_ML_WIN - 1) ? (PGX_ML_SET_WIN / W) : (PGX_ML_WIN - 1); // MEMs per window
+    for (uint64_t wa = ma; wa < mb; wa += win) {
+        const uint64_t wb = wa + win < mb ? wa + win : mb, nm = wb - wa, nw = nm * W;
+        for (uint64_t t = threadIdx.x; t <= nm; t += blockDim.x) s_off[t] = off[wa + t];
+        for (uint64_t t = threadIdx.x; t < nw; t += blockDim.x) s_set[t] = 0;
+        __syncthreads();
+        const uint64_t v_lo = s_off[0] > o_begin ? s_off[0] : o_begin, v_hi = s_off[nm] < o_end ? s_off[nm] : o_end; // the window's values of this block
+        uint64_t k = 0, key = ~0ull;   // k: window-local MEM of the value before (values ascend, so does k)
+        unsigned long long acc = 0;    // bits gathered for word `key` of the window
+        // PGX_ML_SET_BATCH values of a thread at a time, stage by stage, so that their loads are in flight together: the merge below makes one
+        // value depend on the one before, and a loop of whole values would wait for every suffix-array entry on its own
+        for (uint64_t ob = v_lo + threadIdx.x; ob < v_hi; ob += (uint64_t)PGX_ML_SET_BATCH * blockDim.x) {
+            uint64_t kk[PGX_ML_SET_BATCH], q[PGX_ML_SET_BATCH];
+#pragma unroll
+            for (int i = 0; i < PGX_ML_SET_BATCH; i++) {
+                const uint64_t o = ob + (uint64_t)i * blockDim.x;
+                if (o < v_hi && o >= s_off[k + 1]) k = pgx_ml_last_le(s_off, k + 1, nm, o);
+                kk[i] = k;
+            }
+            if (FROM_IDS) {
+#pragma unroll
+                for (int i = 0; i < PGX_ML_SET_BATCH; i++) {
+                    const uint64_t o = ob + (uint64_t)i * blockDim.x;
+                    q[i] = o < v_hi ? ids[o - o_first] : ~0ull;
+                }
+            } else {
+                uint64_t row[PGX_ML_SET_BATCH];
+#pragma unroll
+                for (int i = 0; i < PGX_ML_SET_BATCH; i++) {
+                    const uint64_t o = ob + (uint64_t)i * blockDim.x;
+                    row[i] = o < v_hi ? mems[wa + kk[i]].bwt_start + (o - s_off[kk[i]]) : ~0ull;
+                }
+#pragma unroll
+                for (int i = 0; i < PGX_ML_SET_BATCH; i++) q[i] = row[i] < bwt_n ? sa32[row[i]] : ~0ull; // (always inside for a located MEM, pgx_ml_plan_kernel)
+#pragma unroll
+                for (int i = 0; i < PGX_ML_SET_BATCH; i++)
+                    if (q[i] != ~0ull) q[i] = seq_lds ? pgx_ml_last_le(s_seq, 0, n_seq, q[i]) : pgx_ml_last_le(seq_start, 0, n_seq, q[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < PGX_ML_SET_BATCH; i++) {
+                if (q[i] >= n_bits) continue; // (also the values beyond v_hi)
+                const uint64_t w = kk[i] * W + (q[i] >> 6);
+                if (w != key) {
+                    if (acc) atomicOr(&s_set[key], acc);
+                    key = w; acc = 0;
+                }
+                acc |= 1ull << (q[i] & 63);
+            }
+        }
+        if (acc) atomicOr(&s_set[key], acc);
+        __syncthreads();
+        for (uint64_t t = threadIdx.x; t < nw; t += blockDim.x) {
+            const unsigned long long v = s_set[t];
+            if (!v) continue;
+            const uint64_t j = t / W;
+            unsigned long long *dst = sets + (wa + j - m0) * W + (t - j * W);
+            if (s_off[j] >= o_begin && s_off[j + 1] <= o_end) *dst = v; // the whole MEM is this block's
+            else atomicOr(dst, v);
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(256)
+pgx_ml_sets_kernel(const pgx_mem *__restrict__ mems, const uint64_t *__restrict__ off, uint64_t m0, uint64_t m1, uint64_t o_first, uint64_t nv,
+                   const uint32_t *__restrict__ sa32, uint64_t bwt_n, const uint64_t *__restrict__ seq_start, uint64_t n_seq, uint32_t W,
+                   unsigned long long *__restrict__ sets) {
+    pgx_ml_sets_body<false>(mems, off, m0, m1, o_first, nv, sa32, nullptr, bwt_n, seq_start, n_seq, W, sets);
+}
+
+__global__ void __launch_bounds__(256)
+pgx_ml_sets_ids_kernel(const uint64_t *__restrict__ off, uint64_t m0, uint64_t m1, uint64_t o_first, uint64_t nv, const uint64_t *__restrict__ ids, uint32_t W,
+                       unsigned long long *__restrict__ sets) {
+    pgx_ml_sets_body<true>(nullptr, off, m0, m1, o_first, nv, nullptr, ids, 0, nullptr, 0, W, sets);
+}
+
+// ucount[i] = the number of set bits of MEM i's W words (np MEMs): Wp lanes a MEM (Wp = the power of two >= W), a wave holds 64 / Wp MEMs
+__global__ void __launch_bounds__(256)
+pgx_ml_set_count_kernel(const unsigned long long *__restrict__ sets, uint64_t np, uint32_t W, uint32_t Wp, uint64_t *__restrict__ ucount) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t i = t / Wp;
+    const uint32_t j = (uint32_t)(t % Wp);
+    int c = (i < np && j < W) ? __popcll(sets[i * W + j]) : 0;
+    for (uint32_t d = 1; d < Wp; d <<= 1) c += __shfl_xor(c, (int)d, 64);
+    if (i < np && j == 0) ucount[i] = (uint64_t)c;
+}
+
+// MEM i's set bits as ascending sequence ids at out[uloc[i] ..): a wave per MEM; lane = word for the load and the prefix of the popcounts,
+// then lane = bit, one non-empty word after the other
+__global__ void __launch_bounds__(256)
+pgx_ml_set_expand_kernel(const unsigned long long *__restrict__ sets, uint64_t np, uint32_t W, const uint64_t *__restrict__ uloc, uint64_t *__restrict__ out) {
+    const uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (i >= np) return; // (a whole wave)
+    const int lane = threadIdx.x & 63;
+    const unsigned long long word = (uint32_t)lane < W ? sets[i * W + lane] : 0;
+    int pre = __popcll(word); // -> exclusive prefix over the lanes
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(pre, d, 64);
+        if (lane >= d) pre += up;
+    }
+    pre -= __popcll(word);
+    const uint64_t base = uloc[i];
+    unsigned long long nz = __ballot(word != 0);
+    while (nz) {
+        const int j = __ffsll((long long)nz) - 1;
+        nz &= nz - 1;
+        const unsigned long long wj = __shfl(word, j, 64);
+        const int pj = __shfl(pre, j, 64);
+        if ((wj >> lane) & 1ull) out[base + (uint64_t)pj + (uint64_t)__popcll(wj & ((1ull << lane) - 1ull))] = (uint64_t)j * 64 + (uint64_t)lane;
+    }
+}
+
+// out[i] = i * stride, i < n
+__global__ void __launch_bounds__(256)
+pgx_ml_stride_kernel(uint64_t *__restrict__ out, uint64_t n, uint64_t stride) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = i * stride;
 }

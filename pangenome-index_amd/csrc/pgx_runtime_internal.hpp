@@ -108,16 +108,16 @@ struct TagWork {
 
 // pgx_batch_locate's buffers (grow-only, kept with the batch like its other result buffers) and its result
 struct LocWork {
-    DevBuf cnt, qs, qe, voff, uoff, vals, gbuf, run0, npieces, poff, seg, lists, need, soff, scratch, ucount, uloc, ctr, scan_tmp;
+    DevBuf cnt, qs, qe, voff, uoff, vals, gbuf, run0, npieces, poff, seg, lists, need, soff, scratch, ucount, uloc, ctr, scan_tmp, sets;
     HostBuf h_off, h_vals;
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool valid = false, resident = false;
-    uint32_t flags = 0;
+    uint32_t flags = 0, set_words = 0; // set_words: W when the call built sequence sets (the set form, or the unique ids expanded from them)
     uint64_t n_mems = 0, n_values = 0, n_not_located = 0;
-    const uint64_t *d_off = nullptr; // voff, or uoff with PGX_LOCATE_UNIQUE
+    const uint64_t *d_off = nullptr; // voff, or uoff with PGX_LOCATE_UNIQUE / PGX_LOCATE_SEQ_SETS
     float ms = 0;
     void release() {
-        DevBuf *all[] = {&cnt, &qs, &qe, &voff, &uoff, &vals, &gbuf, &run0, &npieces, &poff, &seg, &lists, &need, &soff, &scratch, &ucount, &uloc, &ctr, &scan_tmp};
+        DevBuf *all[] = {&cnt, &qs, &qe, &voff, &uoff, &vals, &gbuf, &run0, &npieces, &poff, &seg, &lists, &need, &soff, &scratch, &ucount, &uloc, &ctr, &scan_tmp, &sets};
         for (DevBuf *d : all) d->release();
         h_off.release(); h_vals.release();
         for (auto &e : ev)

@@ -54,7 +54,7 @@ class DeviceResult(C.Structure):
 
 class Locations(C.Structure):  # pgx_locations: host pointers (pgx_batch_locations) or device pointers (pgx_batch_device_locations)
     _fields_ = [("n_mems", u64), ("n_values", u64), ("n_not_located", u64), ("flags", u32), ("resident", u32), ("loc_offsets", p),
-                ("values", p), ("ms_locate", C.c_float), ("reserved", C.c_float)]
+                ("values", p), ("ms_locate", C.c_float), ("set_words", C.c_uint32)]
 
 
 class DeviceArray:
@@ -293,6 +293,7 @@ _VIEW_DTYPES = {0: np.uint8, 1: np.uint64, 2: np.uint64, 3: np.uint64, 4: np.uin
                 16: np.uint64, 17: np.uint64, 18: np.uint64, 19: np.uint32, 20: np.uint32, 21: np.uint32, 22: np.uint64, 23: np.uint64}
 LOCATE_SEQ_IDS, LOCATE_UNIQUE = 1, 2
 LOCATE_CHAINS = 4  # pgx_batch_locate: the sample chains even where the suffix array is resident (tests)
+LOCATE_SEQ_SETS = 8  # pgx_batch_locate: one bit per sequence per MEM, set_words words a MEM
 NO_POSITION = 0xFFFFFFFFFFFFFFFF
 
 
@@ -711,14 +712,17 @@ class Batch:
         r = Locations()
         _check(fn(self.b, C.byref(r)))
         return r, dict(n_mems=int(r.n_mems), n_values=int(r.n_values), n_not_located=int(r.n_not_located), flags=int(r.flags),
-                       resident=bool(r.resident), ms_locate=float(r.ms_locate))
+                       resident=bool(r.resident), ms_locate=float(r.ms_locate), set_words=int(r.set_words))
 
     def locations(self):
         """the last locate as numpy arrays: loc_offsets uint64[n_mems + 1] (MEM m's values = values[loc_offsets[m] .. [m + 1])), values,
-        with n_values, n_not_located, flags, resident (1: gathered from the resident suffix array), ms_locate"""
+        with n_values, n_not_located, flags, resident (1: gathered from the resident suffix array), ms_locate, set_words.  After
+        LOCATE_SEQ_SETS also sets: uint64[n_mems, set_words], the same memory as values"""
         r, out = self._locations(self.L.pgx_batch_locations)
         out["loc_offsets"] = _u64_array(C.cast(r.loc_offsets, C.POINTER(u64)), out["n_mems"] + 1)
         out["values"] = _u64_array(C.cast(r.values, C.POINTER(u64)), out["n_values"])
+        if out["flags"] & LOCATE_SEQ_SETS:
+            out["sets"] = out["values"].reshape(out["n_mems"], out["set_words"])
         return out
 
     def device_locations(self):
@@ -727,6 +731,8 @@ class Batch:
         out["device"] = True
         out["loc_offsets"] = DeviceArray(r.loc_offsets, (out["n_mems"] + 1,), self)
         out["values"] = DeviceArray(r.values, (out["n_values"],), self)
+        if out["flags"] & LOCATE_SEQ_SETS:
+            out["sets"] = DeviceArray(r.values, (out["n_mems"], out["set_words"]), self)
         return out
 
     def free(self):
