@@ -416,7 +416,8 @@ static RunKnobs read_run_knobs() {
     return k;
 }
 
-// The variants of pgx_find_mems_kernel the runtime launches (instantiated in pgx_kernels.hip), each named here and nowhere else.
+// The variants of pgx_find_mems_kernel the runtime launches, each named here and in the instantiation list of pgx_fm_kernels.hip (for the pairs kernel below:
+// of pgx_pairs_kernels.hip), and nowhere else.
 // Only images of up to 48 KiB are staged in LDS, and only the run-length and the 64-byte dense image are (pgx_images.hip device_image); the run-length image has
 // neither a 32-bit form nor seeds, the wide dense2 image (kind 3) no 32-bit form.
 // (nullptr: no such instance)
@@ -456,14 +457,14 @@ static const void *find_mems_variant(bool in_lds, uint32_t kind, bool narrow, bo
 static const void *find_mems_pairs_entry(bool wide, bool packed, bool coop, bool s64, bool lce) {
     using K = const void *;
     static const K plain[2][2] = { // [wide][stride 64]
-        {(K)pgx_find_mems_pairs_kernel<true, false, false, false, false, false>, (K)pgx_find_mems_pairs_kernel<true, false, false, false, true, false>},
-        {(K)pgx_find_mems_pairs_kernel<true, true, false, false, false, false>, (K)pgx_find_mems_pairs_kernel<true, true, false, false, true, false>}};
+        {(K)pgx_find_mems_pairs_kernel<false, false, false, false, false>, (K)pgx_find_mems_pairs_kernel<false, false, false, true, false>},
+        {(K)pgx_find_mems_pairs_kernel<true, false, false, false, false>, (K)pgx_find_mems_pairs_kernel<true, false, false, true, false>}};
     static const K pack[2][2][2] = { // [wide][cooperative][stride 64]
-        {{(K)pgx_find_mems_pairs_kernel<true, false, true, false, false, false>, (K)pgx_find_mems_pairs_kernel<true, false, true, false, true, false>},
-         {(K)pgx_find_mems_pairs_kernel<true, false, true, true, false, false>, (K)pgx_find_mems_pairs_kernel<true, false, true, true, true, false>}},
-        {{(K)pgx_find_mems_pairs_kernel<true, true, true, false, false, false>, (K)pgx_find_mems_pairs_kernel<true, true, true, false, true, false>},
-         {(K)pgx_find_mems_pairs_kernel<true, true, true, true, false, false>, (K)pgx_find_mems_pairs_kernel<true, true, true, true, true, false>}}};
-    static const K with_lce[2] = {(K)pgx_find_mems_pairs_kernel<true, false, true, false, false, true>, (K)pgx_find_mems_pairs_kernel<true, false, true, false, true, true>}; // [stride 64]
+        {{(K)pgx_find_mems_pairs_kernel<false, true, false, false, false>, (K)pgx_find_mems_pairs_kernel<false, true, false, true, false>},
+         {(K)pgx_find_mems_pairs_kernel<false, true, true, false, false>, (K)pgx_find_mems_pairs_kernel<false, true, true, true, false>}},
+        {{(K)pgx_find_mems_pairs_kernel<true, true, false, false, false>, (K)pgx_find_mems_pairs_kernel<true, true, false, true, false>},
+         {(K)pgx_find_mems_pairs_kernel<true, true, true, false, false>, (K)pgx_find_mems_pairs_kernel<true, true, true, true, false>}}};
+    static const K with_lce[2] = {(K)pgx_find_mems_pairs_kernel<false, true, false, false, true>, (K)pgx_find_mems_pairs_kernel<false, true, false, true, true>}; // [stride 64]
     if (lce) return (wide || !packed || coop) ? nullptr : with_lce[s64];
     if (!packed) return coop ? nullptr : plain[wide][s64];
     return pack[wide][coop][s64];
@@ -932,7 +933,7 @@ static bool run_pass(RunCtx &r, bool may_speculate, bool &force_worst) {
     record(b, 0, s);
     plan_slots(r);
     const std::vector<pgx_chunk> &chunks = b->chunks;
-    // The slot buffer: a dense array of the first four MEMs of every read (PGX_FAST_SLOTS, pgx_kernels.hip pgx_slot_index) + either an ARENA for the
+    // The slot buffer: a dense array of the first four MEMs of every read (PGX_FAST_SLOTS, pgx_slots_device.h pgx_slot_index) + either an ARENA for the
     // fifth and later MEMs (arena_slots), or -- PGX_SLOT_ARENA=0, tiny batches, and the repeat of a chunk whose arena proved too small -- the
     // worst-case region.  Sized per chunk.
     r.arena_on = r.k.arena && !force_worst;

@@ -39,7 +39,6 @@ enum PgxCounterSlot {
     PGX_CTR_ALL = 64 + 16 * 64
 };
 #define PGX_ARENA_SUBS 64u
-__global__ void pgx_arena_demand_kernel(unsigned long long *ctr);
 #define PGX_TBUCKET_RUNS 10u // run starts a bucket line holds (pgx_tag_bucket_kernel); a bucket with more is flagged and answered through tdir / tpair
 
 #define PGX_DENSE_LDS_U4 5 // uint4 slots per dense block in LDS (64 data bytes + 16 of padding)
@@ -104,7 +103,7 @@ struct PgxDevImage {
 #define PGX_SEED_MAX_K 16
 #define PGX_SEED_SMALL_K 10 // depth of the second table (searches whose min_len is below the depth of the first)
 
-// heavy reads (pgx_kernels.hip): handed from pgx_find_mems_kernel to pgx_find_mems_heavy_kernel
+// heavy reads (pgx_fm_kernels.hip): handed from pgx_find_mems_kernel to pgx_find_mems_heavy_kernel
 struct pgx_heavy_item {
     uint64_t rid;
     uint32_t x, nm; // next start position, MEMs already written
@@ -118,34 +117,44 @@ struct PgxHeavyResult { // find_mems_function(x) of one start position
 #define PGX_FM_HEAVY_MAXLEN 4096u // reads up to this length take part (per-start results live in scratch)
 #define PGX_FM_HEAVY_CAP 8192u    // heavy reads per launch; beyond that lanes simply continue sequentially
 #define PGX_FM_HEAVY_GRID 64u
-template <bool LDS_IMAGE>
-__global__ void pgx_find_mems_heavy_kernel(PgxDevImage img, const uint8_t *reads, const uint64_t *offsets, uint64_t min_len, uint64_t min_occ,
-                                           const uint64_t *slot_off, uint64_t slot_base, pgx_mem *slots, uint32_t *mem_count,
-                                           unsigned long long *n_ext_total, const pgx_heavy_item *heavy_list,
-                                           const unsigned long long *heavy_count, uint32_t heavy_cap, PgxHeavyResult *scratch, uint64_t chunk_first,
-                                           uint64_t chunk_reads, uint32_t *ovf_base, uint64_t ovf_cap);
 
-__global__ void pgx_seed_build_kernel(PgxDevImage img, const uint4 *src, uint4 *dst, uint32_t level, uint64_t n_dst, uint64_t limit, int end_table);
+// ---- pgx_fm_kernels.hip: the one-step find_mems kernel, the rest of heavy reads, find_mems_function per call
 template <bool LDS_IMAGE, int DENSE, bool NARROW, bool SEED> // DENSE = image kind
 __global__ void pgx_find_mems_kernel(PgxDevImage img, const uint8_t *reads, const uint64_t *offsets, uint64_t n_reads,
                                      uint64_t min_len, uint64_t min_occ, const uint64_t *slot_off, pgx_mem *slots,
                                      uint32_t *mem_count, unsigned long long *n_ext_total, unsigned long long *cursor, uint64_t first_read,
                                      uint64_t slot_base, uint32_t heavy_ext, uint32_t heavy_cap, pgx_heavy_item *heavy_list, unsigned long long *heavy_count,
                                      const pgx_heavy_item *rid_list, const unsigned long long *rid_count, uint32_t *ovf_base, uint64_t ovf_cap);
+template <bool LDS_IMAGE>
+__global__ void pgx_find_mems_heavy_kernel(PgxDevImage img, const uint8_t *reads, const uint64_t *offsets, uint64_t min_len, uint64_t min_occ,
+                                           const uint64_t *slot_off, uint64_t slot_base, pgx_mem *slots, uint32_t *mem_count,
+                                           unsigned long long *n_ext_total, const pgx_heavy_item *heavy_list,
+                                           const unsigned long long *heavy_count, uint32_t heavy_cap, PgxHeavyResult *scratch, uint64_t chunk_first,
+                                           uint64_t chunk_reads, uint32_t *ovf_base, uint64_t ovf_cap);
+__global__ void pgx_fmf_kernel(PgxDevImage img, const uint8_t *reads, const uint64_t *offsets, const uint64_t *read_of, const uint64_t *xs, uint64_t n,
+                               uint64_t min_len, uint64_t min_occ, PgxHeavyResult *out);
+__global__ void pgx_arena_demand_kernel(unsigned long long *ctr);
+
+// ---- pgx_pairs_kernels.hip: the two-step find_mems kernel
 // PAIRS image (pgx_image.h): two extensions per loop trip; an extension its blocks cannot answer (special positions) goes through the other image
-template <bool SEED, bool WIDE, bool PACKED, bool COOP, bool S64, bool LCE>
+template <bool WIDE, bool PACKED, bool COOP, bool S64, bool LCE>
 __global__ void pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *reads, const uint64_t *offsets, uint64_t n_reads,
                                            uint64_t min_len, uint64_t min_occ, const uint64_t *slot_off, pgx_mem *slots,
                                            uint32_t *mem_count, unsigned long long *n_ext_total, unsigned long long *cursor, uint64_t first_read,
                                            uint64_t slot_base, uint32_t heavy_ext, uint32_t heavy_cap, pgx_heavy_item *heavy_list, unsigned long long *heavy_count,
                                            const uint8_t *skip, const uint32_t *packed, uint32_t pk_words,
                                            uint32_t *ovf_base, uint64_t ovf_cap);
+
+// ---- pgx_reads_kernels.hip: per-upload passes over the reads
 __global__ void pgx_bad_chunks_kernel(const uint8_t *reads, uint64_t n_bytes, uint64_t *chunks, unsigned long long *count, uint64_t cap, uint32_t *packed);
 __global__ void pgx_unpack_reads_kernel(const uint32_t *packed, uint64_t n_chunks, uint8_t *reads);
 __global__ void pgx_side_reads_kernel(uint8_t *reads, const uint64_t *offsets, const uint64_t *side_ids, const uint64_t *side_off, const uint8_t *side_bytes, uint64_t n_side,
                                       uint8_t *flags, pgx_heavy_item *list, unsigned long long *count);
 __global__ void pgx_classify_reads_kernel(const uint8_t *reads, const uint64_t *offsets, uint64_t n_reads, const uint64_t *chunks, const unsigned long long *n_chunks,
                                           uint64_t cap, uint32_t *flag_words, pgx_heavy_item *list, unsigned long long *count);
+
+// ---- pgx_query_kernels.hip: seed table / first_ext builders, per-call rank / extend / count / LF (pgx_lit_count_kernel: below, with its image)
+__global__ void pgx_seed_build_kernel(PgxDevImage img, const uint4 *src, uint4 *dst, uint32_t level, uint64_t n_dst, uint64_t limit, int end_table);
 __global__ void pgx_first_ext_kernel(PgxDevImage img, uint4 *out); // out[byte] = {k, k', s, 0} of the full interval extended backward by byte; out[256 + byte]: by 0, then by byte
 __global__ void pgx_rank_kernel(PgxDevImage img, const uint64_t *pos, uint64_t n, int true_codes, uint64_t *out);
 template <bool LOOP, bool MULHI> __global__ void pgx_rank_probe_kernel(PgxDevImage img, const uint64_t *pos, uint64_t n, uint64_t *out);
@@ -154,9 +163,9 @@ __global__ void pgx_extend_kernel(PgxDevImage img, const pgx_biint *in, const ui
                                   pgx_biint *out);
 template <bool LDS_IMAGE>
 __global__ void pgx_count_kernel(PgxDevImage img, const uint8_t *reads, const uint64_t *offsets, uint64_t n_reads, pgx_range *out);
-__global__ void pgx_fmf_kernel(PgxDevImage img, const uint8_t *reads, const uint64_t *offsets, const uint64_t *read_of, const uint64_t *xs, uint64_t n,
-                               uint64_t min_len, uint64_t min_occ, PgxHeavyResult *out);
 __global__ void pgx_lf_kernel(PgxDevImage img, const pgx_range *in, const uint8_t *sym, uint64_t n, pgx_range *out);
+
+// ---- pgx_scan_kernels.hip: exclusive scans, MEM compaction
 // n_dev (may be NULL): the element count lives on the device, `n` is then the capacity the launch was sized for
 __global__ void pgx_scan_partial_kernel(int mode, const void *in, uint64_t n, uint64_t min_len, uint64_t *block_sums, const uint64_t *n_dev);
 template <int MODE>
@@ -168,6 +177,8 @@ __global__ void pgx_scan_apply_kernel(int mode, const void *in, uint64_t n, uint
 __global__ void pgx_compact_mems_kernel(uint64_t first_read, uint64_t n_reads, const uint64_t *slot_off, uint64_t slot_base,
                                         const pgx_mem *slots, const uint32_t *mem_count, const uint64_t *local_off,
                                         uint64_t mem_base, pgx_mem *mems, uint64_t cap_mems, uint64_t *abort, const uint32_t *ovf_base, uint64_t ovf_cap);
+
+// ---- pgx_tag_kernels.hip: the tag stage
 __global__ void pgx_tag_pair_kernel(const uint64_t *tstart, const uint64_t *tvals, uint64_t n_runs, uint64_t n_items, ulonglong2 *out);
 __global__ void pgx_tag_bucket_kernel(const uint64_t *tstart, const uint64_t *tvals, uint64_t n_runs, uint64_t n_items, uint32_t shift, uint64_t n_buckets, uint4 *out);
 #define PGX_TAG_LOCATE_THREADS 1024 // workgroup of pgx_tag_locate_kernel (one list atomic per workgroup)
@@ -205,7 +216,7 @@ __global__ void pgx_spec_check_kernel(const uint64_t *v0, uint64_t c0, const uin
                                       const uint64_t *v3, uint64_t c3, uint64_t *abort);
 #define PGX_TAG_COMPACT_SMALL 256 // segments up to this many unique values are copied by the 16-lane kernel
 
-// locate image (pgx_image.h), passed by value to the locate kernels
+// locate image (pgx_image.h), passed by value to the locate kernels (pgx_locate_kernels.hip, with the builders of the LCE image)
 struct PgxLocImage {
     const uint64_t *rstart, *rsamp; // n_runs + 1, n_runs
     const uint32_t *rdir;
@@ -263,7 +274,7 @@ struct PgxLitImage {
     uint64_t C[8];
     uint64_t n, n_blocks;
 };
-// out[i] = LF over `steps` symbols: count mode (in == NULL): the whole read i from {0, n - 1}; LF mode: one symbol sym[i] from in[i]
+// (pgx_query_kernels.hip) out[i] = LF over `steps` symbols: count mode (in == NULL): the whole read i from {0, n - 1}; LF mode: one symbol sym[i] from in[i]
 __global__ void pgx_lit_count_kernel(PgxLitImage lit, const uint8_t *reads, const uint64_t *offsets, const pgx_range *in, const uint8_t *sym,
                                      uint64_t n, pgx_range *out);
 
@@ -306,5 +317,5 @@ __global__ void pgx_fastx_records_kernel(uint64_t n_lines, uint32_t format, cons
 __global__ void pgx_fastx_longest_kernel(const uint64_t *offs, const uint64_t *n_reads, unsigned long long *longest);
 __global__ void pgx_fastx_copy_kernel(const uint8_t *text, const uint64_t *ls, const uint64_t *out_off, uint64_t n_lines, uint64_t total, uint8_t *out);
 
-#define PGX_SCAN_BLOCK_ITEMS 2048 // 256 threads x 8 items (pgx_kernels.hip PGX_SCAN_ITEMS)
+#define PGX_SCAN_BLOCK_ITEMS 2048 // 256 threads x 8 items (pgx_scan_kernels.hip PGX_SCAN_ITEMS)
 #define PGX_SCAN1_TILE_ITEMS 4096 // 256 threads x 16 rounds (pgx_scan_onepass_kernel)

@@ -1,6 +1,6 @@
 /*
  * pgx_image.h -- flat, pointer-free device image of the FastLocate rank structure and the
- * TagArray, shared by the host builder (pgx_index.cpp) and the HIP kernels (pgx_kernels.hip).
+ * TagArray, shared by the host builder (pgx_index.cpp) and the HIP kernels (pgx_rank_device.h and the pgx_*_kernels.hip files).
  *
  * Only rank *values* are observable through the reference API, so the layout is
  * chosen for the GPU, not translated from the reference's Elias-Fano + varint blocks:

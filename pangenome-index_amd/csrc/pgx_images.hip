@@ -51,7 +51,7 @@ void pgx_release_device_images(pgx_index *h) {
     h->dev.clear();
 }
 
-// k-mer seed table of a dense image (pgx_kernels.hip "k-mer seeds"): built level by level on the device,
+// k-mer seed table of a dense image (pgx_rank_device.h "k-mer seeds"): built level by level on the device,
 // 4^L entries at level L, each one pgx_extend of its parent.  K = floor(log4 n), at most 14 (4 GiB of table; chr22 scale, 10 M
 // reads, K = 11 / 12 / 13 / 14: 41.2 / 39.1 / 37.2 / 36.4 ms with the 64-byte dense image; n = 64 M, 1 M reads, K = 0 / 9 / 11 / 12: 3.64 / 3.44 /
 // 3.14 / 3.07 ms), PGX_SEED_K overrides (0 = no table).

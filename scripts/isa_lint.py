@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The LCE variants of pgx_find_mems_pairs_kernel load their lines with asm statements the compiler does not see through, and wait for them by hand
-(see the declaration of `row` in pgx_kernels.hip).  That is only right while no instruction of the compiler's touches the loaded registers between
+(see the declaration of `row` in pgx_pairs_kernels.hip).  That is only right while no instruction of the compiler's touches the loaded registers between
 such a load and the hand-written wait that follows it in the instruction stream (a copy there would read them before the data is in).  This script
 checks exactly that on the device assembly (hipcc --save-temps): usage isa_lint.py <device .s file>; exit status 1 and the offending lines if not."""
 import re

@@ -2,7 +2,7 @@
 
 Lets the CPU-only test tier check the *image* (blocks, directory, extension tables) that
 pgx_index_open builds against the oracle, without a GPU.  It mirrors pgx_rank_ab / pgx_extend of
-pgx_kernels.hip line for line; it is never used by the product.
+pgx_rank_device.h line for line; it is never used by the product.
 """
 import struct
 

@@ -72,7 +72,7 @@ def test_count_tables_cpu(workdir):
 
 
 def _lit_rank(bstart, cum, runs, roff, pos, target):
-    """pgx_lit_rank (pgx_kernels.hip): the reference's rankAt_encoded on an encoded index without N"""
+    """pgx_lit_rank (pgx_query_kernels.hip): the reference's rankAt_encoded on an encoded index without N"""
     b = int(np.searchsorted(bstart, pos, side="right")) - 1
     rel = pos - int(bstart[b])
     rank = cur = 0

@@ -1,4 +1,4 @@
-"""k-mer seed table of the dense find_mems kernels (pgx_kernels.hip "k-mer seeds"): results -- MEMs, tag positions and the exact
+"""k-mer seed table of the dense find_mems kernels (pgx_rank_device.h "k-mer seeds"): results -- MEMs, tag positions and the exact
 extension count -- must not depend on the table or on its depth K.  The table is built per device image, so PGX_SEED_K is set
 before the index is opened; K = 0 runs the stepwise kernels."""
 import os

@@ -1,6 +1,6 @@
-"""The LCE variants of pgx_find_mems_pairs_kernel load their lines with asm statements and wait for them by hand (pgx_kernels.hip, declaration of `row`):
+"""The LCE variants of pgx_find_mems_pairs_kernel load their lines with asm statements and wait for them by hand (pgx_pairs_kernels.hip, declaration of `row`):
 right only while the compiler puts nothing that touches the loaded registers between such a load and the wait behind it.  scripts/isa_lint.py checks the
-device assembly for that; here on the assembly of the sources as they are (one hipcc --save-temps of pgx_kernels.hip, ~20 s)."""
+device assembly for that; here on the assembly of the sources as they are (one hipcc --save-temps of pgx_pairs_kernels.hip, ~20 s)."""
 import os
 import shutil
 import subprocess
@@ -15,7 +15,7 @@ def test_no_instruction_between_an_asm_load_and_its_wait(tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
-    src = os.path.join(ROOT, "pangenome-index_amd", "csrc", "pgx_kernels.hip")
+    src = os.path.join(ROOT, "pangenome-index_amd", "csrc", "pgx_pairs_kernels.hip")
     r = subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
                         "-I" + os.path.join(ROOT, "pangenome-index_amd", "csrc"), "-c", src, "-o", str(tmp_path / "k.o"), "--save-temps"],
                        cwd=tmp_path, capture_output=True, text=True, timeout=600)

@@ -140,7 +140,7 @@ def test_pairs_image_refused_where_the_tables_are_not_the_textbook_ones(workdir,
 
 
 class PairsEmu:
-    """one trip of pgx_find_mems_pairs_kernel in Python, from the image views: the two-step arithmetic of pgx_kernels.hip (counts below relA and
+    """one trip of pgx_find_mems_pairs_kernel in Python, from the image views: the two-step arithmetic of pgx_pairs_kernels.hip (counts below relA and
     in [relA, relB) of the 96-position block of p0, the neighbour block when the interval runs on, the bail conditions), TEST INFRASTRUCTURE ONLY"""
 
     def __init__(self, idx):
@@ -366,7 +366,7 @@ class PairsKernelEmu(PairsEmu):
                     else:
                         two = rem2 and self._reg(b[j2], fwd)
                         got = self.two_step(tri, byte, b[j2] if two else ord("A"), fwd)
-                        if got is None:  # this ONE extension through the image the PAIRS image accompanies, then on with pairs (pgx_kernels.hip "bail")
+                        if got is None:  # this ONE extension through the image the PAIRS image accompanies, then on with pairs (pgx_pairs_kernels.hip "bail")
                             self.other_steps += 1
                             got = (self.base.extend(tri, byte, fwd), None)
                             two = False

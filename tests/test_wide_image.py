@@ -169,7 +169,7 @@ def test_cooperative_line_fetches_against_the_oracle(wide_case, monkeypatch, wid
 @pytest.mark.parametrize("wide", [1, 0])
 def test_every_extension_through_the_other_image(workdir, monkeypatch, wide):
     """The product twin of the round-3 rank primitive that looped over probes (DESIGN.md "stale counts"): the rolled two-probe loop the pairs kernel
-    takes when its own block cannot answer (pgx_kernels.hip, `bail`).  A text with an N at every twentieth position flags EVERY block of the PAIRS
+    takes when its own block cannot answer (pgx_pairs_kernels.hip, `bail`).  A text with an N at every twentieth position flags EVERY block of the PAIRS
     image (some position of each has N as first or second symbol), so every extension behind a stage's first goes through that loop -- 64-bit
     (pgx_dense2w_rank, superblock bases) and narrow --, in a launch of hundreds of workgroups, every run twice, against the oracle."""
     rng = np.random.default_rng(123)
