@@ -189,12 +189,15 @@ def test_tag_queries_all_sort_paths(xy):
     st[:3], en[:3] = [0, 0, 35], [n - 1, 0, 35]
     rn, po, pos, nover = idx.tag_query_batch(st, en)
     seen = set()
+    n_eover = 0
     for i in range(len(st)):
         ern, epos, eover = tags.query(int(st[i]), int(en[i]))
         assert int(rn[i]) == ern
         assert list(pos[po[i]:po[i + 1]]) == epos, i
         seen.add(0 if ern <= 64 else (1 if ern <= 2048 else 2))
+        n_eover += eover
     assert seen == {0, 1, 2}
+    assert nover == n_eover
 
 
 @pytest.mark.parametrize("min_len", [10, 20])

@@ -31,12 +31,15 @@ def test_tag_query_all_size_classes(workdir, x_index):
     en = np.concatenate([en, en[:2], en[:2], en[-40:], en[-40:]])
     rn, po, pos, nover = idx.tag_query_batch(st, en)
     classes = set()
+    n_eover = 0
     for i in range(len(st)):
         ern, epos, eover = t.query(int(st[i]), int(en[i]))
         assert int(rn[i]) == ern, i
         assert np.array_equal(pos[po[i]:po[i + 1]], np.array(epos, dtype=np.uint64)), (i, ern)
         classes.add(0 if ern <= 16 else 1 if ern <= 64 else 2 if ern <= 2048 else 3 if ern <= 16384 else 4)
+        n_eover += eover
     assert classes == {0, 1, 2, 3, 4}
+    assert nover == n_eover
 
 
 def test_tag_buckets_sparse_and_crowded(workdir, x_index):
@@ -61,7 +64,10 @@ def test_tag_buckets_sparse_and_crowded(workdir, x_index):
                          np.array([0, 0, 50, 9000, 4000, 40], dtype=np.uint64)])
     en = np.minimum(st + ln, np.uint64(total - 1))
     rn, po, pos, nover = idx.tag_query_batch(st, en)
+    n_eover = 0
     for i in range(len(st)):
         ern, epos, eover = t.query(int(st[i]), int(en[i]))
         assert int(rn[i]) == ern, (i, int(st[i]), int(en[i]))
         assert np.array_equal(pos[po[i]:po[i + 1]], np.array(epos, dtype=np.uint64)), (i, int(st[i]), int(en[i]), ern)
+        n_eover += eover
+    assert nover == n_eover
