@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset) */
+#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only) */
 
 typedef enum {
     PGX_OK = 0,
@@ -486,6 +486,72 @@ pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t max_occ, void
  * free of the batch; PGX_ERR_ARG when there is none. */
 pgx_status pgx_batch_locations(pgx_batch *b, pgx_locations *out);
 pgx_status pgx_batch_device_locations(pgx_batch *b, pgx_locations *out);
+
+/* ---- compact result: the result of a run as a byte stream, encoded on the device, expanded on the host ---------------------
+ * What pgx_batch_result downloads is six dense uint64 arrays (8 bytes per read, 48 per MEM, 8 per graph position), nearly all of
+ * them zero bits.  The compact form carries the same values and is expanded to the same pgx_result; only it crosses the link.
+ * Opt-in: pgx_batch_result and every other output keep their bytes.  Like them it replaces the reference's per-read result
+ * vectors (std::vector<MEM> of find_all_mems, include/pangenome_index/algorithm.hpp:739-757, and the position sets of
+ * TagArray::query_compressed_compact, src/tag_arrays.cpp:830-890), which never leave the process there.
+ *
+ * THE FORMAT (part of the ABI).  Every number is an unsigned LEB128 varint: seven bits per byte, low bits first, the high bit of
+ * a byte says that another follows; a uint64 takes 1 to 10 bytes (the tenth is 0 or 1); the encoder always emits the shortest
+ * form.  Reads are cut into blocks of PGX_COMPACT_BLOCK_READS = 64 consecutive reads: block k covers reads
+ * [64 k, min(64 k + 64, n_reads)) and occupies bytes[block_offsets[k] .. block_offsets[k + 1]); n_blocks = ceil(n_reads / 64).
+ * Each block is padded with zero bytes (fewer than 8) to a multiple of 8 bytes.  A block is three homogeneous sections without
+ * separators:
+ *   1. for each read of the block: its number of MEMs;
+ *   2. for each MEM of the block, in result order: start, end - start, bwt_start, (uint64_t)size, and with PGX_COMPACT_TAGS also
+ *      tag_run_count and the MEM's number of positions;
+ *   3. with PGX_COMPACT_TAGS: for each MEM in order its positions, the first as it is, each following one as the difference to
+ *      its predecessor.
+ * All differences are taken modulo 2^64, so any values round-trip exactly (negative size, unsorted positions).  Three tables of
+ * n_blocks + 1 entries go with the bytes: block_offsets, block_first_mem (= mem_offsets[min(64 k, n_reads)]) and block_first_pos
+ * (= pos_offsets[block_first_mem[k]]; all zero without PGX_COMPACT_TAGS); with them every block expands independently.  The stream
+ * is canonical: one result has one encoding (tests/compact_emu.py restates it in Python). */
+#define PGX_COMPACT_BLOCK_READS 64u
+#define PGX_COMPACT_TAGS 1u /* pgx_compact_result.flags: the MEMs carry tag_run_count and positions */
+typedef struct {
+    uint64_t n_reads, n_mems, n_positions, n_extensions, n_tag_overflow; /* as in pgx_result */
+    uint32_t flags;       /* PGX_COMPACT_TAGS */
+    uint32_t block_reads; /* PGX_COMPACT_BLOCK_READS */
+    uint64_t n_blocks;
+    uint64_t n_bytes;     /* = block_offsets[n_blocks] */
+    const uint64_t *block_offsets;   /* n_blocks + 1 */
+    const uint64_t *block_first_mem; /* n_blocks + 1 */
+    const uint64_t *block_first_pos; /* n_blocks + 1 */
+    const uint8_t *bytes;            /* n_bytes */
+    float ms_encode;      /* device time of the two encode kernels and the scan between them; 0 unless the run had PGX_RUN_TIMING */
+} pgx_compact_result;
+/* In place of pgx_batch_result: encodes the result of the last run on the batch's own stream (a sizing kernel, the scan of the
+ * block sizes, a fill kernel: one wave per block) and downloads the three tables and the bytes into pinned buffers owned by the
+ * batch, which only ever grow.  The host waits once for the tables -- their last entry sizes the byte buffer -- and once for the
+ * bytes.  Valid until the next run, upload or free of the batch.  PGX_COMPACT_TAGS is set exactly when the run had PGX_RUN_TAGS.
+ * The device result is left untouched: pgx_batch_result, pgx_batch_device_result and pgx_batch_locate give the same bytes before
+ * and after.  PGX_ERR_ARG without a completed run. */
+pgx_status pgx_batch_result_compact(pgx_batch *b, pgx_compact_result *out);
+/* Host only, no device: expands blocks [first_block, first_block + n_blocks) of c into caller arrays sized from c's counters
+ * (mem_offsets n_reads + 1, mems n_mems, and with PGX_COMPACT_TAGS tag_run_counts n_mems, pos_offsets n_mems + 1, positions
+ * n_positions; without it the three may be NULL and are not touched), every entry at its global index: what pgx_batch_result
+ * would have delivered there.  The closing mem_offsets[n_reads] and pos_offsets[n_mems] are written by the call whose range ends
+ * at c->n_blocks (with n_reads = 0 that is the call over no blocks).  Blocks are independent: callers thread it over block
+ * ranges themselves.  It never reads outside bytes[0 .. n_bytes) and never writes outside the index ranges the block tables
+ * give (all checked against the counters first).  PGX_ERR_FORMAT with a message naming the block for: a block that ends inside
+ * a number or before its last one, a varint longer than 10 bytes, a tenth byte above 1, non-zero or excess padding, tables that
+ * decrease or point beyond n_bytes / n_mems / n_positions, counts that disagree with the block tables.  What it wrote for
+ * the blocks before the offending one stays.  PGX_ERR_ARG for a null array or a block range beyond c->n_blocks. */
+pgx_status pgx_compact_expand(const pgx_compact_result *c, uint64_t first_block, uint64_t n_blocks, uint64_t *mem_offsets, pgx_mem *mems,
+                              uint64_t *tag_run_counts, uint64_t *pos_offsets, uint64_t *positions);
+/* Host only: the largest stream any result of these counts can take (every varint 10 bytes, 7 bytes of padding a block);
+ * flags: PGX_COMPACT_TAGS. */
+uint64_t pgx_compact_bound(uint64_t n_reads, uint64_t n_mems, uint64_t n_positions, uint32_t flags);
+/* The encoder alone, on an arbitrary result held in host arrays (how it is tested on values no small index produces): uploads
+ * in->mem_offsets / mems (and, exactly when in->pos_offsets is non-NULL, tag_run_counts / pos_offsets / positions) to `device`,
+ * runs the same two kernels, downloads the stream into bytes[0 .. bytes_cap) and the tables (n_blocks + 1 entries each).
+ * *n_bytes is always the size of the stream; PGX_ERR_NOMEM when it exceeds bytes_cap (nothing is written to bytes then, the tables
+ * are).  PGX_ERR_ARG unless mem_offsets and pos_offsets start at 0, never decrease and end at n_mems / n_positions. */
+pgx_status pgx_compact_encode(int device, const pgx_result *in, uint8_t *bytes, uint64_t bytes_cap, uint64_t *block_offsets,
+                              uint64_t *block_first_mem, uint64_t *block_first_pos, uint64_t *n_bytes);
 
 /* Convenience: create + run + result in one call (what the find_mems CLI uses). */
 pgx_status pgx_find_mems_batch(pgx_index *h, int device, const uint8_t *reads, const uint64_t *offsets,

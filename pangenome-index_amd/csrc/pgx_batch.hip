@@ -19,6 +19,20 @@
 // ------------------------------------------------------------------------------------------
 struct pgx_chunk { uint64_t r0, r1, slot_base, slots; }; // consecutive reads sharing one pass over the slot buffer
 
+// the compact result form (pgx_batch_result_compact; pgx_compact_encode uses one of its own): grow-only like the other result buffers
+struct CompactWork {
+    DevBuf sizes, tab, bytes, scan_tmp; // padded bytes per block; block_offsets | block_first_mem | block_first_pos; the stream
+    HostBuf h_tab, h_bytes;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the sizing kernel + scan, around the fill kernel
+    void release() {
+        DevBuf *all[] = {&sizes, &tab, &bytes, &scan_tmp};
+        for (DevBuf *d : all) d->release();
+        h_tab.release(); h_bytes.release();
+        for (auto &e : ev)
+            if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    }
+};
+
 struct pgx_batch {
     pgx_index *h = nullptr;
     pgx_device_image *dimg = nullptr;
@@ -49,6 +63,7 @@ struct pgx_batch {
     uint64_t max_read_len = 0; // longest read of the upload (sizes the LDS columns of the packed pairs kernel)
     TagWork tw;
     LocWork lw; // pgx_batch_locate
+    CompactWork cw; // pgx_batch_result_compact
     uint64_t n_mems = 0, n_positions = 0, n_ext = 0, n_tag_overflow = 0;
     bool ran = false, ran_tags = false;
     // speculative sizing (pgx_batch_run): what the last run with these parameters produced
@@ -74,6 +89,7 @@ static void batch_release(pgx_batch *b) {
         for (DevBuf *d : all) d->release();
         b->tw.release();
         b->lw.release();
+        b->cw.release();
         HostBuf *hb[] = {&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]};
         for (HostBuf *x : hb) x->release();
         for (auto &e : b->ev)
@@ -1077,6 +1093,146 @@ extern "C" pgx_status pgx_batch_result(pgx_batch *b, pgx_result *out) {
         out->n_tag_overflow = b->n_tag_overflow;
     }
     HIPCHECK(hipStreamSynchronize(b->own)); // (the run itself completed inside pgx_batch_run, on whatever stream it used)
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// compact result form (pgx_compact_kernels.hip; the format: include/pgx.h "compact result"; the host decoder: pgx_compact.cpp)
+// Sizes every block, scans the sizes into block_offsets and brings the three tables to w.h_tab: the host waits for them here, their last entry
+// sizes the byte buffer.  Returns the size of the stream.
+static uint64_t compact_tables(CompactWork &w, const uint64_t *d_mem_off, const pgx_mem *d_mems, const uint64_t *d_run_nums, const uint64_t *d_pos_off,
+                               const uint64_t *d_positions, uint64_t n_reads, bool tags, bool timed, hipStream_t s) {
+    const uint64_t nb = (n_reads + PGX_COMPACT_BLOCK_READS - 1) / PGX_COMPACT_BLOCK_READS;
+    w.sizes.ensure((nb ? nb : 1) * 8);
+    w.tab.ensure(3 * (nb + 1) * 8);
+    w.h_tab.ensure(3 * (nb + 1) * 8);
+    uint64_t *bo = w.tab.as<uint64_t>(), *fm = bo + (nb + 1), *fp = fm + (nb + 1);
+    if (timed) {
+        for (auto &e : w.ev)
+            if (!e) HIPCHECK(hipEventCreate(&e));
+        HIPCHECK(hipEventRecord(w.ev[0], s));
+    }
+    hipLaunchKernelGGL(pgx_compact_size_kernel, dim3(grid_for(nb + 1, 4)), dim3(256), 0, s, d_mem_off, d_mems, d_run_nums, d_pos_off, d_positions, n_reads, nb,
+                       tags ? 1 : 0, w.sizes.as<uint64_t>(), fm, fp);
+    HIPCHECK(hipGetLastError());
+    scan_excl(1, w.sizes.p, nb, 0, bo, w.scan_tmp, s);
+    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
+    HIPCHECK(hipMemcpyAsync(w.h_tab.p, w.tab.p, 3 * (nb + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    return w.h_tab.as<uint64_t>()[nb];
+}
+
+// the stream itself into w.bytes (grown to `total` first); async on s
+static void compact_fill(CompactWork &w, const uint64_t *d_mem_off, const pgx_mem *d_mems, const uint64_t *d_run_nums, const uint64_t *d_pos_off,
+                         const uint64_t *d_positions, uint64_t n_reads, bool tags, bool timed, uint64_t total, hipStream_t s) {
+    const uint64_t nb = (n_reads + PGX_COMPACT_BLOCK_READS - 1) / PGX_COMPACT_BLOCK_READS;
+    w.bytes.ensure(total ? total : 8);
+    if (timed) HIPCHECK(hipEventRecord(w.ev[2], s));
+    if (nb) {
+        // PGX_COMPACT_STAGE=1 (read per call): the fill kernel that stages its bytes in LDS and stores 8-byte words; the same stream either way
+        const char *e = std::getenv("PGX_COMPACT_STAGE");
+        const bool staged = e && e[0] == '1' && e[1] == 0;
+        hipLaunchKernelGGL(staged ? pgx_compact_fill_staged_kernel : pgx_compact_fill_kernel, dim3(grid_for(nb, 4)), dim3(256), 0, s, d_mem_off, d_mems, d_run_nums, d_pos_off, d_positions, n_reads, nb,
+                           tags ? 1 : 0, (const uint64_t *)w.tab.as<uint64_t>(), w.bytes.as<uint8_t>());
+        HIPCHECK(hipGetLastError());
+    }
+    if (timed) HIPCHECK(hipEventRecord(w.ev[3], s));
+}
+
+static float compact_ms(CompactWork &w) { // (behind the synchronisation that follows compact_fill)
+    float a = 0, c = 0;
+    HIPCHECK(hipEventElapsedTime(&a, w.ev[0], w.ev[1]));
+    HIPCHECK(hipEventElapsedTime(&c, w.ev[2], w.ev[3]));
+    return a + c;
+}
+
+extern "C" pgx_status pgx_batch_result_compact(pgx_batch *b, pgx_compact_result *out) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_result_compact");
+    checked_device_count();
+    if (!b || !out || !b->ran) throw Error(PGX_ERR_ARG, "pgx_batch_result_compact: batch has not been run");
+    use_device(b->device);
+    CompactWork &w = b->cw;
+    hipStream_t s = b->own; // (the run itself completed inside pgx_batch_run, on whatever stream it used)
+    const bool tags = b->ran_tags, timed = b->timed;
+    const uint64_t n = b->n_reads, nb = (n + PGX_COMPACT_BLOCK_READS - 1) / PGX_COMPACT_BLOCK_READS;
+    const uint64_t *run_nums = tags ? b->tw.run_nums.as<uint64_t>() : nullptr, *pos_off = tags ? b->tw.pos_off.as<uint64_t>() : nullptr;
+    const uint64_t *positions = tags ? b->tw.positions.as<uint64_t>() : nullptr;
+    const uint64_t total = compact_tables(w, b->mem_off.as<uint64_t>(), b->mems.as<pgx_mem>(), run_nums, pos_off, positions, n, tags, timed, s);
+    compact_fill(w, b->mem_off.as<uint64_t>(), b->mems.as<pgx_mem>(), run_nums, pos_off, positions, n, tags, timed, total, s);
+    w.h_bytes.ensure(total ? total : 8);
+    if (total) HIPCHECK(hipMemcpyAsync(w.h_bytes.p, w.bytes.p, total, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    std::memset(out, 0, sizeof *out);
+    out->n_reads = n;
+    out->n_mems = b->n_mems;
+    out->n_extensions = b->n_ext;
+    if (tags) {
+        out->n_positions = b->n_positions;
+        out->n_tag_overflow = b->n_tag_overflow;
+        out->flags = PGX_COMPACT_TAGS;
+    }
+    out->block_reads = PGX_COMPACT_BLOCK_READS;
+    out->n_blocks = nb;
+    out->n_bytes = total;
+    out->block_offsets = w.h_tab.as<uint64_t>();
+    out->block_first_mem = out->block_offsets + (nb + 1);
+    out->block_first_pos = out->block_first_mem + (nb + 1);
+    out->bytes = w.h_bytes.as<uint8_t>();
+    out->ms_encode = timed ? compact_ms(w) : 0;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_compact_encode(int device, const pgx_result *in, uint8_t *bytes, uint64_t bytes_cap, uint64_t *block_offsets,
+                                         uint64_t *block_first_mem, uint64_t *block_first_pos, uint64_t *n_bytes) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_compact_encode");
+    use_device(device);
+    if (!in || !in->mem_offsets || (in->n_mems && !in->mems) || (bytes_cap && !bytes) || !block_offsets || !block_first_mem || !block_first_pos || !n_bytes)
+        throw Error(PGX_ERR_ARG, "pgx_compact_encode: null argument");
+    const bool tags = in->pos_offsets != nullptr;
+    const uint64_t n = in->n_reads, m = in->n_mems, np = tags ? in->n_positions : 0;
+    if (tags && ((m && !in->tag_run_counts) || (np && !in->positions))) throw Error(PGX_ERR_ARG, "pgx_compact_encode: pos_offsets without tag_run_counts / positions");
+    auto check_csr = [](const uint64_t *off, uint64_t cnt, uint64_t last, const char *name) { // the kernels index the arrays by these
+        bool ok = off[0] == 0 && off[cnt] == last;
+        for (uint64_t i = 0; ok && i < cnt; i++) ok = off[i] <= off[i + 1];
+        if (!ok) throw Error(PGX_ERR_ARG, std::string("pgx_compact_encode: ") + name + " must start at 0, never decrease and end at the count of what it indexes");
+    };
+    check_csr(in->mem_offsets, n, m, "mem_offsets");
+    if (tags) check_csr(in->pos_offsets, m, np, "pos_offsets");
+    struct Work { // device copies of the input + the encoder's buffers, released on every way out
+        DevBuf mem_off, mems, run_nums, pos_off, positions;
+        CompactWork w;
+        ~Work() {
+            DevBuf *all[] = {&mem_off, &mems, &run_nums, &pos_off, &positions};
+            for (DevBuf *d : all) d->release();
+            w.release();
+        }
+    } k;
+    upload(k.mem_off, in->mem_offsets, (n + 1) * 8);
+    upload(k.mems, in->mems, m * sizeof(pgx_mem));
+    if (tags) {
+        upload(k.run_nums, in->tag_run_counts, m * 8);
+        upload(k.pos_off, in->pos_offsets, (m + 1) * 8);
+        upload(k.positions, in->positions, np * 8);
+    }
+    hipStream_t s = nullptr;
+    const uint64_t nb = (n + PGX_COMPACT_BLOCK_READS - 1) / PGX_COMPACT_BLOCK_READS;
+    const uint64_t total = compact_tables(k.w, k.mem_off.as<uint64_t>(), k.mems.as<pgx_mem>(), k.run_nums.as<uint64_t>(), k.pos_off.as<uint64_t>(),
+                                          k.positions.as<uint64_t>(), n, tags, false, s);
+    *n_bytes = total;
+    const uint64_t *t = k.w.h_tab.as<uint64_t>();
+    std::memcpy(block_offsets, t, (nb + 1) * 8);
+    std::memcpy(block_first_mem, t + (nb + 1), (nb + 1) * 8);
+    std::memcpy(block_first_pos, t + 2 * (nb + 1), (nb + 1) * 8);
+    if (total > bytes_cap)
+        throw Error(PGX_ERR_NOMEM, "pgx_compact_encode: the stream takes " + std::to_string(total) + " bytes, bytes_cap is " + std::to_string(bytes_cap));
+    compact_fill(k.w, k.mem_off.as<uint64_t>(), k.mems.as<pgx_mem>(), k.run_nums.as<uint64_t>(), k.pos_off.as<uint64_t>(), k.positions.as<uint64_t>(), n, tags,
+                 false, total, s);
+    if (total) HIPCHECK(hipMemcpyAsync(bytes, k.w.bytes.p, total, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
     return PGX_OK;
     PGX_GUARD_END
 }

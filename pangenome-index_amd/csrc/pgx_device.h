@@ -178,6 +178,17 @@ __global__ void pgx_compact_mems_kernel(uint64_t first_read, uint64_t n_reads, c
                                         const pgx_mem *slots, const uint32_t *mem_count, const uint64_t *local_off,
                                         uint64_t mem_base, pgx_mem *mems, uint64_t cap_mems, uint64_t *abort, const uint32_t *ovf_base, uint64_t ovf_cap);
 
+// ---- pgx_compact_kernels.hip: the compact result form (pgx_batch_result_compact, pgx_compact_encode); one wave per block of 64 reads
+__global__ void pgx_compact_size_kernel(const uint64_t *mem_off, const pgx_mem *mems, const uint64_t *run_nums, const uint64_t *pos_off,
+                                        const uint64_t *positions, uint64_t n_reads, uint64_t n_blocks, int tags, uint64_t *sizes, uint64_t *first_mem,
+                                        uint64_t *first_pos);
+__global__ void pgx_compact_fill_kernel(const uint64_t *mem_off, const pgx_mem *mems, const uint64_t *run_nums, const uint64_t *pos_off,
+                                        const uint64_t *positions, uint64_t n_reads, uint64_t n_blocks, int tags, const uint64_t *block_offsets,
+                                        uint8_t *bytes);
+__global__ void pgx_compact_fill_staged_kernel(const uint64_t *mem_off, const pgx_mem *mems, const uint64_t *run_nums, const uint64_t *pos_off,
+                                               const uint64_t *positions, uint64_t n_reads, uint64_t n_blocks, int tags, const uint64_t *block_offsets,
+                                               uint8_t *bytes);
+
 // ---- pgx_tag_kernels.hip: the tag stage
 __global__ void pgx_tag_pair_kernel(const uint64_t *tstart, const uint64_t *tvals, uint64_t n_runs, uint64_t n_items, ulonglong2 *out);
 __global__ void pgx_tag_bucket_kernel(const uint64_t *tstart, const uint64_t *tvals, uint64_t n_runs, uint64_t n_items, uint32_t shift, uint64_t n_buckets, uint4 *out);

@@ -57,6 +57,17 @@ class Locations(C.Structure):  # pgx_locations: host pointers (pgx_batch_locatio
                 ("values", p), ("ms_locate", C.c_float), ("set_words", C.c_uint32)]
 
 
+class CompactResult(C.Structure):  # pgx_compact_result
+    _fields_ = [("n_reads", u64), ("n_mems", u64), ("n_positions", u64), ("n_extensions", u64), ("n_tag_overflow", u64),
+                ("flags", u32), ("block_reads", u32), ("n_blocks", u64), ("n_bytes", u64),
+                ("block_offsets", C.POINTER(u64)), ("block_first_mem", C.POINTER(u64)), ("block_first_pos", C.POINTER(u64)),
+                ("bytes", C.POINTER(C.c_uint8)), ("ms_encode", C.c_float)]
+
+
+COMPACT_BLOCK_READS = 64
+COMPACT_TAGS = 1  # pgx_compact_result.flags
+
+
 class DeviceArray:
     """a device buffer owned by a batch, exposed through __cuda_array_interface__ (zero copy: torch.as_tensor(a, device="cuda"));
     64-bit unsigned values are presented as int64"""
@@ -175,6 +186,11 @@ def lib():
     L.pgx_batch_locate.argtypes = [p, u32, u64, p]
     L.pgx_batch_locations.argtypes = [p, C.POINTER(Locations)]
     L.pgx_batch_device_locations.argtypes = [p, C.POINTER(Locations)]
+    L.pgx_batch_result_compact.argtypes = [p, C.POINTER(CompactResult)]
+    L.pgx_compact_expand.argtypes = [C.POINTER(CompactResult), u64, u64, p, p, p, p, p]
+    L.pgx_compact_bound.argtypes = [u64, u64, u64, u32]
+    L.pgx_compact_bound.restype = u64
+    L.pgx_compact_encode.argtypes = [C.c_int, C.POINTER(Result), p, u64, p, p, p, C.POINTER(u64)]
     L.pgx_batch_free.argtypes = [p]
     L.pgx_batch_free.restype = None
     L.pgx_find_mems_batch.argtypes = [p, C.c_int, p, p, u64, u64, u64, u32, C.POINTER(p), C.POINTER(Result)]
@@ -528,6 +544,90 @@ def _result_dict(r):
     return out
 
 
+_COMPACT_COUNTERS = ("n_reads", "n_mems", "n_positions", "n_extensions", "n_tag_overflow", "flags", "block_reads", "n_blocks", "n_bytes")
+
+
+def _compact_struct(c):
+    """the pgx_compact_result of a dict as Batch.result_compact() / compact_encode() return it, and the arrays it points into"""
+    keep = [np.ascontiguousarray(c[k], dtype=np.uint64) for k in ("block_offsets", "block_first_mem", "block_first_pos")]
+    keep.append(np.ascontiguousarray(c["bytes"], dtype=np.uint8))
+    r = CompactResult()
+    for k in _COMPACT_COUNTERS:
+        setattr(r, k, int(c[k]))
+    r.block_offsets, r.block_first_mem, r.block_first_pos = (C.cast(a.ctypes.data, C.POINTER(u64)) for a in keep[:3])
+    r.bytes = C.cast(keep[3].ctypes.data, C.POINTER(C.c_uint8))
+    return r, keep
+
+
+def compact_expand_arrays(c):
+    """empty arrays of the sizes a compact result expands to (what compact_expand fills; several calls over block ranges may share them)"""
+    n, m = int(c["n_reads"]), int(c["n_mems"])
+    out = dict(n_extensions=int(c["n_extensions"]), n_tag_overflow=int(c["n_tag_overflow"]))
+    out["mem_offsets"] = np.zeros(n + 1, dtype=np.uint64)
+    out["mems"] = np.zeros(m, dtype=MEM_DTYPE)
+    if int(c["flags"]) & COMPACT_TAGS:
+        out["tag_run_counts"] = np.zeros(m, dtype=np.uint64)
+        out["pos_offsets"] = np.zeros(m + 1, dtype=np.uint64)
+        out["positions"] = np.zeros(int(c["n_positions"]), dtype=np.uint64)
+    return out
+
+
+def compact_expand(c, first_block=0, n_blocks=None, out=None):
+    """pgx_compact_expand (host only): blocks [first_block, first_block + n_blocks) of a compact result (all from first_block on by default)
+    into the dict Batch.result() returns; entries of other blocks stay as they are in `out` (zero in a fresh one)"""
+    r, keep = _compact_struct(c)
+    if n_blocks is None:
+        n_blocks = int(c["n_blocks"]) - first_block
+    if out is None:
+        out = compact_expand_arrays(c)
+    tags = "pos_offsets" in out
+    _check(lib().pgx_compact_expand(C.byref(r), first_block, n_blocks, out["mem_offsets"].ctypes.data, out["mems"].ctypes.data,
+                                    out["tag_run_counts"].ctypes.data if tags else None, out["pos_offsets"].ctypes.data if tags else None,
+                                    out["positions"].ctypes.data if tags else None))
+    del keep
+    return out
+
+
+def compact_bound(n_reads, n_mems, n_positions, flags=0):
+    return int(lib().pgx_compact_bound(n_reads, n_mems, n_positions, flags))
+
+
+def compact_encode(device, result, bytes_cap=None):
+    """pgx_compact_encode: the device encoder on a result dict (mem_offsets, mems and, for the tagged form, tag_run_counts / pos_offsets /
+    positions); returns the dict Batch.result_compact() returns.  bytes_cap: size of the byte buffer handed over (default: the bound)"""
+    mo = np.ascontiguousarray(result["mem_offsets"], dtype=np.uint64)
+    mems = np.ascontiguousarray(result["mems"], dtype=MEM_DTYPE)
+    n, m = len(mo) - 1, len(mems)
+    r = Result()
+    r.n_reads, r.n_mems = n, m
+    r.mem_offsets = C.cast(mo.ctypes.data, C.POINTER(u64))
+    r.mems = mems.ctypes.data
+    tags = "pos_offsets" in result
+    keep = [mo, mems]
+    npos = 0
+    if tags:
+        for k in ("tag_run_counts", "pos_offsets", "positions"):
+            a = np.ascontiguousarray(result[k], dtype=np.uint64)
+            keep.append(a)
+            setattr(r, k, C.cast(a.ctypes.data, C.POINTER(u64)))
+        npos = len(keep[-1])
+        r.n_positions = npos
+    nb = (n + COMPACT_BLOCK_READS - 1) // COMPACT_BLOCK_READS
+    flags = COMPACT_TAGS if tags else 0
+    cap = compact_bound(n, m, npos, flags) if bytes_cap is None else int(bytes_cap)
+    buf = np.zeros(max(cap, 1), dtype=np.uint8)
+    tabs = [np.zeros(nb + 1, dtype=np.uint64) for _ in range(3)]
+    nbytes = u64(0)
+    st = lib().pgx_compact_encode(device, C.byref(r), buf.ctypes.data, cap, tabs[0].ctypes.data, tabs[1].ctypes.data, tabs[2].ctypes.data, C.byref(nbytes))
+    if st != OK:
+        e = PgxError(st, lib().pgx_last_error().decode(errors="replace"))
+        e.n_bytes = int(nbytes.value)  # (ERR_NOMEM: what the stream needs)
+        raise e
+    return dict(n_reads=n, n_mems=m, n_positions=npos, n_extensions=int(result.get("n_extensions", 0)), n_tag_overflow=int(result.get("n_tag_overflow", 0)),
+                flags=flags, block_reads=COMPACT_BLOCK_READS, n_blocks=nb, n_bytes=int(nbytes.value), block_offsets=tabs[0], block_first_mem=tabs[1],
+                block_first_pos=tabs[2], bytes=buf[:int(nbytes.value)].copy(), ms_encode=0.0)
+
+
 def find_mems_sharded(index, devices, reads_cat, offsets, min_len, min_occ, tags=False):
     """pgx_find_mems_sharded: contiguous read slices, slice i on devices[i]; returns the per-slice result dicts in slice order"""
     reads_cat = np.ascontiguousarray(reads_cat, dtype=np.uint8)
@@ -681,6 +781,22 @@ class Batch:
             out["tag_run_counts"] = _u64_array(r.tag_run_counts, m)
             out["pos_offsets"] = _u64_array(r.pos_offsets, m + 1)
             out["positions"] = _u64_array(r.positions, int(r.n_positions))
+        return out
+
+    def result_compact(self, copy=True):
+        """pgx_batch_result_compact: the last run's result as the compact byte stream (include/pgx.h "compact result"): the counters, the tables
+        block_offsets / block_first_mem / block_first_pos (uint64[n_blocks + 1]) and bytes (uint8[n_bytes]); compact_expand() turns it into what
+        result() returns.  copy=False: views of the batch's pinned buffers, valid until its next run / upload / free"""
+        r = CompactResult()
+        _check(self.L.pgx_batch_result_compact(self.b, C.byref(r)))
+        out = {k: int(getattr(r, k)) for k in _COMPACT_COUNTERS}
+        out["ms_encode"] = float(r.ms_encode)
+        nb, nbytes = out["n_blocks"], out["n_bytes"]
+        for k in ("block_offsets", "block_first_mem", "block_first_pos"):
+            a = np.ctypeslib.as_array(getattr(r, k), shape=(nb + 1,))
+            out[k] = a.copy() if copy else a
+        a = np.ctypeslib.as_array(r.bytes, shape=(nbytes,)) if nbytes else np.zeros(0, dtype=np.uint8)
+        out["bytes"] = a.copy() if copy else a
         return out
 
     def result_counts(self):

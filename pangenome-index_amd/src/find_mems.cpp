@@ -8,7 +8,9 @@
 //                 --mode compat|strict, --batch N (reads per device batch), --tags-format auto|bytecode|compact,
 //                 --quiet (no per-read stderr line), --reads-format lines|fasta|fastq|auto (default lines; auto: by the first byte,
 //                 '>' FASTA, '@' FASTQ, otherwise lines), --device-parse (line files parsed on the device too; FASTA / FASTQ always are),
-//                 --locate positions|seqs (the occurrences of every MEM, pgx_batch_locate), --locate-max K (MEMs with more occurrences: not located)
+//                 --locate positions|seqs (the occurrences of every MEM, pgx_batch_locate), --locate-max K (MEMs with more occurrences: not located),
+//                 --result full|compact (default full; compact: the result crosses the link as the compact byte stream, pgx_batch_result_compact,
+//                 and every formatter thread expands its own blocks, pgx_compact_expand; the same text either way)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -173,12 +175,38 @@ static void format_range(const pgx_result &r, size_t lo, size_t hi, uint64_t fir
     out.resize((size_t)(p - &out[0]));
 }
 
+// --result compact: the arrays a worker expands its batches into (grow-only, not cleared: every entry the formatters read is written first)
+template <class T> struct GrowArray {
+    std::unique_ptr<T[]> p;
+    size_t cap = 0;
+    T *ensure(size_t n) {
+        if (n > cap) { cap = n + n / 4 + 64; p.reset(new T[cap]); }
+        return p.get();
+    }
+};
+struct ExpandBufs {
+    GrowArray<uint64_t> mem_off, run_counts, pos_off, positions;
+    GrowArray<pgx_mem> mems;
+};
+// all formatter threads of a batch have expanded their blocks (a range reads the offsets that close it, which its neighbour writes)
+struct Rendezvous {
+    std::mutex mu;
+    std::condition_variable cv;
+    unsigned waiting;
+    explicit Rendezvous(unsigned n) : waiting(n) {}
+    void arrive_and_wait() {
+        std::unique_lock<std::mutex> lk(mu);
+        if (--waiting == 0) cv.notify_all();
+        else cv.wait(lk, [&]() { return waiting == 0; });
+    }
+};
+
 int main(int argc, char **argv) {
     if (argc < 6) {
         std::cerr << "usage: find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ>"
                      " [--device N | --gpus N | --devices a,b,..] [--streams W] [--mode compat|strict] [--batch N]"
                      " [--tags-format auto|bytecode|compact] [--quiet] [--reads-format lines|fasta|fastq|auto] [--device-parse]"
-                     " [--locate positions|seqs] [--locate-max K]" << std::endl;
+                     " [--locate positions|seqs] [--locate-max K] [--result full|compact]" << std::endl;
         return EXIT_FAILURE;
     }
     const std::string r_index_file = argv[1], tag_array_index = argv[2], reads_file = argv[3];
@@ -192,6 +220,7 @@ int main(int argc, char **argv) {
     std::string reads_format = "lines";
     int locate_mode = LOCATE_NONE;
     uint64_t locate_max = 0;
+    bool compact_result = false;
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -232,6 +261,12 @@ int main(int argc, char **argv) {
             const unsigned long long k = f.empty() || f.size() > 19 || f.find_first_not_of("0123456789") != std::string::npos ? 0 : std::strtoull(f.c_str(), &endp, 10);
             if (!endp || *endp || errno) { std::cerr << "--locate-max: a number of occurrences >= 0 (0: no cap)" << std::endl; return EXIT_FAILURE; }
             locate_max = k;
+        }
+        else if (a == "--result") {
+            const std::string f = next();
+            if (f == "compact") compact_result = true;
+            else if (f == "full") compact_result = false;
+            else { std::cerr << "--result: full or compact" << std::endl; return EXIT_FAILURE; }
         }
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
@@ -389,6 +424,8 @@ int main(int argc, char **argv) {
         return j;
     };
     // PGX_CLI_STATS=1: busy seconds of every stage (summed over its threads) on stderr at the end
+    // (with --result compact "download" holds the encode on the device and the download of the stream, and "format" holds the host expansion
+    // of the blocks next to the formatting: the two forms split the same work differently between the two figures)
     const bool cli_stats = std::getenv("PGX_CLI_STATS") != nullptr;
     std::atomic<uint64_t> ns_parse{0}, ns_upload{0}, ns_run{0}, ns_download{0}, ns_format{0}, ns_write{0};
     auto now_ns = []() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -425,6 +462,7 @@ int main(int argc, char **argv) {
 
     auto worker = [&](int device) {
         pgx_batch *b = nullptr; // long-lived: its device and pinned host buffers are reused by every batch of this worker
+        ExpandBufs xb;          // --result compact: what the formatter threads expand into
         for (;;) {
             std::unique_ptr<Job> j;
             {
@@ -498,7 +536,20 @@ int main(int argc, char **argv) {
             uint64_t t1 = now_ns();
             if (st == PGX_OK) st = pgx_batch_run(b, mem_length, min_occ, PGX_RUN_TAGS | PGX_RUN_TIMING, nullptr);
             uint64_t t2 = now_ns();
-            if (st == PGX_OK) st = pgx_batch_result(b, &r);
+            pgx_compact_result cr;
+            if (st == PGX_OK && compact_result) {
+                st = pgx_batch_result_compact(b, &cr);
+                if (st == PGX_OK) { // the arrays of r are filled block range by block range in the formatter threads below
+                    std::memset(&r, 0, sizeof r);
+                    r.n_reads = cr.n_reads; r.n_mems = cr.n_mems; r.n_positions = cr.n_positions;
+                    r.n_extensions = cr.n_extensions; r.n_tag_overflow = cr.n_tag_overflow;
+                    r.mem_offsets = xb.mem_off.ensure(cr.n_reads + 1);
+                    r.mems = xb.mems.ensure(cr.n_mems + 1);
+                    r.tag_run_counts = xb.run_counts.ensure(cr.n_mems + 1);
+                    r.pos_offsets = xb.pos_off.ensure(cr.n_mems + 1);
+                    r.positions = xb.positions.ensure(cr.n_positions + 1);
+                }
+            } else if (st == PGX_OK) st = pgx_batch_result(b, &r);
             pgx_locations loc;
             LocateOut lout = locate_out;
             if (st == PGX_OK && locate_mode) {
@@ -529,12 +580,40 @@ int main(int argc, char **argv) {
                 const unsigned parts = n < 4096 ? 1u : n_fmt;
                 d->outs.resize(parts);
                 d->errs.resize(parts);
-                if (parts == 1) format_range(r, 0, n, j->first_seq, quiet, lout, d->outs[0], d->errs[0]);
-                else {
+                // --result compact: the parts are cut on multiples of 64 reads and every thread expands the blocks of its part first
+                auto cut = [&](unsigned w) -> size_t {
+                    if (w >= parts) return n;
+                    const size_t at = n * w / parts;
+                    return compact_result ? at - at % PGX_COMPACT_BLOCK_READS : at;
+                };
+                auto expand_part = [&](unsigned w) -> std::string {
+                    const uint64_t k0 = cut(w) / PGX_COMPACT_BLOCK_READS, k1 = w + 1 >= parts ? cr.n_blocks : cut(w + 1) / PGX_COMPACT_BLOCK_READS;
+                    if (pgx_compact_expand(&cr, k0, k1 - k0, const_cast<uint64_t *>(r.mem_offsets), const_cast<pgx_mem *>(r.mems), const_cast<uint64_t *>(r.tag_run_counts),
+                                           const_cast<uint64_t *>(r.pos_offsets), const_cast<uint64_t *>(r.positions)) != PGX_OK)
+                        return pgx_last_error(); // (the message is thread-local)
+                    return std::string();
+                };
+                if (parts == 1) {
+                    if (compact_result) d->error = expand_part(0);
+                    if (d->error.empty()) format_range(r, 0, n, j->first_seq, quiet, lout, d->outs[0], d->errs[0]);
+                } else {
                     std::vector<std::thread> pool;
+                    std::vector<std::string> xerr(parts);
+                    Rendezvous expanded(parts);
+                    std::atomic<bool> bad{false};
                     for (unsigned w = 0; w < parts; w++)
-                        pool.emplace_back([&, w]() { format_range(r, n * w / parts, n * (w + 1) / parts, j->first_seq, quiet, lout, d->outs[w], d->errs[w]); });
+                        pool.emplace_back([&, w]() {
+                            if (compact_result) {
+                                xerr[w] = expand_part(w);
+                                if (!xerr[w].empty()) bad = true;
+                                expanded.arrive_and_wait();
+                                if (bad) return;
+                            }
+                            format_range(r, cut(w), cut(w + 1), j->first_seq, quiet, lout, d->outs[w], d->errs[w]);
+                        });
                     for (auto &th : pool) th.join();
+                    for (auto &e : xerr)
+                        if (!e.empty() && d->error.empty()) d->error = e;
                 }
                 ns_format += now_ns() - t3;
             }
