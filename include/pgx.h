@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only) */
+#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only), the device index build (pgx_build_index_from_text_device, pgx_build_index_from_texts_device, pgx_build_index_device_timing: new entry points only) */
 
 typedef enum {
     PGX_OK = 0,
@@ -143,7 +143,7 @@ pgx_status pgx_index_image_view(const pgx_index *h, int which, const void **ptr,
  * nothing is copied where the index has no such image. */
 pgx_status pgx_index_device_view(pgx_index *h, int device, int which, void *out, uint64_t bytes);
 
-/* ---- index construction (build side; CPU, run once) --------------------------------------- */
+/* ---- index construction (build side, run once; on the CPU, or with the suffix sorting on a device: pgx_build_index_from_text[s]_device) --- */
 /* Replaces build_rindex (src/build_rindex.cpp:13-21 -> FastLocate(std::string) src/r-index.cpp:778
  * + serialize_encoded :297-376).  encoded=0 writes the legacy layout (serialize, :266-294). */
 pgx_status pgx_build_rindex(const char *rlbwt_path, const char *out_ri_path, int encoded);
@@ -159,6 +159,33 @@ pgx_status pgx_build_index_from_text(const char *text_path, const char *out_rlbw
  * to what the single call writes for the concatenation; every text must stay below 2^31 symbols, the collection may have any size
  * (the reference takes grlBWT's output of any size: FastLocate(std::string), src/r-index.cpp:778-1139). */
 pgx_status pgx_build_index_from_texts(const char *const *text_paths, uint32_t n_texts, const char *out_rlbwt_path, const char *out_ri_path, int encoded);
+/* pgx_build_index_from_text / _texts with the suffix sorting, the BWT and its runs computed on `device` (prefix doubling over a hand-written
+ * LSD radix sort, pgx_build_sa_kernels.hip); the host writes the two files from the runs and the suffixes at their borders, with the writers of
+ * the CPU calls.  The files are byte-identical to what the CPU calls write for the same input.  No CPU fallback.
+ *   Input     the rules of the CPU calls: a text that does not end in '\n' gets one; an empty file is PGX_ERR_FORMAT; several texts are their
+ *             concatenation in argument order (their sequences in that order).  The device sorts the whole collection at once, so the _texts
+ *             call needs no merge: it exists so that per-chromosome texts need not be concatenated on disk.
+ *   Order     symbols compare by byte value ('\n' < A < C < G < N < T), two endmarkers by sequence number; the symbol before text position 0
+ *             is '\n'.
+ *   Alphabet  exactly '\n' A C G N T.  Any other byte: PGX_ERR_UNSUPPORTED naming the byte and its offset, before any file is written (the CPU
+ *             calls fail on such a text too, at their .ri stage: "BWT symbol outside {\n,A,C,G,N,T}").
+ *   Size      fewer than 2^32 - 2^20 symbols in total (text positions and ranks are uint32_t; twice what one text of the CPU calls may
+ *             hold).  Beyond: PGX_ERR_UNSUPPORTED naming pgx_build_index_from_texts, decided from the file sizes (and the last byte of each
+ *             text: one that lacks its newline counts one more) before any text is read or anything is allocated.
+ *   Memory    the device bytes are computed from the file sizes before the first allocation (about 35 bytes a symbol; the formula is in
+ *             DESIGN.md) and compared with the free device memory, or with PGX_BUILD_DEVICE_BUDGET_MB (environment, read per call, fractions
+ *             allowed) in its place: PGX_ERR_NOMEM with both numbers.  There is no chunked mode.
+ *   Rounds    at most 40 doubling rounds; PGX_ERR_HIP "suffix sort did not converge" after that (no text below the size bound needs more than 29).
+ *   Files     written under temporary names (unique per call) and renamed when both are complete, the .ri first: no output file exists after any error.  out_rlbwt_path
+ *             may be NULL.  PGX_ERR_IO when a text cannot be read or a file cannot be created.
+ *   PGX_ERR_ARG for null paths or n_texts == 0, PGX_ERR_NO_DEVICE without a GPU.  One stream; a roctx range pgx_build_index_device with
+ *   PGX_ROCTX=1; PGX_BUILD_TIMING=1 adds one line on stderr (sizes, device bytes, HIP-event time of the radix passes). */
+pgx_status pgx_build_index_from_text_device(const char *text_path, const char *out_rlbwt_path, const char *out_ri_path, int encoded, int device);
+pgx_status pgx_build_index_from_texts_device(const char *const *text_paths, uint32_t n_texts, const char *out_rlbwt_path, const char *out_ri_path, int encoded, int device);
+/* stage times (ms) of this thread's last call, as pgx_build_tags_timing:
+ * [0] read + upload  [1] sequence table + first sort  [2] doubling rounds  [3] BWT, runs, samples + download
+ * [4] .rl_bwt / .ri written on the host  [5] number of doubling rounds (a count, not a time) */
+pgx_status pgx_build_index_device_timing(double *ms, uint32_t n);
 /* Write a compact sdsl tag file (format 3, src/tag_arrays.cpp:940-974 + :622-654) from parallel
  * arrays of run values (already `offset | rev<<10 | node<<11`) and run lengths. */
 pgx_status pgx_write_compact_tags(const char *out_path, const uint64_t *values,

@@ -178,16 +178,7 @@ struct Sais {
 // convention of the reference's fixtures and of tests/test_rindex.cpp:35-60: rotations of the text
 // with distinct increasing terminators).  Output: grlBWT run file (u64 bytes/symbol = 1,
 // u64 bytes/length, then (symbol, length) records).
-// The BWT of a collection as the builders below hand it on: grlBWT-style maximal runs, and -- for the SA samples of the .ri -- the text
-// position of the suffix at the first and at the last BWT position of every LOGICAL run (every endmarker is a run of its own,
-// src/r-index.cpp:840-848), so that no suffix array has to outlive the merge that produced it.
-struct TextBwt {
-    uint64_t n = 0;                                   // symbols of the collection (every sequence ends in \n)
-    std::vector<uint64_t> seq_start;                  // text position of every sequence
-    std::vector<std::pair<uint8_t, uint64_t>> runs;   // grlBWT-style maximal runs (endmarkers not split)
-    std::vector<uint64_t> head, tail;                 // per logical run: text position of its first / last suffix
-    uint64_t max_len = 1;
-};
+// (TextBwt, the hand-over between "suffixes sorted" and "files written", is declared in pgx_host.hpp: the device builder fills one too)
 
 // suffix array of one newline-terminated text (row 0 = the extra terminator, row p + 1 = the p-th suffix); endmarkers order by sequence
 static void suffix_array_of(const std::vector<uint8_t> &text, std::vector<int32_t> &SA) {
@@ -403,7 +394,7 @@ static void build_text_bwt(const char *text_path, TextBwt &o) {
     const char *one[1] = {text_path};
     build_texts_bwt(one, 1, o);
 }
-static void write_rlbwt(const char *out_rlbwt_path, const TextBwt &b) {
+void pgx::write_rlbwt(const char *out_rlbwt_path, const TextBwt &b) {
     uint64_t bl = 1;
     while (bl < 8 && (b.max_len >> (8 * bl))) bl++;
     std::vector<uint8_t> out;
@@ -450,7 +441,7 @@ static std::vector<std::pair<uint8_t, uint64_t>> read_rlbwt(const std::string &p
 // every sequence, src/r-index.cpp:993-1130) or, when the caller still holds the suffix array the BWT was made from (`tb`),
 // straight from it: the sample of BWT position p is the (sequence, offset) of suffix SA[p] -- the same values, without
 // n binary searches over the run starts.
-static std::vector<uint8_t> build_rindex_core(const std::vector<std::pair<uint8_t, uint64_t>> &file_runs, const TextBwt *tb, int encoded) {
+std::vector<uint8_t> pgx::build_rindex_core(const std::vector<std::pair<uint8_t, uint64_t>> &file_runs, const TextBwt *tb, int encoded) {
     BuildTimer bt;
     // calculate_C, r-index.hpp:440-482: sym_map = rank among present byte values; C = exclusive sums
     uint64_t freq[256] = {0}, n = 0;
@@ -675,7 +666,7 @@ static std::vector<uint8_t> build_rindex_core(const std::vector<std::pair<uint8_
     return out;
 }
 
-static void build_rindex_core(const std::vector<std::pair<uint8_t, uint64_t>> &file_runs, const TextBwt *tb, const char *out_ri_path, int encoded) {
+void pgx::build_rindex_core(const std::vector<std::pair<uint8_t, uint64_t>> &file_runs, const TextBwt *tb, const char *out_ri_path, int encoded) {
     BuildTimer bt;
     const std::vector<uint8_t> out = build_rindex_core(file_runs, tb, encoded);
     write_whole_file(out_ri_path, out);

@@ -328,5 +328,24 @@ __global__ void pgx_fastx_records_kernel(uint64_t n_lines, uint32_t format, cons
 __global__ void pgx_fastx_longest_kernel(const uint64_t *offs, const uint64_t *n_reads, unsigned long long *longest);
 __global__ void pgx_fastx_copy_kernel(const uint8_t *text, const uint64_t *ls, const uint64_t *out_off, uint64_t n_lines, uint64_t total, uint8_t *out);
 
+// text collection -> suffix order, BWT, runs (pgx_build_sa_kernels.hip, pgx_build_index_from_text[s]_device)
+#define PGX_SA_K 10           // symbols of the first key (3 bits each): the depth the doubling starts from
+#define PGX_SA_TILE 2048      // symbols / rows per block of the counting passes (256 threads x 8)
+#define PGX_SA_SORT_TILE 4096 // elements per block of a radix pass (256 threads x 16 rounds)
+__global__ void pgx_sa_classify_kernel(const uint8_t *text, uint64_t n, uint64_t *codes, uint64_t n_words, uint32_t *tile_nl, unsigned long long *first_bad);
+__global__ void pgx_sa_keys_kernel(const uint64_t *codes, uint64_t n_words, uint64_t n, const uint64_t *tile_off, uint64_t n_seq, uint32_t *hi, uint32_t *lo,
+                                   uint32_t *idx, uint32_t *seq_start);
+__global__ void pgx_sa_hist_kernel(const uint32_t *key, uint64_t n, uint32_t shift, uint32_t n_blocks, uint32_t *hist);
+__global__ void pgx_sa_scatter_kernel(const uint32_t *hi, const uint32_t *lo, const uint32_t *idx, uint64_t n, int key_is_hi, uint32_t shift, uint32_t n_blocks,
+                                      const uint64_t *offs, uint32_t *hi_out, uint32_t *lo_out, uint32_t *idx_out);
+__global__ void pgx_sa_heads_kernel(const uint32_t *hi, const uint32_t *lo, uint64_t n, uint32_t *tile_cnt);
+__global__ void pgx_sa_ranks_kernel(const uint32_t *hi, const uint32_t *lo, const uint32_t *idx, uint64_t n, const uint64_t *tile_off, uint32_t *hi_out,
+                                    uint32_t *rank);
+__global__ void pgx_sa_gather_kernel(const uint32_t *idx, const uint32_t *rank, uint64_t n, uint64_t h, uint32_t *lo);
+__global__ void pgx_sa_bwt_kernel(const uint32_t *sa, const uint8_t *text, uint64_t n, uint8_t *bwt);
+__global__ void pgx_sa_run_heads_kernel(const uint8_t *bwt, uint64_t n, uint32_t *tile_cnt);
+__global__ void pgx_sa_runs_kernel(const uint8_t *bwt, const uint32_t *sa, uint64_t n, const uint64_t *tile_off, uint64_t n_runs, uint8_t *run_sym,
+                                   uint32_t *run_start, uint32_t *run_head, uint32_t *run_tail);
+
 #define PGX_SCAN_BLOCK_ITEMS 2048 // 256 threads x 8 items (pgx_scan_kernels.hip PGX_SCAN_ITEMS)
 #define PGX_SCAN1_TILE_ITEMS 4096 // 256 threads x 16 rounds (pgx_scan_onepass_kernel)

@@ -124,6 +124,20 @@ struct GbzGraph {
     std::vector<uint8_t> chars;
 };
 void parse_gbz_graph(const std::string &path, bool forward_only, bool with_sequences, GbzGraph &g);
+// The BWT of a collection as its builders hand it on (pgx_build.cpp on the host, pgx_build_sa.hip on the device): grlBWT-style maximal
+// runs, and -- for the SA samples of the .ri -- the text position of the suffix at the first and at the last BWT position of every LOGICAL
+// run (every endmarker is a run of its own, src/r-index.cpp:840-848), so that no suffix array has to outlive the sort that produced it.
+struct TextBwt {
+    uint64_t n = 0;                                   // symbols of the collection (every sequence ends in \n)
+    std::vector<uint64_t> seq_start;                  // text position of every sequence
+    std::vector<std::pair<uint8_t, uint64_t>> runs;   // grlBWT-style maximal runs (endmarkers not split)
+    std::vector<uint64_t> head, tail;                 // per logical run: text position of its first / last suffix
+    uint64_t max_len = 1;
+};
+// the two files of a TextBwt (pgx_build.cpp): the grlBWT .rl_bwt, and FastLocate(std::string) + serialize[_encoded] with the SA samples taken from tb
+void write_rlbwt(const char *out_rlbwt_path, const TextBwt &b);
+std::vector<uint8_t> build_rindex_core(const std::vector<std::pair<uint8_t, uint64_t>> &file_runs, const TextBwt *tb, int encoded);
+void build_rindex_core(const std::vector<std::pair<uint8_t, uint64_t>> &file_runs, const TextBwt *tb, const char *out_ri_path, int encoded);
 // the r-index of a grlBWT .rl_bwt as the bytes pgx_build_rindex writes (pgx_build.cpp)
 std::vector<uint8_t> build_rindex_bytes(const char *rlbwt_path, int encoded);
 void write_compact_tags(const char *out_path, const uint64_t *values, const uint64_t *lengths, uint64_t n_runs, uint64_t max_node_floor);

@@ -148,6 +148,9 @@ def lib():
     L.pgx_build_rindex.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
     L.pgx_build_rlbwt.argtypes = [C.c_char_p, C.c_char_p]
     L.pgx_build_index_from_text.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
+    L.pgx_build_index_from_text_device.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int]
+    L.pgx_build_index_from_texts_device.argtypes = [C.POINTER(C.c_char_p), u32, C.c_char_p, C.c_char_p, C.c_int, C.c_int]
+    L.pgx_build_index_device_timing.argtypes = [p, u32]
     L.pgx_write_compact_tags.argtypes = [C.c_char_p, p, p, u64]
     L.pgx_convert_tags.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
     L.pgx_merge_tags.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), u32, p, u64, C.c_int, C.c_char_p]
@@ -291,6 +294,29 @@ def build_index_from_texts(text_paths, out_rlbwt_path, out_ri_path, encoded=True
     arr = (C.c_char_p * len(text_paths))(*[t.encode() for t in text_paths])
     _check(lib().pgx_build_index_from_texts(arr, len(text_paths), out_rlbwt_path.encode() if out_rlbwt_path else None, out_ri_path.encode(),
                                             1 if encoded else 0))
+
+
+BUILD_INDEX_DEVICE_STAGES = ("upload", "first_sort", "doubling", "bwt_runs", "files", "rounds")  # ms, except rounds: a count
+
+
+def build_index_from_text_device(text_path, out_rlbwt_path, out_ri_path, encoded=True, device=0):
+    """pgx_build_index_from_text_device: the same two files as build_index_from_text, the suffix sorting on `device`; returns the stage values"""
+    _check(lib().pgx_build_index_from_text_device(text_path.encode(), out_rlbwt_path.encode() if out_rlbwt_path else None, out_ri_path.encode(),
+                                                  1 if encoded else 0, device))
+    return build_index_device_timing()
+
+
+def build_index_from_texts_device(text_paths, out_rlbwt_path, out_ri_path, encoded=True, device=0):
+    arr = (C.c_char_p * len(text_paths))(*[t.encode() for t in text_paths])
+    _check(lib().pgx_build_index_from_texts_device(arr, len(text_paths), out_rlbwt_path.encode() if out_rlbwt_path else None, out_ri_path.encode(),
+                                                   1 if encoded else 0, device))
+    return build_index_device_timing()
+
+
+def build_index_device_timing():
+    ms = (C.c_double * len(BUILD_INDEX_DEVICE_STAGES))()
+    _check(lib().pgx_build_index_device_timing(C.cast(ms, C.c_void_p), len(BUILD_INDEX_DEVICE_STAGES)))
+    return dict(zip(BUILD_INDEX_DEVICE_STAGES, list(ms)))
 
 
 def write_compact_tags(out_path, values, lengths):

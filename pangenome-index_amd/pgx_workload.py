@@ -56,12 +56,15 @@ def build_index_from_rlbwt(rlbwt_path, workdir, name, encoded=True, with_tags=Tr
     return ri, tags
 
 
-def build_index_from_text(text_path, workdir, name, encoded=True, with_tags=True, parts=None):
-    """parts (None: by size): build through pgx_build_index_from_texts with the sequences of the text dealt into that many texts of consecutive
+def build_index_from_text(text_path, workdir, name, encoded=True, with_tags=True, parts=None, device=None):
+    """device (None: the host builder): the BWT on that device, pgx_build_index_from_text_device -- the same bytes; parts is ignored then.
+    parts (None: by size): build through pgx_build_index_from_texts with the sequences of the text dealt into that many texts of consecutive
     sequences -- the same bytes as the single suffix array gives (tests/test_formats.py), in a fraction of the time on a many-core host"""
     os.makedirs(workdir, exist_ok=True)
     rl = os.path.join(workdir, name + ".rl_bwt")
     ri = os.path.join(workdir, name + (".ri" if encoded else ".legacy.ri"))
+    if device is not None:
+        parts = 1
     if parts is None:
         parts = 8 if os.path.getsize(text_path) >= (64 << 20) else 1  # (chr22 workload on 8 cores: 166 s with four texts, 144 s with eight or sixteen)
     pieces = []
@@ -82,6 +85,8 @@ def build_index_from_text(text_path, workdir, name, encoded=True, with_tags=True
         pgx_ffi.build_index_from_texts(pieces, rl, ri, encoded)
         for pth in pieces:
             os.remove(pth)
+    elif device is not None:
+        pgx_ffi.build_index_from_text_device(text_path, rl, ri, encoded, device)
     else:
         pgx_ffi.build_index_from_text(text_path, rl, ri, encoded)  # one suffix array for the BWT and the SA samples
     tags = None
