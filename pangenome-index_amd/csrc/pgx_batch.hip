@@ -1401,13 +1401,13 @@ extern "C" pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t ma
             read_scalars(c, ctr, 24, s);
             const uint64_t n_wave = c[0], n_wg = c[1], S = c[2];
             if (n_wave)
-                hipLaunchKernelGGL(pgx_tag_sort_unique_kernel, dim3(grid_for(n_wave, 4)), dim3(256), 0, s, (const uint64_t *)wave_list, n_wave, (const uint64_t *)nullptr,
-                                   (const uint64_t *)nullptr, cnt, (const uint64_t *)seg, w.gbuf.as<uint64_t>(), ucount);
+                hipLaunchKernelGGL(pgx_tag_sort_unique_kernel<PgxTagDense>, dim3(grid_for(n_wave, 4)), dim3(256), 0, s, PgxTagDense{wave_list, cnt, seg}, n_wave,
+                                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, w.gbuf.as<uint64_t>(), ucount);
             if (n_wg) {
                 w.scratch.ensure((S ? S : 1) * 8);
-                HIPCHECK(hipFuncSetAttribute((const void *)pgx_tag_sort_large_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PGX_SORT_WG_LDS_CAP * 8)));
-                hipLaunchKernelGGL(pgx_tag_sort_large_kernel, dim3(grid_for(n_wg, 1)), dim3(1024), (size_t)PGX_SORT_WG_LDS_CAP * 8, s, (const uint64_t *)wg_list, n_wg,
-                                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, cnt, (const uint64_t *)seg, w.gbuf.as<uint64_t>(), w.scratch.as<uint64_t>(),
+                HIPCHECK(hipFuncSetAttribute((const void *)pgx_tag_sort_large_kernel<PgxTagDense>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PGX_SORT_WG_LDS_CAP * 8)));
+                hipLaunchKernelGGL(pgx_tag_sort_large_kernel<PgxTagDense>, dim3(grid_for(n_wg, 1)), dim3(1024), (size_t)PGX_SORT_WG_LDS_CAP * 8, s, PgxTagDense{wg_list, cnt, seg},
+                                   n_wg, (const uint64_t *)nullptr, (const uint64_t *)nullptr, w.gbuf.as<uint64_t>(), w.scratch.as<uint64_t>(),
                                    (const uint64_t *)w.soff.as<uint64_t>(), ucount);
             }
             HIPCHECK(hipGetLastError());
@@ -1415,8 +1415,8 @@ extern "C" pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t ma
             const uint64_t Up = read_u64(reinterpret_cast<const uint64_t *>(ctr + 3), s);
             w.vals.ensure_keep((U + Up ? U + Up : 1) * 8, U * 8); // (the stream is idle here: the read-back above synchronised it)
             if (Up) {
-                hipLaunchKernelGGL(pgx_tag_compact_kernel, dim3(grid_for(np, 16)), dim3(256), 0, s, (const uint64_t *)nullptr, np, (const uint64_t *)nullptr,
-                                   (const uint64_t *)nullptr, (const uint64_t *)ucount, (const uint64_t *)seg, (const uint64_t *)w.gbuf.as<uint64_t>(),
+                hipLaunchKernelGGL(pgx_tag_compact_kernel<PgxTagDense>, dim3(grid_for(np, 16)), dim3(256), 0, s, PgxTagDense{nullptr, nullptr, seg}, np,
+                                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, (const uint64_t *)ucount, (const uint64_t *)w.gbuf.as<uint64_t>(),
                                    (const uint64_t *)w.uloc.as<uint64_t>(), w.vals.as<uint64_t>() + U, ~0ull);
                 HIPCHECK(hipGetLastError());
             }

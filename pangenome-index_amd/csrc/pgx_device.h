@@ -167,12 +167,17 @@ __global__ void pgx_lf_kernel(PgxDevImage img, const pgx_range *in, const uint8_
 
 // ---- pgx_scan_kernels.hip: exclusive scans, MEM compaction
 // n_dev (may be NULL): the element count lives on the device, `n` is then the capacity the launch was sized for
-__global__ void pgx_scan_partial_kernel(int mode, const void *in, uint64_t n, uint64_t min_len, uint64_t *block_sums, const uint64_t *n_dev);
+// in2: the second input of mode 5 (NULL otherwise)
+__global__ void pgx_scan_partial_kernel(int mode, const void *in, const void *in2, uint64_t n, uint64_t min_len, uint64_t *block_sums, const uint64_t *n_dev);
 template <int MODE>
 __global__ void pgx_scan_onepass_kernel(const void *in, uint64_t n, uint64_t min_len, uint64_t *out, uint64_t *total_out, const uint64_t *n_dev,
                                         unsigned long long *state, uint32_t epoch);
 __global__ void pgx_scan_sums_kernel(uint64_t *block_sums, uint64_t nb);
-__global__ void pgx_scan_apply_kernel(int mode, const void *in, uint64_t n, uint64_t min_len, const uint64_t *block_sums,
+// the tail of the tag stage in one launch: pos_off = exclusive scan of the queries' position counts (pgx_scan_load mode 5), and, with `positions`, every
+// one-run query's value stored at its offset (below pos_cap); the tile with the grand total raises bit 0 of *abort when it exceeds pos_cap
+__global__ void pgx_scan_tag_tail_kernel(const uint64_t *run_nums, const uint64_t *uval, uint64_t n, const uint64_t *n_dev, uint64_t *pos_off, uint64_t *total_out,
+                                         uint64_t *positions, uint64_t pos_cap, uint64_t *abort, unsigned long long *state, uint32_t epoch);
+__global__ void pgx_scan_apply_kernel(int mode, const void *in, const void *in2, uint64_t n, uint64_t min_len, const uint64_t *block_sums,
                                       uint64_t nb, uint64_t *out, uint64_t *total_out, int raw_sums, const uint64_t *n_dev);
 __global__ void pgx_compact_mems_kernel(uint64_t first_read, uint64_t n_reads, const uint64_t *slot_off, uint64_t slot_base,
                                         const pgx_mem *slots, const uint32_t *mem_count, const uint64_t *local_off,
@@ -197,34 +202,55 @@ __global__ void pgx_tag_bucket_kernel(const uint64_t *tstart, const uint64_t *tv
 #define PGX_TAG_SMALL 16      // queries with at most this many runs take the 16-lane path
 #define PGX_SORT_WG_LDS_CAP 16384 // values one workgroup sorts in (dynamic) LDS (pgx_tag_sort_large_kernel)
 
+// A listed query (2 or more runs) as its list carries it: everything the gather, sort and compaction kernels need, read coalesced in list order.
+// `seg` is the start of the query's segment of the gather buffer, assigned when the entry is appended (pgx_tag_locate_kernel); a duplicate of a large
+// query is pointed at its representative's segment (pgx_tag_copy_dups_kernel).
+struct __attribute__((aligned(32))) PgxTagRec { uint64_t q, first, cnt, seg; };
+// How entry e of a list resolves to (query, count, segment start) in the sort and compaction kernels, and where its global sort scratch is listed:
+// the records of the tag stage, or the dense per-query arrays of the locate paths (pgx_locate_batch, pgx_batch_locate; list == NULL: every query).
+struct PgxTagRecs {
+    const PgxTagRec *recs;
+    __device__ __forceinline__ void get(uint64_t e, uint64_t &q, uint64_t &cnt, uint64_t &seg) const { const PgxTagRec r = recs[e]; q = r.q; cnt = r.cnt; seg = r.seg; }
+    __device__ __forceinline__ uint64_t scratch_index(uint64_t e, uint64_t q) const { return e; }
+};
+struct PgxTagDense {
+    const uint64_t *list, *cnt, *seg;
+    __device__ __forceinline__ void get(uint64_t e, uint64_t &q, uint64_t &c, uint64_t &s) const { q = list ? list[e] : e; c = cnt ? cnt[q] : 0; s = seg[q]; }
+    __device__ __forceinline__ uint64_t scratch_index(uint64_t e, uint64_t q) const { return q; }
+};
+
 // every kernel of the tag stage: (count as a value = capacity, device pointer to the actual count or NULL, abort flag or NULL)
+// per query: run_nums[q] and uval[q] -- the value of a one-run query, 0 for an inverted one, the unique count of a listed one (written by the sort kernels).
+// sc: the stage's scalars (tag_pipeline): [0] big-list length [1] large-list length [2] largest run count [3] gathered values [5] small-list length
 __global__ void pgx_tag_locate_kernel(PgxDevImage img, const pgx_mem *mems, const uint64_t *qstart, const uint64_t *qend,
-                                      uint64_t n, const uint64_t *n_dev, const uint64_t *abort, uint64_t *run_nums, uint64_t *first_item, uint64_t *need,
-                                      uint64_t *big_list, uint64_t *large_list, unsigned long long *n_big, unsigned long long *n_large, uint64_t *single,
-                                      uint64_t *ucount, unsigned long long *n_overflow, uint64_t *small_list, unsigned long long *n_small);
-__global__ void pgx_tag_small_kernel(PgxDevImage img, const uint64_t *list, uint64_t n, const uint64_t *n_dev, const uint64_t *abort, const uint64_t *run_nums,
-                                     const uint64_t *first_item, const uint64_t *seg_off, uint64_t *buf, uint64_t *ucount, unsigned long long *n_overflow);
-__global__ void pgx_tag_gather_kernel(PgxDevImage img, const uint64_t *list, uint64_t n_list, const uint64_t *n_dev, const uint64_t *abort,
-                                      const uint64_t *run_nums, const uint64_t *first_item, const uint64_t *seg_off, uint64_t *buf,
+                                      uint64_t n, const uint64_t *n_dev, const uint64_t *abort, uint64_t *run_nums, uint64_t *uval,
+                                      PgxTagRec *small_recs, PgxTagRec *big_recs, PgxTagRec *large_recs, unsigned long long *sc,
                                       unsigned long long *n_overflow);
-__global__ void pgx_tag_sort_unique_kernel(const uint64_t *list, uint64_t n_list, const uint64_t *n_dev, const uint64_t *abort, const uint64_t *run_nums,
-                                           const uint64_t *seg_off, uint64_t *buf, uint64_t *ucount);
-__global__ void pgx_tag_sort_large_kernel(const uint64_t *list, uint64_t n_list, const uint64_t *n_dev, const uint64_t *abort, const uint64_t *run_nums,
-                                          const uint64_t *seg_off, uint64_t *buf, uint64_t *scratch, const uint64_t *scratch_off, uint64_t *ucount);
-__global__ void pgx_tag_dedup_kernel(const uint64_t *list, uint64_t n_list, const uint64_t *n_dev, const uint64_t *abort, const uint64_t *first_item,
-                                     const uint64_t *run_nums, unsigned long long *table, uint64_t table_mask, uint64_t *reps, unsigned long long *n_rep,
-                                     uint64_t *pairs, unsigned long long *n_dup);
+__global__ void pgx_tag_small_kernel(PgxDevImage img, const PgxTagRec *recs, uint64_t n, const uint64_t *n_dev, const uint64_t *abort, uint64_t *buf,
+                                     uint64_t *uval, unsigned long long *n_overflow);
+__global__ void pgx_tag_gather_kernel(PgxDevImage img, const PgxTagRec *recs, uint64_t n_list, const uint64_t *n_dev, const uint64_t *abort, uint64_t *buf,
+                                      unsigned long long *n_overflow);
+template <class L>
+__global__ void pgx_tag_sort_unique_kernel(L src, uint64_t n_list, const uint64_t *n_dev, const uint64_t *abort, uint64_t *buf, uint64_t *ucount);
+template <class L>
+__global__ void pgx_tag_sort_large_kernel(L src, uint64_t n_list, const uint64_t *n_dev, const uint64_t *abort, uint64_t *buf, uint64_t *scratch,
+                                          const uint64_t *scratch_off, uint64_t *ucount);
+__global__ void pgx_tag_need_kernel(const PgxTagRec *recs, uint64_t n_list, uint64_t *need);
+__global__ void pgx_tag_dedup_kernel(const PgxTagRec *recs, uint64_t n_list, const uint64_t *n_dev, const uint64_t *abort, unsigned long long *table,
+                                     uint64_t table_mask, PgxTagRec *reps, unsigned long long *n_rep, uint64_t *pairs, unsigned long long *n_dup);
 __global__ void pgx_tag_copy_dups_kernel(const uint64_t *pairs, uint64_t n_pairs, const uint64_t *n_dev, const uint64_t *abort, uint64_t n_tag_items,
-                                         const uint64_t *first_item, const uint64_t *run_nums, uint64_t *seg_off, uint64_t *buf, uint64_t *ucount,
-                                         unsigned long long *n_overflow);
-__global__ void pgx_tag_compact_kernel(const uint64_t *list, uint64_t n, const uint64_t *n_dev, const uint64_t *abort, const uint64_t *ucount,
-                                       const uint64_t *seg_off, const uint64_t *buf, const uint64_t *pos_off, uint64_t *positions, uint64_t max_count);
-__global__ void pgx_tag_compact_single_kernel(uint64_t n, const uint64_t *n_dev, const uint64_t *abort, const uint64_t *run_nums, const uint64_t *single,
+                                         PgxTagRec *recs, uint64_t *uval, unsigned long long *n_overflow);
+template <class L>
+__global__ void pgx_tag_compact_kernel(L src, uint64_t n, const uint64_t *n_dev, const uint64_t *abort, const uint64_t *ucount, const uint64_t *buf,
+                                       const uint64_t *pos_off, uint64_t *positions, uint64_t max_count);
+__global__ void pgx_tag_compact_single_kernel(uint64_t n, const uint64_t *n_dev, const uint64_t *abort, const uint64_t *run_nums, const uint64_t *uval,
                                               const uint64_t *pos_off, uint64_t *positions);
-__global__ void pgx_tag_compact_list_kernel(const uint64_t *list, uint64_t n_list, const uint64_t *n_dev, const uint64_t *abort, const uint64_t *ucount,
-                                            const uint64_t *seg_off, const uint64_t *buf, const uint64_t *pos_off, uint64_t *positions, uint64_t max_count);
+template <class L>
+__global__ void pgx_tag_compact_list_kernel(L src, uint64_t n_list, const uint64_t *n_dev, const uint64_t *abort, const uint64_t *ucount,
+                                            const uint64_t *buf, const uint64_t *pos_off, uint64_t *positions, uint64_t max_count);
+// *v_i > c_i raises bit i of the abort flag; *v4 > c4 raises bit 0 as well
 __global__ void pgx_spec_check_kernel(const uint64_t *v0, uint64_t c0, const uint64_t *v1, uint64_t c1, const uint64_t *v2, uint64_t c2,
-                                      const uint64_t *v3, uint64_t c3, uint64_t *abort);
+                                      const uint64_t *v3, uint64_t c3, const uint64_t *v4, uint64_t c4, uint64_t *abort);
 #define PGX_TAG_COMPACT_SMALL 256 // segments up to this many unique values are copied by the 16-lane kernel
 
 // locate image (pgx_image.h), passed by value to the locate kernels (pgx_locate_kernels.hip, with the builders of the LCE image)

@@ -78,58 +78,89 @@ extern "C" pgx_status pgx_device_name(int device, char *buf, size_t buflen) {
 }
 
 // ------------------------------------------------------------------------------------------
+// PGX_SCAN_THREE=1: the three-launch form of every scan (partial sums, their scan, apply)
+bool scan_three_launches() {
+    static const bool three = [] { const char *e = std::getenv("PGX_SCAN_THREE"); return e && e[0] == '1'; }();
+    return three;
+}
+// the tile words of a one-launch scan of nt tiles (decoupled look-back, pgx_scan1_lookback) and the epoch it runs under: the words carry the epoch,
+// so the buffer is cleared only when it is new or the 18-bit epoch comes round
+static uint32_t scan_onepass_state(DevBuf &tmp, uint64_t nt, hipStream_t s) {
+    tmp.ensure((nt + 2) * 8);
+    if (tmp.scan_epoch == 0 || tmp.scan_epoch >= 0x3FFFFu) {
+        HIPCHECK(hipMemsetAsync(tmp.p, 0, tmp.cap, s));
+        tmp.scan_epoch = 0;
+        // tests: PGX_SCAN_EPOCH0 = the epoch a cleared buffer starts from (below the last one), so that a few scans reach the wrap
+        if (const char *e = std::getenv("PGX_SCAN_EPOCH0")) tmp.scan_epoch = (uint32_t)std::min<unsigned long>(std::strtoul(e, nullptr, 0), 0x3FFFEul);
+    }
+    return ++tmp.scan_epoch;
+}
+static void scan_in_three_launches(int mode, const void *in, const void *in2, uint64_t n, uint64_t min_len, uint64_t *out, DevBuf &tmp, hipStream_t s, uint64_t *total_out,
+                              const uint64_t *n_dev) {
+    const uint64_t nb = (n + PGX_SCAN_BLOCK_ITEMS - 1) / PGX_SCAN_BLOCK_ITEMS;
+    tmp.ensure((nb + 1) * 8);
+    tmp.scan_epoch = 0; // (the tile words are overwritten)
+    uint64_t *sums = tmp.as<uint64_t>();
+    hipLaunchKernelGGL(pgx_scan_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, mode, in, in2, n, min_len, sums, n_dev);
+    const int raw = nb <= 2048; // up to 4 M items: no separate scan of the block totals
+    if (!raw) hipLaunchKernelGGL(pgx_scan_sums_kernel, dim3(1), dim3(256), 0, s, sums, nb);
+    hipLaunchKernelGGL(pgx_scan_apply_kernel, dim3((unsigned)nb), dim3(256), 0, s, mode, in, in2, n, min_len, (const uint64_t *)sums, nb, out, total_out, raw, n_dev);
+    HIPCHECK(hipGetLastError());
+}
+
 // exclusive scan helper: out[n+1] on device (out[n] = total); returns nothing, async on `s`
 void scan_excl(int mode, const void *in, uint64_t n, uint64_t min_len, uint64_t *out, DevBuf &tmp, hipStream_t s, uint64_t *total_out, const uint64_t *n_dev) {
+    if (mode < 0 || mode > 4) throw Error(PGX_ERR_ARG, "scan_excl: unknown mode"); // (mode 5 takes two inputs: scan_tag_tail)
     if (n == 0) {
         HIPCHECK(hipMemsetAsync(out, 0, 8, s));
         if (total_out) HIPCHECK(hipMemsetAsync(total_out, 0, 8, s));
         return;
     }
-    // one launch (decoupled look-back, pgx_scan_onepass_kernel); the tile words carry an epoch, so the buffer is cleared only when it is new or
-    // the 18-bit epoch comes round.  PGX_SCAN_THREE=1: the three-launch form (partial sums, their scan, apply)
-    static const bool three = [] { const char *e = std::getenv("PGX_SCAN_THREE"); return e && e[0] == '1'; }();
-    if (!three) {
+    if (!scan_three_launches()) { // one launch (pgx_scan_onepass_kernel)
         const uint64_t nt = (n + PGX_SCAN1_TILE_ITEMS - 1) / PGX_SCAN1_TILE_ITEMS;
-        tmp.ensure((nt + 2) * 8);
-        if (tmp.scan_epoch == 0 || tmp.scan_epoch >= 0x3FFFFu) {
-            HIPCHECK(hipMemsetAsync(tmp.p, 0, tmp.cap, s));
-            tmp.scan_epoch = 0;
-            // tests: PGX_SCAN_EPOCH0 = the epoch a cleared buffer starts from (below the last one), so that a few scans reach the wrap
-            if (const char *e = std::getenv("PGX_SCAN_EPOCH0")) tmp.scan_epoch = (uint32_t)std::min<unsigned long>(std::strtoul(e, nullptr, 0), 0x3FFFEul);
-        }
-        tmp.scan_epoch++;
+        const uint32_t ep = scan_onepass_state(tmp, nt, s);
         unsigned long long *st = tmp.as<unsigned long long>();
-        const uint32_t ep = tmp.scan_epoch;
         switch (mode) {
         case 0: hipLaunchKernelGGL(pgx_scan_onepass_kernel<0>, dim3((unsigned)nt), dim3(256), 0, s, in, n, min_len, out, total_out, n_dev, st, ep); break;
         case 1: hipLaunchKernelGGL(pgx_scan_onepass_kernel<1>, dim3((unsigned)nt), dim3(256), 0, s, in, n, min_len, out, total_out, n_dev, st, ep); break;
         case 2: hipLaunchKernelGGL(pgx_scan_onepass_kernel<2>, dim3((unsigned)nt), dim3(256), 0, s, in, n, min_len, out, total_out, n_dev, st, ep); break;
         case 3: hipLaunchKernelGGL(pgx_scan_onepass_kernel<3>, dim3((unsigned)nt), dim3(256), 0, s, in, n, min_len, out, total_out, n_dev, st, ep); break;
         case 4: hipLaunchKernelGGL(pgx_scan_onepass_kernel<4>, dim3((unsigned)nt), dim3(256), 0, s, in, n, min_len, out, total_out, n_dev, st, ep); break;
-        default: hipLaunchKernelGGL(pgx_scan_onepass_kernel<5>, dim3((unsigned)nt), dim3(256), 0, s, in, n, min_len, out, total_out, n_dev, st, ep); break;
+        default: break; // (rejected above)
         }
         HIPCHECK(hipGetLastError());
         return;
     }
-    const uint64_t nb = (n + PGX_SCAN_BLOCK_ITEMS - 1) / PGX_SCAN_BLOCK_ITEMS;
-    tmp.ensure((nb + 1) * 8);
-    tmp.scan_epoch = 0; // (the tile words are overwritten)
-    uint64_t *sums = tmp.as<uint64_t>();
-    hipLaunchKernelGGL(pgx_scan_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, mode, in, n, min_len, sums, n_dev);
-    const int raw = nb <= 2048; // up to 4 M items: no separate scan of the block totals
-    if (!raw) hipLaunchKernelGGL(pgx_scan_sums_kernel, dim3(1), dim3(256), 0, s, sums, nb);
-    hipLaunchKernelGGL(pgx_scan_apply_kernel, dim3((unsigned)nb), dim3(256), 0, s, mode, in, n, min_len, (const uint64_t *)sums, nb, out, total_out, raw, n_dev);
+    scan_in_three_launches(mode, in, nullptr, n, min_len, out, tmp, s, total_out, n_dev);
+}
+
+bool scan_tag_tail(const uint64_t *run_nums, const uint64_t *uval, uint64_t n, uint64_t *pos_off, DevBuf &tmp, hipStream_t s, uint64_t *total_out, const uint64_t *n_dev,
+                   uint64_t *positions, uint64_t pos_cap, uint64_t *abort) {
+    if (n == 0) {
+        HIPCHECK(hipMemsetAsync(pos_off, 0, 8, s));
+        HIPCHECK(hipMemsetAsync(total_out, 0, 8, s));
+        return true;
+    }
+    if (scan_three_launches()) {
+        scan_in_three_launches(5, run_nums, uval, n, 0, pos_off, tmp, s, total_out, n_dev);
+        return false;
+    }
+    const uint64_t nt = (n + PGX_SCAN1_TILE_ITEMS - 1) / PGX_SCAN1_TILE_ITEMS;
+    const uint32_t ep = scan_onepass_state(tmp, nt, s);
+    hipLaunchKernelGGL(pgx_scan_tag_tail_kernel, dim3((unsigned)nt), dim3(256), 0, s, run_nums, uval, n, n_dev, pos_off, total_out, positions, pos_cap,
+                       positions ? abort : nullptr, tmp.as<unsigned long long>(), ep);
     HIPCHECK(hipGetLastError());
+    return positions != nullptr;
 }
 
 void pgx_use_device(int device) { use_device(device); }
 void pgx_scan_u64(const uint64_t *in, uint64_t n, uint64_t *out, uint64_t *tmp, hipStream_t s) {
     if (n == 0) { HIPCHECK(hipMemsetAsync(out, 0, 8, s)); return; }
     const uint64_t nb = (n + PGX_SCAN_BLOCK_ITEMS - 1) / PGX_SCAN_BLOCK_ITEMS;
-    hipLaunchKernelGGL(pgx_scan_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, 1, (const void *)in, n, (uint64_t)0, tmp, (const uint64_t *)nullptr);
+    hipLaunchKernelGGL(pgx_scan_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, 1, (const void *)in, (const void *)nullptr, n, (uint64_t)0, tmp, (const uint64_t *)nullptr);
     const int raw = nb <= 2048;
     if (!raw) hipLaunchKernelGGL(pgx_scan_sums_kernel, dim3(1), dim3(256), 0, s, tmp, nb);
-    hipLaunchKernelGGL(pgx_scan_apply_kernel, dim3((unsigned)nb), dim3(256), 0, s, 1, (const void *)in, n, (uint64_t)0, (const uint64_t *)tmp, nb, out, (uint64_t *)nullptr, raw, (const uint64_t *)nullptr);
+    hipLaunchKernelGGL(pgx_scan_apply_kernel, dim3((unsigned)nb), dim3(256), 0, s, 1, (const void *)in, (const void *)nullptr, n, (uint64_t)0, (const uint64_t *)tmp, nb, out, (uint64_t *)nullptr, raw, (const uint64_t *)nullptr);
     HIPCHECK(hipGetLastError());
 }
 
@@ -233,24 +264,25 @@ void locate_core(pgx_index *h, pgx_device_image *d, const uint64_t *first, const
             if (!wave_list.empty()) HIPCHECK(hipMemcpy(d_wave, wave_list.data(), wave_list.size() * 8, hipMemcpyHostToDevice));
             if (!wg_list.empty()) HIPCHECK(hipMemcpy(d_wg, wg_list.data(), wg_list.size() * 8, hipMemcpyHostToDevice));
             if (!wave_list.empty())
-                hipLaunchKernelGGL(pgx_tag_sort_unique_kernel, dim3(grid_for(wave_list.size(), 4)), dim3(256), 0, s, (const uint64_t *)d_wave,
-                                   (uint64_t)wave_list.size(), (const uint64_t *)nullptr, (const uint64_t *)nullptr, dcnt.as<uint64_t>(), dvoff.as<uint64_t>(),
-                                   gbuf.as<uint64_t>(), ducount.as<uint64_t>());
+                hipLaunchKernelGGL(pgx_tag_sort_unique_kernel<PgxTagDense>, dim3(grid_for(wave_list.size(), 4)), dim3(256), 0, s,
+                                   PgxTagDense{d_wave, dcnt.as<uint64_t>(), dvoff.as<uint64_t>()}, (uint64_t)wave_list.size(), (const uint64_t *)nullptr,
+                                   (const uint64_t *)nullptr, gbuf.as<uint64_t>(), ducount.as<uint64_t>());
             if (!wg_list.empty()) {
                 uint64_t p2max = 64;
                 while (p2max < max_cnt && p2max < PGX_SORT_WG_LDS_CAP) p2max <<= 1;
-                HIPCHECK(hipFuncSetAttribute((const void *)pgx_tag_sort_large_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                HIPCHECK(hipFuncSetAttribute((const void *)pgx_tag_sort_large_kernel<PgxTagDense>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)(PGX_SORT_WG_LDS_CAP * 8)));
-                hipLaunchKernelGGL(pgx_tag_sort_large_kernel, dim3(grid_for(wg_list.size(), 1)), dim3(1024), (size_t)p2max * 8, s,
-                                   (const uint64_t *)d_wg, (uint64_t)wg_list.size(), (const uint64_t *)nullptr, (const uint64_t *)nullptr, dcnt.as<uint64_t>(),
-                                   dvoff.as<uint64_t>(), gbuf.as<uint64_t>(), dscratch.as<uint64_t>(), dsoff.as<uint64_t>(), ducount.as<uint64_t>());
+                hipLaunchKernelGGL(pgx_tag_sort_large_kernel<PgxTagDense>, dim3(grid_for(wg_list.size(), 1)), dim3(1024), (size_t)p2max * 8, s,
+                                   PgxTagDense{d_wg, dcnt.as<uint64_t>(), dvoff.as<uint64_t>()}, (uint64_t)wg_list.size(), (const uint64_t *)nullptr,
+                                   (const uint64_t *)nullptr, gbuf.as<uint64_t>(), dscratch.as<uint64_t>(), (const uint64_t *)dsoff.as<uint64_t>(), ducount.as<uint64_t>());
             }
             HIPCHECK(hipGetLastError());
             scan_excl(1, ducount.p, n, 0, duoff.as<uint64_t>(), scan_tmp, s);
             const uint64_t U = read_u64(duoff.as<uint64_t>() + n, s);
             vals_out.ensure((U ? U : 1) * 8);
-            hipLaunchKernelGGL(pgx_tag_compact_kernel, dim3(grid_for(n, 16)), dim3(256), 0, s, (const uint64_t *)nullptr, n, (const uint64_t *)nullptr, (const uint64_t *)nullptr,
-                               ducount.as<uint64_t>(), dvoff.as<uint64_t>(), gbuf.as<uint64_t>(), duoff.as<uint64_t>(), vals_out.as<uint64_t>(), ~0ull);
+            hipLaunchKernelGGL(pgx_tag_compact_kernel<PgxTagDense>, dim3(grid_for(n, 16)), dim3(256), 0, s, PgxTagDense{nullptr, nullptr, dvoff.as<uint64_t>()}, n,
+                               (const uint64_t *)nullptr, (const uint64_t *)nullptr, (const uint64_t *)ducount.as<uint64_t>(), (const uint64_t *)gbuf.as<uint64_t>(),
+                               (const uint64_t *)duoff.as<uint64_t>(), vals_out.as<uint64_t>(), ~0ull);
             HIPCHECK(hipGetLastError());
             h_off.resize(n + 1);
             HIPCHECK(hipMemcpy(h_off.data(), duoff.p, (n + 1) * 8, hipMemcpyDeviceToHost));

@@ -2,7 +2,9 @@
 // src/tag_arrays.cpp:780-890, minus the printing) as gfx950 kernels.
 //
 //   locate     per MEM: two rank_1 on bwt_intervals (= searches in the sorted run-start array via a
-//              sampled directory) -> run_nums, first item; MEMs with more than 16 runs go on a list
+//              sampled directory) -> run_nums; a one-run MEM's value -> uval; a MEM with more runs goes on the list of its size
+//              class as a record (query, first item, run count, segment of the gather buffer): the only per-MEM arrays are
+//              run_nums and uval, everything else is in list order
 //   small      <= 16 runs (the common case: a MEM's SA interval spans ~#haplotypes positions):
 //              16 lanes per MEM, four MEMs per wavefront; gather + bitonic network in registers +
 //              unique, no LDS, full occupancy
@@ -11,7 +13,8 @@
 //   large      listed MEMs with more runs (a MEM inside a repeat / an N run has a huge SA interval):
 //              one 1024-thread workgroup each, bitonic in 128 KiB of LDS (<= 16384 values) or in
 //              global scratch beyond that
-//   compact    16 lanes per MEM copy the unique prefix to the dense positions array
+//   compact    16 lanes per listed MEM copy the unique prefix to the dense positions array (the one-run MEMs' values are stored by
+//              the scan that computes the offsets, pgx_scan_tag_tail_kernel)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -99,19 +102,18 @@ __device__ __forceinline__ uint32_t pgx_tbucket_le(const uint4 &h0, const uint4 
 __global__ void __launch_bounds__(PGX_TAG_LOCATE_THREADS)
 pgx_tag_locate_kernel(PgxDevImage img, const pgx_mem *__restrict__ mems, const uint64_t *__restrict__ qstart,
                       const uint64_t *__restrict__ qend, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
-                      uint64_t *__restrict__ run_nums,
-                      uint64_t *__restrict__ first_item, uint64_t *__restrict__ need, uint64_t *__restrict__ big_list, uint64_t *__restrict__ large_list,
-                      unsigned long long *__restrict__ n_big, unsigned long long *__restrict__ n_large, uint64_t *__restrict__ single,
-                      uint64_t *__restrict__ ucount, unsigned long long *__restrict__ n_overflow, uint64_t *__restrict__ small_list,
-                      unsigned long long *__restrict__ n_small) {
+                      uint64_t *__restrict__ run_nums, uint64_t *__restrict__ uval, PgxTagRec *__restrict__ small_recs, PgxTagRec *__restrict__ big_recs,
+                      PgxTagRec *__restrict__ large_recs, unsigned long long *__restrict__ sc, unsigned long long *__restrict__ n_overflow) {
+  unsigned long long *const n_big = sc, *const n_large = sc + 1, *const n_gathered = sc + 3, *const n_small = sc + 5;
   if (PGX_ABORTED(abort)) return;
   const uint64_t n = PGX_DEV_COUNT(n_cap, n_dev);
   __shared__ uint32_t s_cnt[PGX_TAG_LOCATE_THREADS / 64];
-  __shared__ unsigned long long s_base;
+  __shared__ uint64_t s_seg[PGX_TAG_LOCATE_THREADS / 64];
+  __shared__ unsigned long long s_base, s_gbase;
   for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += (uint64_t)gridDim.x * blockDim.x) { // (uniform per workgroup)
     const uint64_t i = base + threadIdx.x;
     const bool valid = i < n; // no early return: the small list is appended to by whole waves
-    uint64_t cnt = 0;
+    uint64_t cnt = 0, fi = 0;
     if (valid) {
         uint64_t st, en;
         if (mems) { st = mems[i].bwt_start; en = st + (uint64_t)mems[i].size - 1; } // find_mems.cpp:129
@@ -162,61 +164,75 @@ pgx_tag_locate_kernel(PgxDevImage img, const pgx_mem *__restrict__ mems, const u
         }
         cnt = g - f + 1;
         run_nums[i] = cnt;
-        const uint64_t fi = (f % 10) ? f - 1 : f;
-        first_item[i] = fi;
+        fi = (f % 10) ? f - 1 : f;
         if (cnt == 1) { // one run = one position: the common case (a MEM inside one node); no segment, no sort
             uint64_t v = 0;
             if (fi < img.n_tag_items) v = bval_ok ? bval : (img.tpair ? img.tpair[fi].y : img.tvals[fi]);
             else atomicAdd(n_overflow, 1ull); // the reference reads past the stored runs (UB there): value 0
-            single[i] = v;
-            ucount[i] = 1;
-        } else if (cnt == 0) ucount[i] = 0; // an inverted query is on no list
-        uint64_t p2 = 64;
-        while (p2 < cnt && p2 < (1ull << 62)) p2 <<= 1;
-        need[i] = p2 > PGX_SORT_WG_LDS_CAP ? p2 : 0; // global scratch of the large path
-        if (cnt > PGX_SORT_LDS_CAP) {
-            large_list[atomicAdd(n_large, 1ull)] = i;
-            atomicMax(n_large + 1, (unsigned long long)cnt); // sizes the LDS of the large-path launch
-        }
-        else if (cnt > PGX_TAG_SMALL) big_list[atomicAdd(n_big, 1ull)] = i;
+            uval[i] = v;
+        } else if (cnt == 0) uval[i] = 0; // an inverted query is on no list
     }
-    // queries with 2 .. 16 runs: a list of their own, so that the 16-lane kernels only see those.  One atomic per
-    // 1024-thread workgroup: all of them hit one address, and one per wave (23 k for 1.5 M MEMs) cost 0.27 ms.
-    const bool is_small = valid && cnt >= 2 && cnt <= PGX_TAG_SMALL;
+    // Queries with two or more runs go on the list of their size class, and each gets cnt values of the gather buffer: its segment starts at the
+    // running total of gathered values (where a segment lies never reaches a result).  One atomic per 1024-thread workgroup on that total and one on
+    // the length of the small list (2 .. 16 runs, so that the 16-lane kernels only see those): all of them hit one address, and one per wave (23 k
+    // for 1.5 M MEMs) cost 0.27 ms.  The big and large lists are short: an atomic per entry.
+    const uint64_t seg_cnt = (valid && cnt >= 2) ? cnt : 0;
+    const bool is_small = seg_cnt != 0 && cnt <= PGX_TAG_SMALL;
     const unsigned long long m = __ballot(is_small);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint64_t seg_inc = seg_cnt; // inclusive scan over the wave (most waves hold no listed query at all)
+    if (__ballot(seg_cnt != 0)) {
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint64_t t = __shfl_up(seg_inc, off, 64);
+            if (lane >= off) seg_inc += t;
+        }
+    }
+    if (lane == 63) s_seg[wv] = seg_inc;
     if (lane == 0) s_cnt[wv] = (uint32_t)__popcll(m);
     __syncthreads();
     if (threadIdx.x == 0) {
         uint32_t tot = 0;
-        for (int k = 0; k < PGX_TAG_LOCATE_THREADS / 64; k++) { const uint32_t c = s_cnt[k]; s_cnt[k] = tot; tot += c; }
+        uint64_t gtot = 0;
+        for (int k = 0; k < PGX_TAG_LOCATE_THREADS / 64; k++) {
+            const uint32_t c = s_cnt[k]; s_cnt[k] = tot; tot += c;
+            const uint64_t g = s_seg[k]; s_seg[k] = gtot; gtot += g;
+        }
         s_base = tot ? atomicAdd(n_small, (unsigned long long)tot) : 0ull;
+        s_gbase = gtot ? atomicAdd(n_gathered, (unsigned long long)gtot) : 0ull;
     }
     __syncthreads();
-    if (is_small) small_list[s_base + s_cnt[wv] + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull))] = i;
-    __syncthreads(); // s_cnt / s_base are reused by the next round
+    if (seg_cnt) {
+        PgxTagRec rec;
+        rec.q = i; rec.first = fi; rec.cnt = cnt; rec.seg = s_gbase + s_seg[wv] + seg_inc - seg_cnt;
+        if (is_small) small_recs[s_base + s_cnt[wv] + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull))] = rec;
+        else if (cnt <= PGX_SORT_LDS_CAP) big_recs[atomicAdd(n_big, 1ull)] = rec;
+        else {
+            large_recs[atomicAdd(n_large, 1ull)] = rec;
+            atomicMax(n_large + 1, (unsigned long long)cnt); // sizes the LDS of the large-path launch
+        }
+    }
+    __syncthreads(); // s_cnt / s_seg / s_base / s_gbase are reused by the next round
   }
 }
 
-// 16 lanes per query, <= 16 runs: gather, sort, unique -> seg, ucount
+// 16 lanes per query, <= 16 runs: gather, sort, unique -> segment, uval
 __global__ void __launch_bounds__(256)
-pgx_tag_small_kernel(PgxDevImage img, const uint64_t *__restrict__ list, uint64_t n_cap, const uint64_t *__restrict__ n_dev,
-                     const uint64_t *__restrict__ abort, const uint64_t *__restrict__ run_nums,
-                     const uint64_t *__restrict__ first_item, const uint64_t *__restrict__ seg_off, uint64_t *__restrict__ buf,
-                     uint64_t *__restrict__ ucount, unsigned long long *__restrict__ n_overflow) {
+pgx_tag_small_kernel(PgxDevImage img, const PgxTagRec *__restrict__ recs, uint64_t n_cap, const uint64_t *__restrict__ n_dev,
+                     const uint64_t *__restrict__ abort, uint64_t *__restrict__ buf, uint64_t *__restrict__ uval, unsigned long long *__restrict__ n_overflow) {
   if (PGX_ABORTED(abort)) return;
   const uint64_t n = PGX_DEV_COUNT(n_cap, n_dev);
   const int lane = threadIdx.x & 63, l16 = lane & 15, grp = lane >> 4;
   for (uint64_t wbase = ((uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u)) >> 4; wbase < n; wbase += ((uint64_t)gridDim.x * blockDim.x) >> 4) { // (uniform per wave)
     const uint64_t w16 = wbase + (uint64_t)grp; // entry of the small list (2 .. 16 runs)
-    const bool valid = w16 < n;
-    const uint64_t q = valid ? list[w16] : 0;
-    const uint64_t cnt = valid ? run_nums[q] : 0;
-    const bool mine = valid;
+    const bool mine = w16 < n;
+    PgxTagRec rec = {0, 0, 0, 0};
+    if (mine) rec = recs[w16];
+    const uint64_t cnt = rec.cnt;
     uint64_t v = ~0ull;
     bool over = false;
     if (mine && (uint64_t)l16 < cnt) {
-        const uint64_t it = first_item[q] + (uint64_t)l16;
+        const uint64_t it = rec.first + (uint64_t)l16;
         if (it < img.n_tag_items) v = img.tvals[it];
         else { v = 0; over = true; } // the reference reads past the stored runs (UB): value 0
     }
@@ -235,9 +251,9 @@ pgx_tag_small_kernel(PgxDevImage img, const uint64_t *__restrict__ list, uint64_
     const unsigned long long mask = __ballot(keep);
     const unsigned long long omask = __ballot(over);
     const uint32_t gm = (uint32_t)(mask >> (16 * grp)) & 0xFFFFu;
-    if (keep) buf[seg_off[q] + (uint64_t)__popc(gm & ((1u << l16) - 1u))] = v;
+    if (keep) buf[rec.seg + (uint64_t)__popc(gm & ((1u << l16) - 1u))] = v;
     if (mine && l16 == 0) {
-        ucount[q] = (uint64_t)__popc(gm);
+        uval[rec.q] = (uint64_t)__popc(gm);
         if ((omask >> (16 * grp)) & 0xFFFFull) atomicAdd(n_overflow, 1ull);
     }
   }
@@ -245,16 +261,14 @@ pgx_tag_small_kernel(PgxDevImage img, const uint64_t *__restrict__ list, uint64_
 
 // one wave per listed query: gather run values into its segment of `buf`
 __global__ void __launch_bounds__(256)
-pgx_tag_gather_kernel(PgxDevImage img, const uint64_t *__restrict__ list, uint64_t n_cap, const uint64_t *__restrict__ n_dev,
-                      const uint64_t *__restrict__ abort, const uint64_t *__restrict__ run_nums,
-                      const uint64_t *__restrict__ first_item, const uint64_t *__restrict__ seg_off, uint64_t *__restrict__ buf,
-                      unsigned long long *__restrict__ n_overflow) {
+pgx_tag_gather_kernel(PgxDevImage img, const PgxTagRec *__restrict__ recs, uint64_t n_cap, const uint64_t *__restrict__ n_dev,
+                      const uint64_t *__restrict__ abort, uint64_t *__restrict__ buf, unsigned long long *__restrict__ n_overflow) {
   if (PGX_ABORTED(abort)) return;
   const uint64_t n_list = PGX_DEV_COUNT(n_cap, n_dev);
   const int lane = threadIdx.x & 63;
   for (uint64_t w = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w < n_list; w += ((uint64_t)gridDim.x * blockDim.x) >> 6) {
-    const uint64_t q = list[w];
-    const uint64_t cnt = run_nums[q], src = first_item[q], dst = seg_off[q];
+    const PgxTagRec rec = recs[w];
+    const uint64_t cnt = rec.cnt, src = rec.first, dst = rec.seg;
     bool over = false;
     for (uint64_t t = lane; t < cnt; t += 64) {
         const uint64_t it = src + t;
@@ -303,18 +317,19 @@ __device__ __forceinline__ uint64_t pgx_wave_sort_unique(Ptr arr, uint64_t *__re
 }
 
 // one wave per listed query: sort its segment and drop duplicates in place; ucount[q] = #unique
+// (L: how a list entry resolves to query, count and segment -- PgxTagRecs / PgxTagDense, pgx_device.h)
+template <class L>
 __global__ void __launch_bounds__(256)
-pgx_tag_sort_unique_kernel(const uint64_t *__restrict__ list, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
-                           const uint64_t *__restrict__ run_nums,
-                           const uint64_t *__restrict__ seg_off, uint64_t *__restrict__ buf, uint64_t *__restrict__ ucount) {
+pgx_tag_sort_unique_kernel(L src, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
+                           uint64_t *__restrict__ buf, uint64_t *__restrict__ ucount) {
   __shared__ uint64_t s_sort[4][PGX_SORT_LDS_CAP];
   if (PGX_ABORTED(abort)) return;
   const uint64_t n_list = PGX_DEV_COUNT(n_cap, n_dev);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (uint64_t wi = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; wi < n_list; wi += ((uint64_t)gridDim.x * blockDim.x) >> 6) {
-    const uint64_t q = list[wi];
-    const uint64_t cnt = run_nums[q];
-    uint64_t *seg = buf + seg_off[q];
+    uint64_t q, cnt, seg_at;
+    src.get(wi, q, cnt, seg_at);
+    uint64_t *seg = buf + seg_at;
     if (cnt <= 64) {
         uint64_t v = (uint64_t)lane < cnt ? seg[lane] : ~0ull;
 #pragma unroll
@@ -384,84 +399,107 @@ __device__ __forceinline__ uint64_t pgx_block_sort_unique(Ptr arr, uint64_t *__r
     return outn;
 }
 
-// one 1024-thread workgroup per listed query with more than PGX_SORT_LDS_CAP runs
+// one 1024-thread workgroup per listed query with more than PGX_SORT_LDS_CAP runs; scratch_off (read only for a query beyond
+// PGX_SORT_WG_LDS_CAP) is indexed by list position with records, by query with dense arrays
+template <class L>
 __global__ void __launch_bounds__(1024)
-pgx_tag_sort_large_kernel(const uint64_t *__restrict__ list, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
-                          const uint64_t *__restrict__ run_nums,
-                          const uint64_t *__restrict__ seg_off, uint64_t *__restrict__ buf, uint64_t *__restrict__ scratch,
+pgx_tag_sort_large_kernel(L src, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
+                          uint64_t *__restrict__ buf, uint64_t *__restrict__ scratch,
                           const uint64_t *__restrict__ scratch_off, uint64_t *__restrict__ ucount) {
     extern __shared__ __align__(16) uint64_t pgx_sort_lds[]; // PGX_SORT_WG_LDS_CAP values
     __shared__ uint32_t s_wsum[16];
     if (PGX_ABORTED(abort)) return;
     const uint64_t n_list = PGX_DEV_COUNT(n_cap, n_dev);
     for (uint64_t e = blockIdx.x; e < n_list; e += gridDim.x) {
-        const uint64_t q = list[e];
-        const uint64_t cnt = run_nums[q];
-        uint64_t *seg = buf + seg_off[q];
+        uint64_t q, cnt, seg_at;
+        src.get(e, q, cnt, seg_at);
+        uint64_t *seg = buf + seg_at;
         uint64_t p2 = 64;
         while (p2 < cnt) p2 <<= 1;
         uint64_t outn;
         if (p2 <= PGX_SORT_WG_LDS_CAP) outn = pgx_block_sort_unique(&pgx_sort_lds[0], seg, cnt, p2, s_wsum);
-        else outn = pgx_block_sort_unique(scratch + scratch_off[q], seg, cnt, p2, s_wsum);
+        else outn = pgx_block_sort_unique(scratch + scratch_off[src.scratch_index(e, q)], seg, cnt, p2, s_wsum);
         if (threadIdx.x == 0) ucount[q] = outn;
         __syncthreads();
+    }
+}
+
+// global sort scratch of the large path, per entry of a list: the power of two a query beyond PGX_SORT_WG_LDS_CAP sorts in, 0 otherwise
+__global__ void __launch_bounds__(256)
+pgx_tag_need_kernel(const PgxTagRec *__restrict__ recs, uint64_t n_list, uint64_t *__restrict__ need) {
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_list; e += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t cnt = recs[e].cnt;
+        uint64_t p2 = 64;
+        while (p2 < cnt && p2 < (1ull << 62)) p2 <<= 1;
+        need[e] = p2 > PGX_SORT_WG_LDS_CAP ? p2 : 0;
     }
 }
 
 // 16 lanes per query: copy the unique prefix of its segment to the dense positions array.  Segments with more than
 // `max_count` values are left to pgx_tag_compact_list_kernel (a few huge segments would otherwise keep 16 lanes busy
 // for thousands of iterations while the rest of the grid has finished).
+template <class L>
 __global__ void __launch_bounds__(256)
-pgx_tag_compact_kernel(const uint64_t *__restrict__ list, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
-                       const uint64_t *__restrict__ ucount, const uint64_t *__restrict__ seg_off,
-                       const uint64_t *__restrict__ buf, const uint64_t *__restrict__ pos_off, uint64_t *__restrict__ positions,
-                       uint64_t max_count) {
+pgx_tag_compact_kernel(L src, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
+                       const uint64_t *__restrict__ ucount, const uint64_t *__restrict__ buf, const uint64_t *__restrict__ pos_off,
+                       uint64_t *__restrict__ positions, uint64_t max_count) {
     if (PGX_ABORTED(abort)) return;
     const uint64_t n = PGX_DEV_COUNT(n_cap, n_dev);
     const int l16 = threadIdx.x & 15;
     for (uint64_t w16 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4; w16 < n; w16 += ((uint64_t)gridDim.x * blockDim.x) >> 4) {
-        const uint64_t q = list ? list[w16] : w16; // a list of queries (small / big / large), or all of them
-        const uint64_t c = ucount[q], src = seg_off[q], dst = pos_off[q];
+        uint64_t q, cnt, seg_at;
+        src.get(w16, q, cnt, seg_at);
+        const uint64_t c = ucount[q], dst = pos_off[q];
         if (c > max_count) continue;
-        for (uint64_t t = l16; t < c; t += 16) positions[dst + t] = buf[src + t];
+        for (uint64_t t = l16; t < c; t += 16) positions[dst + t] = buf[seg_at + t];
     }
 }
 
-// one thread per query: single-run queries (answered by the locate kernel) go straight to their place
+// one thread per query: single-run queries (answered by the locate kernel) go straight to their place.  Only behind the three-launch form of
+// the scan of the offsets (PGX_SCAN_THREE=1); pgx_scan_tag_tail_kernel stores them itself.
 __global__ void __launch_bounds__(256)
 pgx_tag_compact_single_kernel(uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort, const uint64_t *__restrict__ run_nums,
-                              const uint64_t *__restrict__ single, const uint64_t *__restrict__ pos_off, uint64_t *__restrict__ positions) {
+                              const uint64_t *__restrict__ uval, const uint64_t *__restrict__ pos_off, uint64_t *__restrict__ positions) {
     if (PGX_ABORTED(abort)) return;
     const uint64_t n = PGX_DEV_COUNT(n_cap, n_dev);
     for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (uint64_t)gridDim.x * blockDim.x)
-        if (run_nums[q] == 1) positions[pos_off[q]] = single[q];
+        if (run_nums[q] == 1) positions[pos_off[q]] = uval[q];
 }
 
 // one workgroup per listed query: the segments pgx_tag_compact_kernel skipped (more than `max_count` values)
+template <class L>
 __global__ void __launch_bounds__(256)
-pgx_tag_compact_list_kernel(const uint64_t *__restrict__ list, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
-                            const uint64_t *__restrict__ ucount,
-                            const uint64_t *__restrict__ seg_off, const uint64_t *__restrict__ buf, const uint64_t *__restrict__ pos_off,
+pgx_tag_compact_list_kernel(L src, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
+                            const uint64_t *__restrict__ ucount, const uint64_t *__restrict__ buf, const uint64_t *__restrict__ pos_off,
                             uint64_t *__restrict__ positions, uint64_t max_count) {
     if (PGX_ABORTED(abort)) return;
     const uint64_t n_list = PGX_DEV_COUNT(n_cap, n_dev);
     for (uint64_t e = blockIdx.x; e < n_list; e += gridDim.x) {
-        const uint64_t q = list[e];
-        const uint64_t c = ucount[q], src = seg_off[q], dst = pos_off[q];
+        uint64_t q, cnt, seg_at;
+        src.get(e, q, cnt, seg_at);
+        const uint64_t c = ucount[q], dst = pos_off[q];
         if (c <= max_count) continue;
-        for (uint64_t t = threadIdx.x; t < c; t += blockDim.x) positions[dst + t] = buf[src + t];
+        for (uint64_t t = threadIdx.x; t < c; t += blockDim.x) positions[dst + t] = buf[seg_at + t];
     }
 }
 
+#define PGX_TAG_INSTANTIATE(L) \
+    template __global__ void pgx_tag_sort_unique_kernel<L>(L, uint64_t, const uint64_t *, const uint64_t *, uint64_t *, uint64_t *); \
+    template __global__ void pgx_tag_sort_large_kernel<L>(L, uint64_t, const uint64_t *, const uint64_t *, uint64_t *, uint64_t *, const uint64_t *, uint64_t *); \
+    template __global__ void pgx_tag_compact_kernel<L>(L, uint64_t, const uint64_t *, const uint64_t *, const uint64_t *, const uint64_t *, const uint64_t *, uint64_t *, uint64_t); \
+    template __global__ void pgx_tag_compact_list_kernel<L>(L, uint64_t, const uint64_t *, const uint64_t *, const uint64_t *, const uint64_t *, const uint64_t *, uint64_t *, uint64_t);
+PGX_TAG_INSTANTIATE(PgxTagRecs) PGX_TAG_INSTANTIATE(PgxTagDense)
+
 // Identical large queries are common (every read from the same repeat / N run yields the same SA interval): one representative
 // per distinct (first item, run count) is sorted, the others copy its result.  Grouping on the device: open addressing over
-// `table` (zeroed by the host, a power of two of slots >= 2 x the list), slot = 1 + the query id of the first query that claimed it;
+// `table` (zeroed by the host, a power of two of slots >= 2 x the list), slot = 1 + the LIST POSITION of the first entry that claimed it
+// (a duplicate may lie anywhere on the list, in another workgroup's part of it than its representative);
 // whichever duplicate wins the slot becomes the representative -- their results are identical, so the output does not depend on it.
+// reps: the representatives' records; pairs: (list position of a duplicate, list position of its representative).
 __global__ void __launch_bounds__(256)
-pgx_tag_dedup_kernel(const uint64_t *__restrict__ list, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
-                     const uint64_t *__restrict__ first_item, const uint64_t *__restrict__ run_nums, unsigned long long *__restrict__ table,
-                     uint64_t table_mask, uint64_t *__restrict__ reps, unsigned long long *__restrict__ n_rep, uint64_t *__restrict__ pairs,
-                     unsigned long long *__restrict__ n_dup) {
+pgx_tag_dedup_kernel(const PgxTagRec *__restrict__ recs, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
+                     unsigned long long *__restrict__ table, uint64_t table_mask, PgxTagRec *__restrict__ reps, unsigned long long *__restrict__ n_rep,
+                     uint64_t *__restrict__ pairs, unsigned long long *__restrict__ n_dup) {
     if (PGX_ABORTED(abort)) return;
     const uint64_t n_list = PGX_DEV_COUNT(n_cap, n_dev);
     // (whole waves walk the list, so that the two global counters take ONE atomic per wave and round instead of one per query: with many identical
@@ -471,18 +509,19 @@ pgx_tag_dedup_kernel(const uint64_t *__restrict__ list, uint64_t n_cap, const ui
     for (uint64_t e0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); e0 < n_list; e0 += stride) {
         const uint64_t e = e0 + lane;
         const bool valid = e < n_list;
-        uint64_t q = 0, r = 0;
-        int kind = 0; // 1: representative, 2: duplicate of r
+        PgxTagRec rec = {0, 0, 0, 0};
+        uint64_t r = 0;
+        int kind = 0; // 1: representative, 2: duplicate of entry r
         if (valid) {
-            q = list[e];
-            const uint64_t f = first_item[q], c = run_nums[q];
+            rec = recs[e];
+            const uint64_t f = rec.first, c = rec.cnt;
             uint64_t h = (f * 0x9E3779B97F4A7C15ull ^ c * 0xC2B2AE3D27D4EB4Full) & table_mask;
             for (;; h = (h + 1) & table_mask) {
                 unsigned long long prev = __hip_atomic_load(&table[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (a slot never changes once it is claimed)
-                if (prev == 0ull) prev = atomicCAS(&table[h], 0ull, (unsigned long long)(q + 1));
+                if (prev == 0ull) prev = atomicCAS(&table[h], 0ull, (unsigned long long)(e + 1));
                 if (prev == 0ull) { kind = 1; break; }
                 r = (uint64_t)prev - 1;
-                if (first_item[r] == f && run_nums[r] == c) { kind = 2; break; }
+                if (recs[r].first == f && recs[r].cnt == c) { kind = 2; break; }
             }
         }
         const unsigned long long m_rep = __ballot(kind == 1), m_dup = __ballot(kind == 2);
@@ -494,45 +533,44 @@ pgx_tag_dedup_kernel(const uint64_t *__restrict__ list, uint64_t n_cap, const ui
         b_rep = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b_rep >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b_rep);
         b_dup = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b_dup >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b_dup);
         const unsigned long long below = (1ull << lane) - 1ull;
-        if (kind == 1) reps[b_rep + (unsigned long long)__popcll(m_rep & below)] = q;
+        if (kind == 1) reps[b_rep + (unsigned long long)__popcll(m_rep & below)] = rec;
         if (kind == 2) {
             const unsigned long long at = b_dup + (unsigned long long)__popcll(m_dup & below);
-            pairs[2 * at] = q; pairs[2 * at + 1] = r;
+            pairs[2 * at] = e; pairs[2 * at + 1] = r;
         }
     }
 }
 
-// a (duplicate, representative) pair: the duplicate query reads exactly the same items, so its sorted unique result is the representative's (and it
-// overflows iff the representative does).  Nothing is copied here (round 4): the duplicate's segment offset is pointed at the representative's
-// values, and the compaction, which only ever reads seg_off[q] as the start of q's values, copies them from there straight to their final place
-// (before, every duplicate's list was written twice: 0.7 ms of a step with 5 % of the reads cut from N runs).
+// a (duplicate, representative) pair of list positions: the duplicate query reads exactly the same items, so its sorted unique result is the
+// representative's (and it overflows iff the representative does).  Nothing is copied here (round 4): the duplicate's record is pointed at the
+// representative's segment, and the compaction, which only ever reads a record's segment as the start of its query's values, copies them from
+// there straight to their final place (before, every duplicate's list was written twice: 0.7 ms of a step with 5 % of the reads cut from N runs).
 __global__ void __launch_bounds__(256)
 pgx_tag_copy_dups_kernel(const uint64_t *__restrict__ pairs, uint64_t n_cap, const uint64_t *__restrict__ n_dev, const uint64_t *__restrict__ abort,
-                         uint64_t n_tag_items,
-                         const uint64_t *__restrict__ first_item, const uint64_t *__restrict__ run_nums,
-                         uint64_t *__restrict__ seg_off, uint64_t *__restrict__ buf, uint64_t *__restrict__ ucount,
-                         unsigned long long *__restrict__ n_overflow) {
+                         uint64_t n_tag_items, PgxTagRec *__restrict__ recs, uint64_t *__restrict__ uval, unsigned long long *__restrict__ n_overflow) {
     if (PGX_ABORTED(abort)) return;
     const uint64_t n_pairs = PGX_DEV_COUNT(n_cap, n_dev);
     for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_pairs; e += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t dup = pairs[2 * e], rep = pairs[2 * e + 1];
-        ucount[dup] = ucount[rep];
-        seg_off[dup] = seg_off[rep]; // (a representative is never a duplicate: its own entry stays)
-        if (first_item[dup] + run_nums[dup] > n_tag_items) atomicAdd(n_overflow, 1ull);
+        const PgxTagRec d = recs[dup];
+        uval[d.q] = uval[recs[rep].q];
+        recs[dup].seg = recs[rep].seg; // (a representative is never a duplicate: its own entry stays)
+        if (d.first + d.cnt > n_tag_items) atomicAdd(n_overflow, 1ull);
     }
-    (void)buf;
 }
 
 // capacity check of a speculatively sized stage: raises the abort flag when a count the following kernels rely on exceeds what
-// their buffers were sized for (the host then repeats the run with exact sizes)
+// their buffers were sized for (the host then repeats the run with exact sizes).  v0 .. v3 raise bits 0 .. 3, v4 bit 0 as well.
 __global__ void pgx_spec_check_kernel(const uint64_t *__restrict__ v0, uint64_t c0, const uint64_t *__restrict__ v1, uint64_t c1,
-                                      const uint64_t *__restrict__ v2, uint64_t c2, const uint64_t *__restrict__ v3, uint64_t c3, uint64_t *__restrict__ abort) {
+                                      const uint64_t *__restrict__ v2, uint64_t c2, const uint64_t *__restrict__ v3, uint64_t c3,
+                                      const uint64_t *__restrict__ v4, uint64_t c4, uint64_t *__restrict__ abort) {
     if (threadIdx.x) return;
     unsigned long long bits = 0;
     if (v0 && *v0 > c0) bits |= 1ull;
     if (v1 && *v1 > c1) bits |= 2ull;
     if (v2 && *v2 > c2) bits |= 4ull;
     if (v3 && *v3 > c3) bits |= 8ull;
+    if (v4 && *v4 > c4) bits |= 1ull;
     if (bits) atomicOr((unsigned long long *)abort, bits);
 }
 
