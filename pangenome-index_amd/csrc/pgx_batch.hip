@@ -724,9 +724,23 @@ static void launch_pairs(RunCtx &r, FmArgs &a, const uint8_t *skip, uint64_t cn,
         b->timing.pairs_reads = lce ? 4u : coop ? 3u : 2u;
         grid = find_mems_grid(r, kp, plds, true, cn);
     }
-    void *pargs[] = {&a.img, &a.reads, &a.off, &a.n, &a.min_len, &a.min_occ, &a.slot_off, &a.slots, &a.cnt, &a.next, &a.cur, &a.first, &a.base,
-                     &a.hext, &a.hcap, &a.hlist, &a.hcount, &skip, &a_packed, &a_pkw, &a.ovf, &a.ovf_cap};
-    HIPCHECK(hipLaunchKernel(kp, dim3(grid), dim3(PGX_FM_THREADS), pargs, plds, r.s));
+    // the kernel's one argument: what it reads of the image, and the launch (pgx_device.h)
+    PgxPairsArgs p = {};
+    p.pairs = img.pairs; p.seed = img.seed; p.seed_end = img.seed_end;
+    p.lce_sa = img.lce_sa; p.lce_text = img.lce_text; p.lce_flags = img.lce_flags; p.lce_lcp = img.lce_lcp;
+    p.reads = a.reads; p.slots = a.slots; p.mem_count = a.cnt;
+    p.n = img.n; p.min_len = a.min_len; p.min_occ = a.min_occ;
+    p.first_read = a.first; p.n_reads = a.n;
+    p.seed_k = img.seed_k; p.seed_end_k = img.seed_end_k; p.lce_max = img.lce_max; p.refill_min = img.refill_min;
+    p.pk_words = a_pkw; p.heavy_ext = a.hext; p.pairs_sb_shift = img.pairs_sb_shift; p.dense = img.dense;
+    p.consts = img.consts; p.first_ext = img.first_ext; p.pbase = img.pbase; p.n_sbp = img.n_sbp;
+    p.offsets = a.off; p.skip = skip; p.packed = a_packed;
+    p.cursor = a.cur; p.ctr = a.next;
+    p.slot_off = a.slot_off; p.slot_base = a.base; p.ovf_base = a.ovf; p.ovf_cap = a.ovf_cap;
+    p.heavy_list = a.hlist; p.heavy_count = a.hcount; p.heavy_cap = a.hcap; p.d2_sb_shift = img.d2_sb_shift;
+    p.blocks = img.blocks; p.exc = img.exc; p.sbase2 = img.sbase2;
+    void *pargs[] = {&p};
+    HIPCHECK(hipLaunchKernel(kp, dim3(grid), dim3(PGX_FM_THREADS), pargs, plds, r.s)); // (PGX_FM_THREADS: the kernel takes its LDS strides from it)
     b->timing.kernels |= kp_bits;
 }
 

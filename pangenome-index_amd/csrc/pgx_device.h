@@ -137,13 +137,48 @@ __global__ void pgx_arena_demand_kernel(unsigned long long *ctr);
 
 // ---- pgx_pairs_kernels.hip: the two-step find_mems kernel
 // PAIRS image (pgx_image.h): two extensions per loop trip; an extension its blocks cannot answer (special positions) goes through the other image
+// Its one argument (launch_pairs fills it): what the kernel reads of the image, and the launch.  The first group is used in every trip of the
+// main loop and lives in scalar registers for the whole kernel; the second is read before the loop only; the third belongs to paths a wave takes
+// rarely (a new group of reads, the fifth MEM of a read, a heavy read, an extension through the other image, the end of the kernel) and is
+// fetched from the kernel argument segment where it is used (PGX_PAIRS_COLD in pgx_pairs_kernels.hip), so that it holds no register in between:
+// with everything in registers the loop kept 82 scalar values in the lanes of two vector registers and fetched 165 of them back per trip.
+// (Those paths read first_read, n_reads, min_len, heavy_ext and slots of the first group that way as well.)
+struct PgxPairsArgs {
+    // every trip
+    const uint4 *pairs;                    // PgxDevImage: the PAIRS image, the seed tables, the LCE image (see there)
+    const uint4 *seed, *seed_end;          // (the LCE instances keep the two tables in LDS: s_seedt)
+    const uint32_t *lce_sa, *lce_text, *lce_flags;
+    const uint8_t *lce_lcp;
+    const uint8_t *reads;                  // the byte-window instances only (the packed ones read LDS)
+    pgx_mem *slots;
+    uint32_t *mem_count;
+    uint64_t n, min_len, min_occ;          // (the LCE instances are launched for min_occ <= 1 only and do not read it)
+    uint64_t first_read, n_reads;          // the launch serves reads [first_read, n_reads), fewer than 2^32
+    uint32_t seed_k, seed_end_k, lce_max, refill_min;
+    uint32_t pk_words, heavy_ext, pairs_sb_shift, dense;
+    // before the loop
+    const PgxConsts *consts;
+    const uint4 *first_ext;
+    const uint64_t *pbase;
+    uint32_t n_sbp, pad0;
+    // rare paths
+    const uint64_t *offsets;
+    const uint8_t *skip;
+    const uint32_t *packed;
+    unsigned long long *cursor, *ctr;      // ctr: the counters (PgxCounterSlot)
+    const uint64_t *slot_off;
+    uint64_t slot_base;
+    uint32_t *ovf_base;
+    uint64_t ovf_cap;
+    pgx_heavy_item *heavy_list;
+    unsigned long long *heavy_count;
+    uint32_t heavy_cap, d2_sb_shift;
+    const uint4 *blocks;                   // the image the PAIRS image accompanies (dense, dense2, wide dense2)
+    const uint32_t *exc;
+    const uint64_t *sbase2;
+};
 template <bool WIDE, bool PACKED, bool COOP, bool S64, bool LCE>
-__global__ void pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *reads, const uint64_t *offsets, uint64_t n_reads,
-                                           uint64_t min_len, uint64_t min_occ, const uint64_t *slot_off, pgx_mem *slots,
-                                           uint32_t *mem_count, unsigned long long *n_ext_total, unsigned long long *cursor, uint64_t first_read,
-                                           uint64_t slot_base, uint32_t heavy_ext, uint32_t heavy_cap, pgx_heavy_item *heavy_list, unsigned long long *heavy_count,
-                                           const uint8_t *skip, const uint32_t *packed, uint32_t pk_words,
-                                           uint32_t *ovf_base, uint64_t ovf_cap);
+__global__ void pgx_find_mems_pairs_kernel(PgxPairsArgs a);
 
 // ---- pgx_reads_kernels.hip: per-upload passes over the reads
 __global__ void pgx_bad_chunks_kernel(const uint8_t *reads, uint64_t n_bytes, uint64_t *chunks, unsigned long long *count, uint64_t cap, uint32_t *packed);

@@ -74,25 +74,43 @@ __device__ __forceinline__ uint32_t pgx_packed_seed_index(const uint32_t *s_rd, 
 // the stage started (FUSE below).  Results are bit-identical (tests run all three ways).
 template <bool WIDE, bool PACKED, bool COOP, bool S64, bool LCE>
 __global__ void __launch_bounds__(PGX_FM_THREADS, LCE ? PGX_LCE_WAVES : ((PACKED && !WIDE && !COOP) ? PGX_PAIRS_PACKED_WAVES : PGX_FM_WAVES_PER_SIMD)) // (<= 96 VGPRs: five waves per SIMD fit and are what the launch uses; four are as fast -- 20.7 against 20.6-21.0 ms at chr22 scale --, three 21.8)
-pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, const uint64_t *__restrict__ offsets,
-                           uint64_t n_reads, uint64_t min_len, uint64_t min_occ, const uint64_t *__restrict__ slot_off,
-                           pgx_mem *__restrict__ slots, uint32_t *__restrict__ mem_count, unsigned long long *__restrict__ n_ext_total,
-                           unsigned long long *__restrict__ cursor, uint64_t first_read, uint64_t slot_base, uint32_t heavy_ext, uint32_t heavy_cap,
-                           pgx_heavy_item *__restrict__ heavy_list, unsigned long long *__restrict__ heavy_count, const uint8_t *__restrict__ skip,
-                           const uint32_t *__restrict__ packed, uint32_t pk_words, uint32_t *__restrict__ ovf_base, uint64_t ovf_cap) {
+pgx_find_mems_pairs_kernel(PgxPairsArgs pa) {
     typedef typename std::conditional<WIDE, uint64_t, uint32_t>::type pos_t;
+    // The arguments of the rare paths (PgxPairsArgs, third group) are read from the kernel argument segment at the point of use: a volatile scalar
+    // load there -- an s_load and a wait on a path the wave seldom takes -- instead of a scalar register held across the loop.
+    const volatile PgxPairsArgs __attribute__((address_space(4))) *const ka = (const volatile PgxPairsArgs __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
+#define PGX_PAIRS_COLD(f) (ka->f)
+    // LCE: the pointers a trip's line loads start from are made opaque here, so that they stay in scalar registers: a plain kernel argument the compiler may
+    // fetch again from the argument segment inside the loop (it did: one s_load of eight dwords and a wait in front of the address of every trip's line)
+    if (LCE) asm volatile("" : "+s"(pa.pairs), "+s"(pa.lce_text), "+s"(pa.lce_flags));
+    const uint8_t *__restrict__ const reads = pa.reads;
+    // (the first MEMs of read r of the launch: slots[nm * chunk_reads + r - first_read]; with the pointer moved back the loop needs no first_read)
+    pgx_mem *__restrict__ const slots_fr = reinterpret_cast<pgx_mem *>(reinterpret_cast<uintptr_t>(pa.slots) - (uintptr_t)pa.first_read * sizeof(pgx_mem));
+    uint32_t *__restrict__ const mem_count = pa.mem_count;
+    const uint32_t pk_words = pa.pk_words;
+    // extensions a read may spend before the rest of it is handed on; 0 = never, which is 2^32 - 1 (a read that takes part is at most
+    // PGX_FM_HEAVY_MAXLEN long: all its start positions together stay far below that).  LCE: no register for it, see hmark
+    const uint32_t heavy_ext = LCE ? 0u : (pa.heavy_ext ? pa.heavy_ext : 0xFFFFFFFFu);
+    // (the launch serves fewer than 2^32 reads, below read number 2^32: pgx_batch_run)
+    const uint32_t chunk_reads = (uint32_t)(pa.n_reads - pa.first_read);
+    // min_len as 32 bits: a read is shorter than 2^31, so anything from 2^31 on means "longer than every read" like 2^31 itself
+    const uint32_t min_len = pa.min_len > 0x80000000ull ? 0x80000000u : (uint32_t)pa.min_len;
     __shared__ uint32_t s_ext[512];
     __shared__ pos_t s_C[8];
     __shared__ pos_t s_t2[32];
     // first_ext: [byte] the full interval extended by byte, [256 + byte] extended by 0 and then by byte (packed like a seed entry); PACKED (every byte is
     // one of A C G T): [code] by "ACTG"[code], [4] by 0, [5 + code] by 0 and then by "ACTG"[code]
     __shared__ uint4 s_fe[PACKED ? 16 : 512];
+    // FUSE: the two seed tables as a lane that starts a stage selects them, [0] the table proper and [1] the end table: {pointer lo, hi, K, extensions an entry
+    // stands for (K, K + 1)} -- one LDS read where the stage starts instead of six scalar registers across the loop and the selects between them
+    typedef uint32_t pgx_u32x4 __attribute__((ext_vector_type(4)));
+    __shared__ pgx_u32x4 s_seedt[2];
     extern __shared__ __align__(16) unsigned char pgx_dyn_lds[];
     static_assert(!COOP || PACKED, "the cooperative loads come with the packed reads");
     static_assert(!LCE || (PACKED && !WIDE && !COOP), "the text comparison reads the packed reads and 32-bit suffix array entries");
     constexpr uint32_t SYMS = PGX_PAIRS_SYMS, STRIDE = S64 ? PGX_PAIRS_STRIDE64 : PGX_PAIRS_SYMS;
-    uint32_t *s_rd = reinterpret_cast<uint32_t *>(pgx_dyn_lds); // PACKED: word w of this thread's read at s_rd[w * blockDim.x + threadIdx.x] (pk_words words per thread)
-    const uint32_t rd_stride = blockDim.x;
+    uint32_t *s_rd = reinterpret_cast<uint32_t *>(pgx_dyn_lds); // PACKED: word w of this thread's read at s_rd[w * PGX_FM_THREADS + threadIdx.x] (pk_words words per thread)
+    constexpr uint32_t rd_stride = PGX_FM_THREADS; // (the workgroup size of every launch: launch_pairs)
     // COOP: behind the packed reads, 8 KiB per wave: piece p of the line of lane q's probe at [q * 8 + (p ^ (q & 7))] (the swizzle spreads the banks)
     uint4 *s_stage = reinterpret_cast<uint4 *>(pgx_dyn_lds + (size_t)pk_words * PGX_FM_THREADS * 4) + (size_t)(threadIdx.x >> 6) * 512;
     // WIDE: behind those, per superblock the sixteen pair-count bases and their four row sums (24 words each, img.n_sbp superblocks)
@@ -104,18 +122,25 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
     uint4 *s_sa4 = reinterpret_cast<uint4 *>(pgx_dyn_lds + (size_t)pk_words * PGX_FM_THREADS * 4);
     uint32_t *s_sae = reinterpret_cast<uint32_t *>(s_sa4 + PGX_FM_THREADS);
     uint32_t *s_lcp = s_sae + PGX_FM_THREADS;
-    for (uint32_t i = threadIdx.x; i < 512; i += blockDim.x) s_ext[i] = img.consts->ext_tab[i];
-    if (threadIdx.x < 8) s_C[threadIdx.x] = (pos_t)img.consts->C[threadIdx.x];
-    if (threadIdx.x < 32) s_t2[threadIdx.x] = (pos_t)img.consts->pair_t2w[threadIdx.x];
-    if (WIDE) for (uint32_t i = threadIdx.x; i < img.n_sbp * 24u; i += blockDim.x) s_pb[i] = img.pbase[i];
-    if (PACKED) { if (threadIdx.x < 9) s_fe[threadIdx.x] = img.first_ext[threadIdx.x == 4 ? 0u : (threadIdx.x > 4 ? 256u : 0u) + ((0x47544341u >> (8u * ((threadIdx.x > 4 ? threadIdx.x - 5u : threadIdx.x) & 3u))) & 0xFFu)]; }
-    else for (uint32_t i = threadIdx.x; i < 512; i += blockDim.x) s_fe[i] = img.first_ext[i];
+    for (uint32_t i = threadIdx.x; i < 512; i += PGX_FM_THREADS) s_ext[i] = pa.consts->ext_tab[i];
+    if (threadIdx.x < 8) s_C[threadIdx.x] = (pos_t)pa.consts->C[threadIdx.x];
+    if (threadIdx.x < 32) s_t2[threadIdx.x] = (pos_t)pa.consts->pair_t2w[threadIdx.x];
+    if (WIDE) for (uint32_t i = threadIdx.x; i < pa.n_sbp * 24u; i += PGX_FM_THREADS) s_pb[i] = pa.pbase[i];
+    if (PACKED) { if (threadIdx.x < 9) s_fe[threadIdx.x] = pa.first_ext[threadIdx.x == 4 ? 0u : (threadIdx.x > 4 ? 256u : 0u) + ((0x47544341u >> (8u * ((threadIdx.x > 4 ? threadIdx.x - 5u : threadIdx.x) & 3u))) & 0xFFu)]; }
+    else for (uint32_t i = threadIdx.x; i < 512; i += PGX_FM_THREADS) s_fe[i] = pa.first_ext[i];
+    if (LCE && threadIdx.x < 2) {
+        const uint64_t tp = (uint64_t)(threadIdx.x ? pa.seed_end : pa.seed);
+        const uint32_t tk = threadIdx.x ? pa.seed_end_k : pa.seed_k;
+        const pgx_u32x4 te = {(uint32_t)tp, (uint32_t)(tp >> 32), tk, tk + threadIdx.x};
+        s_seedt[threadIdx.x] = te;
+    }
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
-    const pos_t n = (pos_t)img.n;
-    const pos_t mo = WIDE ? (pos_t)min_occ : (pos_t)(min_occ > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)min_occ); // narrow: sizes are below 2^32, a larger min_occ makes everything "small" either way
-    const bool mo_huge = !WIDE && min_occ > 0xFFFFFFFFull;
+    const pos_t n = (pos_t)pa.n;
+    // (LCE: launched for min_occ <= 1 only, where "small" is "empty" -- every test against mo stands next to one against 0 --: a constant, no register)
+    const pos_t mo = LCE ? (pos_t)1 : WIDE ? (pos_t)pa.min_occ : (pos_t)(pa.min_occ > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)pa.min_occ); // narrow: sizes are below 2^32, a larger min_occ makes everything "small" either way
+    const bool mo_huge = !LCE && !WIDE && pa.min_occ > 0xFFFFFFFFull; // (min_occ <= 1 is mo <= 1 in all forms)
     // an entry of the seed tables / first_ext: {k lo, k' lo, s lo, k hi | k' hi << 8 | s hi << 16 | depth << 24}
     auto ent_k = [](const uint4 &e) { return WIDE ? (pos_t)((uint64_t)e.x | ((uint64_t)(e.w & 0xFFu) << 32)) : (pos_t)e.x; };
     auto ent_q = [](const uint4 &e) { return WIDE ? (pos_t)((uint64_t)e.y | ((uint64_t)((e.w >> 8) & 0xFFu) << 32)) : (pos_t)e.y; };
@@ -124,16 +149,28 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
     uint64_t base = 0;
     int32_t len = 0, x = 0, j = 0;
     pos_t k = 0, kp = 0, s = 0, Jk = 0, Js = 0;
-    uint32_t nm = 0, next = 0, next0 = 0;
+    uint32_t nm = 0, next = 0;
+    // `next` when the lane took its read.  LCE: `next` at which the read will have spent heavy_ext extensions, worked out from the argument segment when the lane
+    // takes the read and compared as a signed difference (never = 2^31 - 1, and so is anything above it: see heavy_ext)
+    uint32_t hmark = 0;
     int ph = 0;
     uint64_t win = 0, win_hi = 0;
     uint32_t win_at = ~0u; // the cached 16 bytes of the reads buffer: their offset / 16 (16 rather than 32 bytes: four registers less, no difference in time)
     uint32_t X0 = 0; // the four sums (each <= 96: one byte) over the first block of an interval that runs on into the next
     pos_t X0e = 0, X0f = 0;                                   // ... and the two absolute ranks at its start
     uint32_t pend = 0, fresh = 0, restart = 0;
-    uint64_t rnext = 0, rend = 0;
-    bool exhausted = false;
-    unsigned long long ln_blk = 0, ln_seed = 0, ln_two = 0; // wave-uniform (scalar registers): block lines / seed entries the wave asked for, trips with two extensions (PGX_CTR_PAIRS_*)
+    uint32_t rnext = 0, rend = 0; // (read numbers: below 2^32)
+    constexpr uint32_t EXHAUSTED = 0xFFFFFFFFu; // rnext == rend == this: the launch has no more reads (a read number only where it is the launch's last, n_reads: true then as well)
+    // wave-uniform (scalar registers): block lines / seed entries the wave asked for, trips with two extensions (PGX_CTR_PAIRS_*); in 32 bits -- a trip adds
+    // a few hundred at most --, added to the counters at the end of the kernel and whenever one of them has reached 2^31 (ln_flush)
+    uint32_t ln_blk = 0, ln_seed = 0, ln_two = 0;
+    auto ln_flush = [&]() __attribute__((always_inline)) { // (as at the end of the kernel nothing is added for a wave that has asked for no line; one line is kept back, so that the end still adds)
+        if (ln_blk) {
+            unsigned long long *const ctr = PGX_PAIRS_COLD(ctr);
+            if ((threadIdx.x & 63u) == 0u) { atomicAdd(ctr + PGX_CTR_PAIRS_LINES, (unsigned long long)(ln_blk - 1u)); atomicAdd(ctr + PGX_CTR_PAIRS_SEEDS, (unsigned long long)ln_seed); atomicAdd(ctr + PGX_CTR_PAIRS_TWO, (unsigned long long)ln_two); }
+            ln_blk = 1u; ln_seed = 0u; ln_two = 0u;
+        }
+    };
     uint32_t did2 = 0; // this lane's last trip performed two extensions (summed at the top of the next trip, where the wave is converged)
     // LCE: bit 0 = the lane's stage goes through the text (ph == 2), bit 1 = this stage must not (a flagged text line), bit 2 = this trip only reads on in the
     // table of common prefixes (no occurrence is compared), bits 8..15 the occurrence / entry the trip starts with, 16..23 index of the first occurrence with
@@ -149,7 +186,6 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
     // (Two first steps per trip -- a stage that ENDS in its first step, a dead seed entry or step 3 behind a seed, starts the next one at once and applies ITS
     //  entry behind the trip's lines -- made 11 % fewer wave trips in the same time, what a trip saves in number it costs in instructions, and was taken out:
     //  HISTORY.md, round 4 table, row "two first steps per trip".)
-    typedef uint32_t pgx_u32x4 __attribute__((ext_vector_type(4)));
     // (and the lines of the LCE variant are loaded in place by asm statements and waited for by hand: its two kinds of lanes load into the same registers at
     //  different points of a trip, and between them the compiler used those registers as scratch for the other kind -- after waiting for the first kind's loads,
     //  one memory latency in front of the other: the same row of HISTORY.md; scripts/isa_lint.py checks that nothing touches the registers in between)
@@ -163,32 +199,36 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
 #endif
 
     auto begin = [&]() __attribute__((always_inline)) {
-        if (x >= len || (uint64_t)(len - x) < min_len) { ph = 0; mem_count[rid] = nm; return; }
-        if (heavy_ext && next - next0 >= heavy_ext && len <= (int32_t)PGX_FM_HEAVY_MAXLEN) {
-            const unsigned long long at = atomicAdd(heavy_count, 1ull);
-            if (at < (unsigned long long)heavy_cap) {
+        if (x >= len || (uint32_t)(len - x) < min_len) { ph = 0; mem_count[rid] = nm; return; }
+        if ((LCE ? (int32_t)(next - hmark) >= 0 : next - hmark >= heavy_ext) && len <= (int32_t)PGX_FM_HEAVY_MAXLEN) {
+            const unsigned long long at = atomicAdd(PGX_PAIRS_COLD(heavy_count), 1ull);
+            if (at < (unsigned long long)PGX_PAIRS_COLD(heavy_cap)) {
                 pgx_heavy_item it;
                 it.rid = (uint64_t)rid; it.x = (uint32_t)x; it.nm = nm;
-                heavy_list[at] = it;
+                PGX_PAIRS_COLD(heavy_list)[at] = it;
                 ph = 0;
                 return;
             }
         }
         k = 0; kp = 0; s = n;
         if (LCE) lce_st = 0u;
-        if (min_len == 0) { Jk = 0; Js = n; j = x; ph = 2; }
-        else { j = x + (int32_t)min_len - 1; ph = 1; fresh = 1u; }
+        uint32_t ml = min_len;
+        asm volatile("" : "+s"(ml)); // (what follows from min_len is worked out here: held from before the loop it is a lane mask and two more scalar registers)
+        if (ml == 0) { Jk = 0; Js = n; j = x; ph = 2; }
+        else { j = x + (int32_t)ml - 1; ph = 1; fresh = 1u; }
     };
     // a lane on the text path asks for what its next trip reads: the suffix array entry of occurrence t (when it compares that one) and sixteen entries of the table
     // of common prefixes -- those of the occurrences behind t, or from entry t on
+    // (asked where it is needed: hoisted out of the loop the answer is a 64-bit lane mask held in two scalar registers)
+    auto has_lcp = [&]() __attribute__((always_inline)) { const uint8_t *q = pa.lce_lcp; asm volatile("" : "+s"(q)); return q != nullptr; };
     auto lce_ask = [&](uint32_t k32, uint32_t t, bool cmp) __attribute__((always_inline)) {
-        if (cmp) __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(img.lce_sa + k32 + t), (void __attribute__((address_space(3))) *)(s_sae + (threadIdx.x >> 6) * 64u), 4, 0, 0);
-        if (img.lce_lcp) {
+        if (cmp) __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(pa.lce_sa + k32 + t), (void __attribute__((address_space(3))) *)(s_sae + (threadIdx.x >> 6) * 64u), 4, 0, 0);
+        if (has_lcp()) {
             const uint32_t e0 = k32 + t + (cmp ? 1u : 0u), lb = e0 & ~3u;
 #pragma unroll
             for (uint32_t q = 0; q < 5u; q++)
                 if (q < 4u || (e0 & 3u) != 0u) // (sixteen bytes from e0 on: four dwords, five when e0 is not aligned)
-                    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(img.lce_lcp + lb + 4u * q),
+                    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(pa.lce_lcp + lb + 4u * q),
                                                      (void __attribute__((address_space(3))) *)(s_lcp + ((threadIdx.x >> 6) * 5u + q) * 64u), 4, 0, 0);
         }
     };
@@ -196,8 +236,12 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
         pgx_mem m;
         m.start = (uint64_t)x; m.end = (uint64_t)j; m.bwt_start = (uint64_t)Jk; m.size = (int64_t)(uint64_t)Js;
         // (the worst-case offset of the read is looked up only by a fifth MEM: the first PGX_FAST_SLOTS have their own line)
-        const uint64_t slot = nm < PGX_FAST_SLOTS ? 0ull : pgx_slot_extent(slot_off, slot_base, ovf_base, ovf_cap, n_ext_total, (uint64_t)rid, nm, len, x, min_len);
-        slots[pgx_slot_index((uint64_t)rid - first_read, n_reads - first_read, slot, nm)] = m;
+        if (nm < PGX_FAST_SLOTS) slots_fr[pgx_slot_index((uint64_t)rid, (uint64_t)chunk_reads, 0ull, nm)] = m;
+        else { // (everything this branch needs comes from the argument segment)
+            const uint64_t fr = PGX_PAIRS_COLD(first_read), cr = PGX_PAIRS_COLD(n_reads) - fr;
+            const uint64_t slot = pgx_slot_extent(PGX_PAIRS_COLD(slot_off), PGX_PAIRS_COLD(slot_base), PGX_PAIRS_COLD(ovf_base), PGX_PAIRS_COLD(ovf_cap), PGX_PAIRS_COLD(ctr), (uint64_t)rid, nm, len, x, PGX_PAIRS_COLD(min_len));
+            PGX_PAIRS_COLD(slots)[pgx_slot_index((uint64_t)rid - fr, cr, slot, nm)] = m;
+        }
         nm++;
         k = 0; kp = 0; s = n;
         if (LCE) lce_st = 0u;
@@ -218,26 +262,29 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
         // (LCE: a read is ~28 lane trips now instead of ~73, so two or three lanes of a wave finish one in EVERY trip and a refill round -- two memory
         //  latencies in front of the trip's own -- ran in nine trips out of ten, a quarter of the waves' time: idle lanes now wait until img.refill_min of
         //  them have gathered, or until no lane of the wave is live)
-        if (LCE && idle && (uint32_t)__popcll(idle) < img.refill_min && __popcll(idle) != 64) idle = 0ull;
+        if (LCE && idle && (uint32_t)__popcll(idle) < pa.refill_min && __popcll(idle) != 64) idle = 0ull;
 #ifdef PGX_FM_STATS
         const unsigned long long st_r0 = __builtin_readcyclecounter();
         if (idle) st_refills++;
 #endif
         while (idle) {
             if (rnext == rend) {
-                if (exhausted) break;
+                if (rnext == EXHAUSTED) break;
                 unsigned long long got = 0;
-                if (lane == 0) got = first_read + atomicAdd(cursor, 32ull);
+                const unsigned long long n_reads = PGX_PAIRS_COLD(n_reads);
+                if (lane == 0) got = PGX_PAIRS_COLD(first_read) + atomicAdd(PGX_PAIRS_COLD(cursor), 32ull);
                 got = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(got >> 32)) << 32) |
                       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)got);
-                if (got >= n_reads) { exhausted = true; break; }
-                rnext = got;
-                rend = got + 32ull < n_reads ? got + 32ull : n_reads;
+                if (got >= n_reads) { rnext = rend = EXHAUSTED; break; }
+                rnext = (uint32_t)got;
+                rend = (uint32_t)(got + 32ull < n_reads ? got + 32ull : n_reads);
             }
-            const uint64_t avail = rend - rnext;
+            const uint32_t avail = rend - rnext;
             const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-            if (ph == 0 && (uint64_t)rank < avail) {
-                rid = (uint32_t)(rnext + rank);
+            if (ph == 0 && rank < avail) {
+                rid = rnext + rank;
+                const uint8_t *const skip = PGX_PAIRS_COLD(skip);
+                const uint64_t *const offsets = PGX_PAIRS_COLD(offsets);
                 // (the three loads go out together, and so do the packed words below: a refill round is two memory latencies, not one per word --
                 //  word by word, 58 % of the waves' time at chr22 scale went by in this loop: profiles/r03_refill_share.txt)
                 const uint8_t *skp = skip ? skip + rid : reinterpret_cast<const uint8_t *>(offsets); // (always a load, never a branch with a wait of its own)
@@ -249,7 +296,7 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
                 if (sk) ph = -1; // served by the dense2 kernel on the other stream (pgx_classify_reads_kernel)
                 else {
                     if (PACKED) { // the read's packed words into this thread's LDS column (the host sized pk_words for the longest read of the launch)
-                        const uint32_t *src = packed + (base >> 4);
+                        const uint32_t *src = PGX_PAIRS_COLD(packed) + (base >> 4);
                         const uint32_t nw = ((uint32_t)(base & 15ull) + (uint32_t)len + 15u) >> 4;
 #pragma unroll 1
                         for (uint32_t w0 = 0; w0 < nw; w0 += PGX_PK_GROUP) { // (a read of 150 symbols: ten or eleven words, one group)
@@ -261,13 +308,14 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
                         }
                     }
                     x = 0; nm = 0;
-                    next0 = next;
+                    hmark = next;
+                    if (LCE) { const uint32_t hx = PGX_PAIRS_COLD(heavy_ext); hmark += hx != 0u && hx < 0x7FFFFFFFu ? hx : 0x7FFFFFFFu; }
                     begin();
                     if (ph == 0) ph = -1;
                 }
             }
             const uint32_t want = (uint32_t)__popcll(idle);
-            rnext += (uint64_t)want < avail ? (uint64_t)want : avail;
+            rnext += want < avail ? want : avail;
             idle = __ballot(ph == 0);
         }
 #ifdef PGX_FM_STATS
@@ -276,7 +324,7 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
 #endif
         if (ph == -1) ph = 0;
         if (!__any(ph > 0)) {
-            if (exhausted && rnext == rend) break;
+            if (rnext == EXHAUSTED) break;
             continue;
         }
 #ifdef PGX_FM_STATS
@@ -287,10 +335,11 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
         // what the wave asks of the memory system in this trip (wave-uniform sums in scalar registers): a live lane fetches one block line, except in a
         // stage's first trip, which reads block 0 like every other such lane and takes its result from first_ext / the seed table
         // (seed / end table entries: one per first trip -- an upper bound: a stage with fewer than K extensions to go reads the shared entry 0)
-        if (!FUSE) ln_blk += (unsigned long long)__popcll(__ballot(ph > 0 && fresh == 0u));
-        ln_two += (unsigned long long)__popcll(__ballot(did2 != 0u));
+        if (!FUSE) ln_blk += (uint32_t)__popcll(__ballot(ph > 0 && fresh == 0u));
+        if ((ln_blk | ln_seed | ln_two) >> 31) ln_flush();
+        ln_two += (uint32_t)__popcll(__ballot(did2 != 0u));
         did2 = 0u;
-        if (!FUSE) ln_seed += (unsigned long long)__popcll(__ballot(ph > 0 && fresh != 0u));
+        if (!FUSE) ln_seed += (uint32_t)__popcll(__ballot(ph > 0 && fresh != 0u));
         if (COOP) { // every lane names the block it is about to probe (idle lanes: block 0, like the first trip of a stage), the wave fetches all 64 lines
             const pos_t kk_c = (ph == 2) ? kp : k;
             const uint32_t myblk = ph > 0 ? (S64 ? (uint32_t)(kk_c >> 6) : (uint32_t)(((uint64_t)(kk_c >> 5) * 0xAAAAAAABull) >> 33)) + pend : 0u;
@@ -300,7 +349,7 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
             for (int i = 0; i < 8; i++) {
                 const uint32_t q = 8u * (uint32_t)i + ((uint32_t)lane >> 3), piece = ((uint32_t)lane & 7u) ^ (q & 7u);
                 const uint32_t blk = (uint32_t)__shfl((int)myblk, (int)q, 64);
-                __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(img.pairs + ((size_t)blk * 8 + piece)),
+                __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)(pa.pairs + ((size_t)blk * 8 + piece)),
                                                  (void __attribute__((address_space(3))) *)(s_stage + 64 * i), 16, 0, 0);
             }
             __builtin_amdgcn_s_setprio(0);
@@ -336,7 +385,7 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
             const bool small1 = f1.z == 0u || f1.z < mo || mo_huge;
             const uint32_t sdepth = se_pre.w >> 24, se_s = se_pre.z;
             const bool seed_alive = kuse != 0u && se_s != 0u && se_s >= mo && !mo_huge;
-            const bool seed_dead = kuse != 0u && se_s == 0u && sdepth != PGX_SEED_UNUSABLE && min_occ <= 1;
+            const bool seed_dead = kuse != 0u && se_s == 0u && sdepth != PGX_SEED_UNUSABLE && mo <= 1u;
             const bool rem2 = q1 ? (j - 1 >= x) : (j - 1 > x);
             const bool do2 = at_end && rem2 && !seed_alive && !seed_dead && !small1; // (by 0, then by the last symbol of the read: quirk 4)
             uint32_t ns = do2 ? f2.z : f1.z, nk = do2 ? f2.x : f1.x, nq = do2 ? f2.y : f1.y;
@@ -375,55 +424,56 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
             bool asked = false;
             if (ask) {
                 const bool endw = j >= len; // (the end table: see pgx_find_mems_kernel)
-                const int32_t K = endw ? (int32_t)img.seed_end_k : (int32_t)img.seed_k;
+                const pgx_u32x4 tab = *(const volatile pgx_u32x4 *)&s_seedt[endw ? 1u : 0u]; // (volatile: read here, not kept in registers from before the loop)
+                const int32_t K = (int32_t)tab.z;
                 const int32_t avail = (ph == 1) ? (j - x + 1) : (j - x);
                 uint32_t kuse = 0u;
-                if (K && avail >= K + (endw ? 1 : 0)) {
+                if (K && avail >= (int32_t)tab.w) {
                     const uint32_t sidx = pgx_packed_seed_index(s_rd, rd_stride, (uint32_t)(base & 15ull) + (uint32_t)((endw ? len - 1 : j) - K + 1), K);
-                    const uint4 *sp = (endw ? img.seed_end : img.seed) + sidx;
+                    const uint4 *sp = reinterpret_cast<const uint4 *>(((uint64_t)tab.y << 32) | tab.x) + sidx;
                     __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)sp, (void __attribute__((address_space(3))) *)(s_sa4 + (threadIdx.x >> 6) * 64u), 16, 0, 0);
-                    kuse = (uint32_t)K + (endw ? 1u : 0u);
+                    kuse = tab.w;
                     asked = true;
                 }
                 fresh = 2u | (kuse << 8);
             }
-            ln_seed += (unsigned long long)__popcll(__ballot(asked));
+            ln_seed += (uint32_t)__popcll(__ballot(asked));
         };
         if (FUSE && ph > 0 && fresh >= 2u) prestep();
         const bool sit_out = FUSE && (fresh != 0u || em_now || restart != 0u); // no line of the image for this lane in this trip
-        if (FUSE) ln_blk += (unsigned long long)__popcll(__ballot(ph > 0 && !sit_out));
+        if (FUSE) ln_blk += (uint32_t)__popcll(__ballot(ph > 0 && !sit_out));
         const bool lce_cmp = lce_lane && (lce_st & 4u) == 0u; // this trip compares an occurrence with the text
         if (LCE && lce_cmp) {
             lce_pos = s_sae[threadIdx.x];
             lce_g0 = lce_pos + (uint32_t)(j - x);           // text position that faces read symbol j
             const uint32_t w0 = lce_g0 >> 4;                // its word (16 symbols); the window: words w0 .. w0 + 11
-            const uint32_t *tp = img.lce_text + w0;
+            const uint32_t *tp = pa.lce_text + w0;
             // (dword-aligned 16-byte pieces; nothing waits for them here: section C does)
             asm volatile("global_load_dwordx4 %0, %3, off\n\tglobal_load_dwordx4 %1, %3, off offset:16\n\tglobal_load_dwordx4 %2, %3, off offset:32"
                          : "+v"(row), "+v"(hs), "+v"(d0) : "v"(tp) : "memory");
             const uint32_t l0 = w0 >> 5, l1 = (w0 + 11u) >> 5; // the lines of the window
-            const uint32_t *fp0 = img.lce_flags + (l0 >> 5), *fp1 = img.lce_flags + (l1 >> 5);
+            const uint32_t *fp0 = pa.lce_flags + (l0 >> 5), *fp1 = pa.lce_flags + (l1 >> 5);
             asm volatile("global_load_dword %0, %2, off\n\tglobal_load_dword %1, %3, off" : "+v"(lce_f0), "+v"(lce_f1) : "v"(fp0), "v"(fp1) : "memory");
         }
-        if (LCE) ln_blk += (unsigned long long)(__popcll(__ballot(lce_cmp && ((lce_g0 >> 4) >> 5) != (((lce_g0 >> 4) + 11u) >> 5))) + // a window over two lines
+        if (LCE) ln_blk += (uint32_t)(__popcll(__ballot(lce_cmp && ((lce_g0 >> 4) >> 5) != (((lce_g0 >> 4) + 11u) >> 5))) + // a window over two lines
                                                 __popcll(__ballot(lce_cmp)) +                                                    // the line of the suffix array entry
-                                                (img.lce_lcp ? __popcll(__ballot(lce_lane && s > 1u)) : 0)) -                      // ... and of the common prefixes
-                             (unsigned long long)__popcll(__ballot(lce_lane && !lce_cmp));                                        // (no text line in such a trip: counted above as one)
+                                                (has_lcp() ? __popcll(__ballot(lce_lane && s > 1u)) : 0)) -                      // ... and of the common prefixes
+                             (uint32_t)__popcll(__ballot(lce_lane && !lce_cmp));                                        // (no text line in such a trip: counted above as one)
         if (ph > 0 && !lce_lane && !sit_out) {
             const bool fr = !FUSE && fresh != 0u; // first extension of a backward stage: from first_ext / the seed table
             bool seed_lane = false;
             uint32_t kuse = 0u; // extensions the seed entry stands for
             uint4 se = make_uint4(0u, 0u, 0u, 0u);
             if (!FUSE) {
-                const uint4 *sp = img.seed;
+                const uint4 *sp = pa.seed;
                 if (fr) {
                     const bool endw = j >= len; // (the end table: see pgx_find_mems_kernel)
-                    const int32_t K = endw ? (int32_t)img.seed_end_k : (int32_t)img.seed_k;
+                    const int32_t K = endw ? (int32_t)pa.seed_end_k : (int32_t)pa.seed_k;
                     const int32_t avail = (ph == 1) ? (j - x + 1) : (j - x);
                     if (K && avail >= K + (endw ? 1 : 0)) {
                         if (PACKED) {
                             const uint32_t sidx = pgx_packed_seed_index(s_rd, rd_stride, (uint32_t)(base & 15ull) + (uint32_t)((endw ? len - 1 : j) - K + 1), K);
-                            seed_lane = true; sp = (endw ? img.seed_end : img.seed) + sidx; kuse = (uint32_t)K + (endw ? 1u : 0u);
+                            seed_lane = true; sp = (endw ? pa.seed_end : pa.seed) + sidx; kuse = (uint32_t)K + (endw ? 1u : 0u);
                         } else {
                         const uint64_t a = base + (uint64_t)((endw ? len - 1 : j) - K + 1);
                         const uint32_t sh = (uint32_t)(a & 7ull) * 8u;
@@ -431,7 +481,7 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
                         const uint64_t w0 = wp[0], w1 = wp[1], w2 = wp[2];
                         const uint64_t lo = sh ? (w0 >> sh) | (w1 << (64u - sh)) : w0, hi = sh ? (w1 >> sh) | (w2 << (64u - sh)) : w1;
                         uint32_t sidx;
-                        if (pgx_seed_index(lo, hi, (uint32_t)K, sidx)) { seed_lane = true; sp = (endw ? img.seed_end : img.seed) + sidx; kuse = (uint32_t)K + (endw ? 1u : 0u); }
+                        if (pgx_seed_index(lo, hi, (uint32_t)K, sidx)) { seed_lane = true; sp = (endw ? pa.seed_end : pa.seed) + sidx; kuse = (uint32_t)K + (endw ? 1u : 0u); }
                         }
                     }
                 }
@@ -498,7 +548,7 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
 #ifdef PGX_FM_STATS
                 const unsigned long long st_l0 = __builtin_readcyclecounter();
 #endif
-                const uint4 *bp = img.pairs + (size_t)(bfirst + pend) * 8;
+                const uint4 *bp = pa.pairs + (size_t)(bfirst + pend) * 8;
                 // row: pairs (t1, A C G T) before the block; hs: positions before the block with c2 special and c1 = A, C, G, T; bit 31 of .x: flag;
                 // d0 d1 d2: the planes: c1 bit 0, c1 bit 1, c2 bit 0, c2 bit 1, three dwords each
                 if (LCE) { // (in place, and waited for by hand below: see the declaration of row)
@@ -541,7 +591,7 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
             pos_t a01 = (pos_t)(row.x + row.y + row.z + row.w + pts + e1p);                       // rank of the first symbol at p0
             pos_t a02 = (pos_t)((t2 == 0u ? row.x : (t2 == 1u ? row.y : (t2 == 2u ? row.z : row.w))) + e2p); // rank of the pair at p0
             if (WIDE) { // the counts of a block are deltas against its superblock
-                const uint64_t *pb = s_pb + (size_t)((bfirst + pend) >> img.pairs_sb_shift) * 24u;
+                const uint64_t *pb = s_pb + (size_t)((bfirst + pend) >> pa.pairs_sb_shift) * 24u;
                 a01 += (pos_t)pb[16u + t1];
                 a02 += (pos_t)pb[4u * t1 + t2];
             }
@@ -582,12 +632,14 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
                     // (one probe after the other in a rolled loop: this path is rare and must not cost the common one its registers)
                     const uint64_t q0 = (uint64_t)p0 > (uint64_t)n ? (uint64_t)n : (uint64_t)p0, q1 = (uint64_t)p1 > (uint64_t)n ? (uint64_t)n : (uint64_t)p1;
                     uint64_t A0 = 0, A1 = 0, B0 = 0, B1 = 0;
+                    PgxDevImage img = {}; // what the rank functions read of it
+                    img.blocks = PGX_PAIRS_COLD(blocks); img.exc = PGX_PAIRS_COLD(exc); img.sbase2 = PGX_PAIRS_COLD(sbase2); img.d2_sb_shift = PGX_PAIRS_COLD(d2_sb_shift);
 #pragma unroll 1
                     for (int it = 0; it < 2; it++) {
                         const uint64_t q = it ? q1 : q0;
                         uint64_t a, bq;
                         if (WIDE) pgx_dense2w_rank(img, q, PGX_EXT_CV(e1), PGX_EXT_M(e1), a, bq);
-                        else if (img.dense == 1) { // (a small index: the 64-byte dense image)
+                        else if (pa.dense == 1) { // (a small index: the 64-byte dense image)
                             const PgxDenseBlk db = pgx_dense_load<false>(img, nullptr, q);
                             pgx_dense_rank(db, q, PGX_EXT_CV(e1), PGX_EXT_M(e1), a, bq);
                         } else pgx_dense2_rank(img, (uint32_t)q, PGX_EXT_CV(e1), PGX_EXT_M(e1), a, bq);
@@ -598,8 +650,8 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
                     { // (rare, and inside diverged control flow: counted with one atomic by the first lane that is here, not in the wave-uniform sums)
                         const unsigned long long here = __ballot(true);
                         if (lane == (int)__ffsll((long long)here) - 1) {
-                            atomicAdd(n_ext_total + PGX_CTR_REDO, (unsigned long long)__popcll(here));
-                            atomicAdd(n_ext_total + PGX_CTR_PAIRS_LINES, 2ull * (unsigned long long)__popcll(here)); // the two lines of the other image
+                            atomicAdd(PGX_PAIRS_COLD(ctr) + PGX_CTR_REDO, (unsigned long long)__popcll(here));
+                            atomicAdd(PGX_PAIRS_COLD(ctr) + PGX_CTR_PAIRS_LINES, 2ull * (unsigned long long)__popcll(here)); // the two lines of the other image
                         }
                     }
                     const bool none = PGX_EXT_KILL(e1) || A0 >= A1; // rank_k >= rank_ks -> bi_interval(0,0,0), src/r-index.cpp:751
@@ -613,7 +665,7 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
                 const uint32_t sdepth = se.w >> 24;
                 const pos_t se_s = ent_s(se);
                 const bool seed_alive = seed_lane && se_s != 0u && se_s >= mo && !mo_huge;
-                const bool seed_dead = seed_lane && se_s == 0u && sdepth != PGX_SEED_UNUSABLE && min_occ <= 1;
+                const bool seed_dead = seed_lane && se_s == 0u && sdepth != PGX_SEED_UNUSABLE && mo <= 1u;
                 const bool do2 = (fr ? (at_end && rem2 && have2 && !seed_alive && !seed_dead) : (two && !bail && !cont1)) && !small1;
                 pos_t s2 = (pos_t)c2, k2 = r2 + s_C[PGX_EXT_V(e2)] + s_t2[8u * t1 + cv2], q2v = q1v + (pos_t)w2;
                 if (fr) { const uint4 f = s_fe[PACKED ? 5u + ((byte2 >> 1) & 3u) : 256u + byte2]; k2 = ent_k(f); q2v = ent_q(f); s2 = ent_s(f); }
@@ -656,9 +708,9 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
                 em_now = em;
                 // a forward stage over a narrow interval goes on through the text: from the next trip on one occurrence per trip (its first suffix array entry
                 // is asked for now); only where that is fewer trips than two symbols per trip, and where the window of three pieces holds what is left
-                if (LCE && img.lce_sa && ph == 2 && !em && !restart && !(lce_st & 2u) && s >= 1u && (uint32_t)s <= img.lce_max && mo <= 1u && j < len &&
-                    (uint32_t)(len - j) >= 2u * (img.lce_lcp && (uint32_t)s > PGX_LCE_ENTRY_CAP ? PGX_LCE_ENTRY_CAP : (uint32_t)s) && (uint32_t)(len - j) <= 144u &&
-                    ((uint32_t)s <= 16u || (img.lce_lcp && (uint32_t)(len - x) <= PGX_LCP_CAP - 1u))) { // (wider than sixteen only where the table of common prefixes can be used)
+                if (LCE && ph == 2 && !em && !restart && !(lce_st & 2u) && s >= 1u && (uint32_t)s <= pa.lce_max && mo <= 1u && j < len &&
+                    (uint32_t)(len - j) >= 2u * (has_lcp() && (uint32_t)s > PGX_LCE_ENTRY_CAP ? PGX_LCE_ENTRY_CAP : (uint32_t)s) && (uint32_t)(len - j) <= 144u &&
+                    ((uint32_t)s <= 16u || (has_lcp() && (uint32_t)(len - x) <= PGX_LCP_CAP - 1u))) { // (wider than sixteen only where the table of common prefixes can be used)
                     lce_st = 1u;
                     lce_best = 0u;
                     lce_ask((uint32_t)k, 0u, true); // SA[k] and the common prefixes of the sixteen entries behind it
@@ -702,7 +754,7 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
                 // occurrence t may match further -- or an unknown one is compared with the text itself in the next trip.  Sixteen entries per trip.
                 uint32_t tt = t0; // the entry the next trip starts with
                 bool cmp_next = true;
-                if (!fin && tt < (uint32_t)s && img.lce_lcp && (uint32_t)(len - x) <= PGX_LCP_CAP - 1u) { // (m + what is left of the read stays below the cap: a capped entry is "longer than anything asked")
+                if (!fin && tt < (uint32_t)s && has_lcp() && (uint32_t)(len - x) <= PGX_LCP_CAP - 1u) { // (m + what is left of the read stays below the cap: a capped entry is "longer than anything asked")
                     const uint32_t m = (uint32_t)(j - x), bsh = ((uint32_t)k + t0) & 3u;
                     uint32_t L5[5];
 #pragma unroll
@@ -740,12 +792,13 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
         if (restart) begin();
         if (FUSE) prefetch(); // (their seed entries are on the way while the wave loops)
     }
+    unsigned long long *const n_ext_total = PGX_PAIRS_COLD(ctr);
     unsigned long long tot = next;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) tot += __shfl_down(tot, off, 64);
     if (lane == 0 && tot) atomicAdd(n_ext_total + PGX_CTR_EXT, tot);
-    ln_two += (unsigned long long)__popcll(__ballot(did2 != 0u));
-    if (lane == 0 && ln_blk) { atomicAdd(n_ext_total + PGX_CTR_PAIRS_LINES, ln_blk); atomicAdd(n_ext_total + PGX_CTR_PAIRS_SEEDS, ln_seed); atomicAdd(n_ext_total + PGX_CTR_PAIRS_TWO, ln_two); }
+    ln_two += (uint32_t)__popcll(__ballot(did2 != 0u));
+    if (lane == 0 && ln_blk) { atomicAdd(n_ext_total + PGX_CTR_PAIRS_LINES, (unsigned long long)ln_blk); atomicAdd(n_ext_total + PGX_CTR_PAIRS_SEEDS, (unsigned long long)ln_seed); atomicAdd(n_ext_total + PGX_CTR_PAIRS_TWO, (unsigned long long)ln_two); }
 #ifdef PGX_FM_STATS // wave trips / live lane-trips, lane-trips waiting for the second block / fresh
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) st_wait += __shfl_down(st_wait, off, 64);
@@ -754,11 +807,8 @@ pgx_find_mems_pairs_kernel(PgxDevImage img, const uint8_t *__restrict__ reads, c
     if (lane == 0) { atomicAdd(n_ext_total + PGX_CTR_ST_PAIR_TRIPS, st_trips); atomicAdd(n_ext_total + PGX_CTR_ST_PAIR_LIVE, st_live); atomicAdd(n_ext_total + PGX_CTR_ST_PAIR_WAIT, st_wait); atomicAdd(n_ext_total + PGX_CTR_ST_PAIR_FRESH, st_fresh); }
 #endif
 }
-#define PGX_PAIRS_INSTANTIATE(...)                                                                                                                \
-    template __global__ void pgx_find_mems_pairs_kernel<__VA_ARGS__>(PgxDevImage, const uint8_t *, const uint64_t *, uint64_t, uint64_t, uint64_t, const uint64_t *, \
-                                                                     pgx_mem *, uint32_t *, unsigned long long *, unsigned long long *, uint64_t, uint64_t, uint32_t, \
-                                                                     uint32_t, pgx_heavy_item *, unsigned long long *, const uint8_t *, const uint32_t *, uint32_t,  \
-                                                                     uint32_t *, uint64_t);
+#define PGX_PAIRS_INSTANTIATE(...) \
+    template __global__ void pgx_find_mems_pairs_kernel<__VA_ARGS__>(PgxPairsArgs);
 PGX_PAIRS_INSTANTIATE(false, false, false, false, false)
 PGX_PAIRS_INSTANTIATE(true, false, false, false, false)
 PGX_PAIRS_INSTANTIATE(false, true, false, false, false)
