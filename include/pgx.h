@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only), the device index build (pgx_build_index_from_text_device, pgx_build_index_from_texts_device, pgx_build_index_device_timing: new entry points only) */
+#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only), the device index build (pgx_build_index_from_text_device, pgx_build_index_from_texts_device, pgx_build_index_device_timing: new entry points only), the text output (pgx_batch_format, pgx_format_result, pgx_format_params, pgx_text, PGX_FORMAT_*: new entry points only) */
 
 typedef enum {
     PGX_OK = 0,
@@ -579,6 +579,63 @@ uint64_t pgx_compact_bound(uint64_t n_reads, uint64_t n_mems, uint64_t n_positio
  * are).  PGX_ERR_ARG unless mem_offsets and pos_offsets start at 0, never decrease and end at n_mems / n_positions. */
 pgx_status pgx_compact_encode(int device, const pgx_result *in, uint8_t *bytes, uint64_t bytes_cap, uint64_t *block_offsets,
                               uint64_t *block_first_mem, uint64_t *block_first_pos, uint64_t *n_bytes);
+
+/* ---- text output: the find_mems CLI's stdout (and per-read stderr) bytes of a finished batch, written on the device -------------
+ * In place of downloading the result arrays and turning them into decimal text on host threads (the find_mems CLI's format_range,
+ * which restates the reference's prints: src/find_mems.cpp:115-118,138 and src/tag_arrays.cpp:885-889), the device writes the
+ * bytes and the host only downloads and write()s them.  Opt-in: every other output keeps its bytes.
+ *
+ * THE TEXT.  For read i of the batch, with seq = first_seq + i + 1 (format_range is the definition; tests/text_emu.py restates it):
+ *   "Seq: <seq>\n"
+ *   per MEM m of the read, in result order:
+ *     "MEM START: <start>, MEM END: <end> BWT START: <bwt_start> SIZE: <size>\n"            (size as int64, '-' for negatives)
+ *     "Number of unique positions: <pos_offsets[m + 1] - pos_offsets[m]>\n"
+ *     "<position>, " per position, then "\n"                                                 (an empty list is just "\n")
+ *     with PGX_FORMAT_LOCATE_POSITIONS: "Occurrences: <size>\n", "<v / max_length>:<v % max_length>, " per value in stored order, "\n"
+ *     with PGX_FORMAT_LOCATE_SEQS:      "Sequences: <count>\n", "<v>, " per value, "\n"
+ *     either locate form, a MEM without values (loc_offsets[m + 1] == loc_offsets[m]): "Occurrences: <size> (not located)\n" "\n"
+ *   "\n"
+ * and on the stderr side "[find_all_mems] total mems=<count>\n" per read.  Numbers are shortest decimal (uint64: up to 20 digits).
+ * read_offsets[i] .. read_offsets[i + 1] is the text of read i, so a caller may cut the text at any read. */
+#define PGX_FORMAT_STDERR 1u           /* also the per-read "[find_all_mems] total mems=" lines */
+#define PGX_FORMAT_LOCATE_POSITIONS 2u /* needs a completed pgx_batch_locate(flags = 0 [| PGX_LOCATE_CHAINS]) */
+#define PGX_FORMAT_LOCATE_SEQS 4u      /* needs pgx_batch_locate(PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE) */
+typedef struct {
+    uint64_t first_seq;  /* reads before this batch: read i prints as first_seq + i + 1 */
+    uint64_t max_length; /* PGX_FORMAT_LOCATE_POSITIONS: the divisor of the packed values; 0 = the index's own (pgx_batch_format only) */
+    uint32_t flags;      /* PGX_FORMAT_* */
+    uint32_t reserved;   /* must be 0 */
+} pgx_format_params;
+typedef struct {
+    uint64_t n_reads, n_bytes, n_err_bytes;
+    const uint64_t *read_offsets; /* n_reads + 1 */
+    const char *text;             /* n_bytes, not NUL-terminated */
+    const char *err_text;         /* n_err_bytes; NULL without PGX_FORMAT_STDERR */
+    float ms_format;              /* device time of the call when the run had PGX_RUN_TIMING, else 0 */
+} pgx_text;
+/* The text of the last run (and, with a locate flag, of the last locate) of the batch.  Runs on the batch's own stream: a length pass
+ * (one lane per position, per located value, per MEM, per read, and the scans between them), the download of read_offsets -- the host
+ * waits for it once, its last entry sizes the text -- a fill pass, and the download of the text into pinned buffers owned by the batch,
+ * which only ever grow.  Valid until the next run, upload, locate, format or free of the batch -- and beyond that: there are two sets
+ * of those buffers and the calls alternate between them, nothing else writes to them, so what a call returned stays readable until the
+ * next call but one (or the free of the batch).  A writer thread can write the text of one batch while the next is being formatted;
+ * the find_mems CLI does so.  The device result is left untouched:
+ * pgx_batch_result, pgx_batch_result_compact and pgx_batch_locate give the same bytes before and after.
+ * There is no chunked mode: the whole text of the batch is held on the device and in pinned host memory at once (about 450 bytes per
+ * read of 150 at the tested scales), so the caller bounds it by the number of reads it uploads per batch.
+ * PGX_ERR_ARG: no completed run; a run without PGX_RUN_TAGS; both locate flags; a locate flag without a completed locate of exactly
+ * the flags named above (a PGX_LOCATE_SEQ_SETS result never matches); an unknown flag; reserved != 0. */
+pgx_status pgx_batch_format(pgx_batch *b, const pgx_format_params *p, pgx_text *out);
+/* The same kernels on a result held in host arrays (how they are tested on values no small index produces), the counterpart of
+ * pgx_compact_encode: uploads in->mem_offsets / mems / pos_offsets / positions (pos_offsets must be there: the text has the positions)
+ * and, with a locate flag, loc->loc_offsets / values (loc->n_mems must equal in->n_mems) to `device`, formats, and downloads
+ * read_offsets (n_reads + 1 entries), the text into text[0 .. text_cap) and, with PGX_FORMAT_STDERR, the stderr lines into
+ * err_text[0 .. err_cap).  *n_bytes / *n_err_bytes are always the sizes needed; PGX_ERR_NOMEM when one exceeds its capacity (nothing is
+ * written to text / err_text then, read_offsets is).  PGX_ERR_ARG, decided before the device is touched: a null argument, a locate flag
+ * without loc, both locate flags, PGX_FORMAT_LOCATE_POSITIONS with max_length 0, reserved != 0, and offset arrays (mem_offsets,
+ * pos_offsets, loc_offsets) that do not start at 0, decrease somewhere or do not end at the count of what they index. */
+pgx_status pgx_format_result(int device, const pgx_result *in, const pgx_locations *loc, const pgx_format_params *p, char *text, uint64_t text_cap,
+                             uint64_t *read_offsets, uint64_t *n_bytes, char *err_text, uint64_t err_cap, uint64_t *n_err_bytes);
 
 /* Convenience: create + run + result in one call (what the find_mems CLI uses). */
 pgx_status pgx_find_mems_batch(pgx_index *h, int device, const uint8_t *reads, const uint64_t *offsets,

@@ -33,6 +33,25 @@ struct CompactWork {
     }
 };
 
+// the text output (pgx_batch_format; pgx_format_result uses one of its own): grow-only like the other result buffers
+struct FormatWork {
+    // lengths and their scans per level: positions (plen -> pcum), located values (vlen -> vcum), MEMs (mlen -> mcum), reads (rlen -> roff = read_offsets;
+    // elen -> eoff for the stderr lines); pbase / vbase: where a MEM's lists start (pgx_format_fill_mems_kernel); the text and the stderr lines
+    DevBuf plen, pcum, vlen, vcum, mlen, mcum, rlen, roff, elen, eoff, pbase, vbase, text, etext, scan_tmp;
+    // the host side, twice: pgx_batch_format alternates between the two sets, so the text of one call outlives the next call (a writer thread may
+    // still be writing it); h_roff: read_offsets, and behind them the total of the stderr lines
+    HostBuf h_roff[2], h_text[2], h_etext[2];
+    int cur = 0; // the set the last call filled
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the length pass, around the fill pass
+    void release() {
+        DevBuf *all[] = {&plen, &pcum, &vlen, &vcum, &mlen, &mcum, &rlen, &roff, &elen, &eoff, &pbase, &vbase, &text, &etext, &scan_tmp};
+        for (DevBuf *d : all) d->release();
+        for (int i = 0; i < 2; i++) { h_roff[i].release(); h_text[i].release(); h_etext[i].release(); }
+        for (auto &e : ev)
+            if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    }
+};
+
 struct pgx_batch {
     pgx_index *h = nullptr;
     pgx_device_image *dimg = nullptr;
@@ -64,6 +83,7 @@ struct pgx_batch {
     TagWork tw;
     LocWork lw; // pgx_batch_locate
     CompactWork cw; // pgx_batch_result_compact
+    FormatWork fw;  // pgx_batch_format
     uint64_t n_mems = 0, n_positions = 0, n_ext = 0, n_tag_overflow = 0;
     bool ran = false, ran_tags = false;
     // speculative sizing (pgx_batch_run): what the last run with these parameters produced
@@ -90,6 +110,7 @@ static void batch_release(pgx_batch *b) {
         b->tw.release();
         b->lw.release();
         b->cw.release();
+        b->fw.release();
         HostBuf *hb[] = {&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]};
         for (HostBuf *x : hb) x->release();
         for (auto &e : b->ev)
@@ -1246,6 +1267,224 @@ extern "C" pgx_status pgx_compact_encode(int device, const pgx_result *in, uint8
     compact_fill(k.w, k.mem_off.as<uint64_t>(), k.mems.as<pgx_mem>(), k.run_nums.as<uint64_t>(), k.pos_off.as<uint64_t>(), k.positions.as<uint64_t>(), n, tags,
                  false, total, s);
     if (total) HIPCHECK(hipMemcpyAsync(bytes, k.w.bytes.p, total, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// text output (pgx_format_kernels.hip; the grammar: include/pgx.h "text output")
+struct FormatIn { // a result on the device, and what pgx_format_params adds
+    const uint64_t *mem_off, *pos_off, *positions, *loc_off, *values;
+    const pgx_mem *mems;
+    uint64_t n_reads, n_mems, n_positions, n_values, first_seq, max_length;
+    uint32_t flags;
+    bool locate() const { return (flags & (PGX_FORMAT_LOCATE_POSITIONS | PGX_FORMAT_LOCATE_SEQS)) != 0; }
+    PgxFormatArgs args() const { return PgxFormatArgs{mem_off, mems, pos_off, loc_off, n_reads, n_mems, first_seq, flags}; }
+    uint64_t value_divisor() const { return (flags & PGX_FORMAT_LOCATE_POSITIONS) ? max_length : 0; } // (0: the values print as they are)
+};
+
+// what both entry points refuse in a pgx_format_params, said with or without a device
+static void format_check_params(const pgx_format_params *p, const char *who) {
+    if (!p) throw Error(PGX_ERR_ARG, std::string(who) + ": null argument");
+    if (p->flags & ~(PGX_FORMAT_STDERR | PGX_FORMAT_LOCATE_POSITIONS | PGX_FORMAT_LOCATE_SEQS)) throw Error(PGX_ERR_ARG, std::string(who) + ": unknown flag");
+    if (p->reserved) throw Error(PGX_ERR_ARG, std::string(who) + ": reserved must be 0");
+    if ((p->flags & PGX_FORMAT_LOCATE_POSITIONS) && (p->flags & PGX_FORMAT_LOCATE_SEQS))
+        throw Error(PGX_ERR_ARG, std::string(who) + ": PGX_FORMAT_LOCATE_POSITIONS and PGX_FORMAT_LOCATE_SEQS exclude each other");
+}
+
+// The length pass: every level's lengths and scans, then read_offsets (and the total of the stderr lines behind them) to w.h_roff.  The host waits
+// here: the totals size the text buffers.
+static void format_lengths(FormatWork &w, const FormatIn &in, bool timed, hipStream_t s, uint64_t &n_bytes, uint64_t &n_err_bytes) {
+    const uint64_t n = in.n_reads, m = in.n_mems, np = in.n_positions, nv = in.locate() ? in.n_values : 0;
+    const bool err = (in.flags & PGX_FORMAT_STDERR) != 0;
+    w.plen.ensure(np ? np : 1); w.pcum.ensure((np + 1) * 8);
+    if (in.locate()) { w.vlen.ensure(nv ? nv : 1); w.vcum.ensure((nv + 1) * 8); }
+    w.mlen.ensure((m ? m : 1) * 8); w.mcum.ensure((m + 1) * 8);
+    w.rlen.ensure((n ? n : 1) * 8); w.roff.ensure((n + 1) * 8);
+    if (err) { w.elen.ensure(n ? n : 1); w.eoff.ensure((n + 1) * 8); }
+    HostBuf &h_roff = w.h_roff[w.cur];
+    h_roff.ensure((n + 2) * 8);
+    if (timed) {
+        for (auto &e : w.ev)
+            if (!e) HIPCHECK(hipEventCreate(&e));
+        HIPCHECK(hipEventRecord(w.ev[0], s));
+    }
+    if (np) hipLaunchKernelGGL(pgx_format_item_len_kernel, dim3(grid_for(np, 256)), dim3(256), 0, s, in.positions, np, (uint64_t)0, w.plen.as<uint8_t>());
+    scan_excl(4, w.plen.p, np, 0, w.pcum.as<uint64_t>(), w.scan_tmp, s);
+    if (in.locate()) {
+        if (nv) hipLaunchKernelGGL(pgx_format_item_len_kernel, dim3(grid_for(nv, 256)), dim3(256), 0, s, in.values, nv, in.value_divisor(), w.vlen.as<uint8_t>());
+        scan_excl(4, w.vlen.p, nv, 0, w.vcum.as<uint64_t>(), w.scan_tmp, s);
+    }
+    const uint64_t *vcum = in.locate() ? w.vcum.as<uint64_t>() : nullptr;
+    if (m) hipLaunchKernelGGL(pgx_format_mem_len_kernel, dim3(grid_for(m, 256)), dim3(256), 0, s, in.args(), (const uint64_t *)w.pcum.as<uint64_t>(), vcum, w.mlen.as<uint64_t>());
+    scan_excl(1, w.mlen.p, m, 0, w.mcum.as<uint64_t>(), w.scan_tmp, s);
+    if (n) hipLaunchKernelGGL(pgx_format_read_len_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, in.args(), (const uint64_t *)w.mcum.as<uint64_t>(), w.rlen.as<uint64_t>(),
+                              err ? w.elen.as<uint8_t>() : nullptr);
+    HIPCHECK(hipGetLastError());
+    scan_excl(1, w.rlen.p, n, 0, w.roff.as<uint64_t>(), w.scan_tmp, s);
+    if (err) scan_excl(4, w.elen.p, n, 0, w.eoff.as<uint64_t>(), w.scan_tmp, s);
+    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
+    uint64_t *h = h_roff.as<uint64_t>();
+    h[n + 1] = 0;
+    HIPCHECK(hipMemcpyAsync(h, w.roff.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (err) HIPCHECK(hipMemcpyAsync(h + n + 1, w.eoff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    n_bytes = h[n];
+    n_err_bytes = h[n + 1];
+}
+
+// The fill pass into w.text / w.etext (grown to the totals first); async on s.  Every byte of text[0 .. n_bytes) is written by exactly one lane.
+static void format_fill(FormatWork &w, const FormatIn &in, bool timed, hipStream_t s, uint64_t n_bytes, uint64_t n_err_bytes) {
+    const uint64_t n = in.n_reads, m = in.n_mems, np = in.n_positions, nv = in.locate() ? in.n_values : 0;
+    const bool err = (in.flags & PGX_FORMAT_STDERR) != 0;
+    w.text.ensure(n_bytes ? n_bytes : 8);
+    if (err) w.etext.ensure(n_err_bytes ? n_err_bytes : 8);
+    w.pbase.ensure((m ? m : 1) * 8);
+    if (in.locate()) w.vbase.ensure((m ? m : 1) * 8);
+    char *text = w.text.as<char>();
+    const uint64_t *roff = w.roff.as<uint64_t>(), *pcum = w.pcum.as<uint64_t>(), *vcum = in.locate() ? w.vcum.as<uint64_t>() : nullptr;
+    if (timed) HIPCHECK(hipEventRecord(w.ev[2], s));
+    if (n) hipLaunchKernelGGL(pgx_format_fill_reads_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, in.args(), roff, err ? (const uint64_t *)w.eoff.as<uint64_t>() : nullptr, text,
+                              err ? w.etext.as<char>() : nullptr);
+    if (m) hipLaunchKernelGGL(pgx_format_fill_mems_kernel, dim3(grid_for(m, 256)), dim3(256), 0, s, in.args(), roff, (const uint64_t *)w.mcum.as<uint64_t>(), pcum, vcum, text,
+                              w.pbase.as<uint64_t>(), in.locate() ? w.vbase.as<uint64_t>() : nullptr);
+    if (np) hipLaunchKernelGGL(pgx_format_fill_items_kernel, dim3(grid_for(np, 256)), dim3(256), 0, s, in.positions, np, in.pos_off, m, pcum, (const uint64_t *)w.pbase.as<uint64_t>(),
+                               (uint64_t)0, text);
+    if (nv) hipLaunchKernelGGL(pgx_format_fill_items_kernel, dim3(grid_for(nv, 256)), dim3(256), 0, s, in.values, nv, in.loc_off, m, vcum, (const uint64_t *)w.vbase.as<uint64_t>(),
+                               in.value_divisor(), text);
+    HIPCHECK(hipGetLastError());
+    if (timed) HIPCHECK(hipEventRecord(w.ev[3], s));
+}
+
+static float format_ms(FormatWork &w) { // (behind the synchronisation that follows format_fill)
+    float a = 0, c = 0;
+    HIPCHECK(hipEventElapsedTime(&a, w.ev[0], w.ev[1]));
+    HIPCHECK(hipEventElapsedTime(&c, w.ev[2], w.ev[3]));
+    return a + c;
+}
+
+extern "C" pgx_status pgx_batch_format(pgx_batch *b, const pgx_format_params *p, pgx_text *out) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_format");
+    checked_device_count();
+    if (!b || !out) throw Error(PGX_ERR_ARG, "pgx_batch_format: null argument");
+    format_check_params(p, "pgx_batch_format");
+    if (!b->ran) throw Error(PGX_ERR_ARG, "pgx_batch_format: batch has not been run");
+    if (!b->ran_tags) throw Error(PGX_ERR_ARG, "pgx_batch_format: the run had no PGX_RUN_TAGS (the text holds the positions of every MEM)");
+    FormatIn in{};
+    in.flags = p->flags;
+    if (in.locate()) { // the last locate must be of the form the flag prints
+        const LocWork &lw = b->lw;
+        const uint32_t want = (p->flags & PGX_FORMAT_LOCATE_SEQS) ? (PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE) : 0u;
+        if (!lw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_format: a locate flag without a completed pgx_batch_locate");
+        if (lw.flags != want || lw.n_mems != b->n_mems)
+            throw Error(PGX_ERR_ARG, "pgx_batch_format: the last pgx_batch_locate ran with flags " + std::to_string(lw.flags) + ", the locate flag given prints the result of flags " +
+                                         std::to_string(want));
+        in.loc_off = lw.d_off;
+        in.values = lw.vals.as<uint64_t>();
+        in.n_values = lw.n_values;
+    }
+    use_device(b->device);
+    FormatWork &w = b->fw;
+    hipStream_t s = b->own; // (the run and the locate completed inside their calls, on whatever stream they used)
+    const bool timed = b->timed, err = (p->flags & PGX_FORMAT_STDERR) != 0;
+    in.mem_off = b->mem_off.as<uint64_t>();
+    in.mems = b->mems.as<pgx_mem>();
+    in.pos_off = b->tw.pos_off.as<uint64_t>();
+    in.positions = b->tw.positions.as<uint64_t>();
+    in.n_reads = b->n_reads; in.n_mems = b->n_mems; in.n_positions = b->n_positions;
+    in.first_seq = p->first_seq;
+    in.max_length = p->max_length ? p->max_length : b->h->ri.max_length ? b->h->ri.max_length : 1;
+    uint64_t n_bytes = 0, n_err = 0;
+    w.cur ^= 1; // (the set of the call before stays as it is)
+    HostBuf &h_text = w.h_text[w.cur], &h_etext = w.h_etext[w.cur];
+    format_lengths(w, in, timed, s, n_bytes, n_err);
+    format_fill(w, in, timed, s, n_bytes, n_err);
+    h_text.ensure(n_bytes ? n_bytes : 8);
+    if (n_bytes) HIPCHECK(hipMemcpyAsync(h_text.p, w.text.p, n_bytes, hipMemcpyDeviceToHost, s));
+    if (err) {
+        h_etext.ensure(n_err ? n_err : 8);
+        if (n_err) HIPCHECK(hipMemcpyAsync(h_etext.p, w.etext.p, n_err, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(hipStreamSynchronize(s));
+    std::memset(out, 0, sizeof *out);
+    out->n_reads = in.n_reads;
+    out->n_bytes = n_bytes;
+    out->n_err_bytes = n_err;
+    out->read_offsets = w.h_roff[w.cur].as<uint64_t>();
+    out->text = h_text.as<char>();
+    out->err_text = err ? h_etext.as<char>() : nullptr;
+    out->ms_format = timed ? format_ms(w) : 0;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_format_result(int device, const pgx_result *in_, const pgx_locations *loc, const pgx_format_params *p, char *text, uint64_t text_cap,
+                                        uint64_t *read_offsets, uint64_t *n_bytes, char *err_text, uint64_t err_cap, uint64_t *n_err_bytes) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_format_result");
+    // everything the arguments alone decide comes first: said with or without a device
+    format_check_params(p, "pgx_format_result");
+    const bool err = (p->flags & PGX_FORMAT_STDERR) != 0, locate = (p->flags & (PGX_FORMAT_LOCATE_POSITIONS | PGX_FORMAT_LOCATE_SEQS)) != 0;
+    if (!in_ || !in_->mem_offsets || (in_->n_mems && !in_->mems) || !in_->pos_offsets || (in_->n_positions && !in_->positions) || (text_cap && !text) || !read_offsets ||
+        !n_bytes || !n_err_bytes || (err && err_cap && !err_text))
+        throw Error(PGX_ERR_ARG, "pgx_format_result: null argument (pos_offsets included: the text holds the positions of every MEM)");
+    const uint64_t n = in_->n_reads, m = in_->n_mems, np = in_->n_positions;
+    if (locate && (!loc || !loc->loc_offsets || (loc->n_values && !loc->values))) throw Error(PGX_ERR_ARG, "pgx_format_result: a locate flag without loc");
+    if (locate && loc->n_mems != m) throw Error(PGX_ERR_ARG, "pgx_format_result: loc->n_mems differs from in->n_mems");
+    if ((p->flags & PGX_FORMAT_LOCATE_POSITIONS) && !p->max_length) throw Error(PGX_ERR_ARG, "pgx_format_result: PGX_FORMAT_LOCATE_POSITIONS needs max_length");
+    auto check_csr = [](const uint64_t *off, uint64_t cnt, uint64_t last, const char *name) { // the kernels index the arrays by these
+        bool ok = off[0] == 0 && off[cnt] == last;
+        for (uint64_t i = 0; ok && i < cnt; i++) ok = off[i] <= off[i + 1];
+        if (!ok) throw Error(PGX_ERR_ARG, std::string("pgx_format_result: ") + name + " must start at 0, never decrease and end at the count of what it indexes");
+    };
+    check_csr(in_->mem_offsets, n, m, "mem_offsets");
+    check_csr(in_->pos_offsets, m, np, "pos_offsets");
+    if (locate) check_csr(loc->loc_offsets, m, loc->n_values, "loc_offsets");
+    *n_bytes = *n_err_bytes = 0;
+    use_device(device);
+    struct Work { // device copies of the input + the formatter's buffers, released on every way out
+        DevBuf mem_off, mems, pos_off, positions, loc_off, values;
+        FormatWork w;
+        ~Work() {
+            DevBuf *all[] = {&mem_off, &mems, &pos_off, &positions, &loc_off, &values};
+            for (DevBuf *d : all) d->release();
+            w.release();
+        }
+    } k;
+    upload(k.mem_off, in_->mem_offsets, (n + 1) * 8);
+    upload(k.mems, in_->mems, m * sizeof(pgx_mem));
+    upload(k.pos_off, in_->pos_offsets, (m + 1) * 8);
+    upload(k.positions, in_->positions, np * 8);
+    FormatIn in{};
+    in.flags = p->flags;
+    if (locate) {
+        upload(k.loc_off, loc->loc_offsets, (m + 1) * 8);
+        upload(k.values, loc->values, loc->n_values * 8);
+        in.loc_off = k.loc_off.as<uint64_t>();
+        in.values = k.values.as<uint64_t>();
+        in.n_values = loc->n_values;
+    }
+    in.mem_off = k.mem_off.as<uint64_t>();
+    in.mems = k.mems.as<pgx_mem>();
+    in.pos_off = k.pos_off.as<uint64_t>();
+    in.positions = k.positions.as<uint64_t>();
+    in.n_reads = n; in.n_mems = m; in.n_positions = np;
+    in.first_seq = p->first_seq;
+    in.max_length = p->max_length;
+    hipStream_t s = nullptr;
+    uint64_t total = 0, total_err = 0;
+    format_lengths(k.w, in, false, s, total, total_err);
+    *n_bytes = total;
+    *n_err_bytes = total_err;
+    std::memcpy(read_offsets, k.w.h_roff[k.w.cur].as<uint64_t>(), (n + 1) * 8);
+    if (total > text_cap) throw Error(PGX_ERR_NOMEM, "pgx_format_result: the text takes " + std::to_string(total) + " bytes, text_cap is " + std::to_string(text_cap));
+    if (err && total_err > err_cap)
+        throw Error(PGX_ERR_NOMEM, "pgx_format_result: the stderr lines take " + std::to_string(total_err) + " bytes, err_cap is " + std::to_string(err_cap));
+    format_fill(k.w, in, false, s, total, total_err);
+    if (total) HIPCHECK(hipMemcpyAsync(text, k.w.text.p, total, hipMemcpyDeviceToHost, s));
+    if (err && total_err) HIPCHECK(hipMemcpyAsync(err_text, k.w.etext.p, total_err, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     return PGX_OK;
     PGX_GUARD_END

@@ -229,6 +229,24 @@ __global__ void pgx_compact_fill_staged_kernel(const uint64_t *mem_off, const pg
                                                const uint64_t *positions, uint64_t n_reads, uint64_t n_blocks, int tags, const uint64_t *block_offsets,
                                                uint8_t *bytes);
 
+// ---- pgx_format_kernels.hip: the find_mems text of a result (pgx_batch_format, pgx_format_result); lengths, three scans, fill by item class
+struct PgxFormatArgs {
+    const uint64_t *mem_off;   // n_reads + 1
+    const pgx_mem *mems;       // n_mems
+    const uint64_t *pos_off;   // n_mems + 1
+    const uint64_t *loc_off;   // n_mems + 1; only read with a locate flag
+    uint64_t n_reads, n_mems, first_seq;
+    uint32_t flags;            // PGX_FORMAT_*
+};
+__global__ void pgx_format_item_len_kernel(const uint64_t *vals, uint64_t n, uint64_t max_length, uint8_t *len);
+__global__ void pgx_format_mem_len_kernel(PgxFormatArgs a, const uint64_t *pcum, const uint64_t *vcum, uint64_t *mlen);
+__global__ void pgx_format_read_len_kernel(PgxFormatArgs a, const uint64_t *mcum, uint64_t *rlen, uint8_t *elen);
+__global__ void pgx_format_fill_reads_kernel(PgxFormatArgs a, const uint64_t *read_off, const uint64_t *err_off, char *text, char *err_text);
+__global__ void pgx_format_fill_mems_kernel(PgxFormatArgs a, const uint64_t *read_off, const uint64_t *mcum, const uint64_t *pcum, const uint64_t *vcum,
+                                            char *text, uint64_t *pbase, uint64_t *vbase);
+__global__ void pgx_format_fill_items_kernel(const uint64_t *vals, uint64_t n, const uint64_t *off, uint64_t n_mems, const uint64_t *cum,
+                                             const uint64_t *base, uint64_t max_length, char *text);
+
 // ---- pgx_tag_kernels.hip: the tag stage
 __global__ void pgx_tag_pair_kernel(const uint64_t *tstart, const uint64_t *tvals, uint64_t n_runs, uint64_t n_items, ulonglong2 *out);
 __global__ void pgx_tag_bucket_kernel(const uint64_t *tstart, const uint64_t *tvals, uint64_t n_runs, uint64_t n_items, uint32_t shift, uint64_t n_buckets, uint4 *out);

@@ -68,6 +68,18 @@ COMPACT_BLOCK_READS = 64
 COMPACT_TAGS = 1  # pgx_compact_result.flags
 
 
+class FormatParams(C.Structure):  # pgx_format_params
+    _fields_ = [("first_seq", u64), ("max_length", u64), ("flags", u32), ("reserved", u32)]
+
+
+class Text(C.Structure):  # pgx_text
+    _fields_ = [("n_reads", u64), ("n_bytes", u64), ("n_err_bytes", u64), ("read_offsets", C.POINTER(u64)), ("text", p), ("err_text", p),
+                ("ms_format", C.c_float)]
+
+
+FORMAT_STDERR, FORMAT_LOCATE_POSITIONS, FORMAT_LOCATE_SEQS = 1, 2, 4  # pgx_format_params.flags
+
+
 class DeviceArray:
     """a device buffer owned by a batch, exposed through __cuda_array_interface__ (zero copy: torch.as_tensor(a, device="cuda"));
     64-bit unsigned values are presented as int64"""
@@ -194,6 +206,8 @@ def lib():
     L.pgx_compact_bound.argtypes = [u64, u64, u64, u32]
     L.pgx_compact_bound.restype = u64
     L.pgx_compact_encode.argtypes = [C.c_int, C.POINTER(Result), p, u64, p, p, p, C.POINTER(u64)]
+    L.pgx_batch_format.argtypes = [p, C.POINTER(FormatParams), C.POINTER(Text)]
+    L.pgx_format_result.argtypes = [C.c_int, C.POINTER(Result), C.POINTER(Locations), C.POINTER(FormatParams), p, u64, p, C.POINTER(u64), p, u64, C.POINTER(u64)]
     L.pgx_batch_free.argtypes = [p]
     L.pgx_batch_free.restype = None
     L.pgx_find_mems_batch.argtypes = [p, C.c_int, p, p, u64, u64, u64, u32, C.POINTER(p), C.POINTER(Result)]
@@ -654,6 +668,63 @@ def compact_encode(device, result, bytes_cap=None):
                 block_first_pos=tabs[2], bytes=buf[:int(nbytes.value)].copy(), ms_encode=0.0)
 
 
+def format_result(device, result, first_seq=0, flags=0, max_length=0, locations=None, text_cap=None, err_cap=None, guard=0, reserved=0):
+    """pgx_format_result: the device formatter on a result dict (mem_offsets, mems, pos_offsets, positions) and, with a locate flag, a
+    locations dict (loc_offsets, values); returns dict(n_bytes, n_err_bytes, read_offsets, text, err_text) with text / err_text as bytes
+    (err_text None without FORMAT_STDERR).  text_cap / err_cap: the sizes of the buffers handed over (default: a first call sizes them);
+    guard: bytes of 0xA5 kept behind each buffer, returned as text_guard / err_guard.  ERR_NOMEM raises with n_bytes, n_err_bytes,
+    read_offsets and the untouched buffers (text_buf, err_buf) on the exception"""
+    mo = np.ascontiguousarray(result["mem_offsets"], dtype=np.uint64)
+    mems = np.ascontiguousarray(result["mems"], dtype=MEM_DTYPE)
+    n, m = len(mo) - 1, len(mems)
+    r = Result()
+    r.n_reads, r.n_mems = n, m
+    r.mem_offsets = C.cast(mo.ctypes.data, C.POINTER(u64))
+    r.mems = mems.ctypes.data
+    keep = [mo, mems]
+    for k in ("pos_offsets", "positions"):
+        if k in result:
+            a = np.ascontiguousarray(result[k], dtype=np.uint64)
+            keep.append(a)
+            setattr(r, k, C.cast(a.ctypes.data, C.POINTER(u64)))
+    r.n_positions = len(result["positions"]) if "positions" in result else 0
+    loc = None
+    if locations is not None:
+        lo = np.ascontiguousarray(locations["loc_offsets"], dtype=np.uint64)
+        lv = np.ascontiguousarray(locations["values"], dtype=np.uint64)
+        keep += [lo, lv]
+        loc = Locations()
+        loc.n_mems, loc.n_values = int(locations.get("n_mems", len(lo) - 1)), len(lv)
+        loc.loc_offsets, loc.values = lo.ctypes.data, lv.ctypes.data
+    fp = FormatParams(first_seq, max_length, flags, reserved)
+    ro = np.zeros(n + 1, dtype=np.uint64)
+    nb, ne = u64(0), u64(0)
+    L = lib()
+
+    def call(tcap, ecap):
+        tb = np.full(tcap + guard + 1, 0xA5, dtype=np.uint8)
+        eb = np.full(ecap + guard + 1, 0xA5, dtype=np.uint8)
+        st = L.pgx_format_result(device, C.byref(r), C.byref(loc) if loc is not None else None, C.byref(fp), tb.ctypes.data, tcap, ro.ctypes.data,
+                                 C.byref(nb), eb.ctypes.data, ecap, C.byref(ne))
+        return st, tb, eb
+
+    if text_cap is None or err_cap is None:
+        st, tb, eb = call(0, 0)  # sizes only (ERR_NOMEM unless the text is empty)
+        if st not in (OK, ERR_NOMEM):
+            _check(st)
+        text_cap = int(nb.value) if text_cap is None else text_cap
+        err_cap = int(ne.value) if err_cap is None else err_cap
+    st, tb, eb = call(int(text_cap), int(err_cap))
+    if st != OK:
+        e = PgxError(st, L.pgx_last_error().decode(errors="replace"))
+        e.n_bytes, e.n_err_bytes, e.read_offsets, e.text_buf, e.err_buf = int(nb.value), int(ne.value), ro, tb, eb
+        raise e
+    del keep
+    nbv, nev = int(nb.value), int(ne.value)
+    return dict(n_bytes=nbv, n_err_bytes=nev, read_offsets=ro, text=tb[:nbv].tobytes(), err_text=eb[:nev].tobytes() if flags & FORMAT_STDERR else None,
+                text_guard=tb[nbv:], err_guard=eb[nev:])
+
+
 def find_mems_sharded(index, devices, reads_cat, offsets, min_len, min_occ, tags=False):
     """pgx_find_mems_sharded: contiguous read slices, slice i on devices[i]; returns the per-slice result dicts in slice order"""
     reads_cat = np.ascontiguousarray(reads_cat, dtype=np.uint8)
@@ -845,6 +916,20 @@ class Batch:
             out["pos_offsets"] = DeviceArray(r.pos_offsets, (m + 1,), self)
             out["positions"] = DeviceArray(r.positions, (int(r.n_positions),), self)
         return out
+
+    def format(self, first_seq=0, flags=0, max_length=0, reserved=0, copy=True):
+        """pgx_batch_format: the find_mems text of the last run (and, with a locate flag, of the last locate), written on the device:
+        dict(n_reads, n_bytes, n_err_bytes, read_offsets uint64[n_reads + 1], text bytes, err_text bytes or None, ms_format).
+        copy=False: the counters and ms_format only (the text stays in the batch's pinned buffers)"""
+        fp = FormatParams(first_seq, max_length, flags, reserved)
+        t = Text()
+        _check(self.L.pgx_batch_format(self.b, C.byref(fp), C.byref(t)))
+        n = int(t.n_reads)
+        if not copy:
+            return dict(n_reads=n, n_bytes=int(t.n_bytes), n_err_bytes=int(t.n_err_bytes), ms_format=float(t.ms_format))
+        return dict(n_reads=n, n_bytes=int(t.n_bytes), n_err_bytes=int(t.n_err_bytes), read_offsets=_u64_array(t.read_offsets, n + 1),
+                    text=C.string_at(t.text, int(t.n_bytes)), err_text=C.string_at(t.err_text, int(t.n_err_bytes)) if t.err_text else None,
+                    ms_format=float(t.ms_format))
 
     def locate(self, flags=0, max_occ=0, stream=None):
         """pgx_batch_locate: the occurrences of the last run's MEMs, left on the device (locations() / device_locations())"""

@@ -10,7 +10,9 @@
 //                 '>' FASTA, '@' FASTQ, otherwise lines), --device-parse (line files parsed on the device too; FASTA / FASTQ always are),
 //                 --locate positions|seqs (the occurrences of every MEM, pgx_batch_locate), --locate-max K (MEMs with more occurrences: not located),
 //                 --result full|compact (default full; compact: the result crosses the link as the compact byte stream, pgx_batch_result_compact,
-//                 and every formatter thread expands its own blocks, pgx_compact_expand; the same text either way)
+//                 and every formatter thread expands its own blocks, pgx_compact_expand; the same text either way),
+//                 --format host|device (default host; device: the text itself is written on the device, pgx_batch_format -- no result arrays cross the link,
+//                 no formatter threads run, --result has no effect; the same text either way)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -110,6 +112,10 @@ struct Job { // one batch of consecutive reads
 };
 struct Done {
     std::vector<std::string> outs, errs; // text pieces in read order
+    // --format device: the text where pgx_batch_format left it, in pinned buffers of the worker's batch (lent to the writer: the worker formats its
+    // next batch but one only when this one has been written)
+    const char *text = nullptr, *etext = nullptr;
+    size_t text_n = 0, etext_n = 0;
     double mem_s = 0, tag_s = 0;
     std::string error;
 };
@@ -206,7 +212,7 @@ int main(int argc, char **argv) {
         std::cerr << "usage: find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ>"
                      " [--device N | --gpus N | --devices a,b,..] [--streams W] [--mode compat|strict] [--batch N]"
                      " [--tags-format auto|bytecode|compact] [--quiet] [--reads-format lines|fasta|fastq|auto] [--device-parse]"
-                     " [--locate positions|seqs] [--locate-max K] [--result full|compact]" << std::endl;
+                     " [--locate positions|seqs] [--locate-max K] [--result full|compact] [--format host|device]" << std::endl;
         return EXIT_FAILURE;
     }
     const std::string r_index_file = argv[1], tag_array_index = argv[2], reads_file = argv[3];
@@ -221,6 +227,7 @@ int main(int argc, char **argv) {
     int locate_mode = LOCATE_NONE;
     uint64_t locate_max = 0;
     bool compact_result = false;
+    bool format_device = false; // --format device: stdout and the per-read stderr lines come from pgx_batch_format
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -267,6 +274,12 @@ int main(int argc, char **argv) {
             if (f == "compact") compact_result = true;
             else if (f == "full") compact_result = false;
             else { std::cerr << "--result: full or compact" << std::endl; return EXIT_FAILURE; }
+        }
+        else if (a == "--format") {
+            const std::string f = next();
+            if (f == "device") format_device = true;
+            else if (f == "host") format_device = false;
+            else { std::cerr << "--format: host or device" << std::endl; return EXIT_FAILURE; }
         }
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
@@ -347,7 +360,9 @@ int main(int argc, char **argv) {
     unsigned n_parse = std::max(1u, std::min(8u, hw / 4));
     if (const char *e = std::getenv("PGX_CLI_PARSE_THREADS")) n_parse = (unsigned)std::max(1, std::atoi(e));
     std::mutex mu;
-    std::condition_variable cv_jobs, cv_done, cv_space;
+    std::condition_variable cv_jobs, cv_done, cv_space, cv_written;
+    uint64_t written = 0;     // batches the writer is through with (--format device: their text may be overwritten)
+    bool writer_done = false; // the writer has left its loop and reads no text any more
     std::map<uint64_t, std::unique_ptr<Job>> parsed;     // by id, waiting for a device worker
     std::map<uint64_t, std::unique_ptr<Done>> finished;
     bool reader_done = false, failed = false;
@@ -427,7 +442,10 @@ int main(int argc, char **argv) {
     // (with --result compact "download" holds the encode on the device and the download of the stream, and "format" holds the host expansion
     // of the blocks next to the formatting: the two forms split the same work differently between the two figures)
     const bool cli_stats = std::getenv("PGX_CLI_STATS") != nullptr;
-    std::atomic<uint64_t> ns_parse{0}, ns_upload{0}, ns_run{0}, ns_download{0}, ns_format{0}, ns_write{0};
+    // (with --format device "download" holds only the locate, "format" the whole of pgx_batch_format -- length and fill kernels and the download of the
+    // text -- plus any wait for the writer to release a text buffer; a second line splits the two)
+    std::atomic<uint64_t> ns_parse{0}, ns_upload{0}, ns_run{0}, ns_download{0}, ns_format{0}, ns_write{0}, ns_devfmt{0}, ns_lent{0};
+    std::atomic<uint64_t> us_devfmt_kernels{0}, text_bytes{0};
     auto now_ns = []() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const uint64_t t_pipeline0 = now_ns();
     std::vector<std::thread> parsers;
@@ -463,6 +481,18 @@ int main(int argc, char **argv) {
     auto worker = [&](int device) {
         pgx_batch *b = nullptr; // long-lived: its device and pinned host buffers are reused by every batch of this worker
         ExpandBufs xb;          // --result compact: what the formatter threads expand into
+        // --format device: the batches of this worker whose text the writer has not written yet.  The text stays where pgx_batch_format put it, in one of
+        // the two pinned buffer sets of `b` that its calls alternate between, so at most two are lent at a time.  (No deadlock: the writer takes batches in
+        // file order, and the worker that holds the oldest unwritten batch waits for none: everything before it has been written.)
+        std::deque<uint64_t> lent;
+        auto wait_written = [&](size_t keep) {
+            std::unique_lock<std::mutex> lk(mu);
+            while (lent.size() > keep) {
+                const uint64_t id = lent.front();
+                cv_written.wait(lk, [&]() { return writer_done || written > id; });
+                lent.pop_front();
+            }
+        };
         for (;;) {
             std::unique_ptr<Job> j;
             {
@@ -537,7 +567,9 @@ int main(int argc, char **argv) {
             if (st == PGX_OK) st = pgx_batch_run(b, mem_length, min_occ, PGX_RUN_TAGS | PGX_RUN_TIMING, nullptr);
             uint64_t t2 = now_ns();
             pgx_compact_result cr;
-            if (st == PGX_OK && compact_result) {
+            if (format_device) {
+                // nothing to download: the device writes the text below, once the batch knows the number of its first read
+            } else if (st == PGX_OK && compact_result) {
                 st = pgx_batch_result_compact(b, &cr);
                 if (st == PGX_OK) { // the arrays of r are filled block range by block range in the formatter threads below
                     std::memset(&r, 0, sizeof r);
@@ -554,7 +586,7 @@ int main(int argc, char **argv) {
             LocateOut lout = locate_out;
             if (st == PGX_OK && locate_mode) {
                 st = pgx_batch_locate(b, locate_flags, locate_max, nullptr);
-                if (st == PGX_OK) st = pgx_batch_locations(b, &loc);
+                if (st == PGX_OK && !format_device) st = pgx_batch_locations(b, &loc);
                 if (st == PGX_ERR_UNSUPPORTED) d->error = std::string(pgx_last_error()) + " (find_mems: run with --mode strict)";
                 lout.loc = &loc;
             }
@@ -577,9 +609,30 @@ int main(int argc, char **argv) {
                     d->mem_s = 1e-3 * (t.ms_find_mems + t.ms_compact);
                     d->tag_s = 1e-3 * (t.ms_tag_locate + t.ms_tag_gather + t.ms_tag_sort);
                 }
-                const unsigned parts = n < 4096 ? 1u : n_fmt;
-                d->outs.resize(parts);
-                d->errs.resize(parts);
+                if (format_device) {
+                    // the text of the batch from the device, handed to the writer where it is
+                    const uint64_t t3w = now_ns();
+                    wait_written(1);
+                    ns_lent += now_ns() - t3w;
+                    pgx_format_params fp;
+                    std::memset(&fp, 0, sizeof fp);
+                    fp.first_seq = j->first_seq;
+                    fp.flags = (quiet ? 0u : PGX_FORMAT_STDERR) | (locate_mode == LOCATE_POSITIONS ? PGX_FORMAT_LOCATE_POSITIONS : locate_mode == LOCATE_SEQS ? PGX_FORMAT_LOCATE_SEQS : 0u);
+                    pgx_text tx;
+                    const uint64_t t3f = now_ns(); // (behind the wait for the batch's number)
+                    if (pgx_batch_format(b, &fp, &tx) != PGX_OK) d->error = pgx_last_error();
+                    ns_devfmt += now_ns() - t3f;
+                    if (d->error.empty()) {
+                        d->text = tx.text; d->text_n = (size_t)tx.n_bytes;
+                        if (tx.err_text) { d->etext = tx.err_text; d->etext_n = (size_t)tx.n_err_bytes; }
+                        lent.push_back(j->id);
+                        us_devfmt_kernels += (uint64_t)(1e3 * (double)tx.ms_format);
+                        text_bytes += tx.n_bytes + tx.n_err_bytes;
+                    }
+                }
+                const unsigned parts = format_device ? 0u : n < 4096 ? 1u : n_fmt;
+                if (parts) d->outs.resize(parts);
+                if (parts) d->errs.resize(parts);
                 // --result compact: the parts are cut on multiples of 64 reads and every thread expands the blocks of its part first
                 auto cut = [&](unsigned w) -> size_t {
                     if (w >= parts) return n;
@@ -593,7 +646,8 @@ int main(int argc, char **argv) {
                         return pgx_last_error(); // (the message is thread-local)
                     return std::string();
                 };
-                if (parts == 1) {
+                if (parts == 0) { // (--format device: the text is there)
+                } else if (parts == 1) {
                     if (compact_result) d->error = expand_part(0);
                     if (d->error.empty()) format_range(r, 0, n, j->first_seq, quiet, lout, d->outs[0], d->errs[0]);
                 } else {
@@ -623,6 +677,7 @@ int main(int argc, char **argv) {
             cv_done.notify_all();
             if (failed) { cv_jobs.notify_all(); cv_space.notify_all(); }
         }
+        wait_written(0); // (the writer may still be reading this batch's buffers)
         pgx_batch_free(b);
     };
     std::vector<std::thread> workers;
@@ -648,12 +703,19 @@ int main(int argc, char **argv) {
             std::fwrite(d->outs[w].data(), 1, d->outs[w].size(), stdout);
             if (!d->errs[w].empty()) std::fwrite(d->errs[w].data(), 1, d->errs[w].size(), stderr);
         }
+        if (d->text_n) std::fwrite(d->text, 1, d->text_n, stdout);
+        if (d->etext_n) std::fwrite(d->etext, 1, d->etext_n, stderr);
         ns_write += now_ns() - tw0;
         total_mem_time += d->mem_s;
         total_tag_time += d->tag_s;
+        std::lock_guard<std::mutex> lk(mu);
+        written = next_write; // (only this thread changes next_write)
+        cv_written.notify_all();
     }
     {
         std::lock_guard<std::mutex> lk(mu);
+        writer_done = true;
+        cv_written.notify_all();
         if (!error.empty()) failed = true;
         cv_jobs.notify_all();
         cv_space.notify_all();
@@ -674,6 +736,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "[find_mems] pipeline %.3f s wall; busy seconds: parse %.3f (%u threads), upload %.3f, run %.3f, download %.3f, format %.3f (wall of %u-thread pools), write %.3f; %u device workers\n",
                      1e-9 * (double)(now_ns() - t_pipeline0), 1e-9 * (double)ns_parse.load(), n_parse, 1e-9 * (double)ns_upload.load(), 1e-9 * (double)ns_run.load(),
                      1e-9 * (double)ns_download.load(), 1e-9 * (double)ns_format.load(), n_fmt, 1e-9 * (double)ns_write.load(), n_workers);
+    if (cli_stats && format_device)
+        std::fprintf(stderr, "[find_mems] --format device: of format %.3f s: pgx_batch_format %.3f (its kernels %.3f), waiting for the writer to release a text buffer %.3f; %.1f MB of text\n",
+                     1e-9 * (double)ns_format.load(), 1e-9 * (double)ns_devfmt.load(), 1e-6 * (double)us_devfmt_kernels.load(), 1e-9 * (double)ns_lent.load(),
+                     1e-6 * (double)text_bytes.load());
     std::cout << "\nTotal time for finding all MEMs: " << total_mem_time << " seconds" << std::endl; // :144
     std::cout << "Total time for all tag queries: " << total_tag_time << " seconds" << std::endl;   // :145
     pgx_index_close(h);
