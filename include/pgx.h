@@ -204,7 +204,9 @@ pgx_status pgx_convert_tags(const char *in_path, const char *out_path, int compa
  * array by the locate kernels, one scan + gather per file, run-length encoding.  Merged runs are maximal (the reference
  * counts them in a uint16_t, which wraps beyond 65 535) and split at 511 like append_compact_run_streamed
  * (src/tag_arrays.cpp:940-974).  PGX_ERR_FORMAT when a file holds a different number of tags than the BWT has
- * positions of its sequences. */
+ * positions of its sequences; a file that cannot be read is reported the same way, with its path.  PGX_ERR_ARG for
+ * n_files outside 1..250 and for any seq_to_file entry >= n_files, that of an empty sequence included.  A refused call
+ * writes nothing at out_path. */
 pgx_status pgx_merge_tags(const char *ri_path, const char *const *tag_paths, uint32_t n_files, const uint32_t *seq_to_file,
                           uint64_t n_seq, int device, const char *out_path);
 /* As pgx_merge_tags, with flags.  PGX_MERGE_REFERENCE_RUNS: the file byte for byte as the reference writes it.  The reference

@@ -66,6 +66,9 @@ static void merge_tags_core(const char *ri_path, const char *const *tag_paths, u
     const uint64_t n = h->ri.sequence_size, tot = h->ri.C.size() > 1 ? h->ri.C[1] - h->ri.C[0] : 0;
     if (n_seq != tot) throw Error(PGX_ERR_ARG, "pgx_merge_tags: seq_to_file has " + std::to_string(n_seq) + " entries, the index holds " +
                                                    std::to_string(tot) + " sequences");
+    // every entry, also that of an empty sequence, which has no row behind the endmarker block for pgx_mt_file_of_kernel to see
+    for (uint64_t sq = 0; sq < n_seq; sq++)
+        if (seq_to_file[sq] >= n_files) throw Error(PGX_ERR_ARG, "pgx_merge_tags: seq_to_file names a file index >= n_files");
     pgx_device_image *d = locate_image(h, device);
     DevBuf da, file_of, tags, rank, scan_tmp, s2f, ctr, rstart, rval, expanded, flags, out_val, out_start;
     DevBuf *all[] = {&da, &file_of, &tags, &rank, &scan_tmp, &s2f, &ctr, &rstart, &rval, &expanded, &flags, &out_val, &out_start};

@@ -85,8 +85,10 @@ def _sequential_merge(rw, tag_paths, seq_to_file, n_seq):
     streams = []
     for p in tag_paths:
         raw = open(p, "rb").read()
-        if len(raw) >= 8 and int(np.frombuffer(raw[:8], dtype=np.uint64)[0]) == (len(raw) - 8) * 8:
-            raw = raw[8:]
+        if len(raw) >= 8:  # the int_vector<8> header states the body's bits; the body may be zero-padded to whole words (runs of length 0)
+            bits, body = int(np.frombuffer(raw[:8], dtype=np.uint64)[0]), len(raw) - 8
+            if bits == body * 8 or (bits % 8 == 0 and bits // 8 < body and (bits // 8 + 7) // 8 * 8 == body):
+                raw = raw[8:]
         vals, i = [], 0
         while i < len(raw):
             v, sh = 0, 0
