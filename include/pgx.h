@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only), the device index build (pgx_build_index_from_text_device, pgx_build_index_from_texts_device, pgx_build_index_device_timing: new entry points only), the text output (pgx_batch_format, pgx_format_result, pgx_format_params, pgx_text, PGX_FORMAT_*: new entry points only) */
+#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only), the device index build (pgx_build_index_from_text_device, pgx_build_index_from_texts_device, pgx_build_index_device_timing: new entry points only), the text output (pgx_batch_format, pgx_format_result, pgx_format_params, pgx_text, PGX_FORMAT_*: new entry points only), the image file (pgx_index_save_image, pgx_index_open_image, pgx_image_file_info, pgx_image_sum, pgx_image_section_name, PGX_IMAGE_*: new entry points only) */
 
 typedef enum {
     PGX_OK = 0,
@@ -142,6 +142,116 @@ pgx_status pgx_index_image_view(const pgx_index *h, int which, const void **ptr,
  * coordinates (u32 x n), text at two bits per symbol, flag bits per 128-byte text line, common prefixes of neighbouring suffixes (u8 x n);
  * nothing is copied where the index has no such image. */
 pgx_status pgx_index_device_view(pgx_index *h, int device, int which, void *out, uint64_t bytes);
+
+/* ---- image file (.pgi): the built host images of an index, saved once and reopened without a .ri or a tag file ------------
+ * pgx_index_open parses the reference's files (Elias-Fano vectors, ByteCode blocks) and builds the flat images on host threads on every
+ * start; the reference's loaders (FastLocate::load_encoded src/r-index.cpp:406-459, TagArray::load_compressed_tags_sdsl
+ * src/tag_arrays.cpp:766-776) pay the same on every start.  An image file holds what that work produced, so opening it is reading it.
+ *
+ * This is an INTEGRITY check against truncation, bit rot and files of another build.  It is NOT a defence against a crafted file: a
+ * file whose sums and lengths are consistent is trusted, and the kernels index its sections unchecked.
+ *
+ * THE FILE (little-endian, versioned; no time stamp, no host name: the same index saved twice gives the same bytes).
+ *   header, 64 bytes
+ *      0  char[8]  magic "PGXIMAGE"
+ *      8  u32      file-format version (PGX_IMAGE_FILE_VERSION)
+ *     12  u32      PGX_IMAGE_LAYOUT (pgx_image.h)
+ *     16  u32      sizeof(PgxConsts)        20  u32  sizeof(PgxLocConsts)
+ *     24  u32      mode (PGX_MODE_COMPAT / PGX_MODE_STRICT)
+ *     28  u32      has_rank                 32  u32  has_tags
+ *     36  u32      number of sections S (1 .. PGX_IMAGE_MAX_SECTIONS)
+ *     40  u32      bytes of the meta record (PGX_IMAGE_META_BYTES)
+ *     44  u32      flags: bit 0 the locate image is stored, bit 1 the literal count image is stored
+ *     48  u64      header sum: the section sum (below) of bytes [0, 64 + 32 S + meta bytes) with this field read as zero
+ *     56  u64      0
+ *   section table at 64, 32 bytes per entry, in ascending id order
+ *      0  u32 id (PGX_IMAGE_SEC_*)   4  u32 element size   8  u64 bytes   16  u64 file offset (a multiple of 4096)   24  u64 section sum
+ *   meta record behind the table: what a handle keeps of the .ri and the tag file once the images exist
+ *      0  u8[256] sym_map     256  u64[8] C     320  u32 sigma (C.size())   324  u32 encoded   328  u32 hasN   332  u32 tags.format
+ *    336  u64 sequence_size   344  u64 max_length   352  u64 n_file_blocks   360  f64 ref_block_mean_bytes   368  u64 samples.size()
+ *    376  u64[6] symbol totals of the BWT in nuc order (\n A C G N T)
+ *    424  u64 tag values stored (tvals)   432  u64 exception runs stored (exc)   440  u64 blocks / 448  u64 runs of the literal count image
+ *         (the four array lengths no constant states: with them every section's length is implied exactly)
+ *   sections, each at its offset, in id order, zero bytes between them; the file ends with the last section.  An empty section still
+ *   has an entry (bytes 0, offset = where it would start).
+ * SECTION SUM.  The section is read as 8-byte little-endian words w[0 .. ceil(bytes / 8)), the last one padded with zero bytes;
+ *   sum = sum over i of mix(w[i] + (i + 1) * 0x9E3779B97F4A7C15)   (all arithmetic modulo 2^64), with
+ *   mix(z):  z = (z ^ (z >> 32)) * 0xD6E8FEB86659FD93;  z ^ (z >> 32)       (xor-shift, odd multiplier, xor-shift: each step a bijection;
+ *   one multiplication per word keeps the device kernel bound by memory, not by its 64-bit multiplies)
+ *   For a fixed i the term is a bijection of w[i], so one changed word always changes the sum; the index enters every term, so equal
+ *   words at different places give different terms; addition commutes, so threads and lanes may add in any order and the result is
+ *   bitwise reproducible.  The sum of no bytes is 0.  (tests/image_file_emu.py restates the file and the sum in Python.) */
+#define PGX_IMAGE_MAGIC "PGXIMAGE"
+#define PGX_IMAGE_FILE_VERSION 1u
+#define PGX_IMAGE_MAX_SECTIONS 64u
+#define PGX_IMAGE_HEADER_BYTES 64u
+#define PGX_IMAGE_ENTRY_BYTES 32u
+#define PGX_IMAGE_META_BYTES 456u
+#define PGX_IMAGE_ALIGN 4096u
+#define PGX_IMAGE_HAS_LOCATE 1u  /* header flags */
+#define PGX_IMAGE_HAS_LITERAL 2u
+/* section ids; the names pgx_image_section_name gives are the lower-case suffixes (consts, blocks, .. loc_consts, rstart, .. lit_bstart, ..) */
+#define PGX_IMAGE_SEC_CONSTS 1u  /* PgxConsts */
+#define PGX_IMAGE_SEC_BLOCKS 2u  /* views 0, 1, 2, 7, 15, 20, 22, 23, 3, 4, 5 of pgx_index_image_view, in this order: */
+#define PGX_IMAGE_SEC_DIR 3u
+#define PGX_IMAGE_SEC_BSTART 4u
+#define PGX_IMAGE_SEC_BLOW 5u
+#define PGX_IMAGE_SEC_EXC 6u
+#define PGX_IMAGE_SEC_PAIRS 7u
+#define PGX_IMAGE_SEC_SBASE2 8u
+#define PGX_IMAGE_SEC_PBASE 9u
+#define PGX_IMAGE_SEC_TSTART 10u
+#define PGX_IMAGE_SEC_TVALS 11u
+#define PGX_IMAGE_SEC_TDIR 12u
+#define PGX_IMAGE_SEC_N_RUNS 13u /* u64: logical BWT runs (pgx_index_info.n_runs) */
+#define PGX_IMAGE_SEC_LOC_CONSTS 20u /* PgxLocConsts; views 14, 8 .. 13 */
+#define PGX_IMAGE_SEC_RSTART 21u
+#define PGX_IMAGE_SEC_RSAMP 22u
+#define PGX_IMAGE_SEC_RDIR 23u
+#define PGX_IMAGE_SEC_LPOS 24u
+#define PGX_IMAGE_SEC_LNEXT 25u
+#define PGX_IMAGE_SEC_LDIR 26u
+#define PGX_IMAGE_SEC_LIT_BSTART 30u /* views 16 .. 19 */
+#define PGX_IMAGE_SEC_LIT_CUM 31u
+#define PGX_IMAGE_SEC_LIT_RUNS 32u
+#define PGX_IMAGE_SEC_LIT_ROFF 33u
+#define PGX_IMAGE_SEC_LIT_TABS 34u   /* u32 code_of[256], u32 cslot_of[256], u64 C[8] */
+/* What is stored: the rank image with its tag runs (always), the locate image of a handle with an r-index (unless
+ * PGX_IMAGE_NO_LOCATE), the literal count image exactly where pgx_count_batch goes through it (COMPAT, encoded, no N).  What exists
+ * on the device only (seed tables, tag pairs and buckets, the LCE image) is rebuilt there as for any handle. */
+#define PGX_IMAGE_NO_LOCATE 1u /* pgx_index_save_image: leave the locate image out */
+#define PGX_IMAGE_VERIFY 1u    /* pgx_index_open_image: also sum every section on the host before returning */
+typedef struct {
+    uint32_t id, elem_size;
+    uint64_t bytes, offset, sum;
+    char name[16];
+} pgx_image_section_info;
+typedef struct {
+    uint32_t version, layout, consts_bytes, loc_consts_bytes, mode, has_rank, has_tags, n_sections, meta_bytes, flags;
+    uint64_t header_sum, file_bytes;
+    pgx_image_section_info sections[PGX_IMAGE_MAX_SECTIONS];
+} pgx_image_info; /* (not pgx_image_file_info: C keeps functions and typedef names in one name space) */
+/* Host only.  Builds the locate image and the literal image of `h` if they are not built yet, writes the file under a temporary name
+ * next to `path` and renames it; no file is left behind after an error (PGX_ERR_IO).  Works from an image-opened handle too (the same
+ * bytes again).  PGX_IMAGE_NO_LOCATE from a handle that has no locate image is what it already is; without the flag such a handle
+ * is PGX_ERR_UNSUPPORTED.  PGX_ERR_ARG for unknown flags. */
+pgx_status pgx_index_save_image(pgx_index *h, const char *path, uint32_t flags);
+/* Host only.  Checks, in this order: the magic (PGX_ERR_FORMAT: not an image file); version, layout id and struct sizes
+ * (PGX_ERR_UNSUPPORTED: written by another build, make it again); the header sum; every section's entry -- id, element size, length
+ * against what the constants imply, offset and length against the file size, in overflow-safe arithmetic -- (PGX_ERR_FORMAT naming the
+ * section).  Then reads every section straight into its final buffer.  Nothing is allocated by a length that has not passed these checks.
+ * Without PGX_IMAGE_VERIFY the section sums are not computed on the host: the device computes them at memory speed when a section is
+ * uploaded, before any other kernel reads it (pgx_index_to_device and the first locate / literal call return PGX_ERR_FORMAT naming the
+ * section, release that device image whole, and answer the same on the next call).  The handle answers pgx_index_image_view,
+ * pgx_index_device_view, pgx_index_info_get and pgx_index_tables as the handle it was saved from.  From an image without the locate
+ * image the locate entry points and views 8 .. 14 are PGX_ERR_UNSUPPORTED and find_mems runs without the LCE image. */
+pgx_status pgx_index_open_image(const char *path, uint32_t flags, pgx_index **out);
+/* Host only: the header and the section table of a file, after the same checks of the header (not of the sections); nothing is loaded. */
+pgx_status pgx_image_file_info(const char *path, pgx_image_info *out);
+/* The section sum of n bytes.  device >= 0: `bytes` is host memory, uploaded to that device and summed there by pgx_image_sum_kernel
+ * (16-byte loads, grid-stride, 64-bit word indices); device < 0: on host threads.  The two agree bit for bit. */
+pgx_status pgx_image_sum(int device, const void *bytes, uint64_t n, uint64_t *sum);
+const char *pgx_image_section_name(uint32_t id); /* "?" for an unknown id */
 
 /* ---- index construction (build side, run once; on the CPU, or with the suffix sorting on a device: pgx_build_index_from_text[s]_device) --- */
 /* Replaces build_rindex (src/build_rindex.cpp:13-21 -> FastLocate(std::string) src/r-index.cpp:778

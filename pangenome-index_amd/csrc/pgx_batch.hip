@@ -1395,7 +1395,7 @@ extern "C" pgx_status pgx_batch_format(pgx_batch *b, const pgx_format_params *p,
     in.positions = b->tw.positions.as<uint64_t>();
     in.n_reads = b->n_reads; in.n_mems = b->n_mems; in.n_positions = b->n_positions;
     in.first_seq = p->first_seq;
-    in.max_length = p->max_length ? p->max_length : b->h->ri.max_length ? b->h->ri.max_length : 1;
+    in.max_length = p->max_length ? p->max_length : b->h->meta.max_length ? b->h->meta.max_length : 1;
     uint64_t n_bytes = 0, n_err = 0;
     w.cur ^= 1; // (the set of the call before stays as it is)
     HostBuf &h_text = w.h_text[w.cur], &h_etext = w.h_etext[w.cur];
@@ -1532,7 +1532,7 @@ extern "C" pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t ma
     const bool sets_form = (flags & PGX_LOCATE_SEQ_SETS) != 0;
     const bool seq_ids = sets_form || (flags & PGX_LOCATE_SEQ_IDS) != 0, uniq = (flags & PGX_LOCATE_UNIQUE) != 0;
     // sequence sets: the result itself (PGX_LOCATE_SEQ_SETS), or what the sorted unique sequence ids are expanded from (routed) in place of the sort
-    const uint64_t n_seq = b->h->ri.C.size() > 1 ? b->h->ri.C[1] - b->h->ri.C[0] : 0;
+    const uint64_t n_seq = b->h->meta.n_sequences();
     const uint64_t W = (n_seq + 63) / 64;
     const bool sets_fit = W >= 1 && W <= PGX_ML_SET_WORDS_MAX;
     if (sets_form && !sets_fit)

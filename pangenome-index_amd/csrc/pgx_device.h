@@ -188,6 +188,9 @@ __global__ void pgx_side_reads_kernel(uint8_t *reads, const uint64_t *offsets, c
 __global__ void pgx_classify_reads_kernel(const uint8_t *reads, const uint64_t *offsets, uint64_t n_reads, const uint64_t *chunks, const unsigned long long *n_chunks,
                                           uint64_t cap, uint32_t *flag_words, pgx_heavy_item *list, unsigned long long *count);
 
+// ---- pgx_image_sum_kernels.hip: the section sum of an image file over bytes [0, n_bytes) of data (16-byte aligned), added to *sum; blocks of 256 threads
+__global__ void pgx_image_sum_kernel(const uint4 *data, uint64_t n_bytes, unsigned long long *sum);
+
 // ---- pgx_query_kernels.hip: seed table / first_ext builders, per-call rank / extend / count / LF (pgx_lit_count_kernel: below, with its image)
 __global__ void pgx_seed_build_kernel(PgxDevImage img, const uint4 *src, uint4 *dst, uint32_t level, uint64_t n_dst, uint64_t limit, int end_table);
 __global__ void pgx_first_ext_kernel(PgxDevImage img, uint4 *out); // out[byte] = {k, k', s, 0} of the full interval extended backward by byte; out[256 + byte]: by 0, then by byte

@@ -175,6 +175,31 @@ struct LocHostImage { // locate image (pgx_image.h), built on first use
     bool built = false;
 };
 
+// What a handle needs of RiFile / TagFile once the images exist: filled by pgx_index_open[_memory] after the parse and by
+// pgx_index_open_image from the file's meta record (include/pgx.h "image file"), so that nothing behind the build reads h->ri or h->tags.
+struct IndexMeta {
+    uint8_t sym_map[256] = {0};
+    uint64_t C[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t sigma = 0;                 // C.size()
+    uint32_t encoded = 0, hasN = 0;
+    uint32_t tags_format = 0;           // tags.format
+    uint64_t sequence_size = 0, max_length = 0;
+    uint64_t n_file_blocks = 0;
+    double ref_block_mean_bytes = 0;
+    uint64_t n_samples = 0;             // samples.size()
+    uint64_t sym_total[6] = {0, 0, 0, 0, 0, 0}; // symbols of the BWT by nuc code = bucket bounds of the first column (ensure_lce)
+    uint64_t n_sequences() const { return sigma > 1 ? C[1] - C[0] : 0; } // tot_strings, r-index.hpp:484
+};
+void fill_meta(const RiFile *ri, const TagFile *tags, IndexMeta &m);
+
+// one entry of an image file's section table (pgx_image_file.cpp); a handle opened from an image keeps them for the device-side check
+struct ImageSection {
+    uint32_t id = 0, elem_size = 0;
+    uint64_t bytes = 0, offset = 0, sum = 0;
+};
+uint64_t image_sum_host(const void *bytes, uint64_t n, unsigned threads = 0); // the section sum of include/pgx.h on host threads (0 = a few)
+uint64_t image_sum_words(const uint8_t *p, uint64_t first_word, uint64_t n_words, uint64_t n_bytes); // words [first, first + n) of a section of n_bytes
+
 void build_rank_image(const RiFile &ri, uint32_t mode, HostImage &img);
 void build_locate_image(const RiFile &ri, LocHostImage &loc);
 void build_literal_image(const RiFile &ri, LitHostImage &lit);
@@ -193,5 +218,18 @@ struct pgx_index {
     pgx::HostImage img;
     pgx::LocHostImage loc;
     pgx::LitHostImage lit;
+    pgx::IndexMeta meta;                 // the scalars of ri / tags that outlive the build
+    bool from_image = false;             // opened by pgx_index_open_image: ri and tags are empty, loc / lit are what the file held
+    std::vector<pgx::ImageSection> sections; // from_image: the file's table (the sums the device images are checked against)
     std::vector<pgx_device_image *> dev; // one per device ordinal (lazily filled)
+    const pgx::ImageSection *section(uint32_t id) const {
+        for (const auto &s : sections) if (s.id == id) return &s;
+        return nullptr;
+    }
 };
+namespace pgx {
+// the locate / literal host image of a handle, built from the .ri on first use; an image-opened handle has what its file held
+void ensure_locate_host(pgx_index *h);  // PGX_ERR_UNSUPPORTED: image saved with PGX_IMAGE_NO_LOCATE
+void ensure_literal_host(pgx_index *h); // PGX_ERR_UNSUPPORTED: image without the literal count image
+inline bool literal_count(const pgx_index *h) { return (h->mode & PGX_MODE_MASK) == PGX_MODE_COMPAT && h->meta.encoded && !h->meta.hasN; }
+} // namespace pgx

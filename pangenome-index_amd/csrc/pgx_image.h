@@ -43,6 +43,11 @@
 
 #include <stdint.h>
 
+/* Identity of everything below as an image file stores it (include/pgx.h "image file"): bumped with ANY change to a block, table or
+ * constant layout -- a field of PgxConsts / PgxLocConsts, the meaning of a bit in a block, the order of a table.  A file written under
+ * another value is refused (PGX_ERR_UNSUPPORTED) instead of being fed to kernels that would read it differently. */
+#define PGX_IMAGE_LAYOUT 1u
+
 #define PGX_BLOCK_BYTES 64
 #define PGX_BLOCK_RUNS 16
 #define PGX_RUN_LEN_BITS 12

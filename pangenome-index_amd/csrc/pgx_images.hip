@@ -1,5 +1,6 @@
 // pgx_images.hip -- the device images of an index: the rank image with its seed tables, tag runs and PAIRS blocks (device_image), and what is
 // added on first use: the locate image (locate_image), the LCE image (ensure_lce) and the literal count image (literal_image).
+#include <chrono>
 #include <memory>
 #include <mutex>
 
@@ -36,15 +37,114 @@ static ImageKnobs read_image_knobs() {
     return k;
 }
 
+static void release_locate_buffers(pgx_device_image *d) {
+    d->rstart.release(); d->rsamp.release(); d->rdir.release(); d->lpos.release(); d->lnext.release(); d->ldir.release();
+}
+static void release_literal_buffers(pgx_device_image *d) {
+    d->lit_bstart.release(); d->lit_cum.release(); d->lit_runs.release(); d->lit_roff.release(); d->lit_tabs.release();
+}
+// every device buffer of an image (the current device is the image's)
+static void release_buffers(pgx_device_image *d) {
+    d->blocks.release(); d->dir.release(); d->blow.release(); d->consts.release();
+    d->tstart.release(); d->tvals.release(); d->tdir.release(); d->tpair.release(); d->tbucket.release(); d->seed.release(); d->seed_small.release(); d->seed_end.release(); d->exc.release(); d->pairs.release(); d->first_ext.release(); d->sbase2.release(); d->pbase.release();
+    release_literal_buffers(d);
+    release_locate_buffers(d);
+    d->lce_sa.release(); d->lce_text.release(); d->lce_flags.release(); d->lce_lcp.release(); d->lce_seq_start.release();
+}
+
+// ------------------------------------------------------------------------------------------
+// The device side of the image file's integrity check (include/pgx.h "image file").  A handle opened from an image has not summed its
+// sections on the host (unless asked to): the device does, at memory speed, over the bytes it has just received and before any other
+// kernel reads them -- the seed table builder, pgx_first_ext_kernel, the tag pair and bucket kernels and ensure_lce all index these
+// buffers unchecked.  One pgx_image_sum_kernel per section on the stream of the uploads (the null stream: hipMemcpy orders them), the
+// sums side by side in one small buffer, ONE synchronising read-back at the end.  A handle opened from .ri / tags runs none of this.
+struct SectionSums {
+    const pgx_index *h;
+    DevBuf sums;
+    std::vector<uint32_t> ids;
+    // PGX_IMAGE_TIMING=1 (scripts/open_image_bench.py): HIP events around every sum kernel; their total and the bytes summed
+    bool timed = false;
+    std::vector<hipEvent_t> ev;
+    uint64_t bytes_summed = 0;
+    float ms_sums = 0;
+    explicit SectionSums(const pgx_index *h_) : h(h_) {
+        if (!h->from_image) return;
+        timed = std::getenv("PGX_IMAGE_TIMING") != nullptr;
+        sums.ensure(PGX_IMAGE_MAX_SECTIONS * 8);
+        HIPCHECK(hipMemsetAsync(sums.p, 0, PGX_IMAGE_MAX_SECTIONS * 8, nullptr));
+    }
+    ~SectionSums() {
+        sums.release();
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    void mark() {
+        if (!timed) return;
+        hipEvent_t e = nullptr;
+        HIPCHECK(hipEventCreate(&e));
+        ev.push_back(e);
+        HIPCHECK(hipEventRecord(e, nullptr));
+    }
+    SectionSums(const SectionSums &) = delete;
+    SectionSums &operator=(const SectionSums &) = delete;
+    // the upload of section `id` (bytes of it, as the file's table has them) sits in b: launch its sum
+    void add(uint32_t id, const DevBuf &b) {
+        if (!h->from_image) return;
+        const ImageSection *sec = h->section(id);
+        if (!sec) throw Error(PGX_ERR_FORMAT, std::string("image file: section ") + pgx_image_section_name(id) + " is not in the file's table");
+        if (ids.size() >= PGX_IMAGE_MAX_SECTIONS || sec->bytes > b.cap) throw Error(PGX_ERR_ARG, "image check: section does not fit its device buffer");
+        mark();
+        launch_image_sum(b.p, sec->bytes, sums.as<unsigned long long>() + ids.size(), nullptr);
+        mark();
+        bytes_summed += sec->bytes;
+        ids.push_back(id);
+    }
+    // one synchronisation; PGX_ERR_FORMAT naming the first section whose bytes on the device are not what was saved
+    void finish() {
+        if (!h->from_image || ids.empty()) return;
+        std::vector<uint64_t> got(ids.size());
+        HIPCHECK(hipMemcpy(got.data(), sums.p, ids.size() * 8, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i + 1 < ev.size(); i += 2) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) ms_sums += ms;
+        }
+        for (size_t i = 0; i < ids.size(); i++)
+            if (got[i] != h->section(ids[i])->sum)
+                throw Error(PGX_ERR_FORMAT, std::string("image file: section ") + pgx_image_section_name(ids[i]) +
+                                                ": the sum of its bytes, computed on the device, does not match the table (damaged file); nothing has read it");
+    }
+};
+
+void launch_image_sum(const void *data, uint64_t n_bytes, unsigned long long *sum, hipStream_t s) {
+    const uint64_t units = n_bytes >> 4;
+    // four 16-byte loads per thread and trip; at most eight blocks per compute unit of the largest part
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((units + 1023) / 1024, 2048));
+    hipLaunchKernelGGL(pgx_image_sum_kernel, dim3(grid), dim3(256), 0, s, static_cast<const uint4 *>(data), n_bytes, sum);
+    HIPCHECK(hipGetLastError());
+}
+
+extern "C" pgx_status pgx_image_sum(int device, const void *bytes, uint64_t n, uint64_t *sum) {
+    PGX_GUARD_BEGIN
+    if (!sum || (!bytes && n)) throw Error(PGX_ERR_ARG, "pgx_image_sum: null argument");
+    if (device < 0) { *sum = image_sum_host(bytes, n); return PGX_OK; }
+    use_device(device);
+    DevBuf buf, out;
+    try {
+        buf.ensure(n ? n : 16); out.ensure(8);
+        if (n) HIPCHECK(hipMemcpy(buf.p, bytes, n, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemsetAsync(out.p, 0, 8, nullptr));
+        launch_image_sum(buf.p, n, out.as<unsigned long long>(), nullptr);
+        HIPCHECK(hipMemcpy(sum, out.p, 8, hipMemcpyDeviceToHost));
+    } catch (...) { buf.release(); out.release(); throw; }
+    buf.release(); out.release();
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
 void pgx_release_device_images(pgx_index *h) {
     for (auto *d : h->dev) {
         if (!d) continue;
         if (hipSetDevice(d->device) == hipSuccess) {
-            d->blocks.release(); d->dir.release(); d->blow.release(); d->consts.release();
-            d->tstart.release(); d->tvals.release(); d->tdir.release(); d->tpair.release(); d->tbucket.release(); d->seed.release(); d->seed_small.release(); d->seed_end.release(); d->exc.release(); d->pairs.release(); d->first_ext.release(); d->sbase2.release(); d->pbase.release();
-            d->lit_bstart.release(); d->lit_cum.release(); d->lit_runs.release(); d->lit_roff.release(); d->lit_tabs.release();
-            d->rstart.release(); d->rsamp.release(); d->rdir.release(); d->lpos.release(); d->lnext.release(); d->ldir.release();
-            d->lce_sa.release(); d->lce_text.release(); d->lce_flags.release(); d->lce_lcp.release(); d->lce_seq_start.release();
+            release_buffers(d);
         }
         delete d;
     }
@@ -109,6 +209,7 @@ static void build_seed_table(pgx_device_image *d, const ImageKnobs &knobs) {
 
 // one device image per (index, device), created on first use; concurrent first calls from several host threads are serialised
 static std::mutex g_image_mutex;
+static void fill_device_image(pgx_index *h, pgx_device_image *d);
 
 pgx_device_image *device_image(pgx_index *h, int device) {
     use_device(device);
@@ -117,16 +218,50 @@ pgx_device_image *device_image(pgx_index *h, int device) {
     if (h->dev[device]) return h->dev[device];
     std::unique_ptr<pgx_device_image> d(new pgx_device_image());
     d->device = device;
+    try {
+        fill_device_image(h, d.get());
+    } catch (...) { // no half-built image stays behind (an image file whose section sums do not match ends here: the next call answers the same)
+        (void)hipGetLastError();
+        release_buffers(d.get());
+        throw;
+    }
+    h->dev[device] = d.release();
+    return h->dev[device];
+}
+
+static void fill_device_image(pgx_index *h, pgx_device_image *d) {
     const HostImage &m = h->img;
     const ImageKnobs knobs = read_image_knobs();
-    upload(d->blocks, m.blocks.data(), m.blocks.size());
-    upload(d->dir, m.dir.data(), m.dir.size() * 8);
-    upload(d->blow, m.blow.data(), m.blow.size() * 2);
-    upload(d->exc, m.exc.data(), m.exc.size() * 4);
-    upload(d->consts, &m.consts, sizeof(PgxConsts));
-    upload(d->tstart, m.tstart.data(), m.tstart.size() * 8);
-    upload(d->tvals, m.tvals.data(), m.tvals.size() * 8);
-    upload(d->tdir, m.tdir.data(), m.tdir.size() * 4);
+    const bool with_pairs = m.consts.has_pairs && !m.pairs.empty() && h->has_rank; // the two-step image next to dense2 (pgx_image.h)
+    const auto t_begin = std::chrono::steady_clock::now();
+    SectionSums check(h);
+    upload(d->blocks, m.blocks.data(), m.blocks.size());       check.add(PGX_IMAGE_SEC_BLOCKS, d->blocks);
+    upload(d->dir, m.dir.data(), m.dir.size() * 8);            check.add(PGX_IMAGE_SEC_DIR, d->dir);
+    upload(d->blow, m.blow.data(), m.blow.size() * 2);         check.add(PGX_IMAGE_SEC_BLOW, d->blow);
+    upload(d->exc, m.exc.data(), m.exc.size() * 4);            check.add(PGX_IMAGE_SEC_EXC, d->exc);
+    upload(d->consts, &m.consts, sizeof(PgxConsts));           check.add(PGX_IMAGE_SEC_CONSTS, d->consts);
+    upload(d->tstart, m.tstart.data(), m.tstart.size() * 8);   check.add(PGX_IMAGE_SEC_TSTART, d->tstart);
+    upload(d->tvals, m.tvals.data(), m.tvals.size() * 8);      check.add(PGX_IMAGE_SEC_TVALS, d->tvals);
+    upload(d->tdir, m.tdir.data(), m.tdir.size() * 4);         check.add(PGX_IMAGE_SEC_TDIR, d->tdir);
+    upload(d->sbase2, m.sbase2.data(), m.sbase2.size() * 8);   check.add(PGX_IMAGE_SEC_SBASE2, d->sbase2);
+    if (with_pairs) {
+        upload(d->pairs, m.pairs.data(), m.pairs.size());      check.add(PGX_IMAGE_SEC_PAIRS, d->pairs);
+        upload(d->pbase, m.pbase.data(), m.pbase.size() * 8);  check.add(PGX_IMAGE_SEC_PBASE, d->pbase);
+    }
+    check.finish(); // (image-opened handles: every section is what was saved, or PGX_ERR_FORMAT names the one that is not -- before the kernels below)
+    const bool timing = std::getenv("PGX_IMAGE_TIMING") != nullptr; // one line on stderr: the uploads (with the sums of an image-opened handle), the device-side builds
+    const auto t_uploaded = std::chrono::steady_clock::now();
+    struct BuildTime { // (printed when the image is complete)
+        bool on; std::chrono::steady_clock::time_point t0, t1; float ms_sums; uint64_t bytes; bool image;
+        ~BuildTime() {
+            if (!on) return;
+            (void)hipDeviceSynchronize();
+            const auto t2 = std::chrono::steady_clock::now();
+            std::fprintf(stderr, "[pgx] to_device (%s handle): uploads%s %.3f ms wall; sum kernels %.3f ms by HIP events over %llu bytes; device-side builds %.3f ms wall\n",
+                         image ? "image" : "file", image ? " + sums" : "", std::chrono::duration<double, std::milli>(t1 - t0).count(), (double)ms_sums,
+                         (unsigned long long)bytes, std::chrono::duration<double, std::milli>(t2 - t1).count());
+        }
+    } build_time{timing, t_begin, t_uploaded, check.ms_sums, check.bytes_summed, h->from_image};
     PgxDevImage &g = d->img;
     g.blocks = d->blocks.as<uint4>();
     g.dir = d->dir.as<uint64_t>();
@@ -172,7 +307,6 @@ pgx_device_image *device_image(pgx_index *h, int device) {
     g.dense = m.consts.image_kind; // PGX_IMAGE_RL / _DENSE / _DENSE2
     g.wide = m.consts.wide;
     if (g.dense == PGX_IMAGE_DENSE2 && g.wide) g.dense = 3; // dense2 blocks with delta counts: the 64-bit kernels (pgx_image.h "WIDE")
-    upload(d->sbase2, m.sbase2.data(), m.sbase2.size() * 8);
     g.sbase2 = d->sbase2.as<uint64_t>();
     g.d2_sb_shift = m.consts.d2_sb_shift; g.n_sb2 = m.consts.n_sb2;
     g.pbase = nullptr; g.pairs_sb_shift = 0; g.n_sbp = 0; g.pairs_stride = 0;
@@ -188,10 +322,8 @@ pgx_device_image *device_image(pgx_index *h, int device) {
     g.seed_main = g.seed_small = nullptr;
     g.pairs = nullptr; g.first_ext = nullptr; g.pair_runs = 0;
     g.lce_sa = nullptr; g.lce_text = nullptr; g.lce_flags = nullptr; g.lce_lcp = nullptr; g.lce_max = 0; g.refill_min = 1;
-    if (g.dense && h->has_rank) build_seed_table(d.get(), knobs);
-    if (m.consts.has_pairs && !m.pairs.empty() && h->has_rank) { // the two-step image next to dense2 (pgx_image.h)
-        upload(d->pairs, m.pairs.data(), m.pairs.size());
-        upload(d->pbase, m.pbase.data(), m.pbase.size() * 8);
+    if (g.dense && h->has_rank) build_seed_table(d, knobs);
+    if (with_pairs) {
         g.pbase = d->pbase.as<uint64_t>();
         g.pairs_sb_shift = m.consts.pairs_sb_shift; g.n_sbp = m.consts.n_sbp;
         g.pairs_stride = m.consts.pairs_stride;
@@ -203,8 +335,6 @@ pgx_device_image *device_image(pgx_index *h, int device) {
         g.first_ext = d->first_ext.as<uint4>();
         g.pair_runs = m.consts.pair_runs;
     }
-    h->dev[device] = d.release();
-    return h->dev[device];
 }
 
 extern "C" pgx_status pgx_index_to_device(pgx_index *h, int device) {
@@ -254,14 +384,23 @@ pgx_device_image *locate_image(pgx_index *h, int device) {
     pgx_device_image *d = device_image(h, device);
     std::lock_guard<std::mutex> lock(g_image_mutex);
     if (d->has_loc) return d;
-    build_locate_image(h->ri, h->loc);
+    ensure_locate_host(h);
     const LocHostImage &m = h->loc;
-    upload(d->rstart, m.rstart.data(), m.rstart.size() * 8);
-    upload(d->rsamp, m.rsamp.data(), m.rsamp.size() * 8);
-    upload(d->rdir, m.rdir.data(), m.rdir.size() * 4);
-    upload(d->lpos, m.lpos.data(), m.lpos.size() * 8);
-    upload(d->lnext, m.lnext.data(), m.lnext.size() * 8);
-    upload(d->ldir, m.ldir.data(), m.ldir.size() * 4);
+    try {
+        SectionSums check(h);
+        upload(d->rstart, m.rstart.data(), m.rstart.size() * 8); check.add(PGX_IMAGE_SEC_RSTART, d->rstart);
+        upload(d->rsamp, m.rsamp.data(), m.rsamp.size() * 8);    check.add(PGX_IMAGE_SEC_RSAMP, d->rsamp);
+        upload(d->rdir, m.rdir.data(), m.rdir.size() * 4);       check.add(PGX_IMAGE_SEC_RDIR, d->rdir);
+        upload(d->lpos, m.lpos.data(), m.lpos.size() * 8);       check.add(PGX_IMAGE_SEC_LPOS, d->lpos);
+        upload(d->lnext, m.lnext.data(), m.lnext.size() * 8);    check.add(PGX_IMAGE_SEC_LNEXT, d->lnext);
+        upload(d->ldir, m.ldir.data(), m.ldir.size() * 4);       check.add(PGX_IMAGE_SEC_LDIR, d->ldir);
+        if (h->from_image) { // the constants travel as kernel arguments: summed where they are
+            const ImageSection *sec = h->section(PGX_IMAGE_SEC_LOC_CONSTS);
+            if (!sec || image_sum_host(&m.consts, sizeof(PgxLocConsts)) != sec->sum)
+                throw Error(PGX_ERR_FORMAT, "image file: section loc_consts: the sum of its bytes does not match the table (damaged file)");
+        }
+        check.finish();
+    } catch (...) { (void)hipGetLastError(); release_locate_buffers(d); throw; } // (has_loc stays false: the next call answers the same)
     PgxLocImage &g = d->loc;
     g.rstart = d->rstart.as<uint64_t>(); g.rsamp = d->rsamp.as<uint64_t>(); g.rdir = d->rdir.as<uint32_t>();
     g.lpos = d->lpos.as<uint64_t>(); g.lnext = d->lnext.as<uint64_t>(); g.ldir = d->ldir.as<uint32_t>();
@@ -282,10 +421,10 @@ void ensure_lce(pgx_index *h, pgx_device_image *d) {
     d->lce_state = 2;
     const ImageKnobs knobs = read_image_knobs();
     const uint64_t n = d->img.n;
-    if (!knobs.lce || !d->img.pairs || d->img.wide || n < 4096 || n >= (1ull << 32) - (1ull << 20) || h->ri.max_length == 0) return;
-    uint64_t tot[6] = {0, 0, 0, 0, 0, 0}; // symbol counts of the BWT = bucket bounds of the first column
-    for (const auto &blk : h->ri.blocks)
-        for (const auto &ru : blk.runs) if (ru.first < 6) tot[ru.first] += ru.second;
+    if (!knobs.lce || !d->img.pairs || d->img.wide || n < 4096 || n >= (1ull << 32) - (1ull << 20) || h->meta.max_length == 0) return;
+    if (h->from_image && !h->loc.built) return; // an image saved without the locate image: the search runs on the PAIRS image alone
+    uint64_t tot[6]; // symbol counts of the BWT = bucket bounds of the first column
+    for (int i = 0; i < 6; i++) tot[i] = h->meta.sym_total[i];
     const uint64_t n_seq = tot[0];
     if (tot[0] + tot[1] + tot[2] + tot[3] + tot[4] + tot[5] != n || n_seq == 0 || n_seq > (1ull << 24)) return;
     {
@@ -302,7 +441,7 @@ void ensure_lce(pgx_index *h, pgx_device_image *d) {
         uint64_t nv = 0;
         locate_core(h, dl, &first, &last, 1, 0, off, vals, nv);
         if (nv != n) throw Error(PGX_ERR_UNSUPPORTED, "suffix array incomplete");
-        const uint64_t ml = h->ri.max_length;
+        const uint64_t ml = h->meta.max_length;
         seq_len.ensure(n_seq * 8); seq_start.ensure((n_seq + 1) * 8); bad.ensure(16);
         HIPCHECK(hipMemset(seq_len.p, 0, n_seq * 8));
         HIPCHECK(hipMemset(bad.p, 0, 16));
@@ -372,20 +511,27 @@ pgx_device_image *literal_image(pgx_index *h, int device) {
     pgx_device_image *d = device_image(h, device);
     std::lock_guard<std::mutex> lock(g_image_mutex);
     if (d->has_lit) return d;
-    build_literal_image(h->ri, h->lit);
+    ensure_literal_host(h);
     LitHostImage &m = h->lit;
-    upload(d->lit_bstart, m.bstart.data(), m.bstart.size() * 8);
-    upload(d->lit_cum, m.cum.data(), m.cum.size() * 8);
-    upload(d->lit_runs, m.runs.data(), m.runs.size() * 8);
-    upload(d->lit_roff, m.roff.data(), m.roff.size() * 4);
-    d->lit_tabs.ensure(512 * 4);
-    HIPCHECK(hipMemcpy(d->lit_tabs.p, m.code_of, 1024, hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(d->lit_tabs.as<uint32_t>() + 256, m.cslot_of, 1024, hipMemcpyHostToDevice));
+    try {
+        SectionSums check(h);
+        upload(d->lit_bstart, m.bstart.data(), m.bstart.size() * 8); check.add(PGX_IMAGE_SEC_LIT_BSTART, d->lit_bstart);
+        upload(d->lit_cum, m.cum.data(), m.cum.size() * 8);          check.add(PGX_IMAGE_SEC_LIT_CUM, d->lit_cum);
+        upload(d->lit_runs, m.runs.data(), m.runs.size() * 8);       check.add(PGX_IMAGE_SEC_LIT_RUNS, d->lit_runs);
+        upload(d->lit_roff, m.roff.data(), m.roff.size() * 4);       check.add(PGX_IMAGE_SEC_LIT_ROFF, d->lit_roff);
+        // the two byte tables and C in the order of the file's lit_tabs section (the kernels read the tables; C travels as an argument)
+        d->lit_tabs.ensure(512 * 4 + 64);
+        HIPCHECK(hipMemcpy(d->lit_tabs.p, m.code_of, 1024, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d->lit_tabs.as<uint32_t>() + 256, m.cslot_of, 1024, hipMemcpyHostToDevice));
+        HIPCHECK(hipMemcpy(d->lit_tabs.as<uint32_t>() + 512, m.C, 64, hipMemcpyHostToDevice));
+        check.add(PGX_IMAGE_SEC_LIT_TABS, d->lit_tabs);
+        check.finish();
+    } catch (...) { (void)hipGetLastError(); release_literal_buffers(d); throw; } // (has_lit stays false)
     PgxLitImage &g = d->lit;
     g.bstart = d->lit_bstart.as<uint64_t>(); g.cum = d->lit_cum.as<uint64_t>(); g.runs = d->lit_runs.as<uint64_t>();
     g.roff = d->lit_roff.as<uint32_t>(); g.code_of = d->lit_tabs.as<uint32_t>(); g.cslot_of = d->lit_tabs.as<uint32_t>() + 256;
     for (int i = 0; i < 8; i++) g.C[i] = m.C[i];
-    g.n = h->ri.sequence_size; g.n_blocks = m.bstart.size();
+    g.n = h->meta.sequence_size; g.n_blocks = m.bstart.size();
     d->has_lit = true;
     return d;
 }

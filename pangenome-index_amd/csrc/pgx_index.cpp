@@ -983,6 +983,35 @@ void build_locate_image(const RiFile &ri, LocHostImage &loc) {
     loc.built = true;
 }
 
+void fill_meta(const RiFile *ri, const TagFile *tags, IndexMeta &m) {
+    if (ri) {
+        std::memcpy(m.sym_map, ri->sym_map, 256);
+        m.sigma = (uint32_t)ri->C.size();
+        for (int i = 0; i < 8; i++) m.C[i] = i < (int)ri->C.size() ? ri->C[i] : 0;
+        m.encoded = ri->encoded; m.hasN = ri->hasN;
+        m.sequence_size = ri->sequence_size; m.max_length = ri->max_length;
+        m.n_file_blocks = ri->n_file_blocks;
+        m.ref_block_mean_bytes = ri->ref_block_mean_bytes;
+        m.n_samples = ri->samples.size();
+        for (int i = 0; i < 6; i++) m.sym_total[i] = 0;
+        for (const auto &blk : ri->blocks)
+            for (const auto &ru : blk.runs) if (ru.first < 6) m.sym_total[ru.first] += ru.second;
+    }
+    if (tags) m.tags_format = tags->format;
+}
+
+void ensure_locate_host(pgx_index *h) {
+    if (h->loc.built) return;
+    if (h->from_image) throw Error(PGX_ERR_UNSUPPORTED, "locate: the image file was saved without the locate image (PGX_IMAGE_NO_LOCATE); save it again without the flag");
+    build_locate_image(h->ri, h->loc);
+}
+
+void ensure_literal_host(pgx_index *h) {
+    if (h->lit.built) return;
+    if (h->from_image) throw Error(PGX_ERR_UNSUPPORTED, "the image file holds no literal count image (it is stored for COMPAT handles of encoded indexes without N)");
+    build_literal_image(h->ri, h->lit);
+}
+
 } // namespace pgx
 
 // ------------------------------------------------------------------------------------------
@@ -1018,6 +1047,7 @@ static pgx_index *open_impl(const uint8_t *ri, uint64_t ri_n, const uint8_t *tag
         build_tag_image(h->tags, h->img);
         h->has_tags = true;
     }
+    fill_meta(ri ? &h->ri : nullptr, tags ? &h->tags : nullptr, h->meta);
     return h.release();
 }
 
@@ -1050,8 +1080,8 @@ extern "C" pgx_status pgx_index_open_memory(const void *ri_bytes, uint64_t ri_n,
 extern "C" pgx_status pgx_index_tables(const pgx_index *h, uint8_t sym_map[256], uint64_t C[8], uint8_t complement[256]) {
     PGX_GUARD_BEGIN
     if (!h || !h->has_rank) throw Error(PGX_ERR_ARG, "pgx_index_tables: no r-index loaded");
-    if (sym_map) std::memcpy(sym_map, h->ri.sym_map, 256);
-    if (C) for (int i = 0; i < 8; i++) C[i] = i < (int)h->ri.C.size() ? h->ri.C[i] : 0;
+    if (sym_map) std::memcpy(sym_map, h->meta.sym_map, 256);
+    if (C) for (int i = 0; i < 8; i++) C[i] = h->meta.C[i];
     if (complement) complement_table(complement);
     return PGX_OK;
     PGX_GUARD_END
@@ -1070,17 +1100,17 @@ extern "C" pgx_status pgx_index_info_get(const pgx_index *h, pgx_index_info *inf
     const PgxConsts &c = h->img.consts;
     info->bwt_size = c.n;
     info->sigma = c.sigma;
-    info->n_sequences = h->ri.C.size() > 1 ? h->ri.C[1] - h->ri.C[0] : 0; // tot_strings, r-index.hpp:484
-    info->n_ref_blocks = h->ri.n_file_blocks;
+    info->n_sequences = h->meta.n_sequences(); // tot_strings, r-index.hpp:484
+    info->n_ref_blocks = h->meta.n_file_blocks;
     info->n_runs = h->img.n_runs;
     info->n_dev_blocks = c.n_blocks;
     info->dir_entries = c.dir_entries;
     info->dir_shift = c.dir_shift;
-    info->is_encoded = h->ri.encoded;
-    info->has_N = h->ri.hasN;
+    info->is_encoded = h->meta.encoded;
+    info->has_N = h->meta.hasN;
     info->mode = h->mode;
     info->has_tags = h->has_tags;
-    info->tag_format = h->tags.format;
+    info->tag_format = h->meta.tags_format;
     info->n_tag_runs = c.n_tag_runs;
     info->tag_dir_entries = c.tag_dir_entries;
     info->tag_dir_shift = c.tag_dir_shift;
@@ -1089,9 +1119,9 @@ extern "C" pgx_status pgx_index_info_get(const pgx_index *h, pgx_index_info *inf
     info->tag_image_bytes = h->img.tstart.size() * 8 + h->img.tvals.size() * 8 + h->img.tdir.size() * 4;
     info->image_in_lds = h->img.consts.image_kind == PGX_IMAGE_DENSE ? (uint64_t)h->img.consts.n_blocks * 80 + 16 <= 48 * 1024
                                                                      : (h->img.consts.image_kind == PGX_IMAGE_RL && info->image_bytes <= 48 * 1024);
-    info->ref_block_mean_bytes = h->ri.ref_block_mean_bytes;
-    info->max_length = h->ri.max_length;
-    info->n_samples = h->ri.samples.size();
+    info->ref_block_mean_bytes = h->meta.ref_block_mean_bytes;
+    info->max_length = h->meta.max_length;
+    info->n_samples = h->meta.n_samples;
     info->image_kind = c.image_kind;
     info->image_pairs = c.has_pairs;
     info->image_wide = c.wide;
@@ -1106,7 +1136,7 @@ extern "C" pgx_status pgx_index_image_view(const pgx_index *h, int which, const 
     const HostImage &m = h->img;
     if (which >= 8 && which <= 14) { // locate image (built on first use)
         if (!h->has_rank) throw Error(PGX_ERR_ARG, "pgx_index_image_view: no r-index loaded");
-        build_locate_image(h->ri, const_cast<pgx_index *>(h)->loc);
+        ensure_locate_host(const_cast<pgx_index *>(h));
     }
     const LocHostImage &l = h->loc;
     switch (which) {
@@ -1133,9 +1163,9 @@ extern "C" pgx_status pgx_index_image_view(const pgx_index *h, int which, const 
     case 22: *ptr = m.sbase2.data(); *bytes = m.sbase2.size() * 8; break;
     case 23: *ptr = m.pbase.data(); *bytes = m.pbase.size() * 8; break;
     case 16: case 17: case 18: case 19: {
-        if (!(h->ri.encoded && !h->ri.hasN)) throw Error(PGX_ERR_ARG, "pgx_index_image_view: the literal count image exists for encoded indexes without N only");
+        if (!(h->meta.encoded && !h->meta.hasN)) throw Error(PGX_ERR_ARG, "pgx_index_image_view: the literal count image exists for encoded indexes without N only");
         pgx::LitHostImage &l = const_cast<pgx_index *>(h)->lit;
-        build_literal_image(h->ri, l);
+        ensure_literal_host(const_cast<pgx_index *>(h));
         if (which == 16) { *ptr = l.bstart.data(); *bytes = l.bstart.size() * 8; }
         else if (which == 17) { *ptr = l.cum.data(); *bytes = l.cum.size() * 8; }
         else if (which == 18) { *ptr = l.runs.data(); *bytes = l.runs.size() * 8; }

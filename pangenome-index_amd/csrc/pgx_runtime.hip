@@ -298,7 +298,7 @@ void locate_core(pgx_index *h, pgx_device_image *d, const uint64_t *first, const
 }
 
 void locate_check_supported(const pgx_index *h, const char *who) {
-    if (h->mode == PGX_MODE_COMPAT && h->ri.encoded && !h->ri.hasN)
+    if (h->mode == PGX_MODE_COMPAT && h->meta.encoded && !h->meta.hasN)
         throw Error(PGX_ERR_UNSUPPORTED, std::string(who) + ": the reference's encoded run scan skips six header varints where five were "
                                          "written on an index without N (src/r-index.cpp:83-88); open the index in PGX_MODE_STRICT");
 }
@@ -412,9 +412,8 @@ extern "C" pgx_status pgx_extend_batch(pgx_index *h, int device, const pgx_biint
     PGX_GUARD_END
 }
 
-// COMPAT count_encoded / LF_encoded on an encoded index without N go through the literal image (pgx_images.hip literal_image)
-static bool literal_count(const pgx_index *h) { return (h->mode & PGX_MODE_MASK) == PGX_MODE_COMPAT && h->ri.encoded && !h->ri.hasN; }
-
+// COMPAT count_encoded / LF_encoded on an encoded index without N go through the literal image (pgx_images.hip literal_image;
+// pgx_host.hpp literal_count says when)
 extern "C" pgx_status pgx_count_batch(pgx_index *h, int device, const uint8_t *reads, const uint64_t *offsets, uint64_t n_reads,
                                       pgx_range *out) {
     PGX_GUARD_BEGIN

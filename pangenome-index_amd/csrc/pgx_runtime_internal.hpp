@@ -77,6 +77,8 @@ pgx_device_image *device_image(pgx_index *h, int device);
 pgx_device_image *locate_image(pgx_index *h, int device);
 pgx_device_image *literal_image(pgx_index *h, int device);
 void ensure_lce(pgx_index *h, pgx_device_image *d);
+// the section sum of an image file over n_bytes of device memory (16-byte aligned), added to *sum on stream s (pgx_image_sum_kernels.hip)
+void launch_image_sum(const void *data, uint64_t n_bytes, unsigned long long *sum, hipStream_t s);
 
 // pgx_runtime.hip: the r-index walk + optional segmented sort-unique behind pgx_locate_batch; values stay on the device in vals_out
 void locate_core(pgx_index *h, pgx_device_image *d, const uint64_t *first, const uint64_t *last, uint64_t n, uint32_t flags, std::vector<uint64_t> &h_off,

@@ -39,6 +39,21 @@ class IndexInfo(C.Structure):
     ]
 
 
+IMAGE_NO_LOCATE = 1  # pgx_index_save_image
+IMAGE_VERIFY = 1     # pgx_index_open_image
+IMAGE_MAX_SECTIONS = 64
+
+
+class ImageSectionInfo(C.Structure):  # pgx_image_section_info
+    _fields_ = [("id", u32), ("elem_size", u32), ("bytes", u64), ("offset", u64), ("sum", u64), ("name", C.c_char * 16)]
+
+
+class ImageFileInfo(C.Structure):  # pgx_image_file_info
+    _fields_ = [("version", u32), ("layout", u32), ("consts_bytes", u32), ("loc_consts_bytes", u32), ("mode", u32), ("has_rank", u32),
+                ("has_tags", u32), ("n_sections", u32), ("meta_bytes", u32), ("flags", u32), ("header_sum", u64), ("file_bytes", u64),
+                ("sections", ImageSectionInfo * IMAGE_MAX_SECTIONS)]
+
+
 class Result(C.Structure):
     _fields_ = [
         ("n_reads", u64), ("n_mems", u64), ("mem_offsets", C.POINTER(u64)), ("mems", p),
@@ -157,6 +172,13 @@ def lib():
     L.pgx_index_close.restype = None
     L.pgx_index_to_device.argtypes = [p, C.c_int]
     L.pgx_index_image_view.argtypes = [p, C.c_int, C.POINTER(p), C.POINTER(u64)]
+    L.pgx_index_tables.argtypes = [p, p, p, p]
+    L.pgx_index_save_image.argtypes = [p, C.c_char_p, u32]
+    L.pgx_index_open_image.argtypes = [C.c_char_p, u32, C.POINTER(p)]
+    L.pgx_image_file_info.argtypes = [C.c_char_p, C.POINTER(ImageFileInfo)]
+    L.pgx_image_sum.argtypes = [C.c_int, p, u64, C.POINTER(u64)]
+    L.pgx_image_section_name.argtypes = [u32]
+    L.pgx_image_section_name.restype = C.c_char_p
     L.pgx_build_rindex.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
     L.pgx_build_rlbwt.argtypes = [C.c_char_p, C.c_char_p]
     L.pgx_build_index_from_text.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
@@ -416,6 +438,24 @@ def gbz_extract(gbz_path, out_text_path, both=True):
     _check(lib().pgx_gbz_extract(gbz_path.encode(), out_text_path.encode(), 0 if both else BUILD_TAGS_FORWARD_ONLY))
 
 
+def image_file_info(path):
+    """header and section table of an image file (nothing is loaded): dict of the header fields + "sections", a list of dicts"""
+    fi = ImageFileInfo()
+    _check(lib().pgx_image_file_info(path.encode(), C.byref(fi)))
+    out = {k: getattr(fi, k) for k, _ in ImageFileInfo._fields_ if k != "sections"}
+    out["sections"] = [dict(id=s.id, elem_size=s.elem_size, bytes=s.bytes, offset=s.offset, sum=s.sum, name=s.name.decode())
+                       for s in fi.sections[:fi.n_sections]]
+    return out
+
+
+def image_sum(data, device=-1):
+    """the section sum of an image file over `data` (bytes or a numpy array); device < 0: on host threads, else on that device"""
+    a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    out = u64(0)
+    _check(lib().pgx_image_sum(device, C.c_void_p(a.ctypes.data) if a.size else None, a.size, C.byref(out)))
+    return out.value
+
+
 class Index:
     """FastLocate + TagArray behind the C ABI."""
 
@@ -424,6 +464,24 @@ class Index:
         self.h = p()
         _check(self.L.pgx_index_open(ri_path.encode(), tags_path.encode() if tags_path else None, tags_format, mode,
                                      C.byref(self.h)))
+
+    @classmethod
+    def open_image(cls, path, verify=False):
+        """a handle from an image file (save_image, the pgx_image CLI): no .ri, no tag file, nothing parsed or built on the host"""
+        self = cls.__new__(cls)
+        self.L = lib()
+        self.h = p()
+        _check(self.L.pgx_index_open_image(path.encode(), IMAGE_VERIFY if verify else 0, C.byref(self.h)))
+        return self
+
+    def save_image(self, path, no_locate=False):
+        _check(self.L.pgx_index_save_image(self.h, path.encode(), IMAGE_NO_LOCATE if no_locate else 0))
+
+    def tables(self):
+        """(sym_map[256], C[8], complement[256]) of pgx_index_tables"""
+        sm, cc, co = np.zeros(256, np.uint8), np.zeros(8, np.uint64), np.zeros(256, np.uint8)
+        _check(self.L.pgx_index_tables(self.h, sm.ctypes.data, cc.ctypes.data, co.ctypes.data))
+        return sm, cc, co
 
     def close(self):
         if getattr(self, "h", None):

@@ -1,6 +1,7 @@
 // find_mems -- drop-in for the reference CLI (src/find_mems.cpp:13-147) on MI355X.
 //
 //   find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ> [options after the 5 positionals]
+//   find_mems <index.pgi> - <reads.txt> <min_mem_length> <min_occ> [...]      (an image file made by pgx_image: nothing is parsed or built on the host)
 //
 // stdout grammar is the reference's, byte for byte (find_mems.cpp:115-118,138,144-145 and
 // tag_arrays.cpp:885-889); reads are processed in device batches but printed in file order.
@@ -49,6 +50,30 @@
 #include <unistd.h>
 
 #include "../../include/pgx.h"
+
+// An image file (pgx_index_save_image, the pgx_image CLI) in the place of the r-index: the first positional starts with the image magic.  The tags
+// positional must then be "-" (the image holds the tag runs), --mode may only repeat the image's, --tags-format has nothing to say.
+static bool is_image_file(const char *path) {
+    char m[8] = {0};
+    std::ifstream f(path, std::ios::binary);
+    return f && f.read(m, 8) && std::memcmp(m, PGX_IMAGE_MAGIC, 8) == 0;
+}
+// 0, or 1 with a message on stderr
+static int open_image_index(const char *image_path, const char *tags_arg, bool mode_given, uint32_t mode, pgx_index **h) {
+    if (std::string(tags_arg) != "-") {
+        std::cerr << image_path << " is an image file and holds its tag runs: the tags argument must be \"-\", not " << tags_arg << std::endl;
+        return 1;
+    }
+    pgx_image_info fi;
+    if (pgx_image_file_info(image_path, &fi) != PGX_OK) { std::cerr << pgx_last_error() << std::endl; return 1; }
+    if (mode_given && fi.mode != mode) {
+        std::cerr << "--mode " << (mode == PGX_MODE_STRICT ? "strict" : "compat") << ": the image file was made in " << (fi.mode == PGX_MODE_STRICT ? "strict" : "compat")
+                  << " mode (make another with pgx_image --mode)" << std::endl;
+        return 1;
+    }
+    if (pgx_index_open_image(image_path, 0, h) != PGX_OK) { std::cerr << pgx_last_error() << std::endl; return 1; }
+    return 0;
+}
 
 // decimal text of v at p; returns the end.  Two digits per division.
 static inline char *put_u64(char *p, uint64_t v) {
@@ -222,7 +247,7 @@ int main(int argc, char **argv) {
     uint32_t mode = PGX_MODE_COMPAT, tfmt = PGX_TAGS_AUTO;
     size_t batch_reads = 1u << 18; // (reads per batch.  The device alone would like 2^20 -- fresh batches 177 M reads/s at 2^18, 278 M at 2^20, profiles/r04_batch_size_sweep.txt --, but this program is bound by its own host stages: 16 M reads take 0.5-0.7 s with 2^18 and 2.7-2.9 s with 2^20, pinned buffers of 150 MB per job and the formatting of the first and last batch: profiles/r04_cli_e2e.txt)
     unsigned streams = 3;
-    bool quiet = false, device_parse = false;
+    bool quiet = false, device_parse = false, mode_given = false;
     std::string reads_format = "lines";
     int locate_mode = LOCATE_NONE;
     uint64_t locate_max = 0;
@@ -243,7 +268,7 @@ int main(int argc, char **argv) {
             if (devices.empty()) { std::cerr << "--devices: empty list" << std::endl; return EXIT_FAILURE; }
         }
         else if (a == "--streams") streams = (unsigned)std::max(1, std::stoi(next()));
-        else if (a == "--mode") mode = next() == "strict" ? PGX_MODE_STRICT : PGX_MODE_COMPAT;
+        else if (a == "--mode") { mode = next() == "strict" ? PGX_MODE_STRICT : PGX_MODE_COMPAT; mode_given = true; }
         else if (a == "--batch") batch_reads = (size_t)std::stoull(next());
         else if (a == "--tags-format") { const std::string f = next(); tfmt = f == "bytecode" ? PGX_TAGS_BYTECODE : f == "compact" ? PGX_TAGS_COMPACT : PGX_TAGS_AUTO; }
         else if (a == "--quiet") quiet = true;
@@ -294,12 +319,15 @@ int main(int argc, char **argv) {
         std::ifstream rin(r_index_file, std::ios::binary);
         if (!rin) { std::cerr << "Cannot open r-index: " << r_index_file << std::endl; std::exit(EXIT_FAILURE); } // :30
     }
-    {
+    const bool from_image = is_image_file(r_index_file.c_str());
+    if (!from_image) {
         std::ifstream tin(tag_array_index, std::ios::binary);
         if (!tin) { std::cerr << "Cannot open tag array: " << tag_array_index << std::endl; std::exit(EXIT_FAILURE); }
     }
     pgx_index *h = nullptr;
-    if (pgx_index_open(r_index_file.c_str(), tag_array_index.c_str(), tfmt, mode, &h) != PGX_OK) {
+    if (from_image) {
+        if (open_image_index(r_index_file.c_str(), tag_array_index.c_str(), mode_given, mode, &h)) return EXIT_FAILURE;
+    } else if (pgx_index_open(r_index_file.c_str(), tag_array_index.c_str(), tfmt, mode, &h) != PGX_OK) {
         std::cerr << pgx_last_error() << std::endl; // reference: uncaught sdsl::simple_sds::InvalidData
         return EXIT_FAILURE;
     }
