@@ -305,6 +305,23 @@ pgx_status pgx_write_compact_tags(const char *out_path, const uint64_t *values,
  * compact = 0: ByteCode format (load_compressed_tags, tag_arrays.cpp:739); 1: sdsl-compact (find_mems.cpp:79). */
 pgx_status pgx_convert_tags(const char *in_path, const char *out_path, int compact);
 
+/* The query-format tag file of a run list, encoded on `device`: the bytes pgx_write_compact_tags (format = PGX_TAGS_COMPACT) or
+ * pgx_convert_tags(.., compact = 0) (format = PGX_TAGS_BYTECODE) write for the same runs.  values[i] = offset | rev << 10 |
+ * node << 11; lengths[i] may be 0 (writes nothing) and may exceed 511 (pieces of 511, then the rest: while (len >= 512) emit 511).
+ * max_node_floor as in merge_tags (the item width covers at least this node id; compact only).  The ByteCode form is what
+ * pgx_convert_tags makes of the build_tags file of these runs, so it opens, like the reference's own files, with the runs that
+ * convert_tags reads out of that file's 8-byte header; the compact form holds the stated runs only.  Pieces, Elias-Fano parts and select
+ * tables are computed by HIP kernels, one thread per output word; the whole file is assembled in device memory, downloaded once and
+ * written once, after every check: an error leaves no file.  PGX_ERR_ARG for a null path or array and for any other format
+ * (PGX_TAGS_AUTO included), checked before the device is touched; PGX_ERR_FORMAT for a node id beyond 2^53 - 1 (compact: the item
+ * has 64 bits) or 2^44 - 1 (ByteCode). */
+pgx_status pgx_tags_encode(int device, const uint64_t *values, const uint64_t *lengths, uint64_t n_runs, uint64_t max_node_floor,
+                           uint32_t format, const char *out_path);
+/* stage times (ms) of this thread's last encoding (pgx_tags_encode, or pgx_build_tags / pgx_merge_tags with their device-encode
+ * flags), up to n of: [0] pieces + items or ByteCodes [1] the two sd_vector bodies [2] select supports [3] download [4] file write
+ * [5] bytes of the file and [6] peak device bytes of the encoder's own buffers (counts, not times) */
+pgx_status pgx_tags_encode_timing(double *ms, uint32_t n);
+
 /* merge_tags equivalent (src/merge_tags.cpp): per-chromosome tag streams (build_tags' "algorithm format": ByteCode runs
  * offset:10 | rev:1 | len:9 | node<<20, with or without the 8-byte int_vector<8> header of sdsl::int_vector_buffer) ->
  * the whole-genome tag array in the sdsl-compact query format find_mems loads.  `ri_path` is the whole-genome r-index;
@@ -327,6 +344,10 @@ pgx_status pgx_merge_tags(const char *ri_path, const char *const *tag_paths, uin
  * exact; the two outputs are the same bytes whenever no merged run reaches 65 536 positions (tests/test_merge_tags.py restates
  * the reference's job loop and checks that rule). */
 #define PGX_MERGE_REFERENCE_RUNS 0x1u
+/* PGX_MERGE_DEVICE_ENCODE: the output file is encoded on the device from the merged runs where they lie (as pgx_tags_encode) instead
+ * of downloading them to the host writer; lengths, the mod-65 536 rule of PGX_MERGE_REFERENCE_RUNS included, come from a kernel.
+ * The same bytes either way.  (The value leaves 2, 4 and 8 unassigned.) */
+#define PGX_MERGE_DEVICE_ENCODE 0x10u
 pgx_status pgx_merge_tags_ex(const char *ri_path, const char *const *tag_paths, uint32_t n_files, const uint32_t *seq_to_file,
                              uint64_t n_seq, int device, const char *out_path, uint32_t flags);
 
@@ -362,6 +383,11 @@ pgx_status pgx_merge_tags_gbz_ex(const char *gbz_path, const char *ri_path, cons
                                               Without it lengths are exact; the bytes agree whenever no run reaches 65 536 */
 #define PGX_BUILD_TAGS_FORWARD_ONLY 0x2u   /* index sequence s = GBWT sequence 2s; pgx_gbz_extract: even sequences only */
 #define PGX_BUILD_TAGS_INPUT_RLBWT 0x4u    /* ri_path names a grlBWT .rl_bwt; its r-index is built in memory */
+#define PGX_BUILD_TAGS_OUT_COMPACT 0x8u    /* out_path receives the sdsl-compact query format find_mems loads: byte for byte what
+                                              pgx_convert_tags(compact = 1) makes of the file the same call writes without the
+                                              flag.  Encoded on the device from the runs (as pgx_tags_encode); the algorithm-format
+                                              body is neither encoded nor downloaded */
+#define PGX_BUILD_TAGS_OUT_BYTECODE 0x10u  /* likewise the ByteCode query format (pgx_convert_tags(compact = 0)); both: PGX_ERR_ARG */
 pgx_status pgx_build_tags(const char *gbz_path, const char *ri_path, int device, const char *out_path, uint32_t flags);
 /* pgx_build_tags with the graph stated by the caller: n_seq paths, path s = path_nodes[path_offsets[s], path_offsets[s + 1])
  * with nodes as id << 1 | rev; node_length[id - first_node_id] for n_node_ids ids (0: the id has no sequence). */
@@ -370,7 +396,8 @@ pgx_status pgx_build_tags_paths(const char *ri_path, uint64_t n_seq, const uint6
                                 const char *out_path, uint32_t flags);
 /* stage times (ms) of this thread's last pgx_build_tags[_paths] call, up to n of: [0] graph (GBZ parse + path extraction; 0 for
  * _paths) [1] index (read or built, locate image upload) [2] suffix array [3] tag of every row incl. the length checks [4] run
- * encoding incl. the body download [5] file write */
+ * encoding incl. the body download [5] file write.  With an OUT flag [4] ends with the run compaction and [5] is the whole device
+ * encoding, download and write included (its stages: pgx_tags_encode_timing) */
 pgx_status pgx_build_tags_timing(double *ms, uint32_t n);
 /* gbz_extract: the newline-separated text of every GBWT sequence of the graph spelled from its node sequences (reverse
  * complemented where the orientation bit is set), or of the even ones with PGX_BUILD_TAGS_FORWARD_ONLY. */

@@ -747,6 +747,30 @@ extern "C" pgx_status pgx_write_compact_tags(const char *out_path, const uint64_
     PGX_GUARD_END
 }
 
+namespace pgx {
+// What pgx_convert_tags below (like the reference's convert_tags) makes of the int_vector<8> header of a build_tags file: it decodes the
+// file from its first byte, so the header -- the bit count of a body of body_bytes bytes -- is read as ByteCodes too.  Those with a
+// length field (bits 11..19) above 0 are runs in front of the real ones: their compact values and lengths, at most 8, are returned;
+// *max_node is the largest node field of all of them, which widens the compact item whatever the length.
+uint64_t algorithm_header_runs(uint64_t body_bytes, uint64_t values[8], uint64_t lengths[8], uint64_t *max_node) {
+    if (body_bytes >> 60) throw Error(PGX_ERR_UNSUPPORTED, "tag stream of 2^60 bytes or more");
+    uint8_t hdr[8];
+    const uint64_t bits = body_bytes * 8;
+    std::memcpy(hdr, &bits, 8);
+    uint64_t k = 0, loc = 0;
+    *max_node = 0;
+    while (loc < 8) {
+        const uint64_t d = bytecode_read(hdr, 8, loc, "tag file header"); // (hdr[7] < 0x80: the last code ends inside the header)
+        *max_node = std::max(*max_node, d >> 20);
+        const uint64_t len = (d >> 11) & 0x1FF; // decode_run, length_bits = 9
+        if (!len) continue;
+        values[k] = (d & 0x7FF) | ((d >> 20) << 11);
+        lengths[k++] = len;
+    }
+    return k;
+}
+} // namespace pgx
+
 // ------------------------------------------------------------------------------------------
 // convert_tags equivalent: "algorithm format" (bare ByteCode stream of
 // offset:10 | rev:1 | len:9 | node<<20, written by build_tags, src/tag_arrays.cpp:28-36,104-127) ->

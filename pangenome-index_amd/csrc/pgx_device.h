@@ -391,6 +391,36 @@ __global__ void pgx_bt_length_kernel(const uint64_t *run_start, uint64_t n_runs,
 __global__ void pgx_bt_size_kernel(const uint64_t *run_val, const uint64_t *run_len, uint64_t n_runs, uint64_t *bytes);
 __global__ void pgx_bt_write_kernel(const uint64_t *run_val, const uint64_t *run_len, const uint64_t *byte_off, uint64_t n_runs, uint8_t *body);
 
+// tag query files from a run list (pgx_tags_encode_kernels.hip, pgx_tags_encode)
+struct PgxTeRuns { // run i: value val[i]; length aux[i], or aux[i + 1] - aux[i] with the last run ending at n_end; mod16: length mod 65 536
+    const uint64_t *val, *aux;
+    uint64_t n_runs, n_end;
+    uint32_t aux_is_start, mod16;
+};
+struct PgxTeSd { // an sd_vector of m ascending ones (ones == NULL: ones[i] = 10 i) with low width wl
+    const uint64_t *ones;
+    uint64_t m;
+    uint32_t wl;
+};
+struct PgxTeField { // `bytes` low bytes of `value` at byte `offset` of the file
+    uint64_t offset, value;
+    uint32_t bytes, pad;
+};
+#define PGX_TE_EXPAND_PIECES 0u
+#define PGX_TE_EXPAND_STREAM 1u
+__global__ void pgx_te_count_kernel(PgxTeRuns runs, uint32_t zero_counts, uint64_t *n_pieces, uint64_t *lens, uint64_t *n_bytes, unsigned long long *max_node);
+__global__ void pgx_te_expand_kernel(PgxTeRuns runs, const uint64_t *piece_off, const uint64_t *pos_off, const uint64_t *byte_off, uint32_t what, uint64_t *pos,
+                                     uint64_t *items, uint64_t *sstart, uint8_t *stream);
+__global__ void pgx_te_pack_items_kernel(const uint64_t *items, uint64_t count, uint32_t width, uint8_t *out, uint64_t n_words);
+__global__ void pgx_te_sd_low_kernel(PgxTeSd sd, uint8_t *out, uint64_t n_words);
+__global__ void pgx_te_sd_high_kernel(PgxTeSd sd, uint8_t *out, uint64_t n_words);
+__global__ void pgx_te_sel_size_kernel(PgxTeSd sd, uint32_t b, uint64_t arg_cnt, uint64_t n_sb, uint64_t logn4, uint64_t *first, uint8_t *meta, uint64_t *sizes,
+                                       unsigned int *any_long);
+__global__ void pgx_te_sel_super_kernel(const uint64_t *first, uint64_t n_sb, uint32_t logn, uint8_t *out, uint64_t n_words);
+__global__ void pgx_te_sel_kind_kernel(const uint8_t *meta, uint64_t n_sb, uint8_t *out, uint64_t n_words);
+__global__ void pgx_te_sel_body_kernel(PgxTeSd sd, uint32_t b, uint64_t arg_cnt, const uint64_t *first, const uint8_t *meta, const uint64_t *off, uint8_t *out);
+__global__ void pgx_te_fields_kernel(const PgxTeField *fields, uint32_t n, uint8_t *out);
+
 // reads as text -> CSR reads (pgx_fastx_kernels.hip, pgx_batch_upload_text)
 #define PGX_FASTX_ROUNDS 4                        // 16-byte loads per thread and tile
 #define PGX_FASTX_TILE (256 * 16 * PGX_FASTX_ROUNDS) // bytes of text per block of the newline passes

@@ -141,6 +141,8 @@ void build_rindex_core(const std::vector<std::pair<uint8_t, uint64_t>> &file_run
 // the r-index of a grlBWT .rl_bwt as the bytes pgx_build_rindex writes (pgx_build.cpp)
 std::vector<uint8_t> build_rindex_bytes(const char *rlbwt_path, int encoded);
 void write_compact_tags(const char *out_path, const uint64_t *values, const uint64_t *lengths, uint64_t n_runs, uint64_t max_node_floor);
+// the runs convert_tags reads out of the header of a build_tags file with a body of body_bytes bytes (pgx_build.cpp)
+uint64_t algorithm_header_runs(uint64_t body_bytes, uint64_t values[8], uint64_t lengths[8], uint64_t *max_node);
 
 std::vector<uint8_t> read_whole_file(const std::string &path);
 void write_whole_file(const std::string &path, const std::vector<uint8_t> &bytes);

@@ -85,6 +85,11 @@ void locate_core(pgx_index *h, pgx_device_image *d, const uint64_t *first, const
                  DevBuf &vals_out, uint64_t &n_vals_out);
 void locate_check_supported(const pgx_index *h, const char *who);
 
+// pgx_tags_encode.hip: the query-format tag file (PGX_TAGS_COMPACT / PGX_TAGS_BYTECODE) of a run list in device memory, on stream `s` (synchronises it).
+// zero_len_counts: the node of a run of length 0 still widens the compact item (pgx_write_compact_tags sees such runs; the files
+// build_tags and merge_tags write never held them).  Writes out_path last; fills this thread's pgx_tags_encode_timing.
+void tags_encode_device(const PgxTeRuns &runs, bool zero_len_counts, uint64_t max_node_floor, uint32_t format, const char *out_path, hipStream_t s);
+
 inline void upload(DevBuf &b, const void *src, size_t bytes) {
     b.ensure(bytes ? bytes : 16);
     if (bytes) HIPCHECK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));

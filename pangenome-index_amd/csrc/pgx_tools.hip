@@ -23,7 +23,7 @@ static uint64_t algorithm_tags_start(const std::vector<uint8_t> &raw) {
 static void merge_tags_core(const char *ri_path, const char *const *tag_paths, uint32_t n_files, const uint32_t *seq_to_file, uint64_t n_seq,
                             int device, const char *out_path, uint64_t max_node_floor, uint32_t opts) {
     if (!ri_path || !tag_paths || !seq_to_file || !out_path) throw Error(PGX_ERR_ARG, "pgx_merge_tags: null argument");
-    if (opts & ~PGX_MERGE_REFERENCE_RUNS) throw Error(PGX_ERR_ARG, "pgx_merge_tags: unknown flag");
+    if (opts & ~(PGX_MERGE_REFERENCE_RUNS | PGX_MERGE_DEVICE_ENCODE)) throw Error(PGX_ERR_ARG, "pgx_merge_tags: unknown flag");
     if (n_files == 0 || n_files > 250) throw Error(PGX_ERR_ARG, "pgx_merge_tags: between 1 and 250 tag files");
     // only the locate side of the index is needed: parse the file, no rank image
     std::unique_ptr<pgx_index, void (*)(pgx_index *)> guard(new pgx_index(), pgx_index_close);
@@ -127,6 +127,19 @@ static void merge_tags_core(const char *ri_path, const char *const *tag_paths, u
             hipLaunchKernelGGL(pgx_mt_compact_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, tags.as<uint64_t>(), flags.as<uint8_t>(), rank.as<uint64_t>(),
                                n, n_seq, out_val.as<uint64_t>(), out_start.as<uint64_t>());
             HIPCHECK(hipGetLastError());
+        }
+        if (opts & PGX_MERGE_DEVICE_ENCODE) {
+            // the file from (out_val, out_start) where they lie: lengths (next start - start, the last run ends at n; mod 65 536 in
+            // reference mode, 0 = nothing written) come from the encoder's first kernel
+            HIPCHECK(hipStreamSynchronize(s));
+            DevBuf *done[] = {&file_of, &tags, &rank, &scan_tmp, &s2f, &ctr, &rstart, &rval, &expanded, &flags};
+            for (DevBuf *b : done) b->release();
+            const PgxTeRuns runs{out_val.as<uint64_t>(), out_start.as<uint64_t>(), n_out, n, 1u, (opts & PGX_MERGE_REFERENCE_RUNS) ? 1u : 0u};
+            tags_encode_device(runs, false, max_node_floor, PGX_TAGS_COMPACT, out_path, s);
+            for (DevBuf *b : all) b->release();
+            return;
+        }
+        if (n) {
             h_val.resize(n_out); h_start.resize(n_out + 1);
             HIPCHECK(hipMemcpy(h_val.data(), out_val.p, n_out * 8, hipMemcpyDeviceToHost));
             HIPCHECK(hipMemcpy(h_start.data(), out_start.p, n_out * 8, hipMemcpyDeviceToHost));
@@ -275,9 +288,17 @@ static void path_tables(uint64_t n_seq, const uint64_t *path_offsets, const uint
     }
 }
 
+static void build_tags_check_flags(uint32_t flags, const char *who) {
+    if (flags & ~(PGX_BUILD_TAGS_REFERENCE_RUNS | PGX_BUILD_TAGS_FORWARD_ONLY | PGX_BUILD_TAGS_INPUT_RLBWT | PGX_BUILD_TAGS_OUT_COMPACT | PGX_BUILD_TAGS_OUT_BYTECODE))
+        throw Error(PGX_ERR_ARG, std::string(who) + ": unknown flag");
+    if ((flags & PGX_BUILD_TAGS_OUT_COMPACT) && (flags & PGX_BUILD_TAGS_OUT_BYTECODE))
+        throw Error(PGX_ERR_ARG, std::string(who) + ": one output format at most");
+}
+
 static void build_tags_core(const char *ri_path, uint32_t flags, uint64_t n_paths, const uint64_t *path_offsets, const uint64_t *path_nodes,
                             const uint32_t *node_length, uint64_t first_node_id, uint64_t n_node_ids, int device, const char *out_path, double *ms) {
     StageClock clk;
+    const uint32_t out_format = (flags & PGX_BUILD_TAGS_OUT_COMPACT) ? PGX_TAGS_COMPACT : (flags & PGX_BUILD_TAGS_OUT_BYTECODE) ? PGX_TAGS_BYTECODE : 0u;
     // 1. the index: only its locate side (as merge_tags)
     std::unique_ptr<pgx_index, void (*)(pgx_index *)> guard(new pgx_index(), pgx_index_close);
     pgx_index *h = guard.get();
@@ -362,6 +383,41 @@ static void build_tags_core(const char *ri_path, uint32_t flags, uint64_t n_path
         HIPCHECK(hipGetLastError());
         scan_excl(4, head.p, n, 0, scan.as<uint64_t>(), scan_tmp, s);
         R = read_u64(scan.as<uint64_t>() + n, s);
+        if (out_format) {
+            // a query format: the encoder takes (value, start) as they lie; the algorithm-format body is never made, only its size.
+            // That size matters: convert_tags, like the reference's, decodes the file from its first byte, so the int_vector<8> header
+            // (the body's bit count) is read as ByteCodes too -- up to 8 runs in front of the real ones, the zero-length ones of which
+            // still widen the compact item.  They take the PRE slots in front of the compacted runs.
+            const uint64_t PRE = 8;
+            run_val.ensure((R + PRE) * 8); run_aux.ensure((R + PRE) * 8);
+            uint64_t *rv = run_val.as<uint64_t>() + PRE, *rs = run_aux.as<uint64_t>() + PRE;
+            if (R) {
+                body.ensure(R * 8);
+                hipLaunchKernelGGL(pgx_bt_compact_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, sa.as<uint64_t>(), head.as<uint8_t>(), scan.as<uint64_t>(), n, rv, rs);
+                hipLaunchKernelGGL(pgx_bt_length_kernel, dim3(grid_for(R, 256)), dim3(256), 0, s, rs, R, n,
+                                   (uint32_t)((flags & PGX_BUILD_TAGS_REFERENCE_RUNS) ? 1 : 0), sa.as<uint64_t>());
+                hipLaunchKernelGGL(pgx_bt_size_kernel, dim3(grid_for(R, 256)), dim3(256), 0, s, rv, sa.as<uint64_t>(), R, body.as<uint64_t>());
+                HIPCHECK(hipGetLastError());
+                scan_excl(1, body.p, R, 0, scan.as<uint64_t>(), scan_tmp, s);
+                B = read_u64(scan.as<uint64_t>() + R, s);
+            }
+            uint64_t pre_val[PRE], pre_start[PRE], floor = 0;
+            const uint64_t k = algorithm_header_runs(B, pre_val, pre_start, &floor); // (lengths for now; B = 0 gives none)
+            uint64_t next = n_seq; // start of the first real run; the starts of the header's runs count down from it (only differences are read)
+            for (uint64_t j = k; j-- > 0;) { next -= pre_start[j]; pre_start[j] = next; }
+            if (k) {
+                HIPCHECK(hipMemcpy(rv - k, pre_val, k * 8, hipMemcpyHostToDevice));
+                HIPCHECK(hipMemcpy(rs - k, pre_start, k * 8, hipMemcpyHostToDevice));
+            }
+            HIPCHECK(hipDeviceSynchronize());
+            sa.release(); head.release(); scan.release(); scan_tmp.release(); body.release();
+            ms[4] = clk.lap();
+            const PgxTeRuns runs{rv - k, rs - k, R + k, n, 1u, (flags & PGX_BUILD_TAGS_REFERENCE_RUNS) ? 1u : 0u};
+            tags_encode_device(runs, false, floor, out_format, out_path, s);
+            for (DevBuf *b : all) b->release();
+            ms[5] = clk.lap();
+            return;
+        }
         if (R) {
             run_val.ensure(R * 8); run_aux.ensure(R * 8);
             hipLaunchKernelGGL(pgx_bt_compact_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, sa.as<uint64_t>(), head.as<uint8_t>(), scan.as<uint64_t>(), n,
@@ -407,8 +463,7 @@ extern "C" pgx_status pgx_build_tags_paths(const char *ri_path, uint64_t n_seq, 
     std::fill(ms, ms + 6, 0.0);
     if (!ri_path || !out_path || !path_offsets || (path_offsets[n_seq] && !path_nodes) || (n_node_ids && !node_length))
         throw Error(PGX_ERR_ARG, "pgx_build_tags_paths: null argument");
-    if (flags & ~(PGX_BUILD_TAGS_REFERENCE_RUNS | PGX_BUILD_TAGS_FORWARD_ONLY | PGX_BUILD_TAGS_INPUT_RLBWT))
-        throw Error(PGX_ERR_ARG, "pgx_build_tags_paths: unknown flag");
+    build_tags_check_flags(flags, "pgx_build_tags_paths");
     build_tags_core(ri_path, flags, n_seq, path_offsets, path_nodes, node_length, first_node_id, n_node_ids, device, out_path, ms);
     return PGX_OK;
     PGX_GUARD_END
@@ -419,8 +474,7 @@ extern "C" pgx_status pgx_build_tags(const char *gbz_path, const char *ri_path, 
     double *ms = g_build_tags_ms;
     std::fill(ms, ms + 6, 0.0);
     if (!gbz_path || !ri_path || !out_path) throw Error(PGX_ERR_ARG, "pgx_build_tags: null argument");
-    if (flags & ~(PGX_BUILD_TAGS_REFERENCE_RUNS | PGX_BUILD_TAGS_FORWARD_ONLY | PGX_BUILD_TAGS_INPUT_RLBWT))
-        throw Error(PGX_ERR_ARG, "pgx_build_tags: unknown flag");
+    build_tags_check_flags(flags, "pgx_build_tags");
     StageClock clk;
     GbzGraph g;
     try { parse_gbz_graph(gbz_path, (flags & PGX_BUILD_TAGS_FORWARD_ONLY) != 0, false, g); }

@@ -187,6 +187,8 @@ def lib():
     L.pgx_build_index_device_timing.argtypes = [p, u32]
     L.pgx_write_compact_tags.argtypes = [C.c_char_p, p, p, u64]
     L.pgx_convert_tags.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
+    L.pgx_tags_encode.argtypes = [C.c_int, p, p, u64, u64, u32, C.c_char_p]
+    L.pgx_tags_encode_timing.argtypes = [p, u32]
     L.pgx_merge_tags.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), u32, p, u64, C.c_int, C.c_char_p]
     L.pgx_gbz_paths.argtypes = [C.c_char_p, C.POINTER(u64), p, p, u64, C.POINTER(u64), C.POINTER(u32)]
     L.pgx_merge_tags_gbz.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u32, C.c_int, C.c_char_p]
@@ -366,6 +368,27 @@ def convert_tags(in_path, out_path, compact=False):
     _check(lib().pgx_convert_tags(in_path.encode(), out_path.encode(), 1 if compact else 0))
 
 
+TAGS_ENCODE_STAGES = ("pieces", "sd_vectors", "select", "download", "write", "file_bytes", "device_bytes")
+
+
+def tags_encode(values, lengths, out_path, fmt, max_node_floor=0, device=0):
+    """pgx_tags_encode: the query-format tag file (fmt = TAGS_COMPACT or TAGS_BYTECODE) of a run list, encoded on the device: the
+    bytes write_compact_tags / convert_tags(compact=False) write for the same runs.  Returns tags_encode_timing()."""
+    v = np.ascontiguousarray(values, dtype=np.uint64)
+    l = np.ascontiguousarray(lengths, dtype=np.uint64)
+    assert len(v) == len(l)
+    _check(lib().pgx_tags_encode(device, v.ctypes.data if len(v) else None, l.ctypes.data if len(l) else None, len(v), max_node_floor, fmt,
+                                 out_path.encode()))
+    return tags_encode_timing()
+
+
+def tags_encode_timing():
+    """this thread's last device encoding: stage times in ms, then the file's bytes and the encoder's peak device bytes"""
+    ms = (C.c_double * len(TAGS_ENCODE_STAGES))()
+    _check(lib().pgx_tags_encode_timing(C.cast(ms, C.c_void_p), len(TAGS_ENCODE_STAGES)))
+    return dict(zip(TAGS_ENCODE_STAGES, list(ms)))
+
+
 _VIEW_DTYPES = {0: np.uint8, 1: np.uint64, 2: np.uint64, 3: np.uint64, 4: np.uint64, 5: np.uint32, 6: np.uint8, 7: np.uint16,
                 8: np.uint64, 9: np.uint64, 10: np.uint32, 11: np.uint64, 12: np.uint64, 13: np.uint32, 14: np.uint8, 15: np.uint32,
                 16: np.uint64, 17: np.uint64, 18: np.uint64, 19: np.uint32, 20: np.uint32, 21: np.uint32, 22: np.uint64, 23: np.uint64}
@@ -376,6 +399,7 @@ NO_POSITION = 0xFFFFFFFFFFFFFFFF
 
 
 MERGE_REFERENCE_RUNS = 0x1
+MERGE_DEVICE_ENCODE = 0x10  # the output file is encoded on the device (pgx_tags_encode's kernels): the same bytes
 
 
 def merge_tags(ri_path, tag_paths, seq_to_file, out_path, device=0, flags=0):
@@ -404,6 +428,8 @@ def merge_tags_gbz(gbz_path, ri_path, tag_paths, out_path, device=0, flags=0):
 
 
 BUILD_TAGS_REFERENCE_RUNS, BUILD_TAGS_FORWARD_ONLY, BUILD_TAGS_INPUT_RLBWT = 0x1, 0x2, 0x4
+# the output is a query format (what convert_tags makes of the default output), encoded on the device; one of them at most
+BUILD_TAGS_OUT_COMPACT, BUILD_TAGS_OUT_BYTECODE = 0x8, 0x10
 BUILD_TAGS_STAGES = ("graph", "index", "suffix_array", "tags", "runs", "write")
 
 

@@ -2,7 +2,10 @@
 // merge_tags / convert_tags).
 //
 //   build_tags <graph.gbz> <graph_info.rl_bwt> <output.tags> [--ri] [--device N] [--forward-only] [--reference-runs]
+//              [--format algorithm|compact|bytecode]
 //
+// --format compact / bytecode: the output is the query format find_mems loads, encoded on the device -- the file convert_tags
+// would make of the default output, in one step (pgx_build_tags, PGX_BUILD_TAGS_OUT_*).  algorithm is the default.
 // The reference's argument list.  The r-index is built in memory from the .rl_bwt (as build_rindex would write it); with --ri
 // the second argument is an existing .ri instead.  --forward-only: the text holds one orientation per path (index sequence s =
 // GBWT sequence 2s, as gbz_extract without -b writes it); without it, a text of that shape is rejected.  --reference-runs: run
@@ -15,17 +18,27 @@
 
 #include "../../include/pgx.h"
 
+static int usage() {
+    std::cerr << "usage: build_tags <graph.gbz> <graph_info.rl_bwt> <output.tags> [--ri] [--device N] [--forward-only] [--reference-runs]"
+                 " [--format algorithm|compact|bytecode]"
+              << std::endl;
+    return EXIT_FAILURE;
+}
+
 int main(int argc, char **argv) {
-    if (argc < 4) {
-        std::cerr << "usage: build_tags <graph.gbz> <graph_info.rl_bwt> <output.tags> [--ri] [--device N] [--forward-only] [--reference-runs]"
-                  << std::endl;
-        return EXIT_FAILURE;
-    }
+    if (argc < 4) return usage();
     int device = 0;
     uint32_t flags = PGX_BUILD_TAGS_INPUT_RLBWT;
     for (int i = 4; i < argc; i++) {
         const std::string o = argv[i];
         if (o == "--ri") flags &= ~PGX_BUILD_TAGS_INPUT_RLBWT;
+        else if (o == "--format" && i + 1 < argc) {
+            const std::string f = argv[++i];
+            flags &= ~(PGX_BUILD_TAGS_OUT_COMPACT | PGX_BUILD_TAGS_OUT_BYTECODE);
+            if (f == "compact") flags |= PGX_BUILD_TAGS_OUT_COMPACT;
+            else if (f == "bytecode") flags |= PGX_BUILD_TAGS_OUT_BYTECODE;
+            else if (f != "algorithm") return usage();
+        }
         else if (o == "--device" && i + 1 < argc) {
             char *end = nullptr;
             const long v = std::strtol(argv[++i], &end, 10);
@@ -45,6 +58,12 @@ int main(int argc, char **argv) {
     pgx_build_tags_timing(ms, 6);
     std::fprintf(stderr, "graph %.1f ms, index %.1f ms, suffix array %.1f ms, tags %.1f ms, runs %.1f ms, write %.1f ms\n", ms[0], ms[1], ms[2],
                  ms[3], ms[4], ms[5]);
+    if (flags & (PGX_BUILD_TAGS_OUT_COMPACT | PGX_BUILD_TAGS_OUT_BYTECODE)) {
+        double e[6] = {0, 0, 0, 0, 0, 0};
+        pgx_tags_encode_timing(e, 6);
+        std::fprintf(stderr, "write = device encoding: pieces %.1f ms, sd_vectors %.1f ms, select %.1f ms, download %.1f ms, file %.1f ms (%.0f bytes)\n", e[0],
+                     e[1], e[2], e[3], e[4], e[5]);
+    }
     std::cerr << "Tags written to " << argv[3] << std::endl;
     return 0;
 }

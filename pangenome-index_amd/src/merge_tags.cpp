@@ -11,6 +11,7 @@
 // file (inside <tag_dir>) that holds the tags of that sequence.  "--counts f0:n0,f1:n1,..." replaces the file when the
 // sequences are grouped (the first n0 sequences belong to f0, the next n1 to f1, ...), which is what concatenating
 // per-chromosome texts gives.  Output: whole_genome_tag_array_compressed.tags (merge_tags.cpp:541), sdsl-compact format.
+// --device-encode: the output file is encoded on the device from the merged runs (PGX_MERGE_DEVICE_ENCODE): the same bytes.
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -27,7 +28,7 @@
 
 int main(int argc, char **argv) {
     if (argc < 4) {
-        std::cerr << "usage: merge_tags <graph.gbz | seq_map.txt | --counts f0:n0,f1:n1,...> <whole_genome.ri> <tag_dir> [--out FILE] [--device N] [--reference-runs]" << std::endl;
+        std::cerr << "usage: merge_tags <graph.gbz | seq_map.txt | --counts f0:n0,f1:n1,...> <whole_genome.ri> <tag_dir> [--out FILE] [--device N] [--reference-runs] [--device-encode]" << std::endl;
         return EXIT_FAILURE;
     }
     {   // the reference's argv: <graph.gbz> <r_index> <tag_dir>
@@ -43,6 +44,7 @@ int main(int argc, char **argv) {
                 if (o == "--out" && i + 1 < argc) out = argv[++i];
                 else if (o == "--device" && i + 1 < argc) device = std::stoi(argv[++i]);
                 else if (o == "--reference-runs") flags |= PGX_MERGE_REFERENCE_RUNS;
+                else if (o == "--device-encode") flags |= PGX_MERGE_DEVICE_ENCODE;
                 else { std::cerr << "unknown option " << o << std::endl; return EXIT_FAILURE; }
             }
             std::cerr << "Loading the graph file" << std::endl;            // :449
@@ -105,6 +107,7 @@ int main(int argc, char **argv) {
         if (o == "--out" && i + 1 < argc) out = argv[++i];
         else if (o == "--device" && i + 1 < argc) device = std::stoi(argv[++i]);
         else if (o == "--reference-runs") flags |= PGX_MERGE_REFERENCE_RUNS;
+                else if (o == "--device-encode") flags |= PGX_MERGE_DEVICE_ENCODE;
         else { std::cerr << "unknown option " << o << std::endl; return EXIT_FAILURE; }
     }
     std::map<std::string, uint32_t> id;
