@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only), the device index build (pgx_build_index_from_text_device, pgx_build_index_from_texts_device, pgx_build_index_device_timing: new entry points only), the text output (pgx_batch_format, pgx_format_result, pgx_format_params, pgx_text, PGX_FORMAT_*: new entry points only), the image file (pgx_index_save_image, pgx_index_open_image, pgx_image_file_info, pgx_image_sum, pgx_image_section_name, PGX_IMAGE_*: new entry points only) */
+#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only), the device index build (pgx_build_index_from_text_device, pgx_build_index_from_texts_device, pgx_build_index_device_timing: new entry points only), the text output (pgx_batch_format, pgx_format_result, pgx_format_params, pgx_text, PGX_FORMAT_*: new entry points only), the image file (pgx_index_save_image, pgx_index_open_image, pgx_image_file_info, pgx_image_sum, pgx_image_section_name, PGX_IMAGE_*: new entry points only), the read-back of a batch's reads (pgx_batch_reads, pgx_reads_info: a new entry point only) */
 
 typedef enum {
     PGX_OK = 0,
@@ -568,6 +568,11 @@ pgx_status pgx_pack_reads(const uint8_t *reads, const uint64_t *offsets, uint64_
  * *n_reads = records taken.  A refused upload (PGX_ERR_FORMAT / _ARG) leaves the batch exactly as it was.  Device memory per batch:
  * the text, 29 bytes per line (line table, byte and record scans) and the CSR reads.  Pinned `text` uploads at link speed. */
 pgx_status pgx_batch_upload_text(pgx_batch *b, const uint8_t *text, uint64_t n_bytes, uint32_t format, uint64_t *n_reads);
+typedef struct { uint64_t n_reads, n_bytes, longest; } pgx_reads_info;
+/* The reads a batch holds on its device, as the kernels will read them: offsets[n_reads + 1] (rebased to 0) and bytes[n_bytes].
+ * longest = the longest read as the batch recorded it.  offsets / bytes may be NULL (info only); PGX_ERR_ARG when a capacity is too small.
+ * Valid after any of the four upload forms, before or after a run; it exists for tests (tests/test_gpu_fastx_borders.py). */
+pgx_status pgx_batch_reads(pgx_batch *b, pgx_reads_info *info, uint64_t *offsets, uint64_t offsets_cap, uint8_t *bytes, uint64_t bytes_cap);
 /* Host only, no device: the first record start at or after `want` (n_bytes if none); what a caller that cuts a file into batches needs.
  *   LINES  the start of the next non-empty line.
  *   FASTQ  the next line start L with byte L '@' and line L+2 starting with '+' (a quality line that starts with '@' fails: its line

@@ -400,6 +400,22 @@ extern "C" pgx_status pgx_batch_upload_text(pgx_batch *b, const uint8_t *text, u
     PGX_GUARD_END
 }
 
+// the reads as they lie on the device, whichever upload put them there (tests)
+extern "C" pgx_status pgx_batch_reads(pgx_batch *b, pgx_reads_info *info, uint64_t *offsets, uint64_t offsets_cap, uint8_t *bytes, uint64_t bytes_cap) {
+    PGX_GUARD_BEGIN
+    if (!b || !info) throw Error(PGX_ERR_ARG, "pgx_batch_reads: null argument");
+    info->n_reads = b->n_reads;
+    info->n_bytes = b->read_bytes;
+    info->longest = b->max_read_len;
+    if ((offsets && offsets_cap < b->n_reads + 1) || (bytes && bytes_cap < b->read_bytes)) throw Error(PGX_ERR_ARG, "pgx_batch_reads: capacity too small");
+    use_device(b->device);
+    if (offsets) HIPCHECK(hipMemcpyAsync(offsets, b->offsets.p, (b->n_reads + 1) * 8, hipMemcpyDeviceToHost, b->own));
+    if (bytes && b->read_bytes) HIPCHECK(hipMemcpyAsync(bytes, b->reads.p, b->read_bytes, hipMemcpyDeviceToHost, b->own));
+    HIPCHECK(hipStreamSynchronize(b->own));
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
 // ------------------------------------------------------------------------------------------
 // pgx_batch_run
 

@@ -110,7 +110,7 @@ pgx_fastx_role_kernel(const uint8_t *__restrict__ text, const uint64_t *__restri
     const uint64_t s = ls[i], len = ls[i + 1] - 1 - s;
     const uint8_t c0 = len ? text[s] : 0;
     const uint64_t cr = (len && text[s + len - 1] == '\r') ? 1 : 0;
-    uint64_t add = 0, bad_line = i;
+    uint64_t add = 0;
     uint32_t code = 0, r = 0;
     if (format == PGX_READS_LINES) { // std::getline: '\r' kept, empty lines are no read
         r = len != 0;
@@ -124,15 +124,16 @@ pgx_fastx_role_kernel(const uint8_t *__restrict__ text, const uint64_t *__restri
             const uint64_t qs = ls[i - 2], ql = ls[i - 1] - 1 - qs, qcr = (ql && text[qs + ql - 1] == '\r') ? 1 : 0; // the sequence line
             if (len - cr != ql - qcr) code = PGX_FASTX_ERR_QUAL_LEN;
         }
-        if (!code && i == n_lines - 1 && role != 3) { code = PGX_FASTX_ERR_TRUNCATED; bad_line = i - role; }
+        // a text that ends inside its record: reported for the record's header line, whatever the last line says of itself (the smaller word wins)
+        if (i == n_lines - 1 && role != 3 && len < (1ull << 31)) atomicMin(err, (unsigned long long)((i - role) << 8 | PGX_FASTX_ERR_TRUNCATED));
     } else { // FASTA: a '>' line starts a record, every other line adds its bytes ('\r' stripped)
         if (c0 == '>') r = 1;
         else add = len - cr;
     }
-    if (len >= (1ull << 31)) { code = PGX_FASTX_ERR_LONG_LINE; bad_line = i; }
+    if (len >= (1ull << 31)) code = PGX_FASTX_ERR_LONG_LINE;
     contrib[i] = code == PGX_FASTX_ERR_LONG_LINE ? 0u : (uint32_t)add;
     rec[i] = (uint8_t)r;
-    if (code) atomicMin(err, (unsigned long long)(bad_line << 8 | code));
+    if (code) atomicMin(err, (unsigned long long)(i << 8 | code));
 }
 
 // offs[rec_idx[i]] = out_off[i] at every record start; offs[n_reads] = the total.  FASTA: a line with sequence bytes and no '>' line

@@ -108,6 +108,10 @@ class ExchangeResult(C.Structure):
     _fields_ = [("n_reads", u64), ("n_mems", u64), ("mem_offsets", p), ("mems", p), ("shard_of_mem", p)]
 
 
+class ReadsInfo(C.Structure):  # pgx_reads_info
+    _fields_ = [("n_reads", u64), ("n_bytes", u64), ("longest", u64)]
+
+
 class Timing(C.Structure):
     _fields_ = [
         ("ms_find_mems", C.c_float), ("ms_compact", C.c_float), ("ms_tag_locate", C.c_float),
@@ -211,6 +215,7 @@ def lib():
     L.pgx_batch_upload.argtypes = [p, p, p, u64]
     L.pgx_batch_upload_packed.argtypes = [p, p, p, u64, p, p, u64]
     L.pgx_batch_upload_text.argtypes = [p, p, u64, u32, C.POINTER(u64)]
+    L.pgx_batch_reads.argtypes = [p, C.POINTER(ReadsInfo), p, u64, p, u64]
     L.pgx_fastx_cut.argtypes = [p, u64, u32, u64, C.POINTER(u64)]
     L.pgx_pack_reads.argtypes = [p, p, u64, u32, p, p, u64, p, u64, C.POINTER(u64), C.POINTER(u64)]
     L.pgx_host_alloc.argtypes = [C.c_size_t, C.POINTER(p)]
@@ -931,6 +936,15 @@ class Batch:
         _check(self.L.pgx_batch_upload_text(self.b, t.ctypes.data if len(t) else None, len(t), fmt, C.byref(n)))
         self.n = n.value
         return n.value
+
+    def reads(self):
+        """pgx_batch_reads: the reads as the batch holds them on its device -> (cat uint8, offs uint64 rebased to 0, longest read as recorded)"""
+        info = ReadsInfo()
+        _check(self.L.pgx_batch_reads(self.b, C.byref(info), None, 0, None, 0))
+        offs = np.zeros(int(info.n_reads) + 1, dtype=np.uint64)
+        cat = np.zeros(int(info.n_bytes), dtype=np.uint8)
+        _check(self.L.pgx_batch_reads(self.b, C.byref(info), offs.ctypes.data, len(offs), cat.ctypes.data if len(cat) else None, len(cat)))
+        return cat, offs, int(info.longest)
 
     def run(self, min_len, min_occ, flags=0, stream=None):
         _check(self.L.pgx_batch_run(self.b, min_len, min_occ, flags, stream))

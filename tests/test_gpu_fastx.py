@@ -152,6 +152,7 @@ def test_million_reads_fastq_equals_upload(nidx):
     (P.READS_FASTQ, b"@a\nACGT\n+\nIIII\n@b\nACGT\n+\nIIII\n@c\nACGT\nIIII\n@d\nACGT\n+\nIIII\n", 3, "third line does not start with '+'"),
     (P.READS_FASTQ, b"@a\nACGT\n+\nIIII\n@b\nACGT\n+\n", 2, "truncated record (3 of 4 lines)"),
     (P.READS_FASTQ, b"@a\nACGT\n+\nIIII\nb\nACGT\n+\nIIII\n", 2, "header line does not start with '@'"),
+    (P.READS_FASTQ, b"@a\nACGT\nIIII", 1, "truncated record (3 of 4 lines)"),  # (the third line has no '+' either: the header line comes first)
     (P.READS_FASTA, b"ACGT\n>a\nACGT\n", 1, "text before the first '>'"),
 ])
 def test_malformed_refused_batch_intact(x_index, fmt, text, record, what):
