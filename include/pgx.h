@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only), the device index build (pgx_build_index_from_text_device, pgx_build_index_from_texts_device, pgx_build_index_device_timing: new entry points only), the text output (pgx_batch_format, pgx_format_result, pgx_format_params, pgx_text, PGX_FORMAT_*: new entry points only), the image file (pgx_index_save_image, pgx_index_open_image, pgx_image_file_info, pgx_image_sum, pgx_image_section_name, PGX_IMAGE_*: new entry points only), the read-back of a batch's reads (pgx_batch_reads, pgx_reads_info: a new entry point only) */
+#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only), the device index build (pgx_build_index_from_text_device, pgx_build_index_from_texts_device, pgx_build_index_device_timing: new entry points only), the text output (pgx_batch_format, pgx_format_result, pgx_format_params, pgx_text, PGX_FORMAT_*: new entry points only), the image file (pgx_index_save_image, pgx_index_open_image, pgx_image_file_info, pgx_image_sum, pgx_image_section_name, PGX_IMAGE_*: new entry points only), the read-back of a batch's reads (pgx_batch_reads, pgx_reads_info: a new entry point only), the read hits (pgx_batch_read_hits, pgx_batch_hits, pgx_batch_device_hits, pgx_read_hits_arrays, pgx_read_hit, pgx_read_hits, PGX_HITS_*, PGX_NO_SEQUENCE: new entry points only) */
 
 typedef enum {
     PGX_OK = 0,
@@ -657,6 +657,65 @@ pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t max_occ, void
  * free of the batch; PGX_ERR_ARG when there is none. */
 pgx_status pgx_batch_locations(pgx_batch *b, pgx_locations *out);
 pgx_status pgx_batch_device_locations(pgx_batch *b, pgx_locations *out);
+
+/* ---- read hits: every read scored against every sequence, on the device ------------------------------------------------------
+ * The consumer of PGX_LOCATE_SEQ_SETS: the MEMs of a read and their sequence sets reduced to one fixed record per read, so that only
+ * 40 bytes a read cross the link instead of n_mems x W set words plus the MEM array.
+ *
+ * DEFINITIONS.  Read r has the MEMs m in [mem_offsets[r], mem_offsets[r + 1]).
+ *   len(m)    = end - start if end > start, else 0 (end is exclusive, algorithm.hpp:710-713).
+ *   set(m)    = MEM m's W = ceil(n_seq / 64) words in the PGX_LOCATE_SEQ_SETS form; bits at or beyond n_seq are ignored.
+ *   cov(r, s) = the number of read positions in the union of [start, end) over the MEMs of r whose set has bit s.  Overlapping and
+ *               nested MEMs count a position once; a MEM with an all-zero set (not located) adds nothing.
+ * Precondition: within a read the MEM starts ascend strictly (pgx_batch_run guarantees it in both modes: every step of find_all_mems
+ * appends at most one MEM and moves on to a larger start).  Ends need not ascend, and the result is exact when they do not.
+ * pgx_read_hit (40 bytes; offsets 0 best_score, 8 next_score, 16 covered, 24 best_seq, 28 n_best, 32 n_located, 36 n_mems):
+ *   best_score  max over s < n_seq of cov(r, s); 0 if the read has no located MEM
+ *   next_score  the largest cov(r, s) that is < best_score; 0 if there is none
+ *   covered     the union length over all MEMs of r with a non-empty set: what a sequence holding every located MEM would score
+ *   best_seq    the smallest s with cov(r, s) == best_score; PGX_NO_SEQUENCE when best_score == 0
+ *   n_best      the number of such s; 0 when best_score == 0
+ *   n_located   MEMs of r with a non-empty set
+ *   n_mems      all MEMs of r
+ * PGX_HITS_BEST_SETS adds best_sets[r * W + j]: bit s & 63 of word s >> 6 is set iff cov(r, s) == best_score > 0; bits at or beyond
+ * n_seq are zero.  PGX_HITS_SCORES adds scores[r * n_seq + s] = min(cov(r, s), 2^32 - 1). */
+#define PGX_HITS_BEST_SETS 1u
+#define PGX_HITS_SCORES 2u
+#define PGX_NO_SEQUENCE 0xFFFFFFFFu
+typedef struct {
+    uint64_t best_score, next_score, covered;
+    uint32_t best_seq, n_best, n_located, n_mems;
+} pgx_read_hit;
+typedef struct {
+    uint64_t n_reads, n_seq;
+    uint32_t set_words; /* W */
+    uint32_t flags;     /* PGX_HITS_* the call ran with */
+    const pgx_read_hit *hits;  /* n_reads */
+    const uint64_t *best_sets; /* n_reads x W; NULL without PGX_HITS_BEST_SETS */
+    const uint32_t *scores;    /* n_reads x n_seq; NULL without PGX_HITS_SCORES */
+    float ms_hits;             /* device time of the call when the run had PGX_RUN_TIMING, else 0 */
+    uint32_t reserved;
+} pgx_read_hits;
+/* The hits of the last run from the sequence sets of the last locate, which must be a completed pgx_batch_locate(PGX_LOCATE_SEQ_SETS
+ * [| PGX_LOCATE_CHAINS]) and the batch's current locate result: PGX_ERR_ARG otherwise (also for an unknown flag); the run and locate
+ * results then stay as they were and there is no hits result.  One kernel launch on `stream` (NULL = the batch's own), complete on
+ * return; it reads the sets where the locate left them, no value crosses the link.  Buffers grow only.  The hits stay valid until the
+ * next run, upload, pgx_batch_read_hits or free of the batch; a later pgx_batch_locate of any form leaves them valid (hits first,
+ * positions afterwards).  With PGX_HITS_SCORES the n_reads x n_seq x 4 bytes must fit a quarter of the free device memory:
+ * PGX_ERR_NOMEM with both numbers otherwise.  A read takes Sp lanes (the power of two >= min(n_seq, 64)) of the one launch, which holds
+ * fewer than 2^32 threads: a batch of 2^32 / Sp reads or more (2^26 at 64 lanes) is PGX_ERR_UNSUPPORTED, here and in pgx_read_hits_arrays.
+ * The sets are taken as the locate left them: what pgx_batch_locate could not complete is not noticed here. */
+pgx_status pgx_batch_read_hits(pgx_batch *b, uint32_t flags, void *stream);
+/* Host copy of the last hits (pinned buffers owned by the batch) / the same as device pointers.  PGX_ERR_ARG when there are none. */
+pgx_status pgx_batch_hits(pgx_batch *b, pgx_read_hits *out);
+pgx_status pgx_batch_device_hits(pgx_batch *b, pgx_read_hits *out);
+/* The same kernels on host arrays (how they are tested on shapes no index produces): mem_offsets (n_reads + 1 entries, from 0, never
+ * decreasing; mems holds mem_offsets[n_reads] records), sets (that many x set_words words).  PGX_ERR_ARG unless set_words ==
+ * ceil(n_seq / 64) and 1 <= set_words <= 64, and for a read whose MEM starts do not ascend strictly: the first such read is named, the
+ * check runs on the device and nothing is written.  best_sets / scores may be NULL when their flag is clear.  PGX_ERR_NO_DEVICE without
+ * a GPU. */
+pgx_status pgx_read_hits_arrays(int device, const uint64_t *mem_offsets, uint64_t n_reads, const pgx_mem *mems, const uint64_t *sets, uint32_t set_words,
+                                uint64_t n_seq, uint32_t flags, pgx_read_hit *hits, uint64_t *best_sets, uint32_t *scores);
 
 /* ---- compact result: the result of a run as a byte stream, encoded on the device, expanded on the host ---------------------
  * What pgx_batch_result downloads is six dense uint64 arrays (8 bytes per read, 48 per MEM, 8 per graph position), nearly all of

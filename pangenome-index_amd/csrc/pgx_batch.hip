@@ -1,4 +1,4 @@
-// pgx_batch.hip -- the pgx_batch object: uploads, pgx_batch_run, results, pgx_batch_locate.
+// pgx_batch.hip -- the pgx_batch object: uploads, pgx_batch_run, results, pgx_batch_locate, pgx_batch_read_hits.
 //
 // Pipeline of pgx_batch_run (one HIP stream, results stay on the device):
 //   scan(cap)      -> slot offsets (worst-case MEMs per read: min(len, len - min_len + 1)); the slot buffer
@@ -84,6 +84,7 @@ struct pgx_batch {
     LocWork lw; // pgx_batch_locate
     CompactWork cw; // pgx_batch_result_compact
     FormatWork fw;  // pgx_batch_format
+    HitsWork hw;    // pgx_batch_read_hits
     uint64_t n_mems = 0, n_positions = 0, n_ext = 0, n_tag_overflow = 0;
     bool ran = false, ran_tags = false;
     // speculative sizing (pgx_batch_run): what the last run with these parameters produced
@@ -111,6 +112,7 @@ static void batch_release(pgx_batch *b) {
         b->lw.release();
         b->cw.release();
         b->fw.release();
+        b->hw.release();
         HostBuf *hb[] = {&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]};
         for (HostBuf *x : hb) x->release();
         for (auto &e : b->ev)
@@ -134,6 +136,7 @@ static void batch_reset_for_upload(pgx_batch *b, uint64_t n_reads, uint64_t max_
     b->n_reads = n_reads;
     b->ran = b->ran_tags = false;
     b->lw.valid = false;
+    b->hw.valid = false;
     b->plan_valid = false;
     b->slot_off_valid = false;
     b->class_valid = false;
@@ -1059,6 +1062,7 @@ extern "C" pgx_status pgx_batch_run(pgx_batch *b, uint64_t min_len, uint64_t min
     b->ran = false;
     b->ran_tags = false;
     b->lw.valid = false; // (the locate result belongs to the run before)
+    b->hw.valid = false; // (and so do the hits)
     b->n_mems = b->n_positions = b->n_ext = b->n_tag_overflow = 0;
     std::memset(&b->timing, 0, sizeof b->timing);
     bool force_worst = false;
@@ -1746,6 +1750,188 @@ extern "C" pgx_status pgx_batch_locations(pgx_batch *b, pgx_locations *out) {
     locations_header(b, out);
     out->loc_offsets = w.h_off.as<uint64_t>();
     out->values = w.h_vals.as<uint64_t>();
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// read hits (pgx_hits_kernels.hip; the definitions: include/pgx.h "read hits")
+static const uint32_t HITS_FLAGS = PGX_HITS_BEST_SETS | PGX_HITS_SCORES;
+
+// log2 of the lanes a read takes (Sp: the power of two >= n_seq, 64 with more than one word column); refuses what one launch cannot hold
+static uint32_t hits_lane_shift(uint64_t n_reads, uint64_t n_seq, uint32_t W, const char *who) {
+    uint32_t sp_shift = 0;
+    while (W == 1 && (1ull << sp_shift) < n_seq) sp_shift++;
+    if (W > 1) sp_shift = 6;
+    // (a grid holds fewer than 2^32 threads: a larger launch would lose reads without an error)
+    if (n_reads > (((1ull << 32) - PGX_HITS_THREADS) >> sp_shift))
+        throw Error(PGX_ERR_UNSUPPORTED, std::string(who) + ": " + std::to_string(n_reads) + " reads at " + std::to_string(1u << sp_shift) +
+                                             " lanes a read exceed the 2^32 threads of one launch: score the reads in smaller batches");
+    return sp_shift;
+}
+
+// the one launch: sizes the outputs the flags ask for and enqueues the kernel on s (sets: n_mems x W words on the device)
+static void hits_launch(HitsWork &w, const uint64_t *mem_off, const pgx_mem *mems, const uint64_t *sets, uint64_t n_reads, uint64_t n_mems, uint64_t n_seq, uint32_t W,
+                        uint32_t flags, hipStream_t s) {
+    const uint32_t sp_shift = hits_lane_shift(n_reads, n_seq, W, "read hits");
+    w.hits.ensure((n_reads ? n_reads : 1) * sizeof(pgx_read_hit));
+    if (flags & PGX_HITS_BEST_SETS) w.best_sets.ensure((n_reads ? n_reads * W : 1) * 8);
+    if (flags & PGX_HITS_SCORES) w.scores.ensure((n_reads ? n_reads * n_seq : 1) * 4);
+    if (!n_reads) return;
+    unsigned long long *best = (flags & PGX_HITS_BEST_SETS) ? w.best_sets.as<unsigned long long>() : nullptr;
+    uint32_t *scores = (flags & PGX_HITS_SCORES) ? w.scores.as<uint32_t>() : nullptr;
+    const unsigned long long *dsets = reinterpret_cast<const unsigned long long *>(sets);
+    if (W == 1) { // Sp lanes a read
+        hipLaunchKernelGGL(pgx_read_hits_kernel, dim3(grid_for(n_reads, PGX_HITS_THREADS >> sp_shift)), dim3(PGX_HITS_THREADS), 0, s, mem_off, mems, dsets, n_reads, n_mems,
+                           n_seq, sp_shift, flags, w.hits.as<pgx_read_hit>(), best, scores);
+    } else // a wave a read
+        hipLaunchKernelGGL(pgx_read_hits_wide_kernel, dim3(grid_for(n_reads, PGX_HITS_THREADS / 64)), dim3(PGX_HITS_THREADS), 0, s, mem_off, mems, dsets, n_reads, n_mems,
+                           n_seq, W, flags, w.hits.as<pgx_read_hit>(), best, scores);
+    HIPCHECK(hipGetLastError());
+}
+
+extern "C" pgx_status pgx_batch_read_hits(pgx_batch *b, uint32_t flags, void *stream) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_read_hits");
+    checked_device_count();
+    if (!b) throw Error(PGX_ERR_ARG, "pgx_batch_read_hits: null batch");
+    HitsWork &w = b->hw;
+    w.valid = false;
+    if (flags & ~HITS_FLAGS) throw Error(PGX_ERR_ARG, "pgx_batch_read_hits: unknown flag");
+    if (!b->ran) throw Error(PGX_ERR_ARG, "pgx_batch_read_hits: batch has not been run");
+    const LocWork &lw = b->lw;
+    if (!lw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_read_hits: needs a completed pgx_batch_locate(PGX_LOCATE_SEQ_SETS), the batch has no locate result");
+    if (lw.flags != PGX_LOCATE_SEQ_SETS || lw.n_mems != b->n_mems || !lw.set_words)
+        throw Error(PGX_ERR_ARG, "pgx_batch_read_hits: needs a completed pgx_batch_locate(PGX_LOCATE_SEQ_SETS), the last pgx_batch_locate ran with flags " +
+                                     std::to_string(lw.flags));
+    use_device(b->device);
+    hipStream_t s = stream ? (hipStream_t)stream : b->own;
+    const uint64_t n = b->n_reads, n_seq = b->h->meta.n_sequences();
+    const uint32_t W = lw.set_words;
+    (void)hits_lane_shift(n, n_seq, W, "pgx_batch_read_hits");
+    if (flags & PGX_HITS_SCORES) {
+        size_t mem_free = 0, mem_total = 0;
+        if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); mem_free = 1ull << 30; }
+        const uint64_t need = n * n_seq * 4;
+        if (need > mem_free / 4)
+            throw Error(PGX_ERR_NOMEM, "pgx_batch_read_hits: PGX_HITS_SCORES takes " + std::to_string(need) + " bytes, a quarter of the free device memory is " +
+                                           std::to_string(mem_free / 4));
+    }
+    const bool timed = b->timed;
+    if (timed) {
+        for (auto &e : w.ev)
+            if (!e) HIPCHECK(hipEventCreate(&e));
+        HIPCHECK(hipEventRecord(w.ev[0], s));
+    }
+    hits_launch(w, b->mem_off.as<uint64_t>(), b->mems.as<pgx_mem>(), lw.vals.as<uint64_t>(), n, b->n_mems, n_seq, W, flags, s);
+    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
+    HIPCHECK(hipStreamSynchronize(s));
+    w.ms = 0;
+    if (timed) HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
+    w.flags = flags;
+    w.set_words = W;
+    w.n_reads = n;
+    w.n_seq = n_seq;
+    w.valid = true;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+static void hits_header(const pgx_batch *b, pgx_read_hits *out) {
+    const HitsWork &w = b->hw;
+    std::memset(out, 0, sizeof *out);
+    out->n_reads = w.n_reads;
+    out->n_seq = w.n_seq;
+    out->set_words = w.set_words;
+    out->flags = w.flags;
+    out->ms_hits = w.ms;
+}
+
+extern "C" pgx_status pgx_batch_device_hits(pgx_batch *b, pgx_read_hits *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->hw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_hits: batch has no hits result");
+    const HitsWork &w = b->hw;
+    hits_header(b, out);
+    out->hits = w.hits.as<pgx_read_hit>();
+    out->best_sets = (w.flags & PGX_HITS_BEST_SETS) ? w.best_sets.as<uint64_t>() : nullptr;
+    out->scores = (w.flags & PGX_HITS_SCORES) ? w.scores.as<uint32_t>() : nullptr;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_batch_hits(pgx_batch *b, pgx_read_hits *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->hw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_hits: batch has no hits result");
+    use_device(b->device);
+    HitsWork &w = b->hw;
+    const uint64_t n = w.n_reads;
+    const bool best = (w.flags & PGX_HITS_BEST_SETS) != 0, scores = (w.flags & PGX_HITS_SCORES) != 0;
+    w.h_hits.ensure((n ? n : 1) * sizeof(pgx_read_hit));
+    if (n) HIPCHECK(hipMemcpyAsync(w.h_hits.p, w.hits.p, n * sizeof(pgx_read_hit), hipMemcpyDeviceToHost, b->own));
+    if (best) {
+        w.h_best_sets.ensure((n ? n * w.set_words : 1) * 8);
+        if (n) HIPCHECK(hipMemcpyAsync(w.h_best_sets.p, w.best_sets.p, n * w.set_words * 8, hipMemcpyDeviceToHost, b->own));
+    }
+    if (scores) {
+        w.h_scores.ensure((n ? n * w.n_seq : 1) * 4);
+        if (n) HIPCHECK(hipMemcpyAsync(w.h_scores.p, w.scores.p, n * w.n_seq * 4, hipMemcpyDeviceToHost, b->own));
+    }
+    HIPCHECK(hipStreamSynchronize(b->own)); // (the kernel completed inside pgx_batch_read_hits, on whatever stream it used)
+    hits_header(b, out);
+    out->hits = w.h_hits.as<pgx_read_hit>();
+    out->best_sets = best ? w.h_best_sets.as<uint64_t>() : nullptr;
+    out->scores = scores ? w.h_scores.as<uint32_t>() : nullptr;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_read_hits_arrays(int device, const uint64_t *mem_offsets, uint64_t n_reads, const pgx_mem *mems, const uint64_t *sets, uint32_t set_words,
+                                           uint64_t n_seq, uint32_t flags, pgx_read_hit *hits, uint64_t *best_sets, uint32_t *scores) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_read_hits_arrays");
+    checked_device_count();
+    if (flags & ~HITS_FLAGS) throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: unknown flag");
+    if (set_words < 1 || set_words > PGX_ML_SET_WORDS_MAX || n_seq == 0 || (n_seq + 63) / 64 != set_words)
+        throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: set_words must be ceil(n_seq / 64) and 1 .. " + std::to_string(PGX_ML_SET_WORDS_MAX) + ", got set_words " +
+                                     std::to_string(set_words) + " for n_seq " + std::to_string(n_seq));
+    if (!mem_offsets || (n_reads && !hits) || ((flags & PGX_HITS_BEST_SETS) && n_reads && !best_sets) || ((flags & PGX_HITS_SCORES) && n_reads && !scores))
+        throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: null argument");
+    (void)hits_lane_shift(n_reads, n_seq, set_words, "pgx_read_hits_arrays"); // (before the arrays are read)
+    bool ok = mem_offsets[0] == 0;
+    for (uint64_t i = 0; ok && i < n_reads; i++) ok = mem_offsets[i] <= mem_offsets[i + 1];
+    if (!ok) throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: mem_offsets must start at 0 and never decrease");
+    const uint64_t m = mem_offsets[n_reads];
+    if (m && (!mems || !sets)) throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: null argument");
+    use_device(device);
+    struct Work { // device copies of the input + the stage's buffers, released on every way out
+        DevBuf mem_off, mems, sets;
+        HitsWork w;
+        ~Work() {
+            DevBuf *all[] = {&mem_off, &mems, &sets};
+            for (DevBuf *d : all) d->release();
+            w.release();
+        }
+    } k;
+    upload(k.mem_off, mem_offsets, (n_reads + 1) * 8);
+    upload(k.mems, mems, m * sizeof(pgx_mem));
+    upload(k.sets, sets, m * set_words * 8);
+    hipStream_t s = nullptr;
+    if (n_reads) { // the precondition, before anything is written
+        k.w.bad.ensure(8);
+        HIPCHECK(hipMemsetAsync(k.w.bad.p, 0xFF, 8, s));
+        hipLaunchKernelGGL(pgx_read_hits_check_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, s, (const uint64_t *)k.mem_off.as<uint64_t>(),
+                           (const pgx_mem *)k.mems.as<pgx_mem>(), n_reads, m, k.w.bad.as<unsigned long long>());
+        HIPCHECK(hipGetLastError());
+        const uint64_t bad = read_u64(k.w.bad.as<uint64_t>(), s);
+        if (bad != ~0ull) throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: the MEM starts of read " + std::to_string(bad) + " do not ascend strictly");
+    }
+    hits_launch(k.w, k.mem_off.as<uint64_t>(), k.mems.as<pgx_mem>(), k.sets.as<uint64_t>(), n_reads, m, n_seq, set_words, flags, s);
+    if (n_reads) {
+        HIPCHECK(hipMemcpyAsync(hits, k.w.hits.p, n_reads * sizeof(pgx_read_hit), hipMemcpyDeviceToHost, s));
+        if (flags & PGX_HITS_BEST_SETS) HIPCHECK(hipMemcpyAsync(best_sets, k.w.best_sets.p, n_reads * set_words * 8, hipMemcpyDeviceToHost, s));
+        if (flags & PGX_HITS_SCORES) HIPCHECK(hipMemcpyAsync(scores, k.w.scores.p, n_reads * n_seq * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(hipStreamSynchronize(s));
     return PGX_OK;
     PGX_GUARD_END
 }

@@ -358,6 +358,16 @@ __global__ void pgx_ml_set_count_kernel(const unsigned long long *sets, uint64_t
 __global__ void pgx_ml_set_expand_kernel(const unsigned long long *sets, uint64_t np, uint32_t W, const uint64_t *uloc, uint64_t *out);
 __global__ void pgx_ml_stride_kernel(uint64_t *out, uint64_t n, uint64_t stride);
 
+// ---- pgx_hits_kernels.hip: read hits (pgx_batch_read_hits, pgx_read_hits_arrays); sets: n_mems x W words in the PGX_LOCATE_SEQ_SETS form
+#define PGX_HITS_THREADS 256
+// n_seq <= 64: Sp = 1 << sp_shift lanes a read (Sp = the power of two >= n_seq), PGX_HITS_THREADS / Sp reads a block
+__global__ void pgx_read_hits_kernel(const uint64_t *mem_off, const pgx_mem *mems, const unsigned long long *sets, uint64_t n_reads, uint64_t n_mems, uint64_t n_seq,
+                                     uint32_t sp_shift, uint32_t flags, pgx_read_hit *hits, unsigned long long *best_sets, uint32_t *scores);
+// n_seq > 64 (2 <= W <= PGX_ML_SET_WORDS_MAX): a wave a read
+__global__ void pgx_read_hits_wide_kernel(const uint64_t *mem_off, const pgx_mem *mems, const unsigned long long *sets, uint64_t n_reads, uint64_t n_mems,
+                                          uint64_t n_seq, uint32_t W, uint32_t flags, pgx_read_hit *hits, unsigned long long *best_sets, uint32_t *scores);
+__global__ void pgx_read_hits_check_kernel(const uint64_t *mem_off, const pgx_mem *mems, uint64_t n_reads, uint64_t n_mems, unsigned long long *bad);
+
 // literal count image: COMPAT count_encoded / LF_encoded on an encoded index without N, block by block as the
 // reference's rankAt_encoded (src/r-index.cpp:570-590) sees it -- true cumulative counts, run scan one varint late
 struct PgxLitImage {

@@ -140,6 +140,25 @@ struct LocWork {
     }
 };
 
+// pgx_batch_read_hits' buffers (grow-only) and its result; pgx_read_hits_arrays uses one of its own
+struct HitsWork {
+    DevBuf hits, best_sets, scores, bad;
+    HostBuf h_hits, h_best_sets, h_scores;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool valid = false;
+    uint32_t flags = 0, set_words = 0;
+    uint64_t n_reads = 0, n_seq = 0;
+    float ms = 0;
+    void release() {
+        DevBuf *all[] = {&hits, &best_sets, &scores, &bad};
+        for (DevBuf *d : all) d->release();
+        h_hits.release(); h_best_sets.release(); h_scores.release();
+        for (auto &e : ev)
+            if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        valid = false;
+    }
+};
+
 inline uint64_t with_slack(uint64_t v) { return v + v / 4 + 64; }
 
 // Device scalars of the stage, sc[] (zeroed by the caller): [0] big-list length [1] large-list length [2] largest run count on the

@@ -94,14 +94,24 @@ class Text(C.Structure):  # pgx_text
 
 FORMAT_STDERR, FORMAT_LOCATE_POSITIONS, FORMAT_LOCATE_SEQS = 1, 2, 4  # pgx_format_params.flags
 
+HITS_BEST_SETS, HITS_SCORES = 1, 2  # pgx_batch_read_hits / pgx_read_hits_arrays flags
+NO_SEQUENCE = 0xFFFFFFFF            # pgx_read_hit.best_seq of a read without a located MEM
+READ_HIT_DTYPE = np.dtype([("best_score", "<u8"), ("next_score", "<u8"), ("covered", "<u8"), ("best_seq", "<u4"), ("n_best", "<u4"),
+                           ("n_located", "<u4"), ("n_mems", "<u4")])  # pgx_read_hit, 40 bytes
+
+
+class ReadHits(C.Structure):  # pgx_read_hits: host pointers (pgx_batch_hits) or device pointers (pgx_batch_device_hits)
+    _fields_ = [("n_reads", u64), ("n_seq", u64), ("set_words", u32), ("flags", u32), ("hits", p), ("best_sets", p), ("scores", p),
+                ("ms_hits", C.c_float), ("reserved", u32)]
+
 
 class DeviceArray:
     """a device buffer owned by a batch, exposed through __cuda_array_interface__ (zero copy: torch.as_tensor(a, device="cuda"));
     64-bit unsigned values are presented as int64"""
 
-    def __init__(self, ptr, shape, owner):
+    def __init__(self, ptr, shape, owner, typestr="<i8"):
         self.owner = owner  # keeps the batch alive
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<i8", "data": (int(ptr or 0), False), "version": 2, "strides": None}
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr or 0), False), "version": 2, "strides": None}
 
 
 class ExchangeResult(C.Structure):
@@ -230,6 +240,10 @@ def lib():
     L.pgx_batch_locate.argtypes = [p, u32, u64, p]
     L.pgx_batch_locations.argtypes = [p, C.POINTER(Locations)]
     L.pgx_batch_device_locations.argtypes = [p, C.POINTER(Locations)]
+    L.pgx_batch_read_hits.argtypes = [p, u32, p]
+    L.pgx_batch_hits.argtypes = [p, C.POINTER(ReadHits)]
+    L.pgx_batch_device_hits.argtypes = [p, C.POINTER(ReadHits)]
+    L.pgx_read_hits_arrays.argtypes = [C.c_int, p, u64, p, p, u32, u64, u32, p, p, p]
     L.pgx_batch_result_compact.argtypes = [p, C.POINTER(CompactResult)]
     L.pgx_compact_expand.argtypes = [C.POINTER(CompactResult), u64, u64, p, p, p, p, p]
     L.pgx_compact_bound.argtypes = [u64, u64, u64, u32]
@@ -814,6 +828,28 @@ def format_result(device, result, first_seq=0, flags=0, max_length=0, locations=
                 text_guard=tb[nbv:], err_guard=eb[nev:])
 
 
+def read_hits_arrays(device, mem_offsets, mems, sets, n_seq, flags=0, set_words=None, out=None):
+    """pgx_read_hits_arrays: the read-hits kernels on host arrays (mem_offsets uint64[n_reads + 1], mems MEM_DTYPE, sets
+    uint64[n_mems, W]): dict(hits READ_HIT_DTYPE[n_reads], best_sets uint64[n_reads, W] or None, scores uint32[n_reads, n_seq] or
+    None).  set_words: W as handed to the library (default ceil(n_seq / 64)); out: a dict of arrays to write into (tests)"""
+    mem_offsets = np.ascontiguousarray(mem_offsets, dtype=np.uint64)
+    mems = np.ascontiguousarray(mems, dtype=MEM_DTYPE)
+    sets = np.ascontiguousarray(sets, dtype=np.uint64)
+    n = len(mem_offsets) - 1
+    W = (int(n_seq) + 63) // 64 if set_words is None else int(set_words)
+    res = out if out is not None else {}
+    if "hits" not in res:
+        res["hits"] = np.zeros(n, dtype=READ_HIT_DTYPE)
+    if "best_sets" not in res:
+        res["best_sets"] = np.zeros((n, max(W, 0)), dtype=np.uint64) if flags & HITS_BEST_SETS else None
+    if "scores" not in res:
+        res["scores"] = np.zeros((n, int(n_seq)), dtype=np.uint32) if flags & HITS_SCORES else None
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().pgx_read_hits_arrays(device, mem_offsets.ctypes.data, n, mems.ctypes.data, sets.ctypes.data, W, int(n_seq), flags,
+                                      ptr(res["hits"]), ptr(res["best_sets"]), ptr(res["scores"])))
+    return res
+
+
 def find_mems_sharded(index, devices, reads_cat, offsets, min_len, min_occ, tags=False):
     """pgx_find_mems_sharded: contiguous read slices, slice i on devices[i]; returns the per-slice result dicts in slice order"""
     reads_cat = np.ascontiguousarray(reads_cat, dtype=np.uint8)
@@ -1058,6 +1094,37 @@ class Batch:
         out["values"] = DeviceArray(r.values, (out["n_values"],), self)
         if out["flags"] & LOCATE_SEQ_SETS:
             out["sets"] = DeviceArray(r.values, (out["n_mems"], out["set_words"]), self)
+        return out
+
+    def read_hits(self, flags=0, stream=None):
+        """pgx_batch_read_hits on the sets of the last locate(LOCATE_SEQ_SETS), then hits()"""
+        _check(self.L.pgx_batch_read_hits(self.b, flags, stream))
+        return self.hits()
+
+    def _hits(self, fn):
+        r = ReadHits()
+        _check(fn(self.b, C.byref(r)))
+        return r, dict(n_reads=int(r.n_reads), n_seq=int(r.n_seq), set_words=int(r.set_words), flags=int(r.flags), ms_hits=float(r.ms_hits))
+
+    def hits(self):
+        """the last read hits as numpy arrays: hits READ_HIT_DTYPE[n_reads], best_sets uint64[n_reads, W] (None without
+        HITS_BEST_SETS), scores uint32[n_reads, n_seq] (None without HITS_SCORES), with n_reads, n_seq, set_words, flags, ms_hits"""
+        r, out = self._hits(self.L.pgx_batch_hits)
+        n, W, q = out["n_reads"], out["set_words"], out["n_seq"]
+        out["hits"] = np.frombuffer(C.string_at(r.hits, n * 40), dtype=READ_HIT_DTYPE).copy() if n else np.zeros(0, READ_HIT_DTYPE)
+        out["best_sets"] = _u64_array(C.cast(r.best_sets, C.POINTER(u64)), n * W).reshape(n, W) if r.best_sets else None
+        out["scores"] = (np.frombuffer(C.string_at(r.scores, n * q * 4), dtype=np.uint32).copy() if n * q else np.zeros(0, np.uint32)).reshape(n, q) if r.scores else None
+        return out
+
+    def device_hits(self):
+        """the same as device arrays (valid until the next run / upload / read_hits / free): hits int64[n_reads, 5] (the 40-byte
+        records as words), best_sets int64[n_reads, W], scores uint32[n_reads, n_seq]"""
+        r, out = self._hits(self.L.pgx_batch_device_hits)
+        n, W, q = out["n_reads"], out["set_words"], out["n_seq"]
+        out["device"] = True
+        out["hits"] = DeviceArray(r.hits, (n, 5), self)
+        out["best_sets"] = DeviceArray(r.best_sets, (n, W), self) if r.best_sets else None
+        out["scores"] = DeviceArray(r.scores, (n, q), self, "<u4") if r.scores else None
         return out
 
     def free(self):

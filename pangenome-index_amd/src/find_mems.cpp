@@ -13,7 +13,9 @@
 //                 --result full|compact (default full; compact: the result crosses the link as the compact byte stream, pgx_batch_result_compact,
 //                 and every formatter thread expands its own blocks, pgx_compact_expand; the same text either way),
 //                 --format host|device (default host; device: the text itself is written on the device, pgx_batch_format -- no result arrays cross the link,
-//                 no formatter threads run, --result has no effect; the same text either way)
+//                 no formatter threads run, --result has no effect; the same text either way),
+//                 --hits FILE (one line per read: which indexed sequence the read matches best, pgx_batch_read_hits; stdout and stderr stay as they are),
+//                 --hits-max K (MEMs with more occurrences count as not located in the hits), --hits-only (no MEM text: stdout stays empty; not with --locate)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -142,6 +144,7 @@ struct Done {
     const char *text = nullptr, *etext = nullptr;
     size_t text_n = 0, etext_n = 0;
     double mem_s = 0, tag_s = 0;
+    std::string hits; // --hits: the lines of this batch
     std::string error;
 };
 
@@ -232,14 +235,37 @@ struct Rendezvous {
     }
 };
 
-int main(int argc, char **argv) {
-    if (argc < 6) {
-        std::cerr << "usage: find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ>"
-                     " [--device N | --gpus N | --devices a,b,..] [--streams W] [--mode compat|strict] [--batch N]"
-                     " [--tags-format auto|bytecode|compact] [--quiet] [--reads-format lines|fasta|fastq|auto] [--device-parse]"
-                     " [--locate positions|seqs] [--locate-max K] [--result full|compact] [--format host|device]" << std::endl;
-        return EXIT_FAILURE;
+// --hits: the lines of reads [0, n) of a batch, appended to out ("read" is the number of the read's "Seq:" line)
+static const char HITS_HEADER[] = "#read\tmems\tlocated\tcovered\tbest\tn_best\tbest_seq\tnext\n";
+static void format_hits(const pgx_read_hit *hits, size_t n, uint64_t first_seq, std::string &out) {
+    out.resize(n * (8 * 21));
+    char *p = &out[0];
+    for (size_t i = 0; i < n; i++) {
+        const pgx_read_hit &x = hits[i];
+        p = put_u64(p, first_seq + i + 1); *p++ = '\t';
+        p = put_u64(p, x.n_mems); *p++ = '\t';
+        p = put_u64(p, x.n_located); *p++ = '\t';
+        p = put_u64(p, x.covered); *p++ = '\t';
+        p = put_u64(p, x.best_score); *p++ = '\t';
+        p = put_u64(p, x.n_best); *p++ = '\t';
+        if (x.best_seq == PGX_NO_SEQUENCE) *p++ = '*'; else p = put_u64(p, x.best_seq);
+        *p++ = '\t';
+        p = put_u64(p, x.next_score); *p++ = '\n';
     }
+    out.resize((size_t)(p - &out[0]));
+}
+
+static int usage() {
+    std::cerr << "usage: find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ>"
+                 " [--device N | --gpus N | --devices a,b,..] [--streams W] [--mode compat|strict] [--batch N]"
+                 " [--tags-format auto|bytecode|compact] [--quiet] [--reads-format lines|fasta|fastq|auto] [--device-parse]"
+                 " [--locate positions|seqs] [--locate-max K] [--result full|compact] [--format host|device]"
+                 " [--hits FILE [--hits-max K] [--hits-only (not with --locate)]]" << std::endl;
+    return EXIT_FAILURE;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 6) return usage();
     const std::string r_index_file = argv[1], tag_array_index = argv[2], reads_file = argv[3];
     const size_t mem_length = (size_t)std::stoi(argv[4]); // find_mems.cpp:17 (std::stoi -> size_t)
     const size_t min_occ = (size_t)std::stoi(argv[5]);
@@ -253,6 +279,9 @@ int main(int argc, char **argv) {
     uint64_t locate_max = 0;
     bool compact_result = false;
     bool format_device = false; // --format device: stdout and the per-read stderr lines come from pgx_batch_format
+    std::string hits_file;      // --hits: the read hits of every batch go to this file
+    uint64_t hits_max = 0;
+    bool hits_max_given = false, hits_only = false;
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -306,8 +335,22 @@ int main(int argc, char **argv) {
             else if (f == "host") format_device = false;
             else { std::cerr << "--format: host or device" << std::endl; return EXIT_FAILURE; }
         }
+        else if (a == "--hits") { hits_file = next(); if (hits_file.empty()) { std::cerr << "--hits: a file name" << std::endl; return EXIT_FAILURE; } }
+        else if (a == "--hits-max") {
+            const std::string f = next();
+            errno = 0;
+            char *endp = nullptr;
+            const unsigned long long k = f.empty() || f.size() > 19 || f.find_first_not_of("0123456789") != std::string::npos ? 0 : std::strtoull(f.c_str(), &endp, 10);
+            if (!endp || *endp || errno) { std::cerr << "--hits-max: a number of occurrences >= 0 (0: no cap)" << std::endl; return EXIT_FAILURE; }
+            hits_max = k;
+            hits_max_given = true;
+        }
+        else if (a == "--hits-only") hits_only = true;
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
+    if ((hits_max_given || hits_only) && hits_file.empty()) return usage();
+    if (hits_only && locate_mode) { std::cerr << "--hits-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
+    const bool want_hits = !hits_file.empty();
     if (batch_reads == 0) batch_reads = 1;
     if (locate_max && !locate_mode) { std::cerr << "--locate-max needs --locate" << std::endl; return EXIT_FAILURE; }
 
@@ -346,6 +389,24 @@ int main(int argc, char **argv) {
         if (pgx_index_to_device(h, d) != PGX_OK) { std::cerr << pgx_last_error() << std::endl; return EXIT_FAILURE; }
     auto time3 = std::chrono::high_resolution_clock::now();
     std::cerr << "Loading tag arrays took " << std::chrono::duration<double>(time3 - time2).count() << " seconds" << std::endl;
+    // --hits: whether this index serves sequence sets at all is the library's to say, so ask it with a batch of one read before anything
+    // is produced (more than 4096 sequences, a COMPAT index without N, an image file without the locate image)
+    std::FILE *hits_fp = nullptr;
+    if (want_hits) {
+        static const uint8_t probe_read[4] = {'A', 'C', 'G', 'T'};
+        static const uint64_t probe_offs[2] = {0, 4};
+        pgx_batch *pb = nullptr;
+        pgx_status st = pgx_batch_create(h, devices[0], probe_read, probe_offs, 1, &pb);
+        if (st == PGX_OK) st = pgx_batch_run(pb, mem_length, min_occ, 0, nullptr);
+        if (st == PGX_OK) st = pgx_batch_locate(pb, PGX_LOCATE_SEQ_SETS, hits_max, nullptr);
+        if (st == PGX_OK) st = pgx_batch_read_hits(pb, 0, nullptr);
+        const std::string msg = st == PGX_OK ? "" : pgx_last_error();
+        pgx_batch_free(pb);
+        if (st != PGX_OK) { std::cerr << msg << (st == PGX_ERR_UNSUPPORTED ? " (find_mems --hits)" : "") << std::endl; return EXIT_FAILURE; }
+        hits_fp = std::fopen(hits_file.c_str(), "wb");
+        if (!hits_fp) { std::cerr << "Cannot open hits file: " << hits_file << std::endl; return EXIT_FAILURE; }
+        std::fwrite(HITS_HEADER, 1, sizeof HITS_HEADER - 1, hits_fp);
+    }
 
     // ---- the reads file, mapped: the reference reads it with std::getline (find_mems.cpp:96); here a planner cuts it into byte ranges that
     //      end at a newline, PARSE threads turn ranges into batches side by side (line splitting was what bounded the single reader thread of
@@ -592,10 +653,18 @@ int main(int argc, char **argv) {
                                                  reinterpret_cast<const uint8_t *>(j->pk.p) + j->side_at, j->n_side);
             } else if (!dev_parse) st = b ? pgx_batch_upload(b, rp, j->offs.data(), n) : pgx_batch_create(h, device, rp, j->offs.data(), n, &b);
             uint64_t t1 = now_ns();
-            if (st == PGX_OK) st = pgx_batch_run(b, mem_length, min_occ, PGX_RUN_TAGS | PGX_RUN_TIMING, nullptr);
+            if (st == PGX_OK) st = pgx_batch_run(b, mem_length, min_occ, (hits_only ? 0u : PGX_RUN_TAGS) | PGX_RUN_TIMING, nullptr); // (the tag positions are part of the MEM text only)
             uint64_t t2 = now_ns();
             pgx_compact_result cr;
-            if (format_device) {
+            std::vector<pgx_read_hit> hit_recs; // --hits: the 40-byte records, taken before the locate that --locate asks for replaces the sets
+            if (st == PGX_OK && want_hits) {
+                st = pgx_batch_locate(b, PGX_LOCATE_SEQ_SETS, hits_max, nullptr);
+                if (st == PGX_OK) st = pgx_batch_read_hits(b, 0, nullptr);
+                pgx_read_hits rh;
+                if (st == PGX_OK) st = pgx_batch_hits(b, &rh);
+                if (st == PGX_OK) hit_recs.assign(rh.hits, rh.hits + rh.n_reads);
+            }
+            if (format_device || hits_only) {
                 // nothing to download: the device writes the text below, once the batch knows the number of its first read
             } else if (st == PGX_OK && compact_result) {
                 st = pgx_batch_result_compact(b, &cr);
@@ -637,7 +706,8 @@ int main(int argc, char **argv) {
                     d->mem_s = 1e-3 * (t.ms_find_mems + t.ms_compact);
                     d->tag_s = 1e-3 * (t.ms_tag_locate + t.ms_tag_gather + t.ms_tag_sort);
                 }
-                if (format_device) {
+                if (want_hits) format_hits(hit_recs.data(), hit_recs.size(), j->first_seq, d->hits);
+                if (format_device && !hits_only) {
                     // the text of the batch from the device, handed to the writer where it is
                     const uint64_t t3w = now_ns();
                     wait_written(1);
@@ -658,7 +728,7 @@ int main(int argc, char **argv) {
                         text_bytes += tx.n_bytes + tx.n_err_bytes;
                     }
                 }
-                const unsigned parts = format_device ? 0u : n < 4096 ? 1u : n_fmt;
+                const unsigned parts = format_device || hits_only ? 0u : n < 4096 ? 1u : n_fmt;
                 if (parts) d->outs.resize(parts);
                 if (parts) d->errs.resize(parts);
                 // --result compact: the parts are cut on multiples of 64 reads and every thread expands the blocks of its part first
@@ -674,7 +744,7 @@ int main(int argc, char **argv) {
                         return pgx_last_error(); // (the message is thread-local)
                     return std::string();
                 };
-                if (parts == 0) { // (--format device: the text is there)
+                if (parts == 0) { // (--format device: the text is there; --hits-only: there is none)
                 } else if (parts == 1) {
                     if (compact_result) d->error = expand_part(0);
                     if (d->error.empty()) format_range(r, 0, n, j->first_seq, quiet, lout, d->outs[0], d->errs[0]);
@@ -733,6 +803,7 @@ int main(int argc, char **argv) {
         }
         if (d->text_n) std::fwrite(d->text, 1, d->text_n, stdout);
         if (d->etext_n) std::fwrite(d->etext, 1, d->etext_n, stderr);
+        if (hits_fp && !d->hits.empty()) std::fwrite(d->hits.data(), 1, d->hits.size(), hits_fp);
         ns_write += now_ns() - tw0;
         total_mem_time += d->mem_s;
         total_tag_time += d->tag_s;
@@ -754,6 +825,7 @@ int main(int argc, char **argv) {
         for (auto &kv : finished)
             if (!kv.second->error.empty()) { error = kv.second->error; break; }
     if (error.empty() && failed) error = "find_mems: a device batch failed";
+    if (hits_fp && (std::fclose(hits_fp) != 0) && error.empty()) error = "Cannot write hits file: " + hits_file;
     if (!error.empty()) {
         std::cerr << error << std::endl;
         return EXIT_FAILURE;
@@ -768,8 +840,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "[find_mems] --format device: of format %.3f s: pgx_batch_format %.3f (its kernels %.3f), waiting for the writer to release a text buffer %.3f; %.1f MB of text\n",
                      1e-9 * (double)ns_format.load(), 1e-9 * (double)ns_devfmt.load(), 1e-6 * (double)us_devfmt_kernels.load(), 1e-9 * (double)ns_lent.load(),
                      1e-6 * (double)text_bytes.load());
-    std::cout << "\nTotal time for finding all MEMs: " << total_mem_time << " seconds" << std::endl; // :144
-    std::cout << "Total time for all tag queries: " << total_tag_time << " seconds" << std::endl;   // :145
+    if (!hits_only) {
+        std::cout << "\nTotal time for finding all MEMs: " << total_mem_time << " seconds" << std::endl; // :144
+        std::cout << "Total time for all tag queries: " << total_tag_time << " seconds" << std::endl;   // :145
+    }
     pgx_index_close(h);
     return 0;
 }
