@@ -717,6 +717,89 @@ pgx_status pgx_batch_device_hits(pgx_batch *b, pgx_read_hits *out);
 pgx_status pgx_read_hits_arrays(int device, const uint64_t *mem_offsets, uint64_t n_reads, const pgx_mem *mems, const uint64_t *sets, uint32_t set_words,
                                 uint64_t n_seq, uint32_t flags, pgx_read_hit *hits, uint64_t *best_sets, uint32_t *scores);
 
+/* ---- read placement: every read placed on its best sequence diagonal, on the device ------------------------------------------
+ * The consumer of the packed positions (pgx_batch_locate with flags = 0): where on a sequence a read lies, not only on which one.  The
+ * occurrences of a read's MEMs vote for diagonals, every diagonal is scored by the read positions it covers, and one 64-byte record
+ * per read crosses the link instead of 8 bytes per occurrence.
+ *
+ * DEFINITIONS.  Read r has the MEMs m in [mem_offsets[r], mem_offsets[r + 1]); MEM m has the values values[loc_offsets[m] ..
+ * loc_offsets[m + 1]) of a completed pgx_batch_locate(flags = 0 [| PGX_LOCATE_CHAINS]).  With L = pgx_index_info.max_length:
+ *   anchor      of value v of MEM m: seq = v / L, off = v % L, diag = (int64)off - (int64)mems[m].start: the sequence offset on which
+ *               read position 0 falls; negative when the read hangs over the sequence start.
+ *   placement   of read r: a pair (seq, diag) that at least one anchor of r has.
+ *   len(m)      as in read hits: end - start if end > start, else 0.
+ *   cov(r, seq, diag) = the number of read positions in the union of [start, end) over the MEMs of r that have an anchor on
+ *               (seq, diag).  Overlapping and nested MEMs count a position once.
+ * A MEM that is not located (cap, invalid range, size <= 0) has no values and adds nothing.  Placements of a read are ordered by
+ * (seq ascending, diag ascending as signed); "first" means first in that order.  Precondition, as for read hits: MEM starts ascend
+ * strictly within a read (pgx_batch_run guarantees it; ends need not ascend).
+ * pgx_read_place (64 bytes, little endian):
+ *    0 best_score    u64  max over the read's placements of cov; 0 when the read has no anchor
+ *    8 next_score    u64  the largest cov of a placement that is < best_score; 0 if none
+ *   16 best_diag     i64  diag of the first placement that reaches best_score; 0 when best_score == 0
+ *   24 n_anchors     u64  values of the read's MEMs (duplicate values inside one MEM count)
+ *   32 n_placements  u64  distinct (seq, diag)
+ *   40 best_seq      u32  seq of that first best placement; PGX_NO_SEQUENCE when best_score == 0
+ *   44 n_best        u32  placements with cov == best_score > 0, held at 2^32 - 1
+ *   48 best_mems     u32  distinct MEMs with an anchor on the first best placement; 0 when best_score == 0
+ *   52 n_located     u32  MEMs of r with at least one value
+ *   56 n_mems        u32  all MEMs of r
+ *   60 reserved      u32  0
+ * A placement whose MEMs all have len == 0 has cov == 0: it counts in n_placements but is never "best".
+ * PGX_PLACE_LIST adds every placement of every read as a CSR list: place_offsets[n_reads + 1] and places[], 24-byte pgx_placement
+ * records, per read in the placement order above; n_placements of the record equals the read's list length.
+ * The result does not depend on the order of a MEM's values, on the memory budget, on the lane packing or on the locate path. */
+#define PGX_PLACE_LIST 1u
+typedef struct {
+    uint64_t best_score, next_score;
+    int64_t best_diag;
+    uint64_t n_anchors, n_placements;
+    uint32_t best_seq, n_best, best_mems, n_located, n_mems, reserved;
+} pgx_read_place;
+typedef struct {
+    int64_t diag;
+    uint64_t score; /* cov of the placement */
+    uint32_t seq;
+    uint32_t mems;  /* distinct MEMs with an anchor on it */
+} pgx_placement;
+typedef struct {
+    uint64_t n_reads;
+    uint64_t n_anchors;            /* values the call consumed */
+    uint64_t n_places;             /* length of places: 0 without PGX_PLACE_LIST */
+    uint32_t flags;                /* PGX_PLACE_* the call ran with */
+    uint32_t n_passes;             /* passes over consecutive whole reads the key buffer took (PGX_PLACE_BUDGET_MB) */
+    const pgx_read_place *reads;   /* n_reads */
+    const uint64_t *place_offsets; /* n_reads + 1; NULL without PGX_PLACE_LIST */
+    const pgx_placement *places;   /* n_places; NULL without PGX_PLACE_LIST */
+    float ms_place;                /* device time of the call when the run had PGX_RUN_TIMING, else 0 */
+    uint32_t reserved;
+} pgx_read_places;
+/* The placements of the last run from the packed positions of the last locate, which must be a completed pgx_batch_locate(0
+ * [| PGX_LOCATE_CHAINS]) and the batch's current locate result: PGX_ERR_ARG otherwise, with what the last locate ran with (also for an
+ * unknown flag); run, locate and an earlier place result then stay as they were.  Runs on `stream` (NULL = the batch's own), complete on
+ * return.  One 64-bit key per anchor is built, the keys of each read are sorted (the segmented sort of the tag stage) and swept, in
+ * passes over consecutive whole reads whose keys stay within PGX_PLACE_BUDGET_MB (environment, read per call, fractions allowed;
+ * default a quarter of the free device memory); a single read whose anchors exceed it is PGX_ERR_NOMEM naming the read.  The key holds
+ * sequence, biased diagonal and the MEM's ordinal within its read: where bits(n_seq * (max_length + largest MEM start)) + bits(most
+ * MEMs of a read - 1) exceed 64 the call is PGX_ERR_UNSUPPORTED, as are 2^31 reads or MEMs or more, before anything is written.  With
+ * PGX_PLACE_LIST the list must fit a quarter of the free device memory: PGX_ERR_NOMEM with both numbers otherwise.  Buffers grow only
+ * and are the stage's own: the places stay valid until the next run, upload, pgx_batch_read_place or free of the batch, and a later
+ * pgx_batch_locate of any form leaves them valid. */
+pgx_status pgx_batch_read_place(pgx_batch *b, uint32_t flags, void *stream);
+/* Host copy of the last places (pinned buffers owned by the batch) / the same as device pointers.  PGX_ERR_ARG when there are none. */
+pgx_status pgx_batch_places(pgx_batch *b, pgx_read_places *out);
+pgx_status pgx_batch_device_places(pgx_batch *b, pgx_read_places *out);
+/* The same kernels on host arrays (how they are tested on shapes no index produces).  mem_offsets: n_reads + 1 entries; mems:
+ * mem_offsets[n_reads] records; loc_offsets: mem_offsets[n_reads] + 1 entries; values: loc_offsets[last] values.  PGX_ERR_ARG with
+ * nothing written: an unknown flag, max_length or n_seq of 0, offsets that do not start at 0 or decrease, and -- checked on the device,
+ * the first offending read named -- MEM starts that do not ascend strictly and a value with v / max_length >= n_seq.  Duplicate values
+ * inside one MEM are allowed (n_anchors counts them, nothing else changes).  With PGX_PLACE_LIST place_offsets takes n_reads + 1
+ * entries and places up to places_cap records: PGX_ERR_NOMEM with the needed count when the list is longer (nothing is written).
+ * Both may be NULL without the flag.  PGX_ERR_NO_DEVICE without a GPU. */
+pgx_status pgx_read_place_arrays(int device, const uint64_t *mem_offsets, uint64_t n_reads, const pgx_mem *mems, const uint64_t *loc_offsets,
+                                 const uint64_t *values, uint64_t n_seq, uint64_t max_length, uint32_t flags, pgx_read_place *out,
+                                 uint64_t *place_offsets, pgx_placement *places, uint64_t places_cap);
+
 /* ---- compact result: the result of a run as a byte stream, encoded on the device, expanded on the host ---------------------
  * What pgx_batch_result downloads is six dense uint64 arrays (8 bytes per read, 48 per MEM, 8 per graph position), nearly all of
  * them zero bits.  The compact form carries the same values and is expanded to the same pgx_result; only it crosses the link.

@@ -1,4 +1,4 @@
-// pgx_batch.hip -- the pgx_batch object: uploads, pgx_batch_run, results, pgx_batch_locate, pgx_batch_read_hits.
+// pgx_batch.hip -- the pgx_batch object: uploads, pgx_batch_run, results, pgx_batch_locate, pgx_batch_read_hits, pgx_batch_read_place.
 //
 // Pipeline of pgx_batch_run (one HIP stream, results stay on the device):
 //   scan(cap)      -> slot offsets (worst-case MEMs per read: min(len, len - min_len + 1)); the slot buffer
@@ -85,6 +85,7 @@ struct pgx_batch {
     CompactWork cw; // pgx_batch_result_compact
     FormatWork fw;  // pgx_batch_format
     HitsWork hw;    // pgx_batch_read_hits
+    PlaceWork pw;   // pgx_batch_read_place
     uint64_t n_mems = 0, n_positions = 0, n_ext = 0, n_tag_overflow = 0;
     bool ran = false, ran_tags = false;
     // speculative sizing (pgx_batch_run): what the last run with these parameters produced
@@ -113,6 +114,7 @@ static void batch_release(pgx_batch *b) {
         b->cw.release();
         b->fw.release();
         b->hw.release();
+        b->pw.release();
         HostBuf *hb[] = {&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]};
         for (HostBuf *x : hb) x->release();
         for (auto &e : b->ev)
@@ -137,6 +139,7 @@ static void batch_reset_for_upload(pgx_batch *b, uint64_t n_reads, uint64_t max_
     b->ran = b->ran_tags = false;
     b->lw.valid = false;
     b->hw.valid = false;
+    b->pw.valid = false;
     b->plan_valid = false;
     b->slot_off_valid = false;
     b->class_valid = false;
@@ -1063,6 +1066,7 @@ extern "C" pgx_status pgx_batch_run(pgx_batch *b, uint64_t min_len, uint64_t min
     b->ran_tags = false;
     b->lw.valid = false; // (the locate result belongs to the run before)
     b->hw.valid = false; // (and so do the hits)
+    b->pw.valid = false; // (and the places)
     b->n_mems = b->n_positions = b->n_ext = b->n_tag_overflow = 0;
     std::memset(&b->timing, 0, sizeof b->timing);
     bool force_worst = false;
@@ -1930,6 +1934,329 @@ extern "C" pgx_status pgx_read_hits_arrays(int device, const uint64_t *mem_offse
         HIPCHECK(hipMemcpyAsync(hits, k.w.hits.p, n_reads * sizeof(pgx_read_hit), hipMemcpyDeviceToHost, s));
         if (flags & PGX_HITS_BEST_SETS) HIPCHECK(hipMemcpyAsync(best_sets, k.w.best_sets.p, n_reads * set_words * 8, hipMemcpyDeviceToHost, s));
         if (flags & PGX_HITS_SCORES) HIPCHECK(hipMemcpyAsync(scores, k.w.scores.p, n_reads * n_seq * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(hipStreamSynchronize(s));
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// read placement (pgx_place_kernels.hip; the definitions: include/pgx.h "read placement")
+static const uint32_t PLACE_FLAGS = PGX_PLACE_LIST;
+// reads, MEMs or keys one launch takes at a thread an item or fewer: a grid holds fewer than 2^32 threads, and a larger one would lose items without an error
+static const uint64_t PLACE_LAUNCH_ITEMS = 1ull << 31;
+
+// keys one pass may hold: PGX_PLACE_BUDGET_MB (read per call, fractions allowed), default a quarter of the free device memory
+static uint64_t place_budget_keys(size_t mem_free) {
+    uint64_t bytes = 0;
+    if (const char *e = std::getenv("PGX_PLACE_BUDGET_MB")) {
+        const double mb = std::strtod(e, nullptr);
+        if (mb > 0) bytes = (uint64_t)(mb * 1048576.0);
+    }
+    if (!bytes) bytes = mem_free / 4;
+    return std::min<uint64_t>(std::max<uint64_t>(bytes / 8, 1), PLACE_LAUNCH_ITEMS);
+}
+
+static uint32_t place_bits(unsigned __int128 v) {
+    uint32_t b = 0;
+    while (v) { b++; v >>= 1; }
+    return b;
+}
+
+// log2 of the lanes a read of the sweep takes: the power of two >= twice the mean anchors a read of the pass, 4 .. 64 (a longer read takes more
+// steps).  PGX_PLACE_LANES (tests; 1 .. 64, rounded up to a power of two) fixes it.  Results never depend on it.
+static uint32_t place_lane_shift(uint64_t keys, uint64_t reads) {
+    uint64_t want = reads ? 2 * ((keys + reads - 1) / reads) : 4;
+    want = std::min<uint64_t>(std::max<uint64_t>(want, 4), 64);
+    if (const char *e = std::getenv("PGX_PLACE_LANES")) {
+        const long v = std::strtol(e, nullptr, 10);
+        if (v >= 1 && v <= 64) want = (uint64_t)v;
+    }
+    uint32_t sh = 0;
+    while ((1ull << sh) < want) sh++;
+    return sh;
+}
+
+static size_t free_device_memory() {
+    size_t mem_free = 0, mem_total = 0;
+    if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); mem_free = 1ull << 30; }
+    return mem_free;
+}
+
+// The stage on device arrays, enqueued on s (synchronised where a size is read back): w.recs, and with PGX_PLACE_LIST w.place_off / w.places.
+// loc_off: n_mems + 1 value offsets, values: n_values.  Refuses before a result buffer is written.
+static void place_core(PlaceWork &w, const uint64_t *mem_off, const pgx_mem *mems, const uint64_t *loc_off, const uint64_t *values, uint64_t n, uint64_t n_mems,
+                       uint64_t n_values, uint64_t n_seq, uint64_t L, uint32_t flags, size_t mem_free, hipStream_t s, const std::string &who) {
+    if (n >= PLACE_LAUNCH_ITEMS || n_mems >= PLACE_LAUNCH_ITEMS)
+        throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n) + " reads with " + std::to_string(n_mems) + " MEMs exceed the " + std::to_string(PLACE_LAUNCH_ITEMS) +
+                                             " one launch holds: place the reads in smaller batches");
+    const bool list = (flags & PGX_PLACE_LIST) != 0;
+    // 1. plan: the anchors of every read, the first MEM of every MEM's read, the maxima of the key layout
+    //    ctr: [0] most MEMs of a read [1] largest MEM start [2] aoff[n] [3] aoff[0]; later [0] wave list [1] workgroup list [2] scratch total [3] placements of a pass [6..7] cut
+    w.aoff.ensure((n + 1) * 8); w.acnt.ensure((n ? n : 1) * 8); w.mfirst.ensure((n_mems ? n_mems : 1) * 8); w.ctr.ensure(64);
+    unsigned long long *ctr = w.ctr.as<unsigned long long>();
+    HIPCHECK(hipMemsetAsync(w.ctr.p, 0, 64, s));
+    hipLaunchKernelGGL(pgx_place_plan_kernel, dim3(grid_for(n + 1, 256)), dim3(256), 0, s, mem_off, loc_off, mems, n, n_mems, n_values, w.aoff.as<uint64_t>(),
+                       w.acnt.as<uint64_t>(), ctr);
+    if (n_mems) hipLaunchKernelGGL(pgx_place_first_kernel, dim3(grid_for(n_mems, 256)), dim3(256), 0, s, mem_off, n, n_mems, w.mfirst.as<uint64_t>());
+    HIPCHECK(hipGetLastError());
+    uint64_t c[4];
+    read_scalars(c, ctr, 32, s);
+    const uint64_t most_mems = c[0], bias = c[1], a_end = c[2], a_begin = std::min(c[3], c[2]);
+    const uint32_t ordinal_bits = place_bits(most_mems ? most_mems - 1 : 0);
+    const uint64_t span = L + bias;
+    const uint32_t group_bits = span < L ? 65u : place_bits((unsigned __int128)n_seq * span);
+    if (group_bits + ordinal_bits > 64)
+        throw Error(PGX_ERR_UNSUPPORTED, who + ": a key needs " + std::to_string(group_bits) + " bits for sequence and diagonal (" + std::to_string(n_seq) + " sequences x (max_length " +
+                                             std::to_string(L) + " + largest MEM start " + std::to_string(bias) + ")) and " + std::to_string(ordinal_bits) +
+                                             " bits for the MEM of a read (most MEMs of a read: " + std::to_string(most_mems) + "), 64 are available");
+    const uint64_t budget = place_budget_keys(mem_free);
+    const uint64_t *aoff = w.aoff.as<uint64_t>(), *acnt = w.acnt.as<uint64_t>();
+    w.recs.ensure((n ? n : 1) * sizeof(pgx_read_place)); w.pcount.ensure((n ? n : 1) * 8);
+    // 2. passes over consecutive whole reads whose keys fit the budget (one pass unless the batch exceeds it)
+    uint64_t U = 0; // placements listed by the passes so far
+    uint32_t passes = 0;
+    for (uint64_t r0 = 0, o0 = a_begin; r0 < n;) {
+        uint64_t r1 = n, o1 = a_end;
+        if (a_end - o0 > budget) {
+            hipLaunchKernelGGL(pgx_ml_cut_kernel, dim3(1), dim3(64), 0, s, aoff, n, r0, budget, reinterpret_cast<uint64_t *>(ctr + 6));
+            HIPCHECK(hipGetLastError());
+            uint64_t cut[2];
+            read_scalars(cut, ctr + 6, 16, s);
+            r1 = cut[0]; o1 = cut[1];
+            if (o1 - o0 > budget) // (the cut is a read at least)
+                throw Error(PGX_ERR_NOMEM, who + ": read " + std::to_string(r0) + " has " + std::to_string(o1 - o0) + " anchors, the keys of a pass hold " + std::to_string(budget) +
+                                               " (PGX_PLACE_BUDGET_MB)");
+        }
+        const uint64_t np = r1 - r0, nk = o1 - o0;
+        passes++;
+        // keys, then the segmented sort of the tag stage: a read is a segment, the size-class lists are built on the device
+        w.keys.ensure((nk ? nk : 1) * 8);
+        w.seg.ensure((np + 1) * 8); w.lists.ensure(2 * np * 8); w.need.ensure(np * 8); w.soff.ensure((np + 1) * 8); w.ucount.ensure(np * 8);
+        uint64_t *keys = w.keys.as<uint64_t>(), *seg = w.seg.as<uint64_t>(), *wave_list = w.lists.as<uint64_t>(), *wg_list = wave_list + np, *ucount = w.ucount.as<uint64_t>();
+        if (nk) {
+            hipLaunchKernelGGL(pgx_place_keys_kernel, dim3(grid_for(nk, PGX_ML_SPAN)), dim3(256), 0, s, mems, loc_off, (const uint64_t *)w.mfirst.as<uint64_t>(), values,
+                               (uint64_t)0, n_mems, o0, nk, L, span, bias, ordinal_bits, keys);
+            HIPCHECK(hipGetLastError());
+        }
+        HIPCHECK(hipMemsetAsync(w.ctr.p, 0, 32, s));
+        hipLaunchKernelGGL(pgx_ml_classify_kernel, dim3(grid_for(np + 1, 256)), dim3(256), 0, s, acnt + r0, aoff + r0, np, seg, wave_list, wg_list, w.need.as<uint64_t>(),
+                           ucount, ctr);
+        HIPCHECK(hipGetLastError());
+        scan_excl(1, w.need.p, np, 0, w.soff.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 2));
+        uint64_t lc[3];
+        read_scalars(lc, ctr, 24, s);
+        const uint64_t n_wave = lc[0], n_wg = lc[1], S = lc[2];
+        if (n_wave)
+            hipLaunchKernelGGL(pgx_tag_sort_unique_kernel<PgxTagDense>, dim3(grid_for(n_wave, 4)), dim3(256), 0, s, PgxTagDense{wave_list, acnt + r0, seg}, n_wave,
+                               (const uint64_t *)nullptr, (const uint64_t *)nullptr, keys, ucount);
+        if (n_wg) {
+            w.scratch.ensure((S ? S : 1) * 8);
+            HIPCHECK(hipFuncSetAttribute((const void *)pgx_tag_sort_large_kernel<PgxTagDense>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PGX_SORT_WG_LDS_CAP * 8)));
+            hipLaunchKernelGGL(pgx_tag_sort_large_kernel<PgxTagDense>, dim3(grid_for(n_wg, 1)), dim3(1024), (size_t)PGX_SORT_WG_LDS_CAP * 8, s,
+                               PgxTagDense{wg_list, acnt + r0, seg}, n_wg, (const uint64_t *)nullptr, (const uint64_t *)nullptr, keys, w.scratch.as<uint64_t>(),
+                               (const uint64_t *)w.soff.as<uint64_t>(), ucount);
+        }
+        HIPCHECK(hipGetLastError());
+        // the sweep, in launches of fewer than 2^32 threads
+        const uint32_t g_shift = place_lane_shift(nk, np);
+        const uint64_t per_launch = PLACE_LAUNCH_ITEMS >> g_shift;
+        auto sweep = [&](bool fill, const uint64_t *list_off, pgx_placement *places) {
+            for (uint64_t q0 = 0; q0 < np; q0 += per_launch) {
+                const uint64_t nr = std::min(per_launch, np - q0);
+                const dim3 grid(grid_for(nr, PGX_PLACE_THREADS >> g_shift)), block(PGX_PLACE_THREADS);
+                if (fill)
+                    hipLaunchKernelGGL(pgx_place_sweep_kernel<true>, grid, block, 0, s, mem_off, mems, loc_off, acnt, (const uint64_t *)keys, (const uint64_t *)seg,
+                                       (const uint64_t *)ucount, r0, r0 + q0, nr, n_mems, span, bias, ordinal_bits, g_shift, w.recs.as<pgx_read_place>(),
+                                       w.pcount.as<uint64_t>(), list_off, places);
+                else
+                    hipLaunchKernelGGL(pgx_place_sweep_kernel<false>, grid, block, 0, s, mem_off, mems, loc_off, acnt, (const uint64_t *)keys, (const uint64_t *)seg,
+                                       (const uint64_t *)ucount, r0, r0 + q0, nr, n_mems, span, bias, ordinal_bits, g_shift, w.recs.as<pgx_read_place>(),
+                                       w.pcount.as<uint64_t>(), list_off, places);
+                HIPCHECK(hipGetLastError());
+            }
+        };
+        sweep(false, nullptr, nullptr);
+        if (list) { // the pass's counts -> offsets behind the passes before, then the same walk writes the placements
+            w.loff.ensure((np + 1) * 8);
+            scan_excl(1, w.pcount.as<uint64_t>() + r0, np, 0, w.loff.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 3));
+            const uint64_t Up = read_u64(reinterpret_cast<const uint64_t *>(ctr + 3), s);
+            if ((U + Up) > (mem_free / 4) / sizeof(pgx_placement))
+                throw Error(PGX_ERR_NOMEM, who + ": PGX_PLACE_LIST takes at least " + std::to_string((U + Up) * sizeof(pgx_placement)) +
+                                               " bytes, a quarter of the free device memory is " + std::to_string(mem_free / 4));
+            w.places.ensure_keep((U + Up ? U + Up : 1) * sizeof(pgx_placement), U * sizeof(pgx_placement)); // (the stream is idle here: the read-back above synchronised it)
+            if (Up) sweep(true, w.loff.as<uint64_t>(), w.places.as<pgx_placement>() + U);
+            U += Up;
+        }
+        r0 = r1; o0 = o1;
+    }
+    if (list) {
+        w.place_off.ensure((n + 1) * 8);
+        w.places.ensure(sizeof(pgx_placement));
+        scan_excl(1, w.pcount.p, n, 0, w.place_off.as<uint64_t>(), w.scan_tmp, s);
+    }
+    w.flags = flags;
+    w.n_reads = n;
+    w.n_anchors = a_end - a_begin;
+    w.n_places = U;
+    w.n_passes = passes;
+}
+
+extern "C" pgx_status pgx_batch_read_place(pgx_batch *b, uint32_t flags, void *stream) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_read_place");
+    checked_device_count();
+    if (!b) throw Error(PGX_ERR_ARG, "pgx_batch_read_place: null batch");
+    // (what is refused here leaves an earlier place result as it was)
+    if (flags & ~PLACE_FLAGS) throw Error(PGX_ERR_ARG, "pgx_batch_read_place: unknown flag");
+    if (!b->ran) throw Error(PGX_ERR_ARG, "pgx_batch_read_place: batch has not been run");
+    const LocWork &lw = b->lw;
+    if (!lw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_read_place: needs a completed pgx_batch_locate(flags = 0), the batch has no locate result");
+    if (lw.flags != 0 || lw.n_mems != b->n_mems)
+        throw Error(PGX_ERR_ARG, "pgx_batch_read_place: needs a completed pgx_batch_locate(flags = 0), the last pgx_batch_locate ran with flags " + std::to_string(lw.flags));
+    use_device(b->device);
+    pgx_device_image *d = locate_image(b->h, b->device);
+    hipStream_t s = stream ? (hipStream_t)stream : b->own;
+    PlaceWork &w = b->pw;
+    w.valid = false;
+    const size_t mem_free = free_device_memory();
+    const bool timed = b->timed;
+    if (timed) {
+        for (auto &e : w.ev)
+            if (!e) HIPCHECK(hipEventCreate(&e));
+        HIPCHECK(hipEventRecord(w.ev[0], s));
+    }
+    place_core(w, b->mem_off.as<uint64_t>(), b->mems.as<pgx_mem>(), lw.d_off, lw.vals.as<uint64_t>(), b->n_reads, b->n_mems, lw.n_values, b->h->meta.n_sequences(),
+               d->loc.max_length, flags, mem_free, s, "pgx_batch_read_place");
+    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
+    HIPCHECK(hipStreamSynchronize(s));
+    w.ms = 0;
+    if (timed) HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
+    w.valid = true;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+static void places_header(const pgx_batch *b, pgx_read_places *out) {
+    const PlaceWork &w = b->pw;
+    std::memset(out, 0, sizeof *out);
+    out->n_reads = w.n_reads;
+    out->n_anchors = w.n_anchors;
+    out->n_places = w.n_places;
+    out->flags = w.flags;
+    out->n_passes = w.n_passes;
+    out->ms_place = w.ms;
+}
+
+extern "C" pgx_status pgx_batch_device_places(pgx_batch *b, pgx_read_places *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->pw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_places: batch has no place result");
+    const PlaceWork &w = b->pw;
+    places_header(b, out);
+    out->reads = w.recs.as<pgx_read_place>();
+    if (w.flags & PGX_PLACE_LIST) {
+        out->place_offsets = w.place_off.as<uint64_t>();
+        out->places = w.places.as<pgx_placement>();
+    }
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_batch_places(pgx_batch *b, pgx_read_places *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->pw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_places: batch has no place result");
+    use_device(b->device);
+    PlaceWork &w = b->pw;
+    const uint64_t n = w.n_reads;
+    const bool list = (w.flags & PGX_PLACE_LIST) != 0;
+    w.h_recs.ensure((n ? n : 1) * sizeof(pgx_read_place));
+    if (n) HIPCHECK(hipMemcpyAsync(w.h_recs.p, w.recs.p, n * sizeof(pgx_read_place), hipMemcpyDeviceToHost, b->own));
+    if (list) {
+        w.h_place_off.ensure((n + 1) * 8);
+        w.h_places.ensure((w.n_places ? w.n_places : 1) * sizeof(pgx_placement));
+        HIPCHECK(hipMemcpyAsync(w.h_place_off.p, w.place_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, b->own));
+        if (w.n_places) HIPCHECK(hipMemcpyAsync(w.h_places.p, w.places.p, w.n_places * sizeof(pgx_placement), hipMemcpyDeviceToHost, b->own));
+    }
+    HIPCHECK(hipStreamSynchronize(b->own)); // (the stage completed inside pgx_batch_read_place, on whatever stream it used)
+    places_header(b, out);
+    out->reads = w.h_recs.as<pgx_read_place>();
+    if (list) {
+        out->place_offsets = w.h_place_off.as<uint64_t>();
+        out->places = w.h_places.as<pgx_placement>();
+    }
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_read_place_arrays(int device, const uint64_t *mem_offsets, uint64_t n_reads, const pgx_mem *mems, const uint64_t *loc_offsets,
+                                            const uint64_t *values, uint64_t n_seq, uint64_t max_length, uint32_t flags, pgx_read_place *out,
+                                            uint64_t *place_offsets, pgx_placement *places, uint64_t places_cap) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_read_place_arrays");
+    checked_device_count();
+    if (flags & ~PLACE_FLAGS) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: unknown flag");
+    if (n_seq == 0 || max_length == 0) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: n_seq and max_length must be positive");
+    const bool list = (flags & PGX_PLACE_LIST) != 0;
+    if (!mem_offsets || !loc_offsets || (n_reads && !out) || (list && (!place_offsets || (places_cap && !places))))
+        throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: null argument");
+    if (mem_offsets[0] != 0) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: mem_offsets must start at 0");
+    for (uint64_t i = 0; i < n_reads; i++)
+        if (mem_offsets[i] > mem_offsets[i + 1])
+            throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: mem_offsets decrease at read " + std::to_string(i));
+    const uint64_t m = mem_offsets[n_reads];
+    if (loc_offsets[0] != 0) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: loc_offsets must start at 0");
+    for (uint64_t r = 0; r < n_reads; r++)
+        for (uint64_t i = mem_offsets[r]; i < mem_offsets[r + 1]; i++)
+            if (loc_offsets[i] > loc_offsets[i + 1])
+                throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: loc_offsets decrease at MEM " + std::to_string(i) + " of read " + std::to_string(r));
+    const uint64_t nv = loc_offsets[m];
+    if ((m && !mems) || (nv && !values)) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: null argument");
+    use_device(device);
+    struct Work { // device copies of the input + the stage's buffers, released on every way out
+        DevBuf mem_off, mems, loc_off, values;
+        PlaceWork w;
+        ~Work() {
+            DevBuf *all[] = {&mem_off, &mems, &loc_off, &values};
+            for (DevBuf *d : all) d->release();
+            w.release();
+        }
+    } k;
+    const size_t mem_free = free_device_memory();
+    upload(k.mem_off, mem_offsets, (n_reads + 1) * 8);
+    upload(k.mems, mems, m * sizeof(pgx_mem));
+    upload(k.loc_off, loc_offsets, (m + 1) * 8);
+    upload(k.values, values, nv * 8);
+    hipStream_t s = nullptr;
+    if (n_reads) { // the preconditions, before anything is written
+        if (n_reads >= PLACE_LAUNCH_ITEMS || nv >= (1ull << 32) - 256)
+            throw Error(PGX_ERR_UNSUPPORTED, "pgx_read_place_arrays: " + std::to_string(n_reads) + " reads with " + std::to_string(nv) + " values exceed one checking launch");
+        k.w.bad.ensure(8);
+        HIPCHECK(hipMemsetAsync(k.w.bad.p, 0xFF, 8, s));
+        hipLaunchKernelGGL(pgx_read_hits_check_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, s, (const uint64_t *)k.mem_off.as<uint64_t>(),
+                           (const pgx_mem *)k.mems.as<pgx_mem>(), n_reads, m, k.w.bad.as<unsigned long long>());
+        HIPCHECK(hipGetLastError());
+        uint64_t bad = read_u64(k.w.bad.as<uint64_t>(), s);
+        if (bad != ~0ull) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: the MEM starts of read " + std::to_string(bad) + " do not ascend strictly");
+        if (nv) { // (a read's anchors: loc_offsets at its first MEM, what the plan kernel computes too)
+            std::vector<uint64_t> h_aoff(n_reads + 1);
+            for (uint64_t r = 0; r <= n_reads; r++) h_aoff[r] = loc_offsets[mem_offsets[r]];
+            upload(k.w.aoff, h_aoff.data(), (n_reads + 1) * 8);
+            hipLaunchKernelGGL(pgx_place_check_values_kernel, dim3(grid_for(nv, 256)), dim3(256), 0, s, (const uint64_t *)k.values.as<uint64_t>(), nv, max_length, n_seq,
+                               (const uint64_t *)k.w.aoff.as<uint64_t>(), n_reads, k.w.bad.as<unsigned long long>());
+            HIPCHECK(hipGetLastError());
+            bad = read_u64(k.w.bad.as<uint64_t>(), s);
+            if (bad != ~0ull)
+                throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: read " + std::to_string(bad) + " has a value whose sequence is not below n_seq " + std::to_string(n_seq));
+        }
+    }
+    place_core(k.w, k.mem_off.as<uint64_t>(), k.mems.as<pgx_mem>(), k.loc_off.as<uint64_t>(), k.values.as<uint64_t>(), n_reads, m, nv, n_seq, max_length, flags, mem_free, s,
+               "pgx_read_place_arrays");
+    if (list && k.w.n_places > places_cap)
+        throw Error(PGX_ERR_NOMEM, "pgx_read_place_arrays: the list holds " + std::to_string(k.w.n_places) + " placements, places_cap is " + std::to_string(places_cap));
+    if (n_reads) HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, n_reads * sizeof(pgx_read_place), hipMemcpyDeviceToHost, s));
+    if (list) {
+        HIPCHECK(hipMemcpyAsync(place_offsets, k.w.place_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (k.w.n_places) HIPCHECK(hipMemcpyAsync(places, k.w.places.p, k.w.n_places * sizeof(pgx_placement), hipMemcpyDeviceToHost, s));
     }
     HIPCHECK(hipStreamSynchronize(s));
     return PGX_OK;

@@ -368,6 +368,23 @@ __global__ void pgx_read_hits_wide_kernel(const uint64_t *mem_off, const pgx_mem
                                           uint64_t n_seq, uint32_t W, uint32_t flags, pgx_read_hit *hits, unsigned long long *best_sets, uint32_t *scores);
 __global__ void pgx_read_hits_check_kernel(const uint64_t *mem_off, const pgx_mem *mems, uint64_t n_reads, uint64_t n_mems, unsigned long long *bad);
 
+// ---- pgx_place_kernels.hip: read placement (pgx_batch_read_place, pgx_read_place_arrays); loc_off / values: the packed-position form
+#define PGX_PLACE_THREADS 256
+// aoff[n_reads + 1] / acnt[n_reads]: the anchors of a read; mx: [0] most MEMs of a read [1] largest MEM start [2] aoff[n_reads] [3] aoff[0]
+__global__ void pgx_place_plan_kernel(const uint64_t *mem_off, const uint64_t *loc_off, const pgx_mem *mems, uint64_t n_reads, uint64_t n_mems, uint64_t n_values,
+                                      uint64_t *aoff, uint64_t *acnt, unsigned long long *mx);
+__global__ void pgx_place_first_kernel(const uint64_t *mem_off, uint64_t n_reads, uint64_t n_mems, uint64_t *mfirst);
+__global__ void pgx_place_keys_kernel(const pgx_mem *mems, const uint64_t *loc_off, const uint64_t *mfirst, const uint64_t *values, uint64_t m0, uint64_t m1,
+                                      uint64_t a_first, uint64_t na, uint64_t L, uint64_t span, uint64_t bias, uint32_t ordinal_bits, uint64_t *keys);
+// 1 << g_shift lanes a read (g_shift 0 .. 6), PGX_PLACE_THREADS >> g_shift reads a block
+template <bool LIST>
+__global__ void pgx_place_sweep_kernel(const uint64_t *mem_off, const pgx_mem *mems, const uint64_t *loc_off, const uint64_t *acnt, const uint64_t *keys,
+                                       const uint64_t *seg, const uint64_t *ucount, uint64_t r_pass, uint64_t r_first, uint64_t nr, uint64_t n_mems, uint64_t span,
+                                       uint64_t bias, uint32_t ordinal_bits, uint32_t g_shift, pgx_read_place *recs, uint64_t *pcount, const uint64_t *list_off,
+                                       pgx_placement *places);
+__global__ void pgx_place_check_values_kernel(const uint64_t *values, uint64_t n_values, uint64_t L, uint64_t n_seq, const uint64_t *aoff, uint64_t n_reads,
+                                              unsigned long long *bad);
+
 // literal count image: COMPAT count_encoded / LF_encoded on an encoded index without N, block by block as the
 // reference's rankAt_encoded (src/r-index.cpp:570-590) sees it -- true cumulative counts, run scan one varint late
 struct PgxLitImage {

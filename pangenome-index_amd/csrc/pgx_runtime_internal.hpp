@@ -159,6 +159,25 @@ struct HitsWork {
     }
 };
 
+// pgx_batch_read_place's buffers (grow-only, its own: a later locate leaves them alone) and its result; pgx_read_place_arrays uses one of its own
+struct PlaceWork {
+    DevBuf recs, pcount, place_off, places, aoff, acnt, mfirst, keys, seg, lists, need, soff, scratch, ucount, loff, ctr, scan_tmp, bad;
+    HostBuf h_recs, h_place_off, h_places;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool valid = false;
+    uint32_t flags = 0, n_passes = 0;
+    uint64_t n_reads = 0, n_anchors = 0, n_places = 0;
+    float ms = 0;
+    void release() {
+        DevBuf *all[] = {&recs, &pcount, &place_off, &places, &aoff, &acnt, &mfirst, &keys, &seg, &lists, &need, &soff, &scratch, &ucount, &loff, &ctr, &scan_tmp, &bad};
+        for (DevBuf *d : all) d->release();
+        h_recs.release(); h_place_off.release(); h_places.release();
+        for (auto &e : ev)
+            if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        valid = false;
+    }
+};
+
 inline uint64_t with_slack(uint64_t v) { return v + v / 4 + 64; }
 
 // Device scalars of the stage, sc[] (zeroed by the caller): [0] big-list length [1] large-list length [2] largest run count on the

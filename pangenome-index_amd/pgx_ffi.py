@@ -105,6 +105,27 @@ class ReadHits(C.Structure):  # pgx_read_hits: host pointers (pgx_batch_hits) or
                 ("ms_hits", C.c_float), ("reserved", u32)]
 
 
+PLACE_LIST = 1  # pgx_batch_read_place / pgx_read_place_arrays flag
+READ_PLACE_DTYPE = np.dtype([("best_score", "<u8"), ("next_score", "<u8"), ("best_diag", "<i8"), ("n_anchors", "<u8"), ("n_placements", "<u8"),
+                             ("best_seq", "<u4"), ("n_best", "<u4"), ("best_mems", "<u4"), ("n_located", "<u4"), ("n_mems", "<u4"),
+                             ("reserved", "<u4")])  # pgx_read_place, 64 bytes
+PLACEMENT_DTYPE = np.dtype([("diag", "<i8"), ("score", "<u8"), ("seq", "<u4"), ("mems", "<u4")])  # pgx_placement, 24 bytes
+
+
+class ReadPlace(C.Structure):  # pgx_read_place
+    _fields_ = [("best_score", u64), ("next_score", u64), ("best_diag", C.c_int64), ("n_anchors", u64), ("n_placements", u64), ("best_seq", u32),
+                ("n_best", u32), ("best_mems", u32), ("n_located", u32), ("n_mems", u32), ("reserved", u32)]
+
+
+class Placement(C.Structure):  # pgx_placement
+    _fields_ = [("diag", C.c_int64), ("score", u64), ("seq", u32), ("mems", u32)]
+
+
+class ReadPlaces(C.Structure):  # pgx_read_places: host pointers (pgx_batch_places) or device pointers (pgx_batch_device_places)
+    _fields_ = [("n_reads", u64), ("n_anchors", u64), ("n_places", u64), ("flags", u32), ("n_passes", u32), ("reads", p), ("place_offsets", p),
+                ("places", p), ("ms_place", C.c_float), ("reserved", u32)]
+
+
 class DeviceArray:
     """a device buffer owned by a batch, exposed through __cuda_array_interface__ (zero copy: torch.as_tensor(a, device="cuda"));
     64-bit unsigned values are presented as int64"""
@@ -244,6 +265,10 @@ def lib():
     L.pgx_batch_hits.argtypes = [p, C.POINTER(ReadHits)]
     L.pgx_batch_device_hits.argtypes = [p, C.POINTER(ReadHits)]
     L.pgx_read_hits_arrays.argtypes = [C.c_int, p, u64, p, p, u32, u64, u32, p, p, p]
+    L.pgx_batch_read_place.argtypes = [p, u32, p]
+    L.pgx_batch_places.argtypes = [p, C.POINTER(ReadPlaces)]
+    L.pgx_batch_device_places.argtypes = [p, C.POINTER(ReadPlaces)]
+    L.pgx_read_place_arrays.argtypes = [C.c_int, p, u64, p, p, p, u64, u64, u32, p, p, p, u64]
     L.pgx_batch_result_compact.argtypes = [p, C.POINTER(CompactResult)]
     L.pgx_compact_expand.argtypes = [C.POINTER(CompactResult), u64, u64, p, p, p, p, p]
     L.pgx_compact_bound.argtypes = [u64, u64, u64, u32]
@@ -850,6 +875,35 @@ def read_hits_arrays(device, mem_offsets, mems, sets, n_seq, flags=0, set_words=
     return res
 
 
+def read_place_arrays(device, mem_offsets, mems, loc_offsets, values, n_seq, max_length, flags=0, places_cap=None, out=None):
+    """pgx_read_place_arrays: the read-placement kernels on host arrays (mem_offsets uint64[n_reads + 1], mems MEM_DTYPE, loc_offsets
+    uint64[n_mems + 1], values uint64 packed positions): dict(reads READ_PLACE_DTYPE[n_reads], and with PLACE_LIST place_offsets
+    uint64[n_reads + 1] and places PLACEMENT_DTYPE[place_offsets[-1]], else None).  places_cap: the capacity handed to the library
+    (default: one placement a value, which always suffices); out: a dict of arrays to write into (tests)"""
+    mem_offsets = np.ascontiguousarray(mem_offsets, dtype=np.uint64)
+    mems = np.ascontiguousarray(mems, dtype=MEM_DTYPE)
+    loc_offsets = np.ascontiguousarray(loc_offsets, dtype=np.uint64)
+    values = np.ascontiguousarray(values, dtype=np.uint64)
+    n = len(mem_offsets) - 1
+    if len(mems) != int(mem_offsets[-1]) or len(loc_offsets) != len(mems) + 1 or len(values) != int(loc_offsets[-1]):
+        raise ValueError("read_place_arrays: mems, loc_offsets and values must have mem_offsets[-1], that + 1 and loc_offsets[-1] entries")
+    lst = bool(flags & PLACE_LIST)
+    cap = len(values) if places_cap is None else int(places_cap)
+    res = out if out is not None else {}
+    if "reads" not in res:
+        res["reads"] = np.zeros(n, dtype=READ_PLACE_DTYPE)
+    if "place_offsets" not in res:
+        res["place_offsets"] = np.zeros(n + 1, dtype=np.uint64) if lst else None
+    if "places" not in res:
+        res["places"] = np.zeros(max(cap, 1), dtype=PLACEMENT_DTYPE) if lst else None
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().pgx_read_place_arrays(device, mem_offsets.ctypes.data, n, mems.ctypes.data, loc_offsets.ctypes.data, values.ctypes.data, int(n_seq),
+                                       int(max_length), flags, ptr(res["reads"]), ptr(res["place_offsets"]), ptr(res["places"]), cap))
+    if lst and out is None:
+        res["places"] = res["places"][: int(res["place_offsets"][-1])]
+    return res
+
+
 def find_mems_sharded(index, devices, reads_cat, offsets, min_len, min_occ, tags=False):
     """pgx_find_mems_sharded: contiguous read slices, slice i on devices[i]; returns the per-slice result dicts in slice order"""
     reads_cat = np.ascontiguousarray(reads_cat, dtype=np.uint8)
@@ -1125,6 +1179,39 @@ class Batch:
         out["hits"] = DeviceArray(r.hits, (n, 5), self)
         out["best_sets"] = DeviceArray(r.best_sets, (n, W), self) if r.best_sets else None
         out["scores"] = DeviceArray(r.scores, (n, q), self, "<u4") if r.scores else None
+        return out
+
+    def read_place(self, flags=0, stream=None):
+        """pgx_batch_read_place on the packed positions of the last locate(0), then places()"""
+        _check(self.L.pgx_batch_read_place(self.b, flags, stream))
+        return self.places()
+
+    def _places(self, fn):
+        r = ReadPlaces()
+        _check(fn(self.b, C.byref(r)))
+        return r, dict(n_reads=int(r.n_reads), n_anchors=int(r.n_anchors), n_places=int(r.n_places), flags=int(r.flags), n_passes=int(r.n_passes),
+                       ms_place=float(r.ms_place))
+
+    def places(self):
+        """the last read placement as numpy arrays: reads READ_PLACE_DTYPE[n_reads]; with PLACE_LIST place_offsets uint64[n_reads + 1] and
+        places PLACEMENT_DTYPE[n_places] (None without), with n_reads, n_anchors, n_places, flags, n_passes, ms_place"""
+        r, out = self._places(self.L.pgx_batch_places)
+        n, k = out["n_reads"], out["n_places"]
+        records = lambda ptr, count, dt: np.frombuffer((C.c_char * (count * dt.itemsize)).from_address(ptr), dtype=dt).copy() if count else np.zeros(0, dt)  # (string_at takes a C int)
+        out["reads"] = records(r.reads, n, READ_PLACE_DTYPE)
+        out["place_offsets"] = _u64_array(C.cast(r.place_offsets, C.POINTER(u64)), n + 1) if r.place_offsets else None
+        out["places"] = records(r.places, k, PLACEMENT_DTYPE) if r.places else None
+        return out
+
+    def device_places(self):
+        """the same as device arrays (valid until the next run / upload / read_place / free): reads int64[n_reads, 8] (the 64-byte records
+        as words), place_offsets int64[n_reads + 1], places int64[n_places, 3] (the 24-byte records as words)"""
+        r, out = self._places(self.L.pgx_batch_device_places)
+        n, k = out["n_reads"], out["n_places"]
+        out["device"] = True
+        out["reads"] = DeviceArray(r.reads, (n, 8), self)
+        out["place_offsets"] = DeviceArray(r.place_offsets, (n + 1,), self) if r.place_offsets else None
+        out["places"] = DeviceArray(r.places, (k, 3), self) if r.places else None
         return out
 
     def free(self):

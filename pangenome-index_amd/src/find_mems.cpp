@@ -16,6 +16,8 @@
 //                 no formatter threads run, --result has no effect; the same text either way),
 //                 --hits FILE (one line per read: which indexed sequence the read matches best, pgx_batch_read_hits; stdout and stderr stay as they are),
 //                 --hits-max K (MEMs with more occurrences count as not located in the hits), --hits-only (no MEM text: stdout stays empty; not with --locate)
+//                 --place FILE (one line per read: the sequence diagonal the read lies on best, pgx_batch_read_place; stdout and stderr stay as they are),
+//                 --place-max K (MEMs with more occurrences are left unlocated in the placement), --place-only (no MEM text, like --hits-only)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -145,6 +147,7 @@ struct Done {
     size_t text_n = 0, etext_n = 0;
     double mem_s = 0, tag_s = 0;
     std::string hits; // --hits: the lines of this batch
+    std::string places; // --place: the lines of this batch
     std::string error;
 };
 
@@ -255,12 +258,39 @@ static void format_hits(const pgx_read_hit *hits, size_t n, uint64_t first_seq, 
     out.resize((size_t)(p - &out[0]));
 }
 
+// --place: the lines of reads [0, n) of a batch, appended to out; best_seq and best_pos print as * when no placement has a score
+static const char PLACE_HEADER[] = "#read\tmems\tlocated\tanchors\tplacements\tbest\tn_best\tbest_seq\tbest_pos\tbest_mems\tnext\n";
+static void format_places(const pgx_read_place *recs, size_t n, uint64_t first_seq, std::string &out) {
+    out.resize(n * (11 * 21));
+    char *p = &out[0];
+    for (size_t i = 0; i < n; i++) {
+        const pgx_read_place &x = recs[i];
+        p = put_u64(p, first_seq + i + 1); *p++ = '\t';
+        p = put_u64(p, x.n_mems); *p++ = '\t';
+        p = put_u64(p, x.n_located); *p++ = '\t';
+        p = put_u64(p, x.n_anchors); *p++ = '\t';
+        p = put_u64(p, x.n_placements); *p++ = '\t';
+        p = put_u64(p, x.best_score); *p++ = '\t';
+        p = put_u64(p, x.n_best); *p++ = '\t';
+        if (x.best_score == 0) { *p++ = '*'; *p++ = '\t'; *p++ = '*'; }
+        else {
+            p = put_u64(p, x.best_seq); *p++ = '\t';
+            if (x.best_diag < 0) { *p++ = '-'; p = put_u64(p, 0 - (uint64_t)x.best_diag); } else p = put_u64(p, (uint64_t)x.best_diag);
+        }
+        *p++ = '\t';
+        p = put_u64(p, x.best_mems); *p++ = '\t';
+        p = put_u64(p, x.next_score); *p++ = '\n';
+    }
+    out.resize((size_t)(p - &out[0]));
+}
+
 static int usage() {
     std::cerr << "usage: find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ>"
                  " [--device N | --gpus N | --devices a,b,..] [--streams W] [--mode compat|strict] [--batch N]"
                  " [--tags-format auto|bytecode|compact] [--quiet] [--reads-format lines|fasta|fastq|auto] [--device-parse]"
                  " [--locate positions|seqs] [--locate-max K] [--result full|compact] [--format host|device]"
-                 " [--hits FILE [--hits-max K] [--hits-only (not with --locate)]]" << std::endl;
+                 " [--hits FILE [--hits-max K] [--hits-only (not with --locate)]]"
+                 " [--place FILE [--place-max K] [--place-only (not with --locate)]]" << std::endl;
     return EXIT_FAILURE;
 }
 
@@ -282,6 +312,9 @@ int main(int argc, char **argv) {
     std::string hits_file;      // --hits: the read hits of every batch go to this file
     uint64_t hits_max = 0;
     bool hits_max_given = false, hits_only = false;
+    std::string place_file;     // --place: the read placements of every batch go to this file
+    uint64_t place_max = 0;
+    bool place_max_given = false, place_only = false;
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -346,11 +379,25 @@ int main(int argc, char **argv) {
             hits_max_given = true;
         }
         else if (a == "--hits-only") hits_only = true;
+        else if (a == "--place") { place_file = next(); if (place_file.empty()) { std::cerr << "--place: a file name" << std::endl; return EXIT_FAILURE; } }
+        else if (a == "--place-max") {
+            const std::string f = next();
+            errno = 0;
+            char *endp = nullptr;
+            const unsigned long long k = f.empty() || f.size() > 19 || f.find_first_not_of("0123456789") != std::string::npos ? 0 : std::strtoull(f.c_str(), &endp, 10);
+            if (!endp || *endp || errno) { std::cerr << "--place-max: a number of occurrences >= 0 (0: no cap)" << std::endl; return EXIT_FAILURE; }
+            place_max = k;
+            place_max_given = true;
+        }
+        else if (a == "--place-only") place_only = true;
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
     if ((hits_max_given || hits_only) && hits_file.empty()) return usage();
     if (hits_only && locate_mode) { std::cerr << "--hits-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
-    const bool want_hits = !hits_file.empty();
+    if ((place_max_given || place_only) && place_file.empty()) return usage();
+    if (place_only && locate_mode) { std::cerr << "--place-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
+    const bool want_hits = !hits_file.empty(), want_places = !place_file.empty();
+    const bool no_text = hits_only || place_only; // (either one: no tag stage, no download of result arrays, stdout empty)
     if (batch_reads == 0) batch_reads = 1;
     if (locate_max && !locate_mode) { std::cerr << "--locate-max needs --locate" << std::endl; return EXIT_FAILURE; }
 
@@ -406,6 +453,27 @@ int main(int argc, char **argv) {
         hits_fp = std::fopen(hits_file.c_str(), "wb");
         if (!hits_fp) { std::cerr << "Cannot open hits file: " << hits_file << std::endl; return EXIT_FAILURE; }
         std::fwrite(HITS_HEADER, 1, sizeof HITS_HEADER - 1, hits_fp);
+    }
+    // --place: the same question for the packed positions (a COMPAT index without N, an image file without the locate image)
+    std::FILE *place_fp = nullptr;
+    if (want_places) {
+        static const uint8_t probe_read[4] = {'A', 'C', 'G', 'T'};
+        static const uint64_t probe_offs[2] = {0, 4};
+        pgx_batch *pb = nullptr;
+        pgx_status st = pgx_batch_create(h, devices[0], probe_read, probe_offs, 1, &pb);
+        if (st == PGX_OK) st = pgx_batch_run(pb, mem_length, min_occ, 0, nullptr);
+        if (st == PGX_OK) st = pgx_batch_locate(pb, 0, place_max, nullptr);
+        if (st == PGX_OK) st = pgx_batch_read_place(pb, 0, nullptr);
+        const std::string msg = st == PGX_OK ? "" : pgx_last_error();
+        pgx_batch_free(pb);
+        if (st != PGX_OK) {
+            std::cerr << msg << (st == PGX_ERR_UNSUPPORTED ? " (find_mems --place)" : "") << std::endl;
+            if (hits_fp) std::fclose(hits_fp);
+            return EXIT_FAILURE;
+        }
+        place_fp = std::fopen(place_file.c_str(), "wb");
+        if (!place_fp) { std::cerr << "Cannot open place file: " << place_file << std::endl; return EXIT_FAILURE; }
+        std::fwrite(PLACE_HEADER, 1, sizeof PLACE_HEADER - 1, place_fp);
     }
 
     // ---- the reads file, mapped: the reference reads it with std::getline (find_mems.cpp:96); here a planner cuts it into byte ranges that
@@ -653,7 +721,7 @@ int main(int argc, char **argv) {
                                                  reinterpret_cast<const uint8_t *>(j->pk.p) + j->side_at, j->n_side);
             } else if (!dev_parse) st = b ? pgx_batch_upload(b, rp, j->offs.data(), n) : pgx_batch_create(h, device, rp, j->offs.data(), n, &b);
             uint64_t t1 = now_ns();
-            if (st == PGX_OK) st = pgx_batch_run(b, mem_length, min_occ, (hits_only ? 0u : PGX_RUN_TAGS) | PGX_RUN_TIMING, nullptr); // (the tag positions are part of the MEM text only)
+            if (st == PGX_OK) st = pgx_batch_run(b, mem_length, min_occ, (no_text ? 0u : PGX_RUN_TAGS) | PGX_RUN_TIMING, nullptr); // (the tag positions are part of the MEM text only)
             uint64_t t2 = now_ns();
             pgx_compact_result cr;
             std::vector<pgx_read_hit> hit_recs; // --hits: the 40-byte records, taken before the locate that --locate asks for replaces the sets
@@ -664,7 +732,15 @@ int main(int argc, char **argv) {
                 if (st == PGX_OK) st = pgx_batch_hits(b, &rh);
                 if (st == PGX_OK) hit_recs.assign(rh.hits, rh.hits + rh.n_reads);
             }
-            if (format_device || hits_only) {
+            std::vector<pgx_read_place> place_recs; // --place: the 64-byte records; the stage's buffers are its own, the locate below does not touch them
+            if (st == PGX_OK && want_places) {
+                st = pgx_batch_locate(b, 0, place_max, nullptr);
+                if (st == PGX_OK) st = pgx_batch_read_place(b, 0, nullptr);
+                pgx_read_places rp2;
+                if (st == PGX_OK) st = pgx_batch_places(b, &rp2);
+                if (st == PGX_OK) place_recs.assign(rp2.reads, rp2.reads + rp2.n_reads);
+            }
+            if (format_device || no_text) {
                 // nothing to download: the device writes the text below, once the batch knows the number of its first read
             } else if (st == PGX_OK && compact_result) {
                 st = pgx_batch_result_compact(b, &cr);
@@ -707,7 +783,8 @@ int main(int argc, char **argv) {
                     d->tag_s = 1e-3 * (t.ms_tag_locate + t.ms_tag_gather + t.ms_tag_sort);
                 }
                 if (want_hits) format_hits(hit_recs.data(), hit_recs.size(), j->first_seq, d->hits);
-                if (format_device && !hits_only) {
+                if (want_places) format_places(place_recs.data(), place_recs.size(), j->first_seq, d->places);
+                if (format_device && !no_text) {
                     // the text of the batch from the device, handed to the writer where it is
                     const uint64_t t3w = now_ns();
                     wait_written(1);
@@ -728,7 +805,7 @@ int main(int argc, char **argv) {
                         text_bytes += tx.n_bytes + tx.n_err_bytes;
                     }
                 }
-                const unsigned parts = format_device || hits_only ? 0u : n < 4096 ? 1u : n_fmt;
+                const unsigned parts = format_device || no_text ? 0u : n < 4096 ? 1u : n_fmt;
                 if (parts) d->outs.resize(parts);
                 if (parts) d->errs.resize(parts);
                 // --result compact: the parts are cut on multiples of 64 reads and every thread expands the blocks of its part first
@@ -744,7 +821,7 @@ int main(int argc, char **argv) {
                         return pgx_last_error(); // (the message is thread-local)
                     return std::string();
                 };
-                if (parts == 0) { // (--format device: the text is there; --hits-only: there is none)
+                if (parts == 0) { // (--format device: the text is there; --hits-only / --place-only: there is none)
                 } else if (parts == 1) {
                     if (compact_result) d->error = expand_part(0);
                     if (d->error.empty()) format_range(r, 0, n, j->first_seq, quiet, lout, d->outs[0], d->errs[0]);
@@ -804,6 +881,7 @@ int main(int argc, char **argv) {
         if (d->text_n) std::fwrite(d->text, 1, d->text_n, stdout);
         if (d->etext_n) std::fwrite(d->etext, 1, d->etext_n, stderr);
         if (hits_fp && !d->hits.empty()) std::fwrite(d->hits.data(), 1, d->hits.size(), hits_fp);
+        if (place_fp && !d->places.empty()) std::fwrite(d->places.data(), 1, d->places.size(), place_fp);
         ns_write += now_ns() - tw0;
         total_mem_time += d->mem_s;
         total_tag_time += d->tag_s;
@@ -826,6 +904,7 @@ int main(int argc, char **argv) {
             if (!kv.second->error.empty()) { error = kv.second->error; break; }
     if (error.empty() && failed) error = "find_mems: a device batch failed";
     if (hits_fp && (std::fclose(hits_fp) != 0) && error.empty()) error = "Cannot write hits file: " + hits_file;
+    if (place_fp && (std::fclose(place_fp) != 0) && error.empty()) error = "Cannot write place file: " + place_file;
     if (!error.empty()) {
         std::cerr << error << std::endl;
         return EXIT_FAILURE;
@@ -840,7 +919,7 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "[find_mems] --format device: of format %.3f s: pgx_batch_format %.3f (its kernels %.3f), waiting for the writer to release a text buffer %.3f; %.1f MB of text\n",
                      1e-9 * (double)ns_format.load(), 1e-9 * (double)ns_devfmt.load(), 1e-6 * (double)us_devfmt_kernels.load(), 1e-9 * (double)ns_lent.load(),
                      1e-6 * (double)text_bytes.load());
-    if (!hits_only) {
+    if (!no_text) {
         std::cout << "\nTotal time for finding all MEMs: " << total_mem_time << " seconds" << std::endl; // :144
         std::cout << "Total time for all tag queries: " << total_tag_time << " seconds" << std::endl;   // :145
     }
