@@ -390,7 +390,11 @@ pgx_status pgx_merge_tags_gbz_ex(const char *gbz_path, const char *ri_path, cons
 #define PGX_BUILD_TAGS_OUT_BYTECODE 0x10u  /* likewise the ByteCode query format (pgx_convert_tags(compact = 0)); both: PGX_ERR_ARG */
 pgx_status pgx_build_tags(const char *gbz_path, const char *ri_path, int device, const char *out_path, uint32_t flags);
 /* pgx_build_tags with the graph stated by the caller: n_seq paths, path s = path_nodes[path_offsets[s], path_offsets[s + 1])
- * with nodes as id << 1 | rev; node_length[id - first_node_id] for n_node_ids ids (0: the id has no sequence). */
+ * with nodes as id << 1 | rev; node_length[id - first_node_id] for n_node_ids ids (0: the id has no sequence).  first_node_id is
+ * any value; an id below it or from first_node_id + n_node_ids on has no sequence either.  A path of no nodes (path_offsets[s] ==
+ * path_offsets[s + 1], also at the end of path_nodes) is the empty sequence; path_nodes may be NULL when no path has a node.  A path may
+ * visit a node any number of times and paths may share nodes.  A run piece holds node << 20 in 64 bits: a path that visits an id of
+ * 2^44 or more is PGX_ERR_FORMAT naming the id, like the other errors before any device work on the tags and without an output file. */
 pgx_status pgx_build_tags_paths(const char *ri_path, uint64_t n_seq, const uint64_t *path_offsets, const uint64_t *path_nodes,
                                 const uint32_t *node_length, uint64_t first_node_id, uint64_t n_node_ids, int device,
                                 const char *out_path, uint32_t flags);
