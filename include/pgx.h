@@ -804,6 +804,87 @@ pgx_status pgx_read_place_arrays(int device, const uint64_t *mem_offsets, uint64
                                  const uint64_t *values, uint64_t n_seq, uint64_t max_length, uint32_t flags, pgx_read_place *out,
                                  uint64_t *place_offsets, pgx_placement *places, uint64_t places_cap);
 
+/* ---- read verify: every read laid on the indexed text at its placements, on the device ---------------------------------------
+ * What a consumer of a placement does next (the reference's downstream consumer extends its seeds without gaps for the same reason):
+ * the whole read is compared with the text at a candidate placement and what matches is counted, so that a read with one substitution
+ * is told from one whose other half lies elsewhere, and ties between placements are broken by evidence.  The text is the TEXT image,
+ * recovered on the device from the index alone (the first symbol of suffix i is the symbol whose C-bucket holds i), built on first use
+ * for any index pgx_locate_batch supports with bwt_size < 2^32 - 2^20; it is not stored in image files.
+ *
+ * DEFINITIONS.  Read r has bytes R[0, len).  A candidate is a pair (seq, diag).  Sequence seq has Ls symbols T[0, Ls), endmarker excluded.
+ *   span         the read positions i with 0 <= diag + i < Ls: [lo, hi) with lo = max(0, -diag), hi = min(len, Ls - diag); empty
+ *                (hi <= lo, then lo = hi = 0) when the read does not overlap the sequence
+ *   match at i   R[i] is one of upper-case A C G T and equals T[diag + i].  Everything else in the span is a mismatch: lower case, N,
+ *                IUPAC codes, a text N (N opposite N too)
+ *   matches, mismatches   counts over the span; they sum to hi - lo
+ *   longest_run, run_start   the longest stretch of consecutive matches in the span and the smallest start of one; both 0 without a match
+ *   segment      with the mismatch penalty P >= 1 the score of [a, b) inside [lo, hi) is (matches in it) - P * (mismatches in it); the
+ *                segment is the non-empty [a, b) of largest score, ties to the smallest a, then the smallest b.  seg_score is that score
+ *                (at least 1 whenever matches >= 1), seg_mismatches the mismatches inside it.  Without a match seg_score = 0,
+ *                seg_start = seg_end = lo, seg_mismatches = 0.
+ * The maximum is associative -- the monoid (total, best prefix with smallest end, best suffix with smallest start, best with the
+ * lexicographically smallest (a, b)) yields exactly this tie rule --, so a kernel may split a read over lanes or walk it in one.
+ * CANDIDATES of read r in the batch form: its placements with cov == best_score > 0 in placement order (seq ascending, signed diag
+ * ascending), the first max_cand of them, 1 <= max_cand <= 64.  max_cand == 1 needs only the place records (best_seq, best_diag);
+ * max_cand > 1 needs a place result made with PGX_PLACE_LIST.  A read with best_score == 0 has no candidate.
+ * WINNER: the candidate with the largest seg_score, then the most matches, then the first in candidate order.
+ * pgx_read_verify (64 bytes, little endian; every field but diag is u32):
+ *    0 diag i64                  8 seq (PGX_NO_SEQUENCE and everything else 0 when the read has no candidate)
+ *   12 n_cand                    candidates verified for the read (in the per-candidate list: this candidate's ordinal)
+ *   16 span_lo   20 span_hi      24 matches     28 mismatches
+ *   32 seg_start 36 seg_end      40 seg_score   44 seg_mismatches
+ *   48 longest_run 52 run_start
+ *   56 cand_index                the winner's ordinal among the candidates (in the list: this candidate's ordinal)
+ *   60 n_tied                    candidates that equal the winner in (seg_score, matches), the winner included (in the list: 0)
+ * PGX_VERIFY_LIST adds cand_offsets[n_reads + 1] and one such record per candidate, in candidate order.
+ * Reads of 2^31 bytes or more are PGX_ERR_UNSUPPORTED. */
+#define PGX_VERIFY_LIST 1u
+#define PGX_VERIFY_MAX_CAND 64u
+#define PGX_VERIFY_MAX_PENALTY (1u << 20)
+typedef struct {
+    int64_t diag;
+    uint32_t seq, n_cand, span_lo, span_hi, matches, mismatches, seg_start, seg_end, seg_score, seg_mismatches, longest_run, run_start, cand_index, n_tied;
+} pgx_read_verify;
+typedef struct {
+    uint64_t n_reads;
+    uint64_t n_cands;              /* candidates verified over all reads */
+    uint32_t flags;                /* PGX_VERIFY_* the call ran with */
+    uint32_t max_cand, mismatch_penalty, reserved;
+    const pgx_read_verify *reads;  /* n_reads */
+    const uint64_t *cand_offsets;  /* n_reads + 1; NULL without PGX_VERIFY_LIST */
+    const pgx_read_verify *cands;  /* n_cands; NULL without PGX_VERIFY_LIST */
+    float ms_verify;               /* device time of the call when the run had PGX_RUN_TIMING, else 0 (the text image's build is not in it) */
+    uint32_t reserved2;
+} pgx_read_verifies;
+/* The collection the index was built from, recovered on `device` from the index alone: seq_lengths[n_seq] (without endmarkers) and, when
+ * text != NULL, the sequences as bytes, each followed by '\n' (bwt_size bytes in all).  Builds the text image if it is not built.
+ * PGX_ERR_ARG when n_seq_cap is below the number of sequences or text_cap below bwt_size.  PGX_ERR_UNSUPPORTED, naming the reason: COMPAT
+ * mode on an encoded index without N (locate is unsupported there), an image opened from a file saved without the locate image, bwt_size
+ * >= 2^32 - 2^20.  PGX_ERR_NOMEM with both numbers when the free device memory is below what the build needs for a while (the suffix
+ * array at 8 bytes a symbol, a byte a symbol, the image at half a byte a symbol). */
+pgx_status pgx_index_text(pgx_index *h, int device, uint64_t *seq_lengths, uint64_t n_seq_cap, uint8_t *text, uint64_t text_cap);
+/* Verifies the reads of the last run at the candidates of the last pgx_batch_read_place, which must be this run's: PGX_ERR_ARG otherwise,
+ * and for max_cand outside 1 .. 64, max_cand > 1 on a place result without PGX_PLACE_LIST, mismatch_penalty 0 or above 2^20 and an
+ * unknown flag; run, locate, place and an earlier verify result then stay as they were.  Builds the text image on first use
+ * (PGX_ERR_UNSUPPORTED / PGX_ERR_NOMEM as pgx_index_text).  Runs on `stream` (NULL = the batch's own), complete on return.  Buffers grow
+ * only and are the stage's own: the result stays valid until the next run, upload, pgx_batch_read_verify or free of the batch, and a
+ * later pgx_batch_locate of any form leaves it valid. */
+pgx_status pgx_batch_read_verify(pgx_batch *b, uint32_t max_cand, uint32_t mismatch_penalty, uint32_t flags, void *stream);
+/* Host copy of the last verify result (pinned buffers owned by the batch) / the same as device pointers.  PGX_ERR_ARG when there is none. */
+pgx_status pgx_batch_verified(pgx_batch *b, pgx_read_verifies *out);
+pgx_status pgx_batch_device_verified(pgx_batch *b, pgx_read_verifies *out);
+/* The same kernels on host arrays: the sequences as bytes (\n A C G N T; PGX_ERR_UNSUPPORTED naming byte and offset otherwise) with
+ * seq_offsets[n_seq + 1], no endmarkers (packed on the device by the image's pack kernel); the reads as bytes with read_offsets[n_reads + 1];
+ * the candidates as a CSR list per read, cand_offsets[n_reads + 1], of (cand_seq, cand_diag) -- any candidate, one that does not overlap
+ * its sequence included, any number per read.  `out` takes n_reads records; with PGX_VERIFY_LIST list_offsets takes n_reads + 1 entries and
+ * list up to list_cap records (PGX_ERR_NOMEM with the needed count when there are more; both may be NULL without the flag).
+ * PGX_ERR_ARG with nothing written: an unknown flag, a penalty of 0 or above 2^20, offsets that do not start at 0 or decrease and --
+ * checked on the device, the first offending read named -- a cand_seq >= n_seq.  PGX_ERR_NO_DEVICE without a GPU. */
+pgx_status pgx_read_verify_arrays(int device, const uint8_t *text, const uint64_t *seq_offsets, uint64_t n_seq, const uint8_t *reads,
+                                  const uint64_t *read_offsets, uint64_t n_reads, const uint64_t *cand_offsets, const uint32_t *cand_seq,
+                                  const int64_t *cand_diag, uint32_t mismatch_penalty, uint32_t flags, pgx_read_verify *out,
+                                  uint64_t *list_offsets, pgx_read_verify *list, uint64_t list_cap);
+
 /* ---- compact result: the result of a run as a byte stream, encoded on the device, expanded on the host ---------------------
  * What pgx_batch_result downloads is six dense uint64 arrays (8 bytes per read, 48 per MEM, 8 per graph position), nearly all of
  * them zero bits.  The compact form carries the same values and is expanded to the same pgx_result; only it crosses the link.

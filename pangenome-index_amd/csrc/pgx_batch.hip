@@ -1,4 +1,5 @@
-// pgx_batch.hip -- the pgx_batch object: uploads, pgx_batch_run, results, pgx_batch_locate, pgx_batch_read_hits, pgx_batch_read_place.
+// pgx_batch.hip -- the pgx_batch object: uploads, pgx_batch_run, results, pgx_batch_locate, pgx_batch_read_hits, pgx_batch_read_place,
+// pgx_batch_read_verify.
 //
 // Pipeline of pgx_batch_run (one HIP stream, results stay on the device):
 //   scan(cap)      -> slot offsets (worst-case MEMs per read: min(len, len - min_len + 1)); the slot buffer
@@ -86,6 +87,7 @@ struct pgx_batch {
     FormatWork fw;  // pgx_batch_format
     HitsWork hw;    // pgx_batch_read_hits
     PlaceWork pw;   // pgx_batch_read_place
+    VerifyWork vw;  // pgx_batch_read_verify
     uint64_t n_mems = 0, n_positions = 0, n_ext = 0, n_tag_overflow = 0;
     bool ran = false, ran_tags = false;
     // speculative sizing (pgx_batch_run): what the last run with these parameters produced
@@ -115,6 +117,7 @@ static void batch_release(pgx_batch *b) {
         b->fw.release();
         b->hw.release();
         b->pw.release();
+        b->vw.release();
         HostBuf *hb[] = {&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]};
         for (HostBuf *x : hb) x->release();
         for (auto &e : b->ev)
@@ -140,6 +143,7 @@ static void batch_reset_for_upload(pgx_batch *b, uint64_t n_reads, uint64_t max_
     b->lw.valid = false;
     b->hw.valid = false;
     b->pw.valid = false;
+    b->vw.valid = false;
     b->plan_valid = false;
     b->slot_off_valid = false;
     b->class_valid = false;
@@ -1067,6 +1071,7 @@ extern "C" pgx_status pgx_batch_run(pgx_batch *b, uint64_t min_len, uint64_t min
     b->lw.valid = false; // (the locate result belongs to the run before)
     b->hw.valid = false; // (and so do the hits)
     b->pw.valid = false; // (and the places)
+    b->vw.valid = false; // (and what was verified at them)
     b->n_mems = b->n_positions = b->n_ext = b->n_tag_overflow = 0;
     std::memset(&b->timing, 0, sizeof b->timing);
     bool force_worst = false;
@@ -2257,6 +2262,239 @@ extern "C" pgx_status pgx_read_place_arrays(int device, const uint64_t *mem_offs
     if (list) {
         HIPCHECK(hipMemcpyAsync(place_offsets, k.w.place_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
         if (k.w.n_places) HIPCHECK(hipMemcpyAsync(places, k.w.places.p, k.w.n_places * sizeof(pgx_placement), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(hipStreamSynchronize(s));
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// read verify (pgx_verify_kernels.hip; the definitions: include/pgx.h "read verify")
+static const uint32_t VERIFY_FLAGS = PGX_VERIFY_LIST;
+
+static void verify_check_args(const std::string &who, uint32_t penalty, uint32_t flags) {
+    if (flags & ~VERIFY_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
+    if (penalty == 0 || penalty > PGX_VERIFY_MAX_PENALTY)
+        throw Error(PGX_ERR_ARG, who + ": mismatch_penalty " + std::to_string(penalty) + " is outside 1 .. " + std::to_string(PGX_VERIFY_MAX_PENALTY));
+}
+
+// The stage on device arrays, enqueued on s: the candidates w.cand_off / cand_seq / cand_diag / cand_read (n_cands of them) -> w.cands, w.recs.
+// reads: read_bytes bytes, read_off: n + 1 offsets into them.  Every buffer was sized by the caller's checks; nothing is read back.
+static void verify_core(VerifyWork &w, const uint32_t *text4, const uint64_t *seq_start, uint32_t endmark, const uint8_t *reads, uint64_t read_bytes, const uint64_t *read_off,
+                        uint64_t n, uint64_t n_cands, uint32_t penalty, hipStream_t s) {
+    const uint64_t n_rw = (read_bytes + 7) / 8 + 1;
+    w.rcode.ensure(n_rw * 4);
+    w.cands.ensure((n_cands ? n_cands : 1) * sizeof(pgx_read_verify));
+    w.recs.ensure((n ? n : 1) * sizeof(pgx_read_verify));
+    // the reads at the text's symbol width, once per read whatever the number of its candidates
+    hipLaunchKernelGGL(pgx_verify_code_kernel, dim3((unsigned)std::min<uint64_t>((n_rw + 255) / 256, 1u << 20)), dim3(256), 0, s, reads, read_bytes, n_rw, w.rcode.as<uint32_t>());
+    if (n_cands)
+        hipLaunchKernelGGL(pgx_verify_kernel, dim3(grid_for(n_cands, PGX_VERIFY_THREADS)), dim3(PGX_VERIFY_THREADS), 0, s, text4, seq_start, endmark,
+                           (const uint32_t *)w.rcode.as<uint32_t>(), read_off, (const uint64_t *)w.cand_off.as<uint64_t>(), (const uint64_t *)w.cand_read.as<uint64_t>(),
+                           (const uint32_t *)w.cand_seq.as<uint32_t>(), (const int64_t *)w.cand_diag.as<int64_t>(), n_cands, penalty, w.cands.as<pgx_read_verify>());
+    if (n)
+        hipLaunchKernelGGL(pgx_verify_reduce_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const pgx_read_verify *)w.cands.as<pgx_read_verify>(),
+                           (const uint64_t *)w.cand_off.as<uint64_t>(), n, w.recs.as<pgx_read_verify>());
+    HIPCHECK(hipGetLastError());
+}
+
+extern "C" pgx_status pgx_batch_read_verify(pgx_batch *b, uint32_t max_cand, uint32_t mismatch_penalty, uint32_t flags, void *stream) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_read_verify");
+    checked_device_count();
+    const std::string who = "pgx_batch_read_verify";
+    if (!b) throw Error(PGX_ERR_ARG, who + ": null batch");
+    // (what is refused here leaves an earlier verify result as it was)
+    verify_check_args(who, mismatch_penalty, flags);
+    if (max_cand < 1 || max_cand > PGX_VERIFY_MAX_CAND) throw Error(PGX_ERR_ARG, who + ": max_cand " + std::to_string(max_cand) + " is outside 1 .. " + std::to_string(PGX_VERIFY_MAX_CAND));
+    if (!b->ran) throw Error(PGX_ERR_ARG, who + ": batch has not been run");
+    PlaceWork &pw = b->pw;
+    if (!pw.valid || pw.n_reads != b->n_reads) throw Error(PGX_ERR_ARG, who + ": needs a completed pgx_batch_read_place, the batch has no place result");
+    if (max_cand > 1 && !(pw.flags & PGX_PLACE_LIST))
+        throw Error(PGX_ERR_ARG, who + ": max_cand " + std::to_string(max_cand) + " needs a place result made with PGX_PLACE_LIST, the last pgx_batch_read_place ran without it");
+    if (b->max_read_len >= (1ull << 31)) throw Error(PGX_ERR_UNSUPPORTED, who + ": a read of " + std::to_string(b->max_read_len) + " bytes; the records hold read positions below 2^31");
+    const uint64_t n = b->n_reads;
+    if (n >= PLACE_LAUNCH_ITEMS) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n) + " reads exceed one launch");
+    use_device(b->device);
+    pgx_device_image *d = device_image(b->h, b->device);
+    ensure_text(b->h, d); // (throws where the index has no text image, before anything of the batch changes)
+    hipStream_t s = stream ? (hipStream_t)stream : b->own;
+    VerifyWork &w = b->vw;
+    w.valid = false;
+    const bool timed = b->timed;
+    if (timed) {
+        for (auto &e : w.ev)
+            if (!e) HIPCHECK(hipEventCreate(&e));
+        HIPCHECK(hipEventRecord(w.ev[0], s));
+    }
+    // the candidates: counted, scanned, filled
+    const bool from_list = max_cand > 1;
+    const pgx_read_place *recs = pw.recs.as<pgx_read_place>();
+    const uint64_t *place_off = from_list ? pw.place_off.as<uint64_t>() : nullptr;
+    const pgx_placement *places = from_list ? pw.places.as<pgx_placement>() : nullptr;
+    w.count.ensure((n ? n : 1) * 8);
+    w.cand_off.ensure((n + 1) * 8);
+    uint64_t n_cands = 0;
+    if (n) {
+        hipLaunchKernelGGL(pgx_verify_choose_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, recs, place_off, places, n, max_cand, w.count.as<uint64_t>(),
+                           (const uint64_t *)nullptr, (uint32_t *)nullptr, (int64_t *)nullptr);
+        HIPCHECK(hipGetLastError());
+        scan_excl(1, w.count.p, n, 0, w.cand_off.as<uint64_t>(), w.scan_tmp, s);
+        n_cands = read_u64(w.cand_off.as<uint64_t>() + n, s);
+    } else HIPCHECK(hipMemsetAsync(w.cand_off.p, 0, 8, s));
+    if (n_cands >= PLACE_LAUNCH_ITEMS) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_cands) + " candidates exceed one launch; lower max_cand");
+    {
+        const uint64_t need = n_cands * (sizeof(pgx_read_verify) + 20) + n * sizeof(pgx_read_verify) + b->read_bytes / 2;
+        const size_t mem_free = free_device_memory();
+        if (need > w.cands.cap + w.recs.cap + w.rcode.cap && need - (w.cands.cap + w.recs.cap + w.rcode.cap) > mem_free)
+            throw Error(PGX_ERR_NOMEM, who + ": " + std::to_string(n_cands) + " candidates take " + std::to_string(need) + " bytes of device memory, " + std::to_string(mem_free) + " are free");
+    }
+    w.cand_seq.ensure((n_cands ? n_cands : 1) * 4);
+    w.cand_diag.ensure((n_cands ? n_cands : 1) * 8);
+    w.cand_read.ensure((n_cands ? n_cands : 1) * 8);
+    if (n_cands) {
+        hipLaunchKernelGGL(pgx_verify_choose_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, recs, place_off, places, n, max_cand, w.count.as<uint64_t>(),
+                           (const uint64_t *)w.cand_off.as<uint64_t>(), w.cand_seq.as<uint32_t>(), w.cand_diag.as<int64_t>());
+        hipLaunchKernelGGL(pgx_verify_owner_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const uint64_t *)w.cand_off.as<uint64_t>(), n, n_cands, w.cand_read.as<uint64_t>());
+        HIPCHECK(hipGetLastError());
+    }
+    verify_core(w, d->text4.as<uint32_t>(), d->text_seq_start.as<uint64_t>(), 1u, b->reads.as<uint8_t>(), b->read_bytes, b->offsets.as<uint64_t>(), n, n_cands, mismatch_penalty, s);
+    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
+    HIPCHECK(hipStreamSynchronize(s));
+    w.ms = 0;
+    if (timed) HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
+    w.n_reads = n; w.n_cands = n_cands; w.flags = flags; w.max_cand = max_cand; w.penalty = mismatch_penalty;
+    w.valid = true;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+static void verified_header(const pgx_batch *b, pgx_read_verifies *out) {
+    const VerifyWork &w = b->vw;
+    std::memset(out, 0, sizeof *out);
+    out->n_reads = w.n_reads;
+    out->n_cands = w.n_cands;
+    out->flags = w.flags;
+    out->max_cand = w.max_cand;
+    out->mismatch_penalty = w.penalty;
+    out->ms_verify = w.ms;
+}
+
+extern "C" pgx_status pgx_batch_device_verified(pgx_batch *b, pgx_read_verifies *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->vw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_verified: batch has no verify result");
+    const VerifyWork &w = b->vw;
+    verified_header(b, out);
+    out->reads = w.recs.as<pgx_read_verify>();
+    if (w.flags & PGX_VERIFY_LIST) {
+        out->cand_offsets = w.cand_off.as<uint64_t>();
+        out->cands = w.cands.as<pgx_read_verify>();
+    }
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_batch_verified(pgx_batch *b, pgx_read_verifies *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->vw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_verified: batch has no verify result");
+    use_device(b->device);
+    VerifyWork &w = b->vw;
+    const uint64_t n = w.n_reads;
+    const bool list = (w.flags & PGX_VERIFY_LIST) != 0;
+    w.h_recs.ensure((n ? n : 1) * sizeof(pgx_read_verify));
+    if (n) HIPCHECK(hipMemcpyAsync(w.h_recs.p, w.recs.p, n * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, b->own));
+    if (list) {
+        w.h_cand_off.ensure((n + 1) * 8);
+        w.h_cands.ensure((w.n_cands ? w.n_cands : 1) * sizeof(pgx_read_verify));
+        HIPCHECK(hipMemcpyAsync(w.h_cand_off.p, w.cand_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, b->own));
+        if (w.n_cands) HIPCHECK(hipMemcpyAsync(w.h_cands.p, w.cands.p, w.n_cands * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, b->own));
+    }
+    HIPCHECK(hipStreamSynchronize(b->own)); // (the stage completed inside pgx_batch_read_verify, on whatever stream it used)
+    verified_header(b, out);
+    out->reads = w.h_recs.as<pgx_read_verify>();
+    if (list) {
+        out->cand_offsets = w.h_cand_off.as<uint64_t>();
+        out->cands = w.h_cands.as<pgx_read_verify>();
+    }
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_read_verify_arrays(int device, const uint8_t *text, const uint64_t *seq_offsets, uint64_t n_seq, const uint8_t *reads,
+                                             const uint64_t *read_offsets, uint64_t n_reads, const uint64_t *cand_offsets, const uint32_t *cand_seq,
+                                             const int64_t *cand_diag, uint32_t mismatch_penalty, uint32_t flags, pgx_read_verify *out,
+                                             uint64_t *list_offsets, pgx_read_verify *list, uint64_t list_cap) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_read_verify_arrays");
+    checked_device_count();
+    const std::string who = "pgx_read_verify_arrays";
+    verify_check_args(who, mismatch_penalty, flags);
+    const bool want_list = (flags & PGX_VERIFY_LIST) != 0;
+    if (!seq_offsets || !read_offsets || !cand_offsets || (n_reads && !out) || (want_list && (!list_offsets || (list_cap && !list))))
+        throw Error(PGX_ERR_ARG, who + ": null argument");
+    auto check_offsets = [&](const uint64_t *o, uint64_t k, const char *name, const char *item) {
+        if (o[0] != 0) throw Error(PGX_ERR_ARG, who + ": " + name + " must start at 0");
+        for (uint64_t i = 0; i < k; i++)
+            if (o[i] > o[i + 1]) throw Error(PGX_ERR_ARG, who + ": " + name + " decrease at " + item + " " + std::to_string(i));
+    };
+    check_offsets(seq_offsets, n_seq, "seq_offsets", "sequence");
+    check_offsets(read_offsets, n_reads, "read_offsets", "read");
+    check_offsets(cand_offsets, n_reads, "cand_offsets", "read");
+    const uint64_t n_text = seq_offsets[n_seq], read_bytes = read_offsets[n_reads], n_cands = cand_offsets[n_reads];
+    if ((n_text && !text) || (read_bytes && !reads) || (n_cands && (!cand_seq || !cand_diag))) throw Error(PGX_ERR_ARG, who + ": null argument");
+    if (n_text >= (1ull << 32) - (1ull << 20)) throw Error(PGX_ERR_UNSUPPORTED, who + ": a text of " + std::to_string(n_text) + " symbols, the image holds fewer than 2^32 - 2^20");
+    for (uint64_t i = 0; i < n_text; i++) {
+        const uint8_t c = text[i];
+        if (c != '\n' && c != 'A' && c != 'C' && c != 'G' && c != 'N' && c != 'T')
+            throw Error(PGX_ERR_UNSUPPORTED, who + ": text byte " + std::to_string((unsigned)c) + " at offset " + std::to_string(i) + " is none of \\n A C G N T");
+    }
+    for (uint64_t r = 0; r < n_reads; r++)
+        if (read_offsets[r + 1] - read_offsets[r] >= (1ull << 31))
+            throw Error(PGX_ERR_UNSUPPORTED, who + ": read " + std::to_string(r) + " has " + std::to_string(read_offsets[r + 1] - read_offsets[r]) + " bytes; the records hold read positions below 2^31");
+    if (n_reads >= PLACE_LAUNCH_ITEMS || n_cands >= PLACE_LAUNCH_ITEMS)
+        throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_reads) + " reads with " + std::to_string(n_cands) + " candidates exceed one launch");
+    if (want_list && n_cands > list_cap)
+        throw Error(PGX_ERR_NOMEM, who + ": the list holds " + std::to_string(n_cands) + " candidates, list_cap is " + std::to_string(list_cap));
+    use_device(device);
+    struct Work { // device copies of the input + the stage's buffers, released on every way out
+        DevBuf text8, text4, seq_off, reads, read_off;
+        VerifyWork w;
+        ~Work() {
+            DevBuf *all[] = {&text8, &text4, &seq_off, &reads, &read_off};
+            for (DevBuf *d : all) d->release();
+            w.release();
+        }
+    } k;
+    hipStream_t s = nullptr;
+    const uint64_t n_words = (n_text + 7) / 8 + PGX_TEXT_PAD_WORDS;
+    upload(k.text8, text, n_text);
+    upload(k.seq_off, seq_offsets, (n_seq + 1) * 8);
+    upload(k.reads, reads, read_bytes);
+    upload(k.read_off, read_offsets, (n_reads + 1) * 8);
+    upload(k.w.cand_off, cand_offsets, (n_reads + 1) * 8);
+    upload(k.w.cand_seq, cand_seq, n_cands * 4);
+    upload(k.w.cand_diag, cand_diag, n_cands * 8);
+    k.w.cand_read.ensure((n_cands ? n_cands : 1) * 8);
+    if (n_cands) { // the preconditions, before anything is written
+        hipLaunchKernelGGL(pgx_verify_owner_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, s, (const uint64_t *)k.w.cand_off.as<uint64_t>(), n_reads, n_cands,
+                           k.w.cand_read.as<uint64_t>());
+        k.w.bad.ensure(8);
+        HIPCHECK(hipMemsetAsync(k.w.bad.p, 0xFF, 8, s));
+        hipLaunchKernelGGL(pgx_verify_check_kernel, dim3(grid_for(n_cands, 256)), dim3(256), 0, s, (const uint64_t *)k.w.cand_read.as<uint64_t>(),
+                           (const uint32_t *)k.w.cand_seq.as<uint32_t>(), n_cands, n_seq, k.w.bad.as<unsigned long long>());
+        HIPCHECK(hipGetLastError());
+        const uint64_t bad = read_u64(k.w.bad.as<uint64_t>(), s);
+        if (bad != ~0ull) throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(bad) + " has a candidate whose sequence is not below n_seq " + std::to_string(n_seq));
+    }
+    k.text4.ensure(n_words * 4);
+    hipLaunchKernelGGL(pgx_text_pack_kernel, dim3((unsigned)std::min<uint64_t>((n_words + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint8_t *)k.text8.as<uint8_t>(), n_text, n_words,
+                       1u, k.text4.as<uint32_t>());
+    HIPCHECK(hipGetLastError());
+    verify_core(k.w, k.text4.as<uint32_t>(), k.seq_off.as<uint64_t>(), 0u, k.reads.as<uint8_t>(), read_bytes, k.read_off.as<uint64_t>(), n_reads, n_cands, mismatch_penalty, s);
+    if (n_reads) HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, n_reads * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, s));
+    if (want_list) {
+        HIPCHECK(hipMemcpyAsync(list_offsets, k.w.cand_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (n_cands) HIPCHECK(hipMemcpyAsync(list, k.w.cands.p, n_cands * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, s));
     }
     HIPCHECK(hipStreamSynchronize(s));
     return PGX_OK;

@@ -385,6 +385,31 @@ __global__ void pgx_place_sweep_kernel(const uint64_t *mem_off, const pgx_mem *m
 __global__ void pgx_place_check_values_kernel(const uint64_t *values, uint64_t n_values, uint64_t L, uint64_t n_seq, const uint64_t *aoff, uint64_t n_reads,
                                               unsigned long long *bad);
 
+// ---- pgx_verify_kernels.hip: the text image (pgx_image.h "TEXT image") and read verify (pgx_batch_read_verify, pgx_read_verify_arrays)
+#define PGX_TEXT_END 0u // 4-bit codes of the text image: \n A C G N T = 0 .. 5
+#define PGX_TEXT_A 1u
+#define PGX_TEXT_C 2u
+#define PGX_TEXT_G 3u
+#define PGX_TEXT_N 4u
+#define PGX_TEXT_T 5u
+#define PGX_TEXT_SCATTER_END 4u // what pgx_text_mark_kernel writes over the 0xFF of an endmarker in the scattered text bytes
+#define PGX_TEXT_PAD_WORDS 4u   // words behind the text: the verify kernel's aligned 4-byte loads reach at most one word beyond it
+#define PGX_VERIFY_THREADS 256
+__global__ void pgx_text_mark_kernel(const uint64_t *seq_start, uint64_t n_seq, uint64_t n, uint8_t *text8);
+__global__ void pgx_text_scatter32_kernel(const uint32_t *sa32, uint64_t n, uint64_t c1, uint64_t c2, uint64_t c3, uint64_t c4, uint64_t c5, uint8_t *text8);
+// ascii = 0: text8 holds the scatter codes; 1: the bytes of a collection
+__global__ void pgx_text_pack_kernel(const uint8_t *text8, uint64_t n, uint64_t n_words, uint32_t ascii, uint32_t *text4);
+__global__ void pgx_text_unpack_kernel(const uint32_t *text4, uint64_t n, uint8_t *bytes);
+__global__ void pgx_verify_code_kernel(const uint8_t *reads, uint64_t n_bytes, uint64_t n_words, uint32_t *rcode);
+__global__ void pgx_verify_choose_kernel(const pgx_read_place *recs, const uint64_t *place_off, const pgx_placement *places, uint64_t n_reads, uint32_t max_cand,
+                                         uint64_t *count, const uint64_t *cand_off, uint32_t *cand_seq, int64_t *cand_diag);
+__global__ void pgx_verify_owner_kernel(const uint64_t *cand_off, uint64_t n_reads, uint64_t n_cands, uint64_t *cand_read);
+__global__ void pgx_verify_check_kernel(const uint64_t *cand_read, const uint32_t *cand_seq, uint64_t n_cands, uint64_t n_seq, unsigned long long *bad);
+__global__ void pgx_verify_kernel(const uint32_t *text4, const uint64_t *seq_start, uint32_t endmark, const uint32_t *rcode, const uint64_t *read_off,
+                                  const uint64_t *cand_off, const uint64_t *cand_read, const uint32_t *cand_seq, const int64_t *cand_diag, uint64_t n_cands,
+                                  uint32_t penalty, pgx_read_verify *out);
+__global__ void pgx_verify_reduce_kernel(const pgx_read_verify *cands, const uint64_t *cand_off, uint64_t n_reads, pgx_read_verify *out);
+
 // literal count image: COMPAT count_encoded / LF_encoded on an encoded index without N, block by block as the
 // reference's rankAt_encoded (src/r-index.cpp:570-590) sees it -- true cumulative counts, run scan one varint late
 struct PgxLitImage {

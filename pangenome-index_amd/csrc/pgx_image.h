@@ -120,6 +120,21 @@
  * occurrences that match longest are consecutive and ARE the interval the extensions would end with -- in a few trips (one comparison, then sixteen entries of
  * lce_lcp per trip; a further comparison where two lengths tie) instead of (match length) / 2 trips of one line.  The text
  * is recovered from the index alone: the first symbol of suffix i is the symbol whose C-bucket holds i. */
+/* TEXT image (device only, built on the device on its first use: pgx_images.hip ensure_text; pgx_index_text, pgx_batch_read_verify):
+ *   text4          the collection itself with every symbol told apart: FOUR BITS per symbol, eight symbols per u32 (symbol g in bits
+ *                  4 (g % 8) .. of word g / 8), codes \n A C G N T = 0 .. 5 -- 0.5 bytes per symbol (chr22 scale: 0.32 GB).  One XOR and a
+ *                  nibble-nonzero mask compare eight positions; a read's bytes are coded A C G T = 1 2 3 5 and everything else 15, which
+ *                  equals no text code, so N opposite N is a mismatch.  Every sequence is followed by its endmarker; behind the text lie
+ *                  PGX_TEXT_PAD_WORDS words of code 0: the verify kernel loads aligned u32 words, at most one beyond the last word of the text.
+ *   text_seq_start n_seq + 1 text positions (u64): sequence q at [start[q], start[q + 1] - 1), its endmarker at start[q + 1] - 1.
+ * Chosen over two planes (2-bit symbols + a 1-bit "not ACGT" plane, 0.375 bytes per symbol): one load and one XOR per word instead of two
+ * of each, and \n, N told apart without a third plane.  Built by the route of the LCE image (whole suffix array from the locate kernels,
+ * sequence lengths from the endmarker suffixes, first symbols scattered to text positions with pgx_lce_seqlen_kernel / pgx_lce_scatter_kernel
+ * as they are; pgx_text_mark_kernel then gives the endmarkers, which the scatter writes like N, a code of their own); next to a resident LCE
+ * image its lce_sa / lce_seq_start replace the locate and give the same bytes.  Unlike the LCE image it exists for any index that
+ * pgx_locate_batch supports with n < 2^32 - 2^20: forward-only collections (no reverse-complement check), any n, with or without PAIRS.
+ * For a while the build holds 12 n bytes of suffix array (8 n as the locate kernels write it, 4 n as the scatter kernel writes it again), n
+ * text bytes and the image; the free device memory is checked before the first allocation.  Not stored in image files. */
 /* WIDE variants of DENSE2 and PAIRS (BWTs of 2^32 symbols or more, up to PGX_SB_MAX superblocks; FastLocate is size_t end to end,
  * r-index.hpp:118-130): the same 128-byte blocks, but every count in a block header is a 32-bit DELTA against its superblock --
  * 2^sb_shift consecutive blocks, at most 2^31 symbols -- whose 64-bit bases sit in a small table the kernels stage in LDS:

@@ -1,5 +1,6 @@
 // pgx_images.hip -- the device images of an index: the rank image with its seed tables, tag runs and PAIRS blocks (device_image), and what is
-// added on first use: the locate image (locate_image), the LCE image (ensure_lce) and the literal count image (literal_image).
+// added on first use: the locate image (locate_image), the LCE image (ensure_lce), the text image (ensure_text) and the literal count image
+// (literal_image).
 #include <chrono>
 #include <memory>
 #include <mutex>
@@ -50,6 +51,7 @@ static void release_buffers(pgx_device_image *d) {
     release_literal_buffers(d);
     release_locate_buffers(d);
     d->lce_sa.release(); d->lce_text.release(); d->lce_flags.release(); d->lce_lcp.release(); d->lce_seq_start.release();
+    d->text4.release(); d->text_seq_start.release();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -503,6 +505,123 @@ void ensure_lce(pgx_index *h, pgx_device_image *d) {
         d->img.lce_sa = nullptr; d->img.lce_text = nullptr; d->img.lce_flags = nullptr; d->img.lce_lcp = nullptr;
     }
     vals.release(); seq_len.release(); seq_start.release(); text8.release(); bad.release();
+}
+
+// TEXT image (pgx_image.h): the collection itself at four bits per symbol, every symbol told apart, with the sequence starts.  Built once per device image on
+// its first use, by the route of ensure_lce: the whole suffix array from the locate kernels, the sequence lengths from the endmarker suffixes, first symbols
+// scattered to text positions (pgx_lce_seqlen_kernel / pgx_lce_scatter_kernel as they are), then pgx_text_mark_kernel tells endmarkers from N and
+// pgx_text_pack_kernel packs.  Next to a resident LCE image its lce_sa / lce_seq_start stand in for the locate: the same bytes either way.
+// Unlike ensure_lce this one throws: who asks for the text cannot do without it.
+static std::mutex g_text_mutex;
+void ensure_text(pgx_index *h, pgx_device_image *d) {
+    std::lock_guard<std::mutex> lock(g_text_mutex);
+    if (d->has_text) return;
+    if (!h->has_rank) throw Error(PGX_ERR_ARG, "text image: index opened without an r-index");
+    locate_check_supported(h, "text image");
+    if (h->from_image && !h->loc.built)
+        throw Error(PGX_ERR_UNSUPPORTED, "text image: the image file was saved without the locate image (--no-locate), and the text is recovered through it");
+    const uint64_t n = d->img.n;
+    if (n >= (1ull << 32) - (1ull << 20))
+        throw Error(PGX_ERR_UNSUPPORTED, "text image: the BWT has " + std::to_string(n) + " symbols, the image holds fewer than 2^32 - 2^20");
+    uint64_t tot[6]; // symbol counts of the BWT = bucket bounds of the first column
+    for (int i = 0; i < 6; i++) tot[i] = h->meta.sym_total[i];
+    const uint64_t n_seq = tot[0], ml = h->meta.max_length;
+    if (tot[0] + tot[1] + tot[2] + tot[3] + tot[4] + tot[5] != n || n_seq == 0 || ml == 0)
+        throw Error(PGX_ERR_UNSUPPORTED, "text image: the symbol counts of the index do not describe a collection");
+    bool from_lce = false;
+    {
+        std::lock_guard<std::mutex> lce_lock(g_lce_mutex);
+        from_lce = d->lce_state == 1 && d->img.lce_sa && d->lce_seq_start.p && d->lce_n_seq == n_seq;
+    }
+    const uint64_t n_words = (n + 7) / 8 + PGX_TEXT_PAD_WORDS;
+    {
+        // for a while: the suffix array as the locate kernels write it (8 n) and as the scatter kernel writes it again (4 n), a byte a symbol, the image
+        const uint64_t need = (from_lce ? 0 : 12 * n + 128) + n + n_words * 4 + (n_seq + 1) * 16 + (1ull << 20);
+        size_t mem_free = 0, mem_total = 0;
+        if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); throw Error(PGX_ERR_HIP, "text image: hipMemGetInfo failed"); }
+        if ((uint64_t)mem_free < need)
+            throw Error(PGX_ERR_NOMEM, "text image: building it takes " + std::to_string(need) + " bytes of device memory for a while, " + std::to_string(mem_free) + " are free");
+    }
+    DevBuf vals, seq_len, seq_start, text8, sa32, bad, text4;
+    auto drop = [&]() { vals.release(); seq_len.release(); seq_start.release(); text8.release(); sa32.release(); bad.release(); text4.release(); };
+    try {
+        const uint64_t c1 = tot[0], c2 = c1 + tot[1], c3 = c2 + tot[2], c4 = c3 + tot[3], c5 = c4 + tot[4];
+        const unsigned grid_n = (unsigned)std::min<uint64_t>((n + 255) / 256, 1u << 20);
+        seq_start.ensure((n_seq + 1) * 8);
+        text8.ensure(n);
+        if (from_lce) {
+            HIPCHECK(hipMemcpy(seq_start.p, d->lce_seq_start.p, (n_seq + 1) * 8, hipMemcpyDeviceToDevice));
+            hipLaunchKernelGGL(pgx_text_scatter32_kernel, dim3(grid_n), dim3(256), 0, nullptr, (const uint32_t *)d->lce_sa.as<uint32_t>(), n, c1, c2, c3, c4, c5, text8.as<uint8_t>());
+            HIPCHECK(hipGetLastError());
+        } else {
+            pgx_device_image *dl = locate_image(h, d->device);
+            if (!dl->loc.n || dl->loc.n != n) throw Error(PGX_ERR_UNSUPPORTED, "text image: the locate image does not cover the BWT");
+            const uint64_t first = 0, last = n - 1;
+            std::vector<uint64_t> off;
+            uint64_t nv = 0;
+            locate_core(h, dl, &first, &last, 1, 0, off, vals, nv);
+            if (nv != n) throw Error(PGX_ERR_UNSUPPORTED, "text image: the suffix array is incomplete");
+            seq_len.ensure(n_seq * 8); bad.ensure(16);
+            HIPCHECK(hipMemset(seq_len.p, 0, n_seq * 8));
+            HIPCHECK(hipMemset(bad.p, 0, 16));
+            hipLaunchKernelGGL(pgx_lce_seqlen_kernel, dim3(grid_for(n_seq, 256)), dim3(256), 0, nullptr, vals.as<uint64_t>(), n_seq, ml, seq_len.as<unsigned long long>());
+            HIPCHECK(hipGetLastError());
+            std::vector<uint64_t> hl(n_seq), hs(n_seq + 1, 0);
+            HIPCHECK(hipMemcpy(hl.data(), seq_len.p, n_seq * 8, hipMemcpyDeviceToHost));
+            for (uint64_t q = 0; q < n_seq; q++) {
+                if (hl[q] == 0) throw Error(PGX_ERR_UNSUPPORTED, "text image: sequence " + std::to_string(q) + " has no endmarker suffix");
+                hs[q + 1] = hs[q] + hl[q];
+            }
+            if (hs[n_seq] != n) throw Error(PGX_ERR_UNSUPPORTED, "text image: the sequence lengths do not add up to the BWT size");
+            HIPCHECK(hipMemcpy(seq_start.p, hs.data(), (n_seq + 1) * 8, hipMemcpyHostToDevice));
+            sa32.ensure(n * 4 + 128);
+            hipLaunchKernelGGL(pgx_lce_scatter_kernel, dim3(grid_n), dim3(256), 0, nullptr, vals.as<uint64_t>(), n, ml, seq_start.as<uint64_t>(), n_seq, c1, c2, c3, c4, c5,
+                               sa32.as<uint32_t>(), text8.as<uint8_t>(), bad.as<unsigned long long>());
+            HIPCHECK(hipGetLastError());
+            unsigned long long n_bad = 0;
+            HIPCHECK(hipMemcpy(&n_bad, bad.p, 8, hipMemcpyDeviceToHost));
+            if (n_bad) throw Error(PGX_ERR_UNSUPPORTED, "text image: suffix array values outside the collection");
+            vals.release(); sa32.release();
+        }
+        hipLaunchKernelGGL(pgx_text_mark_kernel, dim3(grid_for(n_seq, 256)), dim3(256), 0, nullptr, (const uint64_t *)seq_start.as<uint64_t>(), n_seq, n, text8.as<uint8_t>());
+        HIPCHECK(hipGetLastError());
+        text4.ensure(n_words * 4);
+        hipLaunchKernelGGL(pgx_text_pack_kernel, dim3((unsigned)std::min<uint64_t>((n_words + 255) / 256, 1u << 20)), dim3(256), 0, nullptr, (const uint8_t *)text8.as<uint8_t>(), n,
+                           n_words, 0u, text4.as<uint32_t>());
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipDeviceSynchronize());
+    } catch (...) { (void)hipGetLastError(); drop(); throw; }
+    d->text4 = text4; text4 = DevBuf();
+    d->text_seq_start = seq_start; seq_start = DevBuf();
+    d->text_n_seq = n_seq;
+    d->has_text = true;
+    drop();
+}
+
+extern "C" pgx_status pgx_index_text(pgx_index *h, int device, uint64_t *seq_lengths, uint64_t n_seq_cap, uint8_t *text, uint64_t text_cap) {
+    PGX_GUARD_BEGIN
+    if (!h || !seq_lengths) throw Error(PGX_ERR_ARG, "pgx_index_text: null argument");
+    pgx_device_image *d = device_image(h, device);
+    ensure_text(h, d);
+    const uint64_t n = d->img.n, n_seq = d->text_n_seq;
+    if (n_seq_cap < n_seq) throw Error(PGX_ERR_ARG, "pgx_index_text: the index has " + std::to_string(n_seq) + " sequences, n_seq_cap is " + std::to_string(n_seq_cap));
+    if (text && text_cap < n) throw Error(PGX_ERR_ARG, "pgx_index_text: the text has " + std::to_string(n) + " bytes, text_cap is " + std::to_string(text_cap));
+    std::vector<uint64_t> hs(n_seq + 1);
+    HIPCHECK(hipMemcpy(hs.data(), d->text_seq_start.p, (n_seq + 1) * 8, hipMemcpyDeviceToHost));
+    for (uint64_t q = 0; q < n_seq; q++) seq_lengths[q] = hs[q + 1] - hs[q] - 1;
+    if (text && n) {
+        DevBuf bytes;
+        try {
+            bytes.ensure(n);
+            hipLaunchKernelGGL(pgx_text_unpack_kernel, dim3((unsigned)std::min<uint64_t>(((n + 7) / 8 + 255) / 256, 1u << 20)), dim3(256), 0, nullptr,
+                               (const uint32_t *)d->text4.as<uint32_t>(), n, bytes.as<uint8_t>());
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipMemcpy(text, bytes.p, n, hipMemcpyDeviceToHost));
+        } catch (...) { bytes.release(); throw; }
+        bytes.release();
+    }
+    return PGX_OK;
+    PGX_GUARD_END
 }
 
 // COMPAT count_encoded / LF_encoded on an encoded index without N: the reference mis-parses every block (quirk 3); the literal

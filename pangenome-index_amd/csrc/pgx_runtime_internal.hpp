@@ -64,6 +64,9 @@ struct pgx_device_image {
     DevBuf lce_seq_start;                          // with it: n_seq + 1 text positions, sequence q at [start[q], start[q + 1]) (pgx_batch_locate)
     uint64_t lce_n_seq = 0;
     int lce_state = 0;                             // 0 not tried, 1 built, 2 not available for this index / device
+    DevBuf text4, text_seq_start;                  // TEXT image (ensure_text), built on its first use: 4-bit symbols; n_seq + 1 text positions
+    uint64_t text_n_seq = 0;
+    bool has_text = false;
     DevBuf lit_bstart, lit_cum, lit_runs, lit_roff, lit_tabs; // literal count image (quirk 3), uploaded on first use
     PgxLitImage lit{};
     bool has_lit = false;
@@ -77,6 +80,7 @@ pgx_device_image *device_image(pgx_index *h, int device);
 pgx_device_image *locate_image(pgx_index *h, int device);
 pgx_device_image *literal_image(pgx_index *h, int device);
 void ensure_lce(pgx_index *h, pgx_device_image *d);
+void ensure_text(pgx_index *h, pgx_device_image *d); // throws where the image cannot be built (include/pgx.h pgx_index_text)
 // the section sum of an image file over n_bytes of device memory (16-byte aligned), added to *sum on stream s (pgx_image_sum_kernels.hip)
 void launch_image_sum(const void *data, uint64_t n_bytes, unsigned long long *sum, hipStream_t s);
 
@@ -172,6 +176,25 @@ struct PlaceWork {
         DevBuf *all[] = {&recs, &pcount, &place_off, &places, &aoff, &acnt, &mfirst, &keys, &seg, &lists, &need, &soff, &scratch, &ucount, &loff, &ctr, &scan_tmp, &bad};
         for (DevBuf *d : all) d->release();
         h_recs.release(); h_place_off.release(); h_places.release();
+        for (auto &e : ev)
+            if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        valid = false;
+    }
+};
+
+// pgx_batch_read_verify's buffers (grow-only, its own: a later locate leaves them alone) and its result; pgx_read_verify_arrays uses one of its own
+struct VerifyWork {
+    DevBuf recs, count, cand_off, cand_seq, cand_diag, cand_read, cands, rcode, scan_tmp, bad;
+    HostBuf h_recs, h_cand_off, h_cands;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool valid = false;
+    uint32_t flags = 0, max_cand = 0, penalty = 0;
+    uint64_t n_reads = 0, n_cands = 0;
+    float ms = 0;
+    void release() {
+        DevBuf *all[] = {&recs, &count, &cand_off, &cand_seq, &cand_diag, &cand_read, &cands, &rcode, &scan_tmp, &bad};
+        for (DevBuf *d : all) d->release();
+        h_recs.release(); h_cand_off.release(); h_cands.release();
         for (auto &e : ev)
             if (e) { (void)hipEventDestroy(e); e = nullptr; }
         valid = false;

@@ -126,6 +126,18 @@ class ReadPlaces(C.Structure):  # pgx_read_places: host pointers (pgx_batch_plac
                 ("places", p), ("ms_place", C.c_float), ("reserved", u32)]
 
 
+VERIFY_LIST = 1  # pgx_batch_read_verify / pgx_read_verify_arrays flag
+VERIFY_DTYPE = np.dtype([("diag", "<i8"), ("seq", "<u4"), ("n_cand", "<u4"), ("span_lo", "<u4"), ("span_hi", "<u4"), ("matches", "<u4"), ("mismatches", "<u4"),
+                         ("seg_start", "<u4"), ("seg_end", "<u4"), ("seg_score", "<u4"), ("seg_mismatches", "<u4"), ("longest_run", "<u4"), ("run_start", "<u4"),
+                         ("cand_index", "<u4"), ("n_tied", "<u4")])  # pgx_read_verify, 64 bytes
+assert VERIFY_DTYPE.itemsize == 64
+
+
+class ReadVerifies(C.Structure):  # pgx_read_verifies: host pointers (pgx_batch_verified) or device pointers (pgx_batch_device_verified)
+    _fields_ = [("n_reads", u64), ("n_cands", u64), ("flags", u32), ("max_cand", u32), ("mismatch_penalty", u32), ("reserved", u32), ("reads", p),
+                ("cand_offsets", p), ("cands", p), ("ms_verify", C.c_float), ("reserved2", u32)]
+
+
 class DeviceArray:
     """a device buffer owned by a batch, exposed through __cuda_array_interface__ (zero copy: torch.as_tensor(a, device="cuda"));
     64-bit unsigned values are presented as int64"""
@@ -269,6 +281,11 @@ def lib():
     L.pgx_batch_places.argtypes = [p, C.POINTER(ReadPlaces)]
     L.pgx_batch_device_places.argtypes = [p, C.POINTER(ReadPlaces)]
     L.pgx_read_place_arrays.argtypes = [C.c_int, p, u64, p, p, p, u64, u64, u32, p, p, p, u64]
+    L.pgx_index_text.argtypes = [p, C.c_int, p, u64, p, u64]
+    L.pgx_batch_read_verify.argtypes = [p, u32, u32, u32, p]
+    L.pgx_batch_verified.argtypes = [p, C.POINTER(ReadVerifies)]
+    L.pgx_batch_device_verified.argtypes = [p, C.POINTER(ReadVerifies)]
+    L.pgx_read_verify_arrays.argtypes = [C.c_int, p, p, u64, p, p, u64, p, p, p, u32, u32, p, p, p, u64]
     L.pgx_batch_result_compact.argtypes = [p, C.POINTER(CompactResult)]
     L.pgx_compact_expand.argtypes = [C.POINTER(CompactResult), u64, u64, p, p, p, p, p]
     L.pgx_compact_bound.argtypes = [u64, u64, u64, u32]
@@ -582,6 +599,15 @@ class Index:
         out = np.zeros(host.nbytes, dtype=np.uint8)
         _check(self.L.pgx_index_device_view(self.h, device, which, C.c_void_p(out.ctypes.data), u64(host.nbytes)))
         return out.view(host.dtype)
+
+    def text(self, device=0):
+        """pgx_index_text: (seq_lengths uint64[n_sequences], the collection as bytes, every sequence followed by a newline), recovered on the
+        device from the index alone (builds the text image on first use)"""
+        inf = self.info()
+        lens = np.zeros(int(inf.n_sequences), dtype=np.uint64)
+        buf = np.zeros(int(inf.bwt_size), dtype=np.uint8)
+        _check(self.L.pgx_index_text(self.h, device, lens.ctypes.data, len(lens), buf.ctypes.data, len(buf)))
+        return lens, buf.tobytes()
 
     def lce_view(self, which, nbytes, device=0):
         """the device's LCE image (which = 30 suffix array, 31 text, 32 line flags, 33 common prefixes) as bytes; zeros where the index has none"""
@@ -904,6 +930,38 @@ def read_place_arrays(device, mem_offsets, mems, loc_offsets, values, n_seq, max
     return res
 
 
+def read_verify_arrays(device, text, seq_offsets, reads, read_offsets, cand_offsets, cand_seq, cand_diag, penalty=4, flags=0, list_cap=None, out=None):
+    """pgx_read_verify_arrays: the verify kernels on host arrays (text uint8, the sequences without endmarkers, with seq_offsets uint64[n_seq + 1];
+    reads uint8 with read_offsets uint64[n_reads + 1]; the candidates of read r at [cand_offsets[r], cand_offsets[r + 1]) of cand_seq uint32 /
+    cand_diag int64): dict(reads VERIFY_DTYPE[n_reads], and with VERIFY_LIST cand_offsets uint64[n_reads + 1] and cands VERIFY_DTYPE[n_cands], else
+    None).  list_cap: the capacity handed to the library (default: the number of candidates); out: a dict of arrays to write into (tests)"""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+    read_offsets = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    cand_offsets = np.ascontiguousarray(cand_offsets, dtype=np.uint64)
+    cand_seq = np.ascontiguousarray(cand_seq, dtype=np.uint32)
+    cand_diag = np.ascontiguousarray(cand_diag, dtype=np.int64)
+    n, n_seq = len(read_offsets) - 1, len(seq_offsets) - 1
+    if len(cand_offsets) != n + 1 or len(cand_seq) != len(cand_diag):
+        raise ValueError("read_verify_arrays: cand_offsets must have len(read_offsets) entries, cand_seq and cand_diag the same length")
+    lst = bool(flags & VERIFY_LIST)
+    cap = len(cand_seq) if list_cap is None else int(list_cap)
+    res = dict(out) if out else {}
+    if "reads" not in res:
+        res["reads"] = np.zeros(n, dtype=VERIFY_DTYPE)
+    if "cand_offsets" not in res:
+        res["cand_offsets"] = np.zeros(n + 1, dtype=np.uint64) if lst else None
+    if "cands" not in res:
+        res["cands"] = np.zeros(max(cap, 1), dtype=VERIFY_DTYPE) if lst else None
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().pgx_read_verify_arrays(device, text.ctypes.data, seq_offsets.ctypes.data, n_seq, reads.ctypes.data, read_offsets.ctypes.data, n, cand_offsets.ctypes.data,
+                                        cand_seq.ctypes.data, cand_diag.ctypes.data, penalty, flags, ptr(res["reads"]), ptr(res["cand_offsets"]), ptr(res["cands"]), cap))
+    if lst:
+        res["cands"] = res["cands"][: int(res["cand_offsets"][-1])]
+    return res
+
+
 def find_mems_sharded(index, devices, reads_cat, offsets, min_len, min_occ, tags=False):
     """pgx_find_mems_sharded: contiguous read slices, slice i on devices[i]; returns the per-slice result dicts in slice order"""
     reads_cat = np.ascontiguousarray(reads_cat, dtype=np.uint8)
@@ -1212,6 +1270,39 @@ class Batch:
         out["reads"] = DeviceArray(r.reads, (n, 8), self)
         out["place_offsets"] = DeviceArray(r.place_offsets, (n + 1,), self) if r.place_offsets else None
         out["places"] = DeviceArray(r.places, (k, 3), self) if r.places else None
+        return out
+
+    def read_verify(self, max_cand=1, penalty=4, flags=0, stream=None):
+        """pgx_batch_read_verify at the candidates of the last read_place (with PLACE_LIST when max_cand > 1), then verified()"""
+        _check(self.L.pgx_batch_read_verify(self.b, max_cand, penalty, flags, stream))
+        return self.verified()
+
+    def _verified(self, fn):
+        r = ReadVerifies()
+        _check(fn(self.b, C.byref(r)))
+        return r, dict(n_reads=int(r.n_reads), n_cands=int(r.n_cands), flags=int(r.flags), max_cand=int(r.max_cand), mismatch_penalty=int(r.mismatch_penalty),
+                       ms_verify=float(r.ms_verify))
+
+    def verified(self):
+        """the last verify result as numpy arrays: reads VERIFY_DTYPE[n_reads]; with VERIFY_LIST cand_offsets uint64[n_reads + 1] and cands
+        VERIFY_DTYPE[n_cands] (None without), with n_reads, n_cands, flags, max_cand, mismatch_penalty, ms_verify"""
+        r, out = self._verified(self.L.pgx_batch_verified)
+        n, k = out["n_reads"], out["n_cands"]
+        records = lambda ptr, count, dt: np.frombuffer((C.c_char * (count * dt.itemsize)).from_address(ptr), dtype=dt).copy() if count else np.zeros(0, dt)
+        out["reads"] = records(r.reads, n, VERIFY_DTYPE)
+        out["cand_offsets"] = _u64_array(C.cast(r.cand_offsets, C.POINTER(u64)), n + 1) if r.cand_offsets else None
+        out["cands"] = records(r.cands, k, VERIFY_DTYPE) if r.cands else None
+        return out
+
+    def device_verified(self):
+        """the same as device arrays (valid until the next run / upload / read_verify / free): reads and cands int64[., 8] (the 64-byte
+        records as words), cand_offsets int64[n_reads + 1]"""
+        r, out = self._verified(self.L.pgx_batch_device_verified)
+        n, k = out["n_reads"], out["n_cands"]
+        out["device"] = True
+        out["reads"] = DeviceArray(r.reads, (n, 8), self)
+        out["cand_offsets"] = DeviceArray(r.cand_offsets, (n + 1,), self) if r.cand_offsets else None
+        out["cands"] = DeviceArray(r.cands, (k, 8), self) if r.cands else None
         return out
 
     def free(self):

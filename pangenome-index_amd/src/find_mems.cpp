@@ -18,6 +18,9 @@
 //                 --hits-max K (MEMs with more occurrences count as not located in the hits), --hits-only (no MEM text: stdout stays empty; not with --locate)
 //                 --place FILE (one line per read: the sequence diagonal the read lies on best, pgx_batch_read_place; stdout and stderr stay as they are),
 //                 --place-max K (MEMs with more occurrences are left unlocated in the placement), --place-only (no MEM text, like --hits-only)
+//                 --verify FILE (one line per read: the read laid on the indexed text at its best placements, pgx_batch_read_verify; runs the place
+//                 stage itself without --place; stdout and stderr stay as they are), --verify-max C (candidates per read, 1 .. 64, default 1),
+//                 --verify-mismatch P (the segment's mismatch penalty, default 4), --verify-only (no MEM text, like --place-only)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -148,6 +151,7 @@ struct Done {
     double mem_s = 0, tag_s = 0;
     std::string hits; // --hits: the lines of this batch
     std::string places; // --place: the lines of this batch
+    std::string verifies; // --verify: the lines of this batch
     std::string error;
 };
 
@@ -284,13 +288,34 @@ static void format_places(const pgx_read_place *recs, size_t n, uint64_t first_s
     out.resize((size_t)(p - &out[0]));
 }
 
+// --verify: the lines of reads [0, n) of a batch, appended to out; seq and pos print as * when the read has no candidate
+static const char VERIFY_HEADER[] = "#read\tseq\tpos\tspan_lo\tspan_hi\tmatches\tmismatches\tseg_start\tseg_end\tseg_score\tseg_mismatches\trun\trun_start\tcands\ttied\n";
+static void format_verifies(const pgx_read_verify *recs, size_t n, uint64_t first_seq, std::string &out) {
+    out.resize(n * (15 * 21));
+    char *p = &out[0];
+    for (size_t i = 0; i < n; i++) {
+        const pgx_read_verify &x = recs[i];
+        p = put_u64(p, first_seq + i + 1); *p++ = '\t';
+        if (x.seq == PGX_NO_SEQUENCE) { *p++ = '*'; *p++ = '\t'; *p++ = '*'; }
+        else {
+            p = put_u64(p, x.seq); *p++ = '\t';
+            if (x.diag < 0) { *p++ = '-'; p = put_u64(p, 0 - (uint64_t)x.diag); } else p = put_u64(p, (uint64_t)x.diag);
+        }
+        const uint32_t f[12] = {x.span_lo, x.span_hi, x.matches, x.mismatches, x.seg_start, x.seg_end, x.seg_score, x.seg_mismatches, x.longest_run, x.run_start, x.n_cand, x.n_tied};
+        for (uint32_t v : f) { *p++ = '\t'; p = put_u64(p, v); }
+        *p++ = '\n';
+    }
+    out.resize((size_t)(p - &out[0]));
+}
+
 static int usage() {
     std::cerr << "usage: find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ>"
                  " [--device N | --gpus N | --devices a,b,..] [--streams W] [--mode compat|strict] [--batch N]"
                  " [--tags-format auto|bytecode|compact] [--quiet] [--reads-format lines|fasta|fastq|auto] [--device-parse]"
                  " [--locate positions|seqs] [--locate-max K] [--result full|compact] [--format host|device]"
                  " [--hits FILE [--hits-max K] [--hits-only (not with --locate)]]"
-                 " [--place FILE [--place-max K] [--place-only (not with --locate)]]" << std::endl;
+                 " [--place FILE [--place-max K] [--place-only (not with --locate)]]"
+                 " [--verify FILE [--verify-max C] [--verify-mismatch P] [--verify-only (not with --locate)]]" << std::endl;
     return EXIT_FAILURE;
 }
 
@@ -315,6 +340,9 @@ int main(int argc, char **argv) {
     std::string place_file;     // --place: the read placements of every batch go to this file
     uint64_t place_max = 0;
     bool place_max_given = false, place_only = false;
+    std::string verify_file;    // --verify: the verified placements of every batch go to this file
+    uint32_t verify_max = 1, verify_penalty = 4;
+    bool verify_opt_given = false, verify_only = false;
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -390,14 +418,29 @@ int main(int argc, char **argv) {
             place_max_given = true;
         }
         else if (a == "--place-only") place_only = true;
+        else if (a == "--verify") { verify_file = next(); if (verify_file.empty()) { std::cerr << "--verify: a file name" << std::endl; return EXIT_FAILURE; } }
+        else if (a == "--verify-max" || a == "--verify-mismatch") {
+            const std::string v = next();
+            char *endp = nullptr;
+            errno = 0;
+            const unsigned long long k = v.empty() || v[0] == '-' ? 0 : std::strtoull(v.c_str(), &endp, 10);
+            const unsigned long long top = a == "--verify-max" ? PGX_VERIFY_MAX_CAND : PGX_VERIFY_MAX_PENALTY;
+            if (!endp || *endp || errno || k < 1 || k > top) { std::cerr << a << ": a number in 1 .. " << top << std::endl; return EXIT_FAILURE; }
+            (a == "--verify-max" ? verify_max : verify_penalty) = (uint32_t)k;
+            verify_opt_given = true;
+        }
+        else if (a == "--verify-only") verify_only = true;
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
     if ((hits_max_given || hits_only) && hits_file.empty()) return usage();
     if (hits_only && locate_mode) { std::cerr << "--hits-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if ((place_max_given || place_only) && place_file.empty()) return usage();
     if (place_only && locate_mode) { std::cerr << "--place-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
-    const bool want_hits = !hits_file.empty(), want_places = !place_file.empty();
-    const bool no_text = hits_only || place_only; // (either one: no tag stage, no download of result arrays, stdout empty)
+    if ((verify_opt_given || verify_only) && verify_file.empty()) return usage();
+    if (verify_only && locate_mode) { std::cerr << "--verify-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
+    const bool want_hits = !hits_file.empty(), want_places = !place_file.empty(), want_verify = !verify_file.empty();
+    const uint32_t place_flags = want_verify && verify_max > 1 ? PGX_PLACE_LIST : 0u; // (the candidates beyond the first come from the list)
+    const bool no_text = hits_only || place_only || verify_only; // (either one: no tag stage, no download of result arrays, stdout empty)
     if (batch_reads == 0) batch_reads = 1;
     if (locate_max && !locate_mode) { std::cerr << "--locate-max needs --locate" << std::endl; return EXIT_FAILURE; }
 
@@ -474,6 +517,33 @@ int main(int argc, char **argv) {
         place_fp = std::fopen(place_file.c_str(), "wb");
         if (!place_fp) { std::cerr << "Cannot open place file: " << place_file << std::endl; return EXIT_FAILURE; }
         std::fwrite(PLACE_HEADER, 1, sizeof PLACE_HEADER - 1, place_fp);
+    }
+    // --verify: the same question for the text image (what --place asks, and a collection of 2^32 - 2^20 symbols or more)
+    std::FILE *verify_fp = nullptr;
+    if (want_verify) {
+        static const uint8_t probe_read[4] = {'A', 'C', 'G', 'T'};
+        static const uint64_t probe_offs[2] = {0, 4};
+        pgx_status st = PGX_OK;
+        std::string msg;
+        for (size_t i = 0; st == PGX_OK && i < devices.size(); i++) { // (the text image of every device is built here, before any batch)
+            pgx_batch *pb = nullptr;
+            st = pgx_batch_create(h, devices[i], probe_read, probe_offs, 1, &pb);
+            if (st == PGX_OK) st = pgx_batch_run(pb, mem_length, min_occ, 0, nullptr);
+            if (st == PGX_OK) st = pgx_batch_locate(pb, 0, place_max, nullptr);
+            if (st == PGX_OK) st = pgx_batch_read_place(pb, place_flags, nullptr);
+            if (st == PGX_OK) st = pgx_batch_read_verify(pb, verify_max, verify_penalty, 0, nullptr);
+            if (st != PGX_OK) msg = pgx_last_error();
+            pgx_batch_free(pb);
+        }
+        if (st != PGX_OK) {
+            std::cerr << msg << (st == PGX_ERR_UNSUPPORTED ? " (find_mems --verify)" : "") << std::endl;
+            if (hits_fp) std::fclose(hits_fp);
+            if (place_fp) std::fclose(place_fp);
+            return EXIT_FAILURE;
+        }
+        verify_fp = std::fopen(verify_file.c_str(), "wb");
+        if (!verify_fp) { std::cerr << "Cannot open verify file: " << verify_file << std::endl; return EXIT_FAILURE; }
+        std::fwrite(VERIFY_HEADER, 1, sizeof VERIFY_HEADER - 1, verify_fp);
     }
 
     // ---- the reads file, mapped: the reference reads it with std::getline (find_mems.cpp:96); here a planner cuts it into byte ranges that
@@ -733,12 +803,19 @@ int main(int argc, char **argv) {
                 if (st == PGX_OK) hit_recs.assign(rh.hits, rh.hits + rh.n_reads);
             }
             std::vector<pgx_read_place> place_recs; // --place: the 64-byte records; the stage's buffers are its own, the locate below does not touch them
-            if (st == PGX_OK && want_places) {
+            if (st == PGX_OK && (want_places || want_verify)) {
                 st = pgx_batch_locate(b, 0, place_max, nullptr);
-                if (st == PGX_OK) st = pgx_batch_read_place(b, 0, nullptr);
+                if (st == PGX_OK) st = pgx_batch_read_place(b, place_flags, nullptr);
                 pgx_read_places rp2;
-                if (st == PGX_OK) st = pgx_batch_places(b, &rp2);
-                if (st == PGX_OK) place_recs.assign(rp2.reads, rp2.reads + rp2.n_reads);
+                if (st == PGX_OK && want_places) st = pgx_batch_places(b, &rp2);
+                if (st == PGX_OK && want_places) place_recs.assign(rp2.reads, rp2.reads + rp2.n_reads);
+            }
+            std::vector<pgx_read_verify> verify_recs; // --verify: the 64-byte records, at the candidates of the place stage above
+            if (st == PGX_OK && want_verify) {
+                st = pgx_batch_read_verify(b, verify_max, verify_penalty, 0, nullptr);
+                pgx_read_verifies rv;
+                if (st == PGX_OK) st = pgx_batch_verified(b, &rv);
+                if (st == PGX_OK) verify_recs.assign(rv.reads, rv.reads + rv.n_reads);
             }
             if (format_device || no_text) {
                 // nothing to download: the device writes the text below, once the batch knows the number of its first read
@@ -784,6 +861,7 @@ int main(int argc, char **argv) {
                 }
                 if (want_hits) format_hits(hit_recs.data(), hit_recs.size(), j->first_seq, d->hits);
                 if (want_places) format_places(place_recs.data(), place_recs.size(), j->first_seq, d->places);
+                if (want_verify) format_verifies(verify_recs.data(), verify_recs.size(), j->first_seq, d->verifies);
                 if (format_device && !no_text) {
                     // the text of the batch from the device, handed to the writer where it is
                     const uint64_t t3w = now_ns();
@@ -882,6 +960,7 @@ int main(int argc, char **argv) {
         if (d->etext_n) std::fwrite(d->etext, 1, d->etext_n, stderr);
         if (hits_fp && !d->hits.empty()) std::fwrite(d->hits.data(), 1, d->hits.size(), hits_fp);
         if (place_fp && !d->places.empty()) std::fwrite(d->places.data(), 1, d->places.size(), place_fp);
+        if (verify_fp && !d->verifies.empty()) std::fwrite(d->verifies.data(), 1, d->verifies.size(), verify_fp);
         ns_write += now_ns() - tw0;
         total_mem_time += d->mem_s;
         total_tag_time += d->tag_s;
@@ -905,6 +984,7 @@ int main(int argc, char **argv) {
     if (error.empty() && failed) error = "find_mems: a device batch failed";
     if (hits_fp && (std::fclose(hits_fp) != 0) && error.empty()) error = "Cannot write hits file: " + hits_file;
     if (place_fp && (std::fclose(place_fp) != 0) && error.empty()) error = "Cannot write place file: " + place_file;
+    if (verify_fp && (std::fclose(verify_fp) != 0) && error.empty()) error = "Cannot write verify file: " + verify_file;
     if (!error.empty()) {
         std::cerr << error << std::endl;
         return EXIT_FAILURE;
