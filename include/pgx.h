@@ -885,6 +885,87 @@ pgx_status pgx_read_verify_arrays(int device, const uint8_t *text, const uint64_
                                   const int64_t *cand_diag, uint32_t mismatch_penalty, uint32_t flags, pgx_read_verify *out,
                                   uint64_t *list_offsets, pgx_read_verify *list, uint64_t list_cap);
 
+/* ---- read align: every read aligned with gaps at its verified placement, on the device -------------------------------------------
+ * Verify knows only substitutions: a read with a one-base insertion or deletion places on two neighbouring diagonals, each covering part of
+ * it, and the winner reads as "half the read matches, then a wall of mismatches".  This stage computes the banded unit-cost alignment of the
+ * read against the text around the verify winner and traces it back, so that the answer is "one deletion at read position 71".
+ *
+ * DEFINITIONS.  Read r has bytes R[0, len).  Its candidate is (seq, diag).  Sequence seq has Ls symbols T[0, Ls).  The band half-width is W,
+ * 0 <= W <= 31.
+ *   clips        [lo, hi) is the verify span of the candidate: lo = max(0, -diag), hi = min(len, Ls - diag).  Only Q = R[lo, hi) is aligned,
+ *                with m = hi - lo and d0 = diag + lo; clip_lo = lo and clip_hi = len - hi are reported as soft clips.  Empty span:
+ *                clip_lo = 0, clip_hi = len, everything else 0 (seq and diag stay the candidate's), and one S operation if len > 0.
+ *                Because of the clips the main diagonal j = d0 + i lies inside the sequence for every row, so the recurrence is defined
+ *                for every candidate.
+ *   cells        a cell is (i, j), with i symbols of Q and text offset j consumed.  It is valid iff 0 <= i <= m, 0 <= j <= Ls and |k| <= W,
+ *                where k = j - i - d0.  Cells off the sequence do not exist: nothing reads the endmarker or a neighbouring sequence.
+ *   match        as in verify: Q[i-1] is an upper-case A C G T and equals T[j-1].  N, lower case, IUPAC codes and a text N never match.
+ *   recurrence   unit costs.  D[0][j] = 0 for every valid j, so the start in the text is free.  D[i][j] is the minimum over valid
+ *                predecessors of D[i-1][j-1] + (0 if match else 1), D[i-1][j] + 1 (insertion: a read symbol without text),
+ *                D[i][j-1] + 1 (deletion).
+ *   end cell     the valid cell of row m with the smallest D.  Ties go to the smallest |k|, then to the negative k.
+ *   traceback    from the end cell to row 0, the first of these that reproduces D[i][j] is taken: 1. the diagonal move (= on a match, else
+ *                X), 2. the insertion (I), 3. the deletion (D).  The path never starts or ends with D.
+ *   results      text_start is j at row 0, text_end is j of the end cell (offsets in the sequence); edits = D of the end cell;
+ *                n_match + n_mismatch + n_ins = m; n_match + n_mismatch + n_del = text_end - text_start; edits = n_mismatch + n_ins + n_del
+ *   band_hit     1 iff W > 0 and some cell of the traced path, ends included, has |k| == W: the banded optimum may then not be the unbanded one
+ *   CIGAR        u32 words of length << 4 | op with the BAM codes I = 1, D = 2, S = 4, = is 7, X = 8.  Operations come in read order, equal
+ *                neighbours are merged.  A leading S is clip_lo, a trailing S is clip_hi, each only when non-zero.
+ *   W = 0        the ungapped case: edits equals verify's mismatches, and text_start == diag + lo
+ * pgx_read_align (64 bytes, little endian):
+ *    0 diag i64      8 text_start u64     16 text_end u64
+ *   24 seq u32 (PGX_NO_SEQUENCE and everything else 0 when the read has no candidate)
+ *   28 clip_lo  32 clip_hi  36 edits  40 n_match  44 n_mismatch  48 n_ins  52 n_del  56 n_ops  60 band_hit   (u32 each; nothing is left to pad)
+ * n_ops counts the read's CIGAR operations, clips included, with and without PGX_ALIGN_CIGAR.  PGX_ALIGN_CIGAR adds op_offsets[n_reads + 1]
+ * and the operations.  The direction planes of the traceback (two bits a cell, max(G, 8) / 4 bytes a read position, G the power of two
+ * >= 2 W + 1) live in a scratch buffer that is filled in passes over consecutive whole reads; the passes stay within PGX_ALIGN_BUDGET_MB
+ * (read per call, fractions allowed, default a quarter of the free device memory) and results never depend on it.  A single read above the
+ * budget is PGX_ERR_NOMEM naming the read.  Reads of 2^28 bytes or more are PGX_ERR_UNSUPPORTED (an operation's length has 28 bits). */
+#define PGX_ALIGN_CIGAR 1u
+#define PGX_ALIGN_MAX_BAND 31u
+#define PGX_ALIGN_OP_I 1u
+#define PGX_ALIGN_OP_D 2u
+#define PGX_ALIGN_OP_S 4u
+#define PGX_ALIGN_OP_EQ 7u
+#define PGX_ALIGN_OP_X 8u
+typedef struct {
+    int64_t diag;
+    uint64_t text_start, text_end;
+    uint32_t seq, clip_lo, clip_hi, edits, n_match, n_mismatch, n_ins, n_del, n_ops, band_hit;
+} pgx_read_align;
+typedef struct {
+    uint64_t n_reads;
+    uint64_t n_ops;               /* CIGAR operations over all reads (with and without PGX_ALIGN_CIGAR) */
+    uint32_t flags;               /* PGX_ALIGN_* the call ran with */
+    uint32_t band;
+    uint32_t passes;              /* passes over the scratch buffer of the direction planes */
+    uint32_t reserved;
+    const pgx_read_align *reads;  /* n_reads */
+    const uint64_t *op_offsets;   /* n_reads + 1; NULL without PGX_ALIGN_CIGAR */
+    const uint32_t *ops;          /* n_ops; NULL without PGX_ALIGN_CIGAR */
+    uint64_t scratch_bytes;       /* direction planes of the largest pass */
+    float ms_align;               /* device time of the call when the run had PGX_RUN_TIMING, else 0 */
+    float ms_forward, ms_trace;   /* of it: the forward kernel's launches / the traceback's launches */
+    uint32_t reserved2;
+} pgx_read_aligns;
+/* Aligns the reads of the last run at the winners of the last pgx_batch_read_verify, which must be this run's.  PGX_ERR_ARG with nothing
+ * changed: no verify result, band > 31, an unknown flag.  Runs on `stream` (NULL = the batch's own), complete on return.  The result stays
+ * valid until the next run, upload, pgx_batch_read_align or free of the batch; a later pgx_batch_locate of any form leaves it valid.  The
+ * stage's buffers grow only and are its own. */
+pgx_status pgx_batch_read_align(pgx_batch *b, uint32_t band, uint32_t flags, void *stream);
+/* Host copy of the last align result (pinned buffers owned by the batch) / the same as device pointers.  PGX_ERR_ARG when there is none. */
+pgx_status pgx_batch_aligned(pgx_batch *b, pgx_read_aligns *out);
+pgx_status pgx_batch_device_aligned(pgx_batch *b, pgx_read_aligns *out);
+/* The same kernels on host arrays, with one candidate per read: text, seq_offsets, reads and read_offsets as in pgx_read_verify_arrays;
+ * cand_seq[n_reads] / cand_diag[n_reads], PGX_NO_SEQUENCE meaning none, any other candidate allowed, a non-overlapping one included.  `out`
+ * takes n_reads records; with PGX_ALIGN_CIGAR op_offsets takes n_reads + 1 entries and ops up to ops_cap words (PGX_ERR_NOMEM with the needed
+ * count when there are more; both may be NULL without the flag).  The argument checks are those of pgx_read_verify_arrays (PGX_ERR_ARG with
+ * nothing written: an unknown flag, band > 31, offsets that do not start at 0 or decrease, a cand_seq that is neither below n_seq nor
+ * PGX_NO_SEQUENCE, the first offending read named).  PGX_ERR_NO_DEVICE without a GPU. */
+pgx_status pgx_read_align_arrays(int device, const uint8_t *text, const uint64_t *seq_offsets, uint64_t n_seq, const uint8_t *reads,
+                                 const uint64_t *read_offsets, uint64_t n_reads, const uint32_t *cand_seq, const int64_t *cand_diag, uint32_t band,
+                                 uint32_t flags, pgx_read_align *out, uint64_t *op_offsets, uint32_t *ops, uint64_t ops_cap);
+
 /* ---- compact result: the result of a run as a byte stream, encoded on the device, expanded on the host ---------------------
  * What pgx_batch_result downloads is six dense uint64 arrays (8 bytes per read, 48 per MEM, 8 per graph position), nearly all of
  * them zero bits.  The compact form carries the same values and is expanded to the same pgx_result; only it crosses the link.

@@ -1,5 +1,5 @@
 // pgx_batch.hip -- the pgx_batch object: uploads, pgx_batch_run, results, pgx_batch_locate, pgx_batch_read_hits, pgx_batch_read_place,
-// pgx_batch_read_verify.
+// pgx_batch_read_verify, pgx_batch_read_align.
 //
 // Pipeline of pgx_batch_run (one HIP stream, results stay on the device):
 //   scan(cap)      -> slot offsets (worst-case MEMs per read: min(len, len - min_len + 1)); the slot buffer
@@ -88,6 +88,7 @@ struct pgx_batch {
     HitsWork hw;    // pgx_batch_read_hits
     PlaceWork pw;   // pgx_batch_read_place
     VerifyWork vw;  // pgx_batch_read_verify
+    AlignWork aw;   // pgx_batch_read_align
     uint64_t n_mems = 0, n_positions = 0, n_ext = 0, n_tag_overflow = 0;
     bool ran = false, ran_tags = false;
     // speculative sizing (pgx_batch_run): what the last run with these parameters produced
@@ -118,6 +119,7 @@ static void batch_release(pgx_batch *b) {
         b->hw.release();
         b->pw.release();
         b->vw.release();
+        b->aw.release();
         HostBuf *hb[] = {&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]};
         for (HostBuf *x : hb) x->release();
         for (auto &e : b->ev)
@@ -144,6 +146,7 @@ static void batch_reset_for_upload(pgx_batch *b, uint64_t n_reads, uint64_t max_
     b->hw.valid = false;
     b->pw.valid = false;
     b->vw.valid = false;
+    b->aw.valid = false;
     b->plan_valid = false;
     b->slot_off_valid = false;
     b->class_valid = false;
@@ -1072,6 +1075,7 @@ extern "C" pgx_status pgx_batch_run(pgx_batch *b, uint64_t min_len, uint64_t min
     b->hw.valid = false; // (and so do the hits)
     b->pw.valid = false; // (and the places)
     b->vw.valid = false; // (and what was verified at them)
+    b->aw.valid = false; // (and aligned there)
     b->n_mems = b->n_positions = b->n_ext = b->n_tag_overflow = 0;
     std::memset(&b->timing, 0, sizeof b->timing);
     bool force_worst = false;
@@ -2495,6 +2499,303 @@ extern "C" pgx_status pgx_read_verify_arrays(int device, const uint8_t *text, co
     if (want_list) {
         HIPCHECK(hipMemcpyAsync(list_offsets, k.w.cand_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
         if (n_cands) HIPCHECK(hipMemcpyAsync(list, k.w.cands.p, n_cands * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(hipStreamSynchronize(s));
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// read align (pgx_align_kernels.hip; the definitions: include/pgx.h "read align")
+static const uint32_t ALIGN_FLAGS = PGX_ALIGN_CIGAR;
+static const uint64_t ALIGN_MAX_READ = 1ull << 28; // an operation's length has 28 bits
+
+static void align_check_args(const std::string &who, uint32_t band, uint32_t flags) {
+    if (flags & ~ALIGN_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
+    if (band > PGX_ALIGN_MAX_BAND) throw Error(PGX_ERR_ARG, who + ": band " + std::to_string(band) + " is outside 0 .. " + std::to_string(PGX_ALIGN_MAX_BAND));
+}
+
+// bytes of direction planes one pass may hold: PGX_ALIGN_BUDGET_MB (read per call, fractions allowed), default a quarter of the free device memory
+static uint64_t align_budget_bytes(size_t mem_free) {
+    uint64_t bytes = 0;
+    if (const char *e = std::getenv("PGX_ALIGN_BUDGET_MB")) {
+        const double mb = std::strtod(e, nullptr);
+        if (mb > 0) bytes = (uint64_t)(mb * 1048576.0);
+    }
+    if (!bytes) bytes = mem_free / 4;
+    return std::max<uint64_t>(bytes, 16);
+}
+
+struct AlignPass { uint64_t r0, r1, bytes; };
+
+// The passes over consecutive whole reads whose planes fit the budget, from the host's read offsets: a read of len bytes takes len rows of
+// row_bytes, rounded up to 16 (pgx_align_need_kernel computes the same on the device).  Throws before anything is launched.
+static std::vector<AlignPass> align_plan(const uint64_t *h_read_off, uint64_t n, uint32_t row_bytes, uint64_t budget, const std::string &who) {
+    std::vector<AlignPass> passes;
+    AlignPass cur{0, 0, 0};
+    for (uint64_t r = 0; r < n; r++) {
+        const uint64_t len = h_read_off[r + 1] - h_read_off[r];
+        if (len >= ALIGN_MAX_READ) throw Error(PGX_ERR_UNSUPPORTED, who + ": read " + std::to_string(r) + " has " + std::to_string(len) + " bytes; an operation's length is below 2^28");
+        const uint64_t need = (len * row_bytes + 15) & ~15ull;
+        if (need > budget)
+            throw Error(PGX_ERR_NOMEM, who + ": read " + std::to_string(r) + " needs " + std::to_string(need) + " bytes of direction planes, a pass holds " + std::to_string(budget) +
+                                           " (PGX_ALIGN_BUDGET_MB)");
+        if (cur.bytes + need > budget) { passes.push_back(cur); cur = AlignPass{r, r, 0}; }
+        cur.bytes += need;
+        cur.r1 = r + 1;
+    }
+    if (cur.r1 > cur.r0) passes.push_back(cur);
+    return passes;
+}
+
+template <int LG>
+static void align_launch_forward(const uint32_t *text4, const uint64_t *seq_start, uint32_t endmark, const uint32_t *rcode, const uint64_t *read_off, const AlignWork &w,
+                                 const AlignPass &p, uint32_t band, hipStream_t s) {
+    hipLaunchKernelGGL(pgx_align_forward_kernel<LG>, dim3(grid_for(p.r1 - p.r0, PGX_ALIGN_THREADS >> LG)), dim3(PGX_ALIGN_THREADS), 0, s, text4, seq_start, endmark, rcode, read_off,
+                       (const uint32_t *)w.cand_seq.as<uint32_t>(), (const int64_t *)w.cand_diag.as<int64_t>(), p.r0, p.r1, band, (const uint64_t *)w.plane_off.as<uint64_t>(),
+                       w.planes.as<uint8_t>(), w.fwd.as<uint2>());
+}
+
+// The stage on device arrays, enqueued on s (synchronised where the number of operations is read back): w.cand_seq / w.cand_diag (n of each) -> w.recs,
+// w.op_off and, with PGX_ALIGN_CIGAR, w.ops.  rcode: the reads coded by pgx_verify_code_kernel.  The plan was made by the caller: nothing here refuses.
+// With one pass the planes stay in place between the counting walk and the writing walk; with more, the forward kernel runs again before the writing walk.
+static void align_core(AlignWork &w, const uint32_t *text4, const uint64_t *seq_start, uint32_t endmark, const uint32_t *rcode, const uint64_t *read_off, uint64_t n,
+                       const std::vector<AlignPass> &plan, uint32_t band, uint32_t flags, bool timed, hipStream_t s) {
+    uint32_t lg = 0;
+    while ((1u << lg) < 2 * band + 1) lg++;
+    const uint32_t row_bytes = std::max(1u << lg, 8u) / 4;
+    uint64_t scratch = 16;
+    for (const AlignPass &p : plan) scratch = std::max(scratch, p.bytes);
+    w.recs.ensure((n ? n : 1) * sizeof(pgx_read_align));
+    w.need.ensure((n ? n : 1) * 8); w.plane_off.ensure((n + 1) * 8); w.fwd.ensure((n ? n : 1) * sizeof(uint2));
+    w.count.ensure((n ? n : 1) * 8); w.op_off.ensure((n + 1) * 8);
+    w.planes.ensure(scratch);
+    size_t n_ev = 2;
+    auto stamp = [&]() { // the next event of the call, recorded on s
+        if (!timed) return;
+        if (w.ev.size() <= n_ev) w.ev.resize(n_ev + 1, nullptr);
+        if (!w.ev[n_ev]) HIPCHECK(hipEventCreate(&w.ev[n_ev]));
+        HIPCHECK(hipEventRecord(w.ev[n_ev++], s));
+    };
+    std::vector<int> kinds; // of every pair of events: 0 forward, 1 trace
+    auto forward = [&](const AlignPass &p) {
+        stamp();
+        switch (lg) {
+        case 0: align_launch_forward<0>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
+        case 1: align_launch_forward<1>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
+        case 2: align_launch_forward<2>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
+        case 3: align_launch_forward<3>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
+        case 4: align_launch_forward<4>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
+        case 5: align_launch_forward<5>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
+        default: align_launch_forward<6>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
+        }
+        stamp();
+        kinds.push_back(0);
+    };
+    auto trace = [&](const AlignPass &p, uint32_t write) {
+        stamp();
+        hipLaunchKernelGGL(pgx_align_trace_kernel, dim3(grid_for(p.r1 - p.r0, 256)), dim3(256), 0, s, seq_start, endmark, read_off, (const uint32_t *)w.cand_seq.as<uint32_t>(),
+                           (const int64_t *)w.cand_diag.as<int64_t>(), p.r0, p.r1, band, row_bytes, (const uint64_t *)w.plane_off.as<uint64_t>(),
+                           (const uint8_t *)w.planes.as<uint8_t>(), (const uint2 *)w.fwd.as<uint2>(), write, w.recs.as<pgx_read_align>(), w.count.as<uint64_t>(),
+                           (const uint64_t *)w.op_off.as<uint64_t>(), w.ops.as<uint32_t>());
+        stamp();
+        kinds.push_back(1);
+    };
+    uint64_t n_ops = 0;
+    if (n) {
+        hipLaunchKernelGGL(pgx_align_need_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, read_off, n, row_bytes, w.need.as<uint64_t>());
+        HIPCHECK(hipGetLastError());
+        scan_excl(1, w.need.p, n, 0, w.plane_off.as<uint64_t>(), w.scan_tmp, s);
+        for (const AlignPass &p : plan) { forward(p); trace(p, 0); }
+        HIPCHECK(hipGetLastError());
+        scan_excl(1, w.count.p, n, 0, w.op_off.as<uint64_t>(), w.scan_tmp, s);
+        n_ops = read_u64(w.op_off.as<uint64_t>() + n, s);
+    } else HIPCHECK(hipMemsetAsync(w.op_off.p, 0, 8, s));
+    if ((flags & PGX_ALIGN_CIGAR) && n_ops) {
+        w.ops.ensure(n_ops * 4);
+        for (const AlignPass &p : plan) {
+            if (plan.size() > 1) forward(p);
+            trace(p, 1);
+        }
+        HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipStreamSynchronize(s));
+    w.ms_forward = w.ms_trace = 0;
+    for (size_t i = 0; timed && i < kinds.size(); i++) {
+        float ms = 0;
+        HIPCHECK(hipEventElapsedTime(&ms, w.ev[2 + 2 * i], w.ev[3 + 2 * i]));
+        (kinds[i] ? w.ms_trace : w.ms_forward) += ms;
+    }
+    w.n_reads = n; w.n_ops = n_ops; w.flags = flags; w.band = band; w.passes = (uint32_t)plan.size(); w.scratch_bytes = plan.empty() ? 0 : scratch;
+}
+
+extern "C" pgx_status pgx_batch_read_align(pgx_batch *b, uint32_t band, uint32_t flags, void *stream) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_read_align");
+    checked_device_count();
+    const std::string who = "pgx_batch_read_align";
+    if (!b) throw Error(PGX_ERR_ARG, who + ": null batch");
+    // (what is refused here leaves an earlier align result as it was)
+    align_check_args(who, band, flags);
+    if (!b->ran) throw Error(PGX_ERR_ARG, who + ": batch has not been run");
+    VerifyWork &vw = b->vw;
+    if (!vw.valid || vw.n_reads != b->n_reads) throw Error(PGX_ERR_ARG, who + ": needs a completed pgx_batch_read_verify, the batch has no verify result");
+    const uint64_t n = b->n_reads;
+    if (n >= PLACE_LAUNCH_ITEMS) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n) + " reads exceed one launch");
+    use_device(b->device);
+    pgx_device_image *d = device_image(b->h, b->device);
+    ensure_text(b->h, d); // (built by the verify stage)
+    uint32_t lg = 0;
+    while ((1u << lg) < 2 * band + 1) lg++;
+    const std::vector<AlignPass> plan = align_plan(b->h_offsets(), n, std::max(1u << lg, 8u) / 4, align_budget_bytes(free_device_memory()), who);
+    hipStream_t s = stream ? (hipStream_t)stream : b->own;
+    AlignWork &w = b->aw;
+    w.valid = false;
+    const bool timed = b->timed;
+    if (timed) {
+        if (w.ev.size() < 2) w.ev.resize(2, nullptr);
+        for (int i = 0; i < 2; i++)
+            if (!w.ev[i]) HIPCHECK(hipEventCreate(&w.ev[i]));
+        HIPCHECK(hipEventRecord(w.ev[0], s));
+    }
+    w.cand_seq.ensure((n ? n : 1) * 4); w.cand_diag.ensure((n ? n : 1) * 8);
+    if (n) {
+        hipLaunchKernelGGL(pgx_align_cand_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const pgx_read_verify *)vw.recs.as<pgx_read_verify>(), n, w.cand_seq.as<uint32_t>(),
+                           w.cand_diag.as<int64_t>());
+        HIPCHECK(hipGetLastError());
+    }
+    // (the reads were coded by the verify call for all of its candidates: vw.rcode describes this run's reads)
+    align_core(w, d->text4.as<uint32_t>(), d->text_seq_start.as<uint64_t>(), 1u, (const uint32_t *)vw.rcode.as<uint32_t>(), b->offsets.as<uint64_t>(), n, plan, band, flags, timed, s);
+    w.ms = 0;
+    if (timed) {
+        HIPCHECK(hipEventRecord(w.ev[1], s));
+        HIPCHECK(hipStreamSynchronize(s));
+        HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
+    }
+    w.valid = true;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+static void aligned_header(const pgx_batch *b, pgx_read_aligns *out) {
+    const AlignWork &w = b->aw;
+    std::memset(out, 0, sizeof *out);
+    out->n_reads = w.n_reads;
+    out->n_ops = w.n_ops;
+    out->flags = w.flags;
+    out->band = w.band;
+    out->passes = w.passes;
+    out->scratch_bytes = w.scratch_bytes;
+    out->ms_align = w.ms;
+    out->ms_forward = w.ms_forward;
+    out->ms_trace = w.ms_trace;
+}
+
+extern "C" pgx_status pgx_batch_device_aligned(pgx_batch *b, pgx_read_aligns *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->aw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_aligned: batch has no align result");
+    const AlignWork &w = b->aw;
+    aligned_header(b, out);
+    out->reads = w.recs.as<pgx_read_align>();
+    if (w.flags & PGX_ALIGN_CIGAR) {
+        out->op_offsets = w.op_off.as<uint64_t>();
+        out->ops = w.ops.as<uint32_t>();
+    }
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_batch_aligned(pgx_batch *b, pgx_read_aligns *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->aw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_aligned: batch has no align result");
+    use_device(b->device);
+    AlignWork &w = b->aw;
+    const uint64_t n = w.n_reads;
+    const bool list = (w.flags & PGX_ALIGN_CIGAR) != 0;
+    w.h_recs.ensure((n ? n : 1) * sizeof(pgx_read_align));
+    if (n) HIPCHECK(hipMemcpyAsync(w.h_recs.p, w.recs.p, n * sizeof(pgx_read_align), hipMemcpyDeviceToHost, b->own));
+    if (list) {
+        w.h_op_off.ensure((n + 1) * 8);
+        w.h_ops.ensure((w.n_ops ? w.n_ops : 1) * 4);
+        HIPCHECK(hipMemcpyAsync(w.h_op_off.p, w.op_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, b->own));
+        if (w.n_ops) HIPCHECK(hipMemcpyAsync(w.h_ops.p, w.ops.p, w.n_ops * 4, hipMemcpyDeviceToHost, b->own));
+    }
+    HIPCHECK(hipStreamSynchronize(b->own)); // (the stage completed inside pgx_batch_read_align, on whatever stream it used)
+    aligned_header(b, out);
+    out->reads = w.h_recs.as<pgx_read_align>();
+    if (list) {
+        out->op_offsets = w.h_op_off.as<uint64_t>();
+        out->ops = w.h_ops.as<uint32_t>();
+    }
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_read_align_arrays(int device, const uint8_t *text, const uint64_t *seq_offsets, uint64_t n_seq, const uint8_t *reads,
+                                            const uint64_t *read_offsets, uint64_t n_reads, const uint32_t *cand_seq, const int64_t *cand_diag, uint32_t band,
+                                            uint32_t flags, pgx_read_align *out, uint64_t *op_offsets, uint32_t *ops, uint64_t ops_cap) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_read_align_arrays");
+    checked_device_count();
+    const std::string who = "pgx_read_align_arrays";
+    align_check_args(who, band, flags);
+    const bool want_ops = (flags & PGX_ALIGN_CIGAR) != 0;
+    if (!seq_offsets || !read_offsets || (n_reads && (!out || !cand_seq || !cand_diag)) || (want_ops && (!op_offsets || (ops_cap && !ops))))
+        throw Error(PGX_ERR_ARG, who + ": null argument");
+    auto check_offsets = [&](const uint64_t *o, uint64_t k, const char *name, const char *item) {
+        if (o[0] != 0) throw Error(PGX_ERR_ARG, who + ": " + name + " must start at 0");
+        for (uint64_t i = 0; i < k; i++)
+            if (o[i] > o[i + 1]) throw Error(PGX_ERR_ARG, who + ": " + name + " decrease at " + item + " " + std::to_string(i));
+    };
+    check_offsets(seq_offsets, n_seq, "seq_offsets", "sequence");
+    check_offsets(read_offsets, n_reads, "read_offsets", "read");
+    const uint64_t n_text = seq_offsets[n_seq], read_bytes = read_offsets[n_reads];
+    if ((n_text && !text) || (read_bytes && !reads)) throw Error(PGX_ERR_ARG, who + ": null argument");
+    if (n_text >= (1ull << 32) - (1ull << 20)) throw Error(PGX_ERR_UNSUPPORTED, who + ": a text of " + std::to_string(n_text) + " symbols, the image holds fewer than 2^32 - 2^20");
+    for (uint64_t i = 0; i < n_text; i++) {
+        const uint8_t c = text[i];
+        if (c != '\n' && c != 'A' && c != 'C' && c != 'G' && c != 'N' && c != 'T')
+            throw Error(PGX_ERR_UNSUPPORTED, who + ": text byte " + std::to_string((unsigned)c) + " at offset " + std::to_string(i) + " is none of \\n A C G N T");
+    }
+    for (uint64_t r = 0; r < n_reads; r++)
+        if (cand_seq[r] != PGX_NO_SEQUENCE && cand_seq[r] >= n_seq)
+            throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " has a candidate whose sequence is not below n_seq " + std::to_string(n_seq));
+    if (n_reads >= PLACE_LAUNCH_ITEMS) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_reads) + " reads exceed one launch");
+    use_device(device);
+    uint32_t lg = 0;
+    while ((1u << lg) < 2 * band + 1) lg++;
+    const std::vector<AlignPass> plan = align_plan(read_offsets, n_reads, std::max(1u << lg, 8u) / 4, align_budget_bytes(free_device_memory()), who);
+    struct Work { // device copies of the input + the stage's buffers, released on every way out
+        DevBuf text8, text4, seq_off, reads, read_off;
+        AlignWork w;
+        ~Work() {
+            DevBuf *all[] = {&text8, &text4, &seq_off, &reads, &read_off};
+            for (DevBuf *d : all) d->release();
+            w.release();
+        }
+    } k;
+    hipStream_t s = nullptr;
+    const uint64_t n_words = (n_text + 7) / 8 + PGX_TEXT_PAD_WORDS, n_rw = (read_bytes + 7) / 8 + 1;
+    upload(k.text8, text, n_text);
+    upload(k.seq_off, seq_offsets, (n_seq + 1) * 8);
+    upload(k.reads, reads, read_bytes);
+    upload(k.read_off, read_offsets, (n_reads + 1) * 8);
+    upload(k.w.cand_seq, cand_seq, n_reads * 4);
+    upload(k.w.cand_diag, cand_diag, n_reads * 8);
+    k.text4.ensure(n_words * 4);
+    k.w.rcode.ensure(n_rw * 4);
+    hipLaunchKernelGGL(pgx_text_pack_kernel, dim3((unsigned)std::min<uint64_t>((n_words + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint8_t *)k.text8.as<uint8_t>(), n_text, n_words,
+                       1u, k.text4.as<uint32_t>());
+    hipLaunchKernelGGL(pgx_verify_code_kernel, dim3((unsigned)std::min<uint64_t>((n_rw + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint8_t *)k.reads.as<uint8_t>(), read_bytes, n_rw,
+                       k.w.rcode.as<uint32_t>());
+    HIPCHECK(hipGetLastError());
+    align_core(k.w, k.text4.as<uint32_t>(), k.seq_off.as<uint64_t>(), 0u, (const uint32_t *)k.w.rcode.as<uint32_t>(), k.read_off.as<uint64_t>(), n_reads, plan, band, flags, false, s);
+    if (want_ops && k.w.n_ops > ops_cap)
+        throw Error(PGX_ERR_NOMEM, who + ": the list holds " + std::to_string(k.w.n_ops) + " operations, ops_cap is " + std::to_string(ops_cap));
+    if (n_reads) HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, n_reads * sizeof(pgx_read_align), hipMemcpyDeviceToHost, s));
+    if (want_ops) {
+        HIPCHECK(hipMemcpyAsync(op_offsets, k.w.op_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (k.w.n_ops) HIPCHECK(hipMemcpyAsync(ops, k.w.ops.p, k.w.n_ops * 4, hipMemcpyDeviceToHost, s));
     }
     HIPCHECK(hipStreamSynchronize(s));
     return PGX_OK;

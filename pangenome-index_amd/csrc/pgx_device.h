@@ -410,6 +410,19 @@ __global__ void pgx_verify_kernel(const uint32_t *text4, const uint64_t *seq_sta
                                   uint32_t penalty, pgx_read_verify *out);
 __global__ void pgx_verify_reduce_kernel(const pgx_read_verify *cands, const uint64_t *cand_off, uint64_t n_reads, pgx_read_verify *out);
 
+// ---- pgx_align_kernels.hip: read align (pgx_batch_read_align, pgx_read_align_arrays)
+#define PGX_ALIGN_THREADS 256
+__global__ void pgx_align_cand_kernel(const pgx_read_verify *recs, uint64_t n_reads, uint32_t *cand_seq, int64_t *cand_diag);
+__global__ void pgx_align_need_kernel(const uint64_t *read_off, uint64_t n_reads, uint32_t row_bytes, uint64_t *need);
+// LG: log2 of the lanes a read takes, the smallest with 2^LG >= 2 W + 1; reads [r0, r1), their planes behind plane_off[r] - plane_off[r0]
+template <int LG>
+__global__ void pgx_align_forward_kernel(const uint32_t *text4, const uint64_t *seq_start, uint32_t endmark, const uint32_t *rcode, const uint64_t *read_off,
+                                         const uint32_t *cand_seq, const int64_t *cand_diag, uint64_t r0, uint64_t r1, uint32_t W, const uint64_t *plane_off,
+                                         uint8_t *planes, uint2 *fwd);
+__global__ void pgx_align_trace_kernel(const uint64_t *seq_start, uint32_t endmark, const uint64_t *read_off, const uint32_t *cand_seq, const int64_t *cand_diag,
+                                       uint64_t r0, uint64_t r1, uint32_t W, uint32_t row_bytes, const uint64_t *plane_off, const uint8_t *planes, const uint2 *fwd,
+                                       uint32_t write, pgx_read_align *out, uint64_t *count, const uint64_t *op_off, uint32_t *ops);
+
 // literal count image: COMPAT count_encoded / LF_encoded on an encoded index without N, block by block as the
 // reference's rankAt_encoded (src/r-index.cpp:570-590) sees it -- true cumulative counts, run scan one varint late
 struct PgxLitImage {

@@ -201,6 +201,26 @@ struct VerifyWork {
     }
 };
 
+// pgx_batch_read_align's buffers (grow-only, its own) and its result; pgx_read_align_arrays uses one of its own
+struct AlignWork {
+    DevBuf recs, cand_seq, cand_diag, need, plane_off, planes, fwd, count, op_off, ops, rcode, scan_tmp;
+    HostBuf h_recs, h_op_off, h_ops;
+    std::vector<hipEvent_t> ev; // [0], [1]: around the call; then a pair a launch of the forward and of the trace kernel
+    bool valid = false;
+    uint32_t flags = 0, band = 0, passes = 0;
+    uint64_t n_reads = 0, n_ops = 0, scratch_bytes = 0;
+    float ms = 0, ms_forward = 0, ms_trace = 0;
+    void release() {
+        DevBuf *all[] = {&recs, &cand_seq, &cand_diag, &need, &plane_off, &planes, &fwd, &count, &op_off, &ops, &rcode, &scan_tmp};
+        for (DevBuf *d : all) d->release();
+        h_recs.release(); h_op_off.release(); h_ops.release();
+        for (auto &e : ev)
+            if (e) (void)hipEventDestroy(e);
+        ev.clear();
+        valid = false;
+    }
+};
+
 inline uint64_t with_slack(uint64_t v) { return v + v / 4 + 64; }
 
 // Device scalars of the stage, sc[] (zeroed by the caller): [0] big-list length [1] large-list length [2] largest run count on the

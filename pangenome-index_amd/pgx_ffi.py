@@ -138,6 +138,23 @@ class ReadVerifies(C.Structure):  # pgx_read_verifies: host pointers (pgx_batch_
                 ("cand_offsets", p), ("cands", p), ("ms_verify", C.c_float), ("reserved2", u32)]
 
 
+ALIGN_CIGAR = 1  # pgx_batch_read_align / pgx_read_align_arrays flag
+ALIGN_DTYPE = np.dtype([("diag", "<i8"), ("text_start", "<u8"), ("text_end", "<u8"), ("seq", "<u4"), ("clip_lo", "<u4"), ("clip_hi", "<u4"), ("edits", "<u4"),
+                        ("n_match", "<u4"), ("n_mismatch", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4"), ("n_ops", "<u4"), ("band_hit", "<u4")])  # pgx_read_align, 64 bytes
+assert ALIGN_DTYPE.itemsize == 64
+ALIGN_OPS = {1: "I", 2: "D", 4: "S", 7: "=", 8: "X"}  # the BAM codes of an operation word (length << 4 | op)
+
+
+def cigar_text(words):
+    """3S70=1D76=1X from the operation words of a read"""
+    return "".join("%d%s" % (int(x) >> 4, ALIGN_OPS[int(x) & 15]) for x in words)
+
+
+class ReadAligns(C.Structure):  # pgx_read_aligns: host pointers (pgx_batch_aligned) or device pointers (pgx_batch_device_aligned)
+    _fields_ = [("n_reads", u64), ("n_ops", u64), ("flags", u32), ("band", u32), ("passes", u32), ("reserved", u32), ("reads", p), ("op_offsets", p), ("ops", p),
+                ("scratch_bytes", u64), ("ms_align", C.c_float), ("ms_forward", C.c_float), ("ms_trace", C.c_float), ("reserved2", u32)]
+
+
 class DeviceArray:
     """a device buffer owned by a batch, exposed through __cuda_array_interface__ (zero copy: torch.as_tensor(a, device="cuda"));
     64-bit unsigned values are presented as int64"""
@@ -286,6 +303,10 @@ def lib():
     L.pgx_batch_verified.argtypes = [p, C.POINTER(ReadVerifies)]
     L.pgx_batch_device_verified.argtypes = [p, C.POINTER(ReadVerifies)]
     L.pgx_read_verify_arrays.argtypes = [C.c_int, p, p, u64, p, p, u64, p, p, p, u32, u32, p, p, p, u64]
+    L.pgx_batch_read_align.argtypes = [p, u32, u32, p]
+    L.pgx_batch_aligned.argtypes = [p, C.POINTER(ReadAligns)]
+    L.pgx_batch_device_aligned.argtypes = [p, C.POINTER(ReadAligns)]
+    L.pgx_read_align_arrays.argtypes = [C.c_int, p, p, u64, p, p, u64, p, p, u32, u32, p, p, p, u64]
     L.pgx_batch_result_compact.argtypes = [p, C.POINTER(CompactResult)]
     L.pgx_compact_expand.argtypes = [C.POINTER(CompactResult), u64, u64, p, p, p, p, p]
     L.pgx_compact_bound.argtypes = [u64, u64, u64, u32]
@@ -962,6 +983,37 @@ def read_verify_arrays(device, text, seq_offsets, reads, read_offsets, cand_offs
     return res
 
 
+def read_align_arrays(device, text, seq_offsets, reads, read_offsets, cand_seq, cand_diag, band=8, flags=0, ops_cap=None, out=None):
+    """pgx_read_align_arrays: the align kernels on host arrays (text, seq_offsets, reads, read_offsets as in read_verify_arrays; one candidate per
+    read, cand_seq uint32[n_reads] with NO_SEQUENCE 0xFFFFFFFF for none, cand_diag int64[n_reads]): dict(reads ALIGN_DTYPE[n_reads], and with
+    ALIGN_CIGAR op_offsets uint64[n_reads + 1] and ops uint32[n_ops], else None).  ops_cap: the capacity handed to the library (default: enough for
+    any alignment of these reads); out: a dict of arrays to write into (tests)"""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+    read_offsets = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    cand_seq = np.ascontiguousarray(cand_seq, dtype=np.uint32)
+    cand_diag = np.ascontiguousarray(cand_diag, dtype=np.int64)
+    n, n_seq = len(read_offsets) - 1, len(seq_offsets) - 1
+    if len(cand_seq) != n or len(cand_diag) != n:
+        raise ValueError("read_align_arrays: cand_seq and cand_diag must have an entry per read")
+    lst = bool(flags & ALIGN_CIGAR)
+    cap = int(read_offsets[-1]) + 2 * int(band) * n + 2 * n if ops_cap is None else int(ops_cap)  # (a path holds at most len + 2 W moves and two clips)
+    res = dict(out) if out else {}
+    if "reads" not in res:
+        res["reads"] = np.zeros(n, dtype=ALIGN_DTYPE)
+    if "op_offsets" not in res:
+        res["op_offsets"] = np.zeros(n + 1, dtype=np.uint64) if lst else None
+    if "ops" not in res:
+        res["ops"] = np.zeros(max(cap, 1), dtype=np.uint32) if lst else None
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().pgx_read_align_arrays(device, text.ctypes.data, seq_offsets.ctypes.data, n_seq, reads.ctypes.data, read_offsets.ctypes.data, n, cand_seq.ctypes.data,
+                                       cand_diag.ctypes.data, band, flags, ptr(res["reads"]), ptr(res["op_offsets"]), ptr(res["ops"]), cap))
+    if lst:
+        res["ops"] = res["ops"][: int(res["op_offsets"][-1])]
+    return res
+
+
 def find_mems_sharded(index, devices, reads_cat, offsets, min_len, min_occ, tags=False):
     """pgx_find_mems_sharded: contiguous read slices, slice i on devices[i]; returns the per-slice result dicts in slice order"""
     reads_cat = np.ascontiguousarray(reads_cat, dtype=np.uint8)
@@ -1303,6 +1355,38 @@ class Batch:
         out["reads"] = DeviceArray(r.reads, (n, 8), self)
         out["cand_offsets"] = DeviceArray(r.cand_offsets, (n + 1,), self) if r.cand_offsets else None
         out["cands"] = DeviceArray(r.cands, (k, 8), self) if r.cands else None
+        return out
+
+    def read_align(self, band=8, flags=0, stream=None):
+        """pgx_batch_read_align at the winners of the last read_verify, then aligned()"""
+        _check(self.L.pgx_batch_read_align(self.b, band, flags, stream))
+        return self.aligned()
+
+    def _aligned(self, fn):
+        r = ReadAligns()
+        _check(fn(self.b, C.byref(r)))
+        return r, dict(n_reads=int(r.n_reads), n_ops=int(r.n_ops), flags=int(r.flags), band=int(r.band), passes=int(r.passes), scratch_bytes=int(r.scratch_bytes),
+                       ms_align=float(r.ms_align), ms_forward=float(r.ms_forward), ms_trace=float(r.ms_trace))
+
+    def aligned(self):
+        """the last align result as numpy arrays: reads ALIGN_DTYPE[n_reads]; with ALIGN_CIGAR op_offsets uint64[n_reads + 1] and ops uint32[n_ops]
+        (None without), with n_reads, n_ops, flags, band, passes, scratch_bytes, ms_align, ms_forward, ms_trace"""
+        r, out = self._aligned(self.L.pgx_batch_aligned)
+        n, k = out["n_reads"], out["n_ops"]
+        out["reads"] = np.frombuffer((C.c_char * (n * 64)).from_address(r.reads), dtype=ALIGN_DTYPE).copy() if n else np.zeros(0, ALIGN_DTYPE)
+        out["op_offsets"] = _u64_array(C.cast(r.op_offsets, C.POINTER(u64)), n + 1) if r.op_offsets else None
+        out["ops"] = (np.frombuffer((C.c_char * (k * 4)).from_address(r.ops), dtype=np.uint32).copy() if k else np.zeros(0, np.uint32)) if r.op_offsets else None
+        return out
+
+    def device_aligned(self):
+        """the same as device arrays (valid until the next run / upload / read_align / free): reads int64[n_reads, 8] (the 64-byte records as
+        words), op_offsets int64[n_reads + 1], ops uint32[n_ops]"""
+        r, out = self._aligned(self.L.pgx_batch_device_aligned)
+        n, k = out["n_reads"], out["n_ops"]
+        out["device"] = True
+        out["reads"] = DeviceArray(r.reads, (n, 8), self)
+        out["op_offsets"] = DeviceArray(r.op_offsets, (n + 1,), self) if r.op_offsets else None
+        out["ops"] = DeviceArray(r.ops, (k,), self, "<u4") if r.ops else None
         return out
 
     def free(self):

@@ -21,6 +21,9 @@
 //                 --verify FILE (one line per read: the read laid on the indexed text at its best placements, pgx_batch_read_verify; runs the place
 //                 stage itself without --place; stdout and stderr stay as they are), --verify-max C (candidates per read, 1 .. 64, default 1),
 //                 --verify-mismatch P (the segment's mismatch penalty, default 4), --verify-only (no MEM text, like --place-only)
+//                 --align FILE (one line per read: the banded alignment with gaps at the verify winner and its CIGAR, pgx_batch_read_align; runs the
+//                 place and verify stages itself when they are not requested, with --place-max, --verify-max and --verify-mismatch as there; stdout
+//                 and stderr stay as they are), --align-band W (0 .. 31, default 8), --align-only (no MEM text, like --verify-only)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -152,6 +155,7 @@ struct Done {
     std::string hits; // --hits: the lines of this batch
     std::string places; // --place: the lines of this batch
     std::string verifies; // --verify: the lines of this batch
+    std::string aligns; // --align: the lines of this batch
     std::string error;
 };
 
@@ -308,6 +312,31 @@ static void format_verifies(const pgx_read_verify *recs, size_t n, uint64_t firs
     out.resize((size_t)(p - &out[0]));
 }
 
+// --align: the lines of reads [0, n) of a batch, appended to out; seq, start, end and cigar print as * when the read has no candidate
+static const char ALIGN_HEADER[] = "#read\tseq\tstart\tend\tclip_lo\tclip_hi\tedits\tmatches\tmismatches\tins\tdel\tband_hit\tcigar\n";
+static void format_aligns(const pgx_read_align *recs, const uint64_t *op_off, const uint32_t *ops, size_t n, uint64_t first_seq, std::string &out) {
+    out.resize(n * (12 * 21 + 2) + (size_t)(op_off[n] - op_off[0]) * 11);
+    char *p = &out[0];
+    for (size_t i = 0; i < n; i++) {
+        const pgx_read_align &x = recs[i];
+        const bool none = x.seq == PGX_NO_SEQUENCE;
+        p = put_u64(p, first_seq + i + 1); *p++ = '\t';
+        if (none) { *p++ = '*'; *p++ = '\t'; *p++ = '*'; *p++ = '\t'; *p++ = '*'; }
+        else { p = put_u64(p, x.seq); *p++ = '\t'; p = put_u64(p, x.text_start); *p++ = '\t'; p = put_u64(p, x.text_end); }
+        const uint32_t f[8] = {x.clip_lo, x.clip_hi, x.edits, x.n_match, x.n_mismatch, x.n_ins, x.n_del, x.band_hit};
+        for (uint32_t v : f) { *p++ = '\t'; p = put_u64(p, v); }
+        *p++ = '\t';
+        if (none || op_off[i + 1] == op_off[i]) *p++ = '*';
+        for (uint64_t o = op_off[i]; o < op_off[i + 1]; o++) {
+            const uint32_t op = ops[o] & 15u;
+            p = put_u64(p, ops[o] >> 4);
+            *p++ = op == PGX_ALIGN_OP_I ? 'I' : (op == PGX_ALIGN_OP_D ? 'D' : (op == PGX_ALIGN_OP_S ? 'S' : (op == PGX_ALIGN_OP_EQ ? '=' : 'X')));
+        }
+        *p++ = '\n';
+    }
+    out.resize((size_t)(p - &out[0]));
+}
+
 static int usage() {
     std::cerr << "usage: find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ>"
                  " [--device N | --gpus N | --devices a,b,..] [--streams W] [--mode compat|strict] [--batch N]"
@@ -315,7 +344,8 @@ static int usage() {
                  " [--locate positions|seqs] [--locate-max K] [--result full|compact] [--format host|device]"
                  " [--hits FILE [--hits-max K] [--hits-only (not with --locate)]]"
                  " [--place FILE [--place-max K] [--place-only (not with --locate)]]"
-                 " [--verify FILE [--verify-max C] [--verify-mismatch P] [--verify-only (not with --locate)]]" << std::endl;
+                 " [--verify FILE [--verify-max C] [--verify-mismatch P] [--verify-only (not with --locate)]]"
+                 " [--align FILE [--align-band W (0 .. 31)] [--align-only (not with --locate)]]" << std::endl;
     return EXIT_FAILURE;
 }
 
@@ -343,6 +373,9 @@ int main(int argc, char **argv) {
     std::string verify_file;    // --verify: the verified placements of every batch go to this file
     uint32_t verify_max = 1, verify_penalty = 4;
     bool verify_opt_given = false, verify_only = false;
+    std::string align_file;     // --align: the gapped alignments of every batch go to this file
+    uint32_t align_band = 8;
+    bool align_band_given = false, align_only = false;
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -430,17 +463,31 @@ int main(int argc, char **argv) {
             verify_opt_given = true;
         }
         else if (a == "--verify-only") verify_only = true;
+        else if (a == "--align") { align_file = next(); if (align_file.empty()) { std::cerr << "--align: a file name" << std::endl; return EXIT_FAILURE; } }
+        else if (a == "--align-band") {
+            const std::string v = next();
+            char *endp = nullptr;
+            errno = 0;
+            const unsigned long long k = v.empty() || v[0] == '-' ? ~0ull : std::strtoull(v.c_str(), &endp, 10);
+            if (!endp || *endp || errno || k > PGX_ALIGN_MAX_BAND) return usage();
+            align_band = (uint32_t)k;
+            align_band_given = true;
+        }
+        else if (a == "--align-only") align_only = true;
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
     if ((hits_max_given || hits_only) && hits_file.empty()) return usage();
     if (hits_only && locate_mode) { std::cerr << "--hits-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if ((place_max_given || place_only) && place_file.empty()) return usage();
     if (place_only && locate_mode) { std::cerr << "--place-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
-    if ((verify_opt_given || verify_only) && verify_file.empty()) return usage();
+    if ((verify_only && verify_file.empty()) || (verify_opt_given && verify_file.empty() && align_file.empty())) return usage();
     if (verify_only && locate_mode) { std::cerr << "--verify-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
-    const bool want_hits = !hits_file.empty(), want_places = !place_file.empty(), want_verify = !verify_file.empty();
-    const uint32_t place_flags = want_verify && verify_max > 1 ? PGX_PLACE_LIST : 0u; // (the candidates beyond the first come from the list)
-    const bool no_text = hits_only || place_only || verify_only; // (either one: no tag stage, no download of result arrays, stdout empty)
+    if ((align_band_given || align_only) && align_file.empty()) return usage();
+    if (align_only && locate_mode) { std::cerr << "--align-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
+    const bool want_hits = !hits_file.empty(), want_places = !place_file.empty(), want_verify = !verify_file.empty(), want_align = !align_file.empty();
+    const bool run_verify = want_verify || want_align; // (--align runs the verify stage itself)
+    const uint32_t place_flags = run_verify && verify_max > 1 ? PGX_PLACE_LIST : 0u; // (the candidates beyond the first come from the list)
+    const bool no_text = hits_only || place_only || verify_only || align_only; // (either one: no tag stage, no download of result arrays, stdout empty)
     if (batch_reads == 0) batch_reads = 1;
     if (locate_max && !locate_mode) { std::cerr << "--locate-max needs --locate" << std::endl; return EXIT_FAILURE; }
 
@@ -519,8 +566,8 @@ int main(int argc, char **argv) {
         std::fwrite(PLACE_HEADER, 1, sizeof PLACE_HEADER - 1, place_fp);
     }
     // --verify: the same question for the text image (what --place asks, and a collection of 2^32 - 2^20 symbols or more)
-    std::FILE *verify_fp = nullptr;
-    if (want_verify) {
+    std::FILE *verify_fp = nullptr, *align_fp = nullptr;
+    if (run_verify) {
         static const uint8_t probe_read[4] = {'A', 'C', 'G', 'T'};
         static const uint64_t probe_offs[2] = {0, 4};
         pgx_status st = PGX_OK;
@@ -532,18 +579,26 @@ int main(int argc, char **argv) {
             if (st == PGX_OK) st = pgx_batch_locate(pb, 0, place_max, nullptr);
             if (st == PGX_OK) st = pgx_batch_read_place(pb, place_flags, nullptr);
             if (st == PGX_OK) st = pgx_batch_read_verify(pb, verify_max, verify_penalty, 0, nullptr);
+            if (st == PGX_OK && want_align) st = pgx_batch_read_align(pb, align_band, PGX_ALIGN_CIGAR, nullptr);
             if (st != PGX_OK) msg = pgx_last_error();
             pgx_batch_free(pb);
         }
         if (st != PGX_OK) {
-            std::cerr << msg << (st == PGX_ERR_UNSUPPORTED ? " (find_mems --verify)" : "") << std::endl;
+            std::cerr << msg << (st != PGX_ERR_UNSUPPORTED ? "" : (want_verify ? " (find_mems --verify)" : " (find_mems --align)")) << std::endl;
             if (hits_fp) std::fclose(hits_fp);
             if (place_fp) std::fclose(place_fp);
             return EXIT_FAILURE;
         }
-        verify_fp = std::fopen(verify_file.c_str(), "wb");
-        if (!verify_fp) { std::cerr << "Cannot open verify file: " << verify_file << std::endl; return EXIT_FAILURE; }
-        std::fwrite(VERIFY_HEADER, 1, sizeof VERIFY_HEADER - 1, verify_fp);
+        if (want_verify) {
+            verify_fp = std::fopen(verify_file.c_str(), "wb");
+            if (!verify_fp) { std::cerr << "Cannot open verify file: " << verify_file << std::endl; return EXIT_FAILURE; }
+            std::fwrite(VERIFY_HEADER, 1, sizeof VERIFY_HEADER - 1, verify_fp);
+        }
+        if (want_align) {
+            align_fp = std::fopen(align_file.c_str(), "wb");
+            if (!align_fp) { std::cerr << "Cannot open align file: " << align_file << std::endl; return EXIT_FAILURE; }
+            std::fwrite(ALIGN_HEADER, 1, sizeof ALIGN_HEADER - 1, align_fp);
+        }
     }
 
     // ---- the reads file, mapped: the reference reads it with std::getline (find_mems.cpp:96); here a planner cuts it into byte ranges that
@@ -803,7 +858,7 @@ int main(int argc, char **argv) {
                 if (st == PGX_OK) hit_recs.assign(rh.hits, rh.hits + rh.n_reads);
             }
             std::vector<pgx_read_place> place_recs; // --place: the 64-byte records; the stage's buffers are its own, the locate below does not touch them
-            if (st == PGX_OK && (want_places || want_verify)) {
+            if (st == PGX_OK && (want_places || run_verify)) {
                 st = pgx_batch_locate(b, 0, place_max, nullptr);
                 if (st == PGX_OK) st = pgx_batch_read_place(b, place_flags, nullptr);
                 pgx_read_places rp2;
@@ -811,11 +866,24 @@ int main(int argc, char **argv) {
                 if (st == PGX_OK && want_places) place_recs.assign(rp2.reads, rp2.reads + rp2.n_reads);
             }
             std::vector<pgx_read_verify> verify_recs; // --verify: the 64-byte records, at the candidates of the place stage above
-            if (st == PGX_OK && want_verify) {
+            if (st == PGX_OK && run_verify) {
                 st = pgx_batch_read_verify(b, verify_max, verify_penalty, 0, nullptr);
                 pgx_read_verifies rv;
-                if (st == PGX_OK) st = pgx_batch_verified(b, &rv);
-                if (st == PGX_OK) verify_recs.assign(rv.reads, rv.reads + rv.n_reads);
+                if (st == PGX_OK && want_verify) st = pgx_batch_verified(b, &rv);
+                if (st == PGX_OK && want_verify) verify_recs.assign(rv.reads, rv.reads + rv.n_reads);
+            }
+            std::vector<pgx_read_align> align_recs; // --align: the 64-byte records and the operations, at the winners of the verify stage above
+            std::vector<uint64_t> align_op_off;
+            std::vector<uint32_t> align_ops;
+            if (st == PGX_OK && want_align) {
+                st = pgx_batch_read_align(b, align_band, PGX_ALIGN_CIGAR, nullptr);
+                pgx_read_aligns ra;
+                if (st == PGX_OK) st = pgx_batch_aligned(b, &ra);
+                if (st == PGX_OK) {
+                    align_recs.assign(ra.reads, ra.reads + ra.n_reads);
+                    align_op_off.assign(ra.op_offsets, ra.op_offsets + ra.n_reads + 1);
+                    align_ops.assign(ra.ops, ra.ops + ra.n_ops);
+                }
             }
             if (format_device || no_text) {
                 // nothing to download: the device writes the text below, once the batch knows the number of its first read
@@ -862,6 +930,7 @@ int main(int argc, char **argv) {
                 if (want_hits) format_hits(hit_recs.data(), hit_recs.size(), j->first_seq, d->hits);
                 if (want_places) format_places(place_recs.data(), place_recs.size(), j->first_seq, d->places);
                 if (want_verify) format_verifies(verify_recs.data(), verify_recs.size(), j->first_seq, d->verifies);
+                if (want_align && !align_op_off.empty()) format_aligns(align_recs.data(), align_op_off.data(), align_ops.data(), align_recs.size(), j->first_seq, d->aligns);
                 if (format_device && !no_text) {
                     // the text of the batch from the device, handed to the writer where it is
                     const uint64_t t3w = now_ns();
@@ -961,6 +1030,7 @@ int main(int argc, char **argv) {
         if (hits_fp && !d->hits.empty()) std::fwrite(d->hits.data(), 1, d->hits.size(), hits_fp);
         if (place_fp && !d->places.empty()) std::fwrite(d->places.data(), 1, d->places.size(), place_fp);
         if (verify_fp && !d->verifies.empty()) std::fwrite(d->verifies.data(), 1, d->verifies.size(), verify_fp);
+        if (align_fp && !d->aligns.empty()) std::fwrite(d->aligns.data(), 1, d->aligns.size(), align_fp);
         ns_write += now_ns() - tw0;
         total_mem_time += d->mem_s;
         total_tag_time += d->tag_s;
@@ -985,6 +1055,7 @@ int main(int argc, char **argv) {
     if (hits_fp && (std::fclose(hits_fp) != 0) && error.empty()) error = "Cannot write hits file: " + hits_file;
     if (place_fp && (std::fclose(place_fp) != 0) && error.empty()) error = "Cannot write place file: " + place_file;
     if (verify_fp && (std::fclose(verify_fp) != 0) && error.empty()) error = "Cannot write verify file: " + verify_file;
+    if (align_fp && (std::fclose(align_fp) != 0) && error.empty()) error = "Cannot write align file: " + align_file;
     if (!error.empty()) {
         std::cerr << error << std::endl;
         return EXIT_FAILURE;
