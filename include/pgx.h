@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only), the device index build (pgx_build_index_from_text_device, pgx_build_index_from_texts_device, pgx_build_index_device_timing: new entry points only), the text output (pgx_batch_format, pgx_format_result, pgx_format_params, pgx_text, PGX_FORMAT_*: new entry points only), the image file (pgx_index_save_image, pgx_index_open_image, pgx_image_file_info, pgx_image_sum, pgx_image_section_name, PGX_IMAGE_*: new entry points only), the read-back of a batch's reads (pgx_batch_reads, pgx_reads_info: a new entry point only), the read hits (pgx_batch_read_hits, pgx_batch_hits, pgx_batch_device_hits, pgx_read_hits_arrays, pgx_read_hit, pgx_read_hits, PGX_HITS_*, PGX_NO_SEQUENCE: new entry points only) */
+#define PGX_ABI_VERSION 7 /* 2: pgx_timing grew (pairs_reads, redo_reads), pgx_index_info.image_pairs, PGX_MODE_IMAGE_PAIRS; 3: pgx_timing grew (ms_find_mems_main, traffic counters); 4: pgx_timing.ms_per_upload, pgx_pack_reads, pgx_batch_upload_packed; 5: pgx_batch_upload_text, pgx_fastx_cut, PGX_READS_*; 6: pgx_batch_locate, pgx_batch_locations, pgx_batch_device_locations, pgx_locations, PGX_LOCATE_CHAINS; 7: pgx_timing.kernels, PGX_KERNELS_*, pgx_kernel_variants; still 7, additions a caller of 7 does not see: PGX_LOCATE_SEQ_SETS (a flag 7 refused), pgx_locations.set_words (the field `reserved`, always 0 before, at the same offset), the compact result (pgx_compact_result, pgx_batch_result_compact, pgx_compact_expand, pgx_compact_bound, pgx_compact_encode: new entry points only), the device index build (pgx_build_index_from_text_device, pgx_build_index_from_texts_device, pgx_build_index_device_timing: new entry points only), the text output (pgx_batch_format, pgx_format_result, pgx_format_params, pgx_text, PGX_FORMAT_*: new entry points only), the image file (pgx_index_save_image, pgx_index_open_image, pgx_image_file_info, pgx_image_sum, pgx_image_section_name, PGX_IMAGE_*: new entry points only), the read-back of a batch's reads (pgx_batch_reads, pgx_reads_info: a new entry point only), the read hits (pgx_batch_read_hits, pgx_batch_hits, pgx_batch_device_hits, pgx_read_hits_arrays, pgx_read_hit, pgx_read_hits, PGX_HITS_*, PGX_NO_SEQUENCE: new entry points only), the read walk (pgx_batch_read_walk, pgx_batch_walked, pgx_batch_device_walked, pgx_index_paths, pgx_read_walk_arrays, pgx_read_walk, pgx_read_walks, PGX_WALK_STEPS: new entry points only) */
 
 typedef enum {
     PGX_OK = 0,
@@ -965,6 +965,72 @@ pgx_status pgx_batch_device_aligned(pgx_batch *b, pgx_read_aligns *out);
 pgx_status pgx_read_align_arrays(int device, const uint8_t *text, const uint64_t *seq_offsets, uint64_t n_seq, const uint8_t *reads,
                                  const uint64_t *read_offsets, uint64_t n_reads, const uint32_t *cand_seq, const int64_t *cand_diag, uint32_t band,
                                  uint32_t flags, pgx_read_align *out, uint64_t *op_offsets, uint32_t *ops, uint64_t ops_cap);
+
+/* ---- read walk: every aligned read as a walk through the graph, on the device ------------------------------------------------------
+ * The align stage ends on one indexed sequence, that is on one haplotype: "sequence 37, [81 244, 81 394)".  The tag array exists to turn the
+ * index's rows into graph positions, and a path covers whole nodes, so the graph walk of a text stretch is a slice of its sequence's node
+ * list.  That list is recovered from the index and its tags alone (the WALK image, csrc/pgx_image.h; no graph file is read): a text position
+ * is MARKED iff its tag -- the tag of the run that truly holds its row, not the item the reference's query reads when f % 10 == 0 -- has
+ * offset 0, i.e. a node visit starts there.  Reads that verify left tied between haplotypes that agree over the read have one and the same walk.
+ *
+ * DEFINITIONS.  Within sequence seq of Ls symbols the marks are m_0 = 0 < m_1 < ...; visit k covers [m_k, m_k+1), the last one [m_k, Ls), and
+ * its node is node << 1 | rev of the tag at m_k.  A node has at most 1024 symbols (the tag's offset has ten bits).  For a read whose align
+ * record has (seq, text_start, text_end) with text_end > text_start:
+ *   steps        the visits that meet [text_start, text_end): k0 = the last mark <= text_start to k1 = the last mark < text_end, both inclusive
+ *   n_steps      k1 - k0 + 1
+ *   path_start   text_start - m_k0: where the stretch starts on the concatenated nodes of its steps
+ *   path_end     path_start + (text_end - text_start)
+ *   path_len     (end of visit k1) - m_k0: the summed lengths of the steps' nodes, as GAF wants it
+ * A read without a candidate (seq == PGX_NO_SEQUENCE) or with an empty stretch has n_steps = 0 and every other field 0; seq is kept.
+ * pgx_read_walk (32 bytes, little endian):  0 path_len u64   8 path_start u64   16 path_end u64   24 n_steps u32   28 seq u32
+ * PGX_WALK_STEPS adds step_offsets[n_reads + 1] and the steps (u64, node << 1 | rev) as a CSR list; n_steps is present either way.
+ * The image is defined for any tag array whose sequences start on a mark, whether or not it describes paths (tags with offset 0 everywhere
+ * make every position a visit of length 1); where two marks of one sequence lie more than 1024 positions apart the two bit scans stop at
+ * 1024 and path_start / path_len are cut there.
+ * The WALK image is built on the first call (pgx_index_paths or pgx_batch_read_walk) and lives with the index's device image: n / 8 bytes of
+ * marks, n / 64 of rank directory, 8 bytes per visit.  PGX_ERR_UNSUPPORTED naming the reason: an index without tags or without an r-index
+ * (PGX_ERR_ARG), a COMPAT index without N, an image file saved without the locate image or before the span of its tag runs was kept, a BWT
+ * of 2^32 - 2^20 symbols or more.  PGX_ERR_FORMAT "the tags do not belong to this index", naming the sequence: the first position of some
+ * non-empty sequence is not marked (or the runs cover fewer rows than the index has).  PGX_ERR_NOMEM with the bytes needed and free. */
+#define PGX_WALK_STEPS 1u
+typedef struct {
+    uint64_t path_len, path_start, path_end;
+    uint32_t n_steps, seq;
+} pgx_read_walk;
+typedef struct {
+    uint64_t n_reads;
+    uint64_t n_steps;               /* steps over all reads (with and without PGX_WALK_STEPS) */
+    uint32_t flags;                 /* PGX_WALK_* the call ran with */
+    uint32_t reserved;
+    const pgx_read_walk *reads;     /* n_reads */
+    const uint64_t *step_offsets;   /* n_reads + 1; NULL without PGX_WALK_STEPS */
+    const uint64_t *steps;          /* n_steps; NULL without PGX_WALK_STEPS */
+    float ms_walk;                  /* device time of the call when the run had PGX_RUN_TIMING, else 0 */
+    uint32_t reserved2;
+} pgx_read_walks;
+/* Walks the reads of the last run along the stretches of the last pgx_batch_read_align, which must be this run's.  PGX_ERR_ARG with nothing
+ * changed: no align result, an unknown flag.  Runs on `stream` (NULL = the batch's own), complete on return; one read-back, the number of
+ * steps.  The result stays valid until the next run, upload, pgx_batch_read_walk or free of the batch; a later pgx_batch_locate of any
+ * form leaves it valid.  The stage's buffers grow only and are its own. */
+pgx_status pgx_batch_read_walk(pgx_batch *b, uint32_t flags, void *stream);
+/* Host copy of the last walk result (pinned buffers owned by the batch) / the same as device pointers.  PGX_ERR_ARG when there is none. */
+pgx_status pgx_batch_walked(pgx_batch *b, pgx_read_walks *out);
+pgx_status pgx_batch_device_walked(pgx_batch *b, pgx_read_walks *out);
+/* The recovered node list itself: path_offsets takes n_seq + 1 entries (n_seq_cap >= the index's sequence count, else PGX_ERR_ARG naming it),
+ * sequence q's visits are [path_offsets[q], path_offsets[q + 1]).  path_nodes / visit_length (either may be NULL) take the visits' node << 1 | rev
+ * and lengths when cap >= the number of visits; with both NULL the call only gives the counts, with cap too small it is PGX_ERR_NOMEM with the
+ * number needed, path_offsets filled.  For tags made from a graph this is the graph's path table. */
+pgx_status pgx_index_paths(pgx_index *h, int device, uint64_t *path_offsets, uint64_t n_seq_cap, uint64_t *path_nodes, uint32_t *visit_length, uint64_t cap);
+/* The stage's count and fill kernels on stated path tables: sequence q is seq_offsets[q] .. seq_offsets[q + 1] (no endmarkers) and consists of
+ * the visits [visit_offsets[q], visit_offsets[q + 1]) with nodes visit_nodes and lengths visit_length; read r walks [text_start[r], text_end[r])
+ * of sequence seq[r] (PGX_NO_SEQUENCE: none).  `out` takes n_reads records; with PGX_WALK_STEPS step_offsets takes n_reads + 1 entries and steps
+ * up to steps_cap (PGX_ERR_NOMEM with the needed count when there are more; both may be NULL without the flag).  PGX_ERR_ARG with nothing
+ * written, naming the first offender: an unknown flag, offsets that do not start at 0 or decrease, a visit length of 0 or above 1024, lengths
+ * that do not sum to their sequence's length, a stretch that ends behind its sequence or before its start, a seq that is neither below n_seq
+ * nor PGX_NO_SEQUENCE.  PGX_ERR_NO_DEVICE without a GPU. */
+pgx_status pgx_read_walk_arrays(int device, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
+                                const uint32_t *visit_length, uint64_t n_reads, const uint32_t *seq, const uint64_t *text_start, const uint64_t *text_end,
+                                uint32_t flags, pgx_read_walk *out, uint64_t *step_offsets, uint64_t *steps, uint64_t steps_cap);
 
 /* ---- compact result: the result of a run as a byte stream, encoded on the device, expanded on the host ---------------------
  * What pgx_batch_result downloads is six dense uint64 arrays (8 bytes per read, 48 per MEM, 8 per graph position), nearly all of

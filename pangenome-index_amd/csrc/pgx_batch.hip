@@ -1,5 +1,5 @@
 // pgx_batch.hip -- the pgx_batch object: uploads, pgx_batch_run, results, pgx_batch_locate, pgx_batch_read_hits, pgx_batch_read_place,
-// pgx_batch_read_verify, pgx_batch_read_align.
+// pgx_batch_read_verify, pgx_batch_read_align, pgx_batch_read_walk.
 //
 // Pipeline of pgx_batch_run (one HIP stream, results stay on the device):
 //   scan(cap)      -> slot offsets (worst-case MEMs per read: min(len, len - min_len + 1)); the slot buffer
@@ -89,6 +89,7 @@ struct pgx_batch {
     PlaceWork pw;   // pgx_batch_read_place
     VerifyWork vw;  // pgx_batch_read_verify
     AlignWork aw;   // pgx_batch_read_align
+    WalkWork ww;    // pgx_batch_read_walk
     uint64_t n_mems = 0, n_positions = 0, n_ext = 0, n_tag_overflow = 0;
     bool ran = false, ran_tags = false;
     // speculative sizing (pgx_batch_run): what the last run with these parameters produced
@@ -120,6 +121,7 @@ static void batch_release(pgx_batch *b) {
         b->pw.release();
         b->vw.release();
         b->aw.release();
+        b->ww.release();
         HostBuf *hb[] = {&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]};
         for (HostBuf *x : hb) x->release();
         for (auto &e : b->ev)
@@ -147,6 +149,7 @@ static void batch_reset_for_upload(pgx_batch *b, uint64_t n_reads, uint64_t max_
     b->pw.valid = false;
     b->vw.valid = false;
     b->aw.valid = false;
+    b->ww.valid = false;
     b->plan_valid = false;
     b->slot_off_valid = false;
     b->class_valid = false;
@@ -1076,6 +1079,7 @@ extern "C" pgx_status pgx_batch_run(pgx_batch *b, uint64_t min_len, uint64_t min
     b->pw.valid = false; // (and the places)
     b->vw.valid = false; // (and what was verified at them)
     b->aw.valid = false; // (and aligned there)
+    b->ww.valid = false; // (and walked through the graph)
     b->n_mems = b->n_positions = b->n_ext = b->n_tag_overflow = 0;
     std::memset(&b->timing, 0, sizeof b->timing);
     bool force_worst = false;
@@ -2796,6 +2800,203 @@ extern "C" pgx_status pgx_read_align_arrays(int device, const uint8_t *text, con
     if (want_ops) {
         HIPCHECK(hipMemcpyAsync(op_offsets, k.w.op_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
         if (k.w.n_ops) HIPCHECK(hipMemcpyAsync(ops, k.w.ops.p, k.w.n_ops * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(hipStreamSynchronize(s));
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// read walk (pgx_walk_kernels.hip; the definitions: include/pgx.h "read walk")
+static const uint32_t WALK_FLAGS = PGX_WALK_STEPS;
+
+// The stage on device arrays, enqueued on s (synchronised where the number of steps is read back): the align records, or seq / text_start / text_end
+// (n of each), -> w.recs, w.step_off and, with PGX_WALK_STEPS, w.steps.  Nothing here refuses.
+static void walk_core(WalkWork &w, const PgxWalkImage &img, const uint64_t *seq_start, uint32_t endmark, uint64_t n_seq, const pgx_read_align *recs, const uint32_t *seq,
+                      const uint64_t *text_start, const uint64_t *text_end, uint64_t n, uint32_t flags, hipStream_t s) {
+    w.recs.ensure((n ? n : 1) * sizeof(pgx_read_walk));
+    w.count.ensure((n ? n : 1) * 8); w.first.ensure((n ? n : 1) * 8); w.step_off.ensure((n + 1) * 8);
+    uint64_t n_steps = 0;
+    if (n) {
+        hipLaunchKernelGGL(pgx_walk_count_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, img, seq_start, endmark, n_seq, recs, seq, text_start, text_end, n,
+                           w.recs.as<pgx_read_walk>(), w.count.as<uint64_t>(), w.first.as<uint64_t>());
+        HIPCHECK(hipGetLastError());
+        scan_excl(1, w.count.p, n, 0, w.step_off.as<uint64_t>(), w.scan_tmp, s);
+        n_steps = read_u64(w.step_off.as<uint64_t>() + n, s); // (the stage's one read-back)
+    } else HIPCHECK(hipMemsetAsync(w.step_off.p, 0, 8, s));
+    if ((flags & PGX_WALK_STEPS) && n_steps) {
+        w.steps.ensure(n_steps * 8);
+        hipLaunchKernelGGL(pgx_walk_fill_kernel, dim3(grid_for(n, 256 / PGX_WALK_FILL_LANES)), dim3(256), 0, s, img, (const uint64_t *)w.count.as<uint64_t>(),
+                           (const uint64_t *)w.first.as<uint64_t>(), (const uint64_t *)w.step_off.as<uint64_t>(), n, w.steps.as<uint64_t>());
+        HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipStreamSynchronize(s));
+    w.n_reads = n; w.n_steps = n_steps; w.flags = flags;
+}
+
+extern "C" pgx_status pgx_batch_read_walk(pgx_batch *b, uint32_t flags, void *stream) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_read_walk");
+    checked_device_count();
+    const std::string who = "pgx_batch_read_walk";
+    if (!b) throw Error(PGX_ERR_ARG, who + ": null batch");
+    // (what is refused here leaves an earlier walk result as it was)
+    if (flags & ~WALK_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
+    if (!b->ran) throw Error(PGX_ERR_ARG, who + ": batch has not been run");
+    AlignWork &aw = b->aw;
+    if (!aw.valid || aw.n_reads != b->n_reads) throw Error(PGX_ERR_ARG, who + ": needs a completed pgx_batch_read_align, the batch has no align result");
+    const uint64_t n = b->n_reads;
+    if (n >= PLACE_LAUNCH_ITEMS / PGX_WALK_FILL_LANES) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n) + " reads exceed one launch");
+    use_device(b->device);
+    pgx_device_image *d = device_image(b->h, b->device);
+    ensure_walk(b->h, d); // (throws before anything of the batch changes)
+    hipStream_t s = stream ? (hipStream_t)stream : b->own;
+    WalkWork &w = b->ww;
+    w.valid = false;
+    const bool timed = b->timed;
+    if (timed) {
+        for (auto &e : w.ev)
+            if (!e) HIPCHECK(hipEventCreate(&e));
+        HIPCHECK(hipEventRecord(w.ev[0], s));
+    }
+    walk_core(w, d->walk, d->text_seq_start.as<uint64_t>(), 1u, d->text_n_seq, (const pgx_read_align *)aw.recs.as<pgx_read_align>(), nullptr, nullptr, nullptr, n, flags, s);
+    w.ms = 0;
+    if (timed) {
+        HIPCHECK(hipEventRecord(w.ev[1], s));
+        HIPCHECK(hipStreamSynchronize(s));
+        HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
+    }
+    w.valid = true;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+static void walked_header(const pgx_batch *b, pgx_read_walks *out) {
+    const WalkWork &w = b->ww;
+    std::memset(out, 0, sizeof *out);
+    out->n_reads = w.n_reads;
+    out->n_steps = w.n_steps;
+    out->flags = w.flags;
+    out->ms_walk = w.ms;
+}
+
+extern "C" pgx_status pgx_batch_device_walked(pgx_batch *b, pgx_read_walks *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->ww.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_walked: batch has no walk result");
+    const WalkWork &w = b->ww;
+    walked_header(b, out);
+    out->reads = w.recs.as<pgx_read_walk>();
+    if (w.flags & PGX_WALK_STEPS) {
+        out->step_offsets = w.step_off.as<uint64_t>();
+        out->steps = w.steps.as<uint64_t>();
+    }
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_batch_walked(pgx_batch *b, pgx_read_walks *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->ww.valid) throw Error(PGX_ERR_ARG, "pgx_batch_walked: batch has no walk result");
+    use_device(b->device);
+    WalkWork &w = b->ww;
+    const uint64_t n = w.n_reads;
+    const bool list = (w.flags & PGX_WALK_STEPS) != 0;
+    w.h_recs.ensure((n ? n : 1) * sizeof(pgx_read_walk));
+    if (n) HIPCHECK(hipMemcpyAsync(w.h_recs.p, w.recs.p, n * sizeof(pgx_read_walk), hipMemcpyDeviceToHost, b->own));
+    if (list) {
+        w.h_step_off.ensure((n + 1) * 8);
+        w.h_steps.ensure((w.n_steps ? w.n_steps : 1) * 8);
+        HIPCHECK(hipMemcpyAsync(w.h_step_off.p, w.step_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, b->own));
+        if (w.n_steps) HIPCHECK(hipMemcpyAsync(w.h_steps.p, w.steps.p, w.n_steps * 8, hipMemcpyDeviceToHost, b->own));
+    }
+    HIPCHECK(hipStreamSynchronize(b->own)); // (the stage completed inside pgx_batch_read_walk, on whatever stream it used)
+    walked_header(b, out);
+    out->reads = w.h_recs.as<pgx_read_walk>();
+    if (list) {
+        out->step_offsets = w.h_step_off.as<uint64_t>();
+        out->steps = w.h_steps.as<uint64_t>();
+    }
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_read_walk_arrays(int device, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
+                                           const uint32_t *visit_length, uint64_t n_reads, const uint32_t *seq, const uint64_t *text_start, const uint64_t *text_end,
+                                           uint32_t flags, pgx_read_walk *out, uint64_t *step_offsets, uint64_t *steps, uint64_t steps_cap) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_read_walk_arrays");
+    checked_device_count();
+    const std::string who = "pgx_read_walk_arrays";
+    if (flags & ~WALK_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
+    const bool want_steps = (flags & PGX_WALK_STEPS) != 0;
+    if (!seq_offsets || !visit_offsets || (n_reads && (!out || !seq || !text_start || !text_end)) || (want_steps && (!step_offsets || (steps_cap && !steps))))
+        throw Error(PGX_ERR_ARG, who + ": null argument");
+    auto check_offsets = [&](const uint64_t *o, uint64_t k, const char *name) {
+        if (o[0] != 0) throw Error(PGX_ERR_ARG, who + ": " + name + " must start at 0");
+        for (uint64_t i = 0; i < k; i++)
+            if (o[i] > o[i + 1]) throw Error(PGX_ERR_ARG, who + ": " + name + " decrease at sequence " + std::to_string(i));
+    };
+    check_offsets(seq_offsets, n_seq, "seq_offsets");
+    check_offsets(visit_offsets, n_seq, "visit_offsets");
+    const uint64_t n_text = seq_offsets[n_seq], V = visit_offsets[n_seq];
+    if (V && (!visit_nodes || !visit_length)) throw Error(PGX_ERR_ARG, who + ": null argument");
+    if (n_text >= (1ull << 32) - (1ull << 20)) throw Error(PGX_ERR_UNSUPPORTED, who + ": a text of " + std::to_string(n_text) + " symbols, the image holds fewer than 2^32 - 2^20");
+    std::vector<uint64_t> marks(V);
+    for (uint64_t q = 0; q < n_seq; q++) {
+        uint64_t p = seq_offsets[q];
+        for (uint64_t k = visit_offsets[q]; k < visit_offsets[q + 1]; k++) {
+            if (visit_length[k] == 0 || visit_length[k] > PGX_WALK_MAX_VISIT)
+                throw Error(PGX_ERR_ARG, who + ": visit " + std::to_string(k) + " of sequence " + std::to_string(q) + " has length " + std::to_string(visit_length[k]) + ", outside 1 .. 1024");
+            marks[k] = p;
+            p += visit_length[k];
+        }
+        if (p != seq_offsets[q + 1])
+            throw Error(PGX_ERR_ARG, who + ": the visits of sequence " + std::to_string(q) + " sum to " + std::to_string(p - seq_offsets[q]) + " symbols, the sequence has " +
+                                         std::to_string(seq_offsets[q + 1] - seq_offsets[q]));
+    }
+    for (uint64_t r = 0; r < n_reads; r++) {
+        if (seq[r] == PGX_NO_SEQUENCE) continue;
+        if (seq[r] >= n_seq) throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " names a sequence that is not below n_seq " + std::to_string(n_seq));
+        const uint64_t ls = seq_offsets[(uint64_t)seq[r] + 1] - seq_offsets[seq[r]];
+        if (text_start[r] > text_end[r] || text_end[r] > ls)
+            throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " has the stretch [" + std::to_string(text_start[r]) + ", " + std::to_string(text_end[r]) +
+                                         "), its sequence has " + std::to_string(ls) + " symbols");
+    }
+    if (n_reads >= PLACE_LAUNCH_ITEMS / PGX_WALK_FILL_LANES) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_reads) + " reads exceed one launch");
+    use_device(device);
+    struct Work { // device copies of the input, the image + the stage's buffers, released on every way out
+        DevBuf seq_off, marks, bits, dir, nodes, counts, seq, ts, te;
+        WalkWork w;
+        ~Work() {
+            DevBuf *all[] = {&seq_off, &marks, &bits, &dir, &nodes, &counts, &seq, &ts, &te};
+            for (DevBuf *d : all) d->release();
+            w.release();
+        }
+    } k;
+    hipStream_t s = nullptr;
+    const uint64_t n_blocks = n_text / PGX_WALK_BLOCK_BITS + 1, n_words = n_blocks * PGX_WALK_BLOCK_WORDS;
+    upload(k.seq_off, seq_offsets, (n_seq + 1) * 8);
+    upload(k.marks, marks.data(), V * 8);
+    upload(k.nodes, visit_nodes, V * 8);
+    upload(k.seq, seq, n_reads * 4);
+    upload(k.ts, text_start, n_reads * 8);
+    upload(k.te, text_end, n_reads * 8);
+    k.bits.ensure(n_words * 8); k.dir.ensure((n_blocks + 1) * 8);
+    HIPCHECK(hipMemsetAsync(k.bits.p, 0, n_words * 8, s));
+    if (V) {
+        hipLaunchKernelGGL(pgx_walk_set_kernel, dim3((unsigned)std::min<uint64_t>((V + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint64_t *)k.marks.as<uint64_t>(), V, k.bits.as<uint32_t>());
+        HIPCHECK(hipGetLastError());
+    }
+    walk_directory(k.bits.as<uint64_t>(), n_blocks, k.counts, k.dir.as<uint64_t>(), k.w.scan_tmp, s);
+    const PgxWalkImage img{k.bits.as<uint64_t>(), k.dir.as<uint64_t>(), k.nodes.as<uint64_t>(), n_text, n_words, n_blocks, V};
+    walk_core(k.w, img, k.seq_off.as<uint64_t>(), 0u, n_seq, nullptr, (const uint32_t *)k.seq.as<uint32_t>(), (const uint64_t *)k.ts.as<uint64_t>(),
+              (const uint64_t *)k.te.as<uint64_t>(), n_reads, flags, s);
+    if (want_steps && k.w.n_steps > steps_cap)
+        throw Error(PGX_ERR_NOMEM, who + ": the list holds " + std::to_string(k.w.n_steps) + " steps, steps_cap is " + std::to_string(steps_cap));
+    if (n_reads) HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, n_reads * sizeof(pgx_read_walk), hipMemcpyDeviceToHost, s));
+    if (want_steps) {
+        HIPCHECK(hipMemcpyAsync(step_offsets, k.w.step_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (k.w.n_steps) HIPCHECK(hipMemcpyAsync(steps, k.w.steps.p, k.w.n_steps * 8, hipMemcpyDeviceToHost, s));
     }
     HIPCHECK(hipStreamSynchronize(s));
     return PGX_OK;

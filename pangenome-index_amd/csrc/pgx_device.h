@@ -103,6 +103,22 @@ struct PgxDevImage {
 #define PGX_SEED_MAX_K 16
 #define PGX_SEED_SMALL_K 10 // depth of the second table (searches whose min_len is below the depth of the first)
 
+// run start r: from the interleaved (start, value) array when the image has one -- the locate kernel then finds the run's value in the
+// cache line its search ended in (three random lines per MEM -> two)
+#define PGX_TSTART(img, r) ((img).tpair ? (img).tpair[(r)].x : (img).tstart[(r)])
+// rank_1(bwt_intervals, x + 1) = number of run starts <= x  (src/tag_arrays.cpp:857-858)
+__device__ __forceinline__ uint64_t pgx_tag_rank(const PgxDevImage &img, uint64_t x) {
+    const uint64_t nr = img.n_tag_runs;
+    uint64_t di = x >> img.tag_dir_shift;
+    if (di + 1 >= img.tag_dir_entries) return nr; // beyond bwt_intervals.size(): all ones
+    uint64_t lo = img.tdir[di], hi = img.tdir[di + 1];
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (PGX_TSTART(img, mid) <= x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // heavy reads (pgx_fm_kernels.hip): handed from pgx_find_mems_kernel to pgx_find_mems_heavy_kernel
 struct pgx_heavy_item {
     uint64_t rid;
@@ -422,6 +438,26 @@ __global__ void pgx_align_forward_kernel(const uint32_t *text4, const uint64_t *
 __global__ void pgx_align_trace_kernel(const uint64_t *seq_start, uint32_t endmark, const uint64_t *read_off, const uint32_t *cand_seq, const int64_t *cand_diag,
                                        uint64_t r0, uint64_t r1, uint32_t W, uint32_t row_bytes, const uint64_t *plane_off, const uint8_t *planes, const uint2 *fwd,
                                        uint32_t write, pgx_read_align *out, uint64_t *count, const uint64_t *op_off, uint32_t *ops);
+
+// ---- pgx_walk_kernels.hip: the WALK image (pgx_image.h) and the read walk stage (pgx_batch_read_walk, pgx_read_walk_arrays, pgx_index_paths)
+struct PgxWalkImage {
+    const uint64_t *bits;  // n_words
+    const uint64_t *dir;   // n_blocks + 1
+    const uint64_t *nodes; // n_visits
+    uint64_t n, n_words, n_blocks, n_visits;
+};
+__global__ void pgx_walk_mark_kernel(PgxDevImage img, const uint32_t *sa32, const uint64_t *sa64, uint64_t max_length, const uint64_t *seq_start, uint64_t n_seq, uint64_t n,
+                                     int64_t delta, uint32_t *bits32, unsigned long long *bad);
+__global__ void pgx_walk_set_kernel(const uint64_t *marks, uint64_t n_marks, uint32_t *bits32);
+__global__ void pgx_walk_popc_kernel(const uint64_t *bits, uint64_t n_blocks, uint64_t *counts);
+__global__ void pgx_walk_nodes_kernel(PgxDevImage img, PgxWalkImage w, const uint32_t *sa32, const uint64_t *sa64, uint64_t max_length, const uint64_t *seq_start,
+                                      uint64_t n_seq, uint64_t n, int64_t delta, uint64_t *nodes);
+__global__ void pgx_walk_check_kernel(PgxWalkImage w, const uint64_t *seq_start, uint64_t n_seq, uint32_t endmark, unsigned long long *bad);
+__global__ void pgx_walk_positions_kernel(PgxWalkImage w, uint64_t *pos);
+// recs (the batch's align records) or seq / text_start / text_end (arrays); first[r] = k0, the read's first visit
+__global__ void pgx_walk_count_kernel(PgxWalkImage w, const uint64_t *seq_start, uint32_t endmark, uint64_t n_seq, const pgx_read_align *recs, const uint32_t *seq,
+                                      const uint64_t *text_start, const uint64_t *text_end, uint64_t n_reads, pgx_read_walk *out, uint64_t *n_steps, uint64_t *first);
+__global__ void pgx_walk_fill_kernel(PgxWalkImage w, const uint64_t *n_steps, const uint64_t *first, const uint64_t *step_off, uint64_t n_reads, uint64_t *steps);
 
 // literal count image: COMPAT count_encoded / LF_encoded on an encoded index without N, block by block as the
 // reference's rankAt_encoded (src/r-index.cpp:570-590) sees it -- true cumulative counts, run scan one varint late

@@ -135,6 +135,25 @@
  * pgx_locate_batch supports with n < 2^32 - 2^20: forward-only collections (no reverse-complement check), any n, with or without PAIRS.
  * For a while the build holds 12 n bytes of suffix array (8 n as the locate kernels write it, 4 n as the scatter kernel writes it again), n
  * text bytes and the image; the free device memory is checked before the first allocation.  Not stored in image files. */
+/* WALK image (device only, built on the device on its first use: pgx_images.hip ensure_walk; pgx_index_paths, pgx_batch_read_walk): the node list of every
+ * sequence, recovered from the suffix array and the tag runs -- a path covers whole nodes, so the graph walk of a text stretch is a slice of it.
+ *   walk_bits   one bit per text position in the TEXT image's coordinates (text_seq_start[q] + off), u64 words, bit p % 64 of word p / 64: set iff the
+ *               tag of the position has offset 0, i.e. a node visit starts there.  Endmarker positions are never set.  n / 512 + 1 directory blocks
+ *               of PGX_WALK_BLOCK_WORDS words, so that every position 0 .. n has a word.
+ *   walk_dir    the rank directory: one u64 per PGX_WALK_BLOCK_BITS = 512 positions, the set bits before the block; one more entry holds V, the number
+ *               of visits.  A rank is one entry, at most seven whole-word popcounts and a masked one.  8 bytes per 64 bytes of bits.
+ *   walk_nodes  V u64, tag >> 10 = node << 1 | rev of every visit in text order.
+ * Visit k covers [m_k, m_k+1) cut at its sequence's end, m_k the k-th set bit; a node has at most PGX_WALK_MAX_VISIT symbols (ten offset bits).
+ * WHICH RUN HOLDS ROW i.  The run starts of a tag file are the prefix sums of its run lengths from 0.  The runs cover the rows from n_seq on (build_tags,
+ * merge_tags of such files) or all rows (pgx_write_compact_tags of whole-BWT runs), and in a converted build_tags file they follow up to eight runs
+ * that convert_tags reads out of the file's 8-byte header (algorithm_header_runs), so the first real run starts neither at 0 nor at n_seq.  What holds in
+ * every case is that the last run ends with the last row: row i is position x = i + (span - 1 - n), span = bwt_intervals.size() (PgxConsts.tag_span_lo).
+ * The golden xy fixture: n = 8022, n_seq = 8, span = 8038, one header run of 23 rows: x = i + 15, which is neither i nor i - n_seq.
+ * Not stored in image files. */
+#define PGX_WALK_BLOCK_WORDS 8u
+#define PGX_WALK_BLOCK_BITS 512u
+#define PGX_WALK_MAX_VISIT 1024u
+#define PGX_WALK_FILL_LANES 8u /* lanes that copy the steps of one read (pgx_walk_fill_kernel) */
 /* WIDE variants of DENSE2 and PAIRS (BWTs of 2^32 symbols or more, up to PGX_SB_MAX superblocks; FastLocate is size_t end to end,
  * r-index.hpp:118-130): the same 128-byte blocks, but every count in a block header is a 32-bit DELTA against its superblock --
  * 2^sb_shift consecutive blocks, at most 2^31 symbols -- whose 64-bit bases sit in a small table the kernels stage in LDS:
@@ -178,7 +197,8 @@ typedef struct {
     uint32_t has_pairs;   /* a PAIRS image accompanies the DENSE / DENSE2 image */
     uint32_t pair_t2[32]; /* [8 y + c], y = 2-bit code of a regular symbol, c = nuc code: number of c in BWT[0, first suffix starting with y) */
     uint32_t pair_runs;   /* special runs of the PAIRS image: maximal runs of positions whose c1 or c2 is \n or N (statistics only) */
-    uint32_t reserved1;
+    uint32_t tag_span_lo; /* low 32 bits of bwt_intervals.size() = rows the tag runs cover + 1 (0: no tags, or an image saved before the field was kept);
+                             the walk image aligns the runs' last row with the BWT's last row by it ("WALK image" below) */
     /* WIDE images (appended: the offsets above are what tests/image_emu.py reads) */
     uint32_t wide;            /* header counts are deltas against superblock bases; 64-bit kernels */
     uint32_t d2_sb_shift, pairs_sb_shift; /* blocks per superblock = 1 << shift */

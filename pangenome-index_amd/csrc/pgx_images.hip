@@ -1,5 +1,5 @@
 // pgx_images.hip -- the device images of an index: the rank image with its seed tables, tag runs and PAIRS blocks (device_image), and what is
-// added on first use: the locate image (locate_image), the LCE image (ensure_lce), the text image (ensure_text) and the literal count image
+// added on first use: the locate image (locate_image), the LCE image (ensure_lce), the text image (ensure_text), the walk image (ensure_walk) and the literal count image
 // (literal_image).
 #include <chrono>
 #include <memory>
@@ -52,6 +52,7 @@ static void release_buffers(pgx_device_image *d) {
     release_locate_buffers(d);
     d->lce_sa.release(); d->lce_text.release(); d->lce_flags.release(); d->lce_lcp.release(); d->lce_seq_start.release();
     d->text4.release(); d->text_seq_start.release();
+    d->walk_bits.release(); d->walk_dir.release(); d->walk_nodes.release();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -620,6 +621,146 @@ extern "C" pgx_status pgx_index_text(pgx_index *h, int device, uint64_t *seq_len
         } catch (...) { bytes.release(); throw; }
         bytes.release();
     }
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// WALK image (pgx_image.h): one bit per text position that starts a node visit, a rank directory over the bits and the node of every visit.  Built once per
+// device image on its first use, on the TEXT image's coordinates (ensure_text first: its text_seq_start is the sequence table here too).  The text position
+// of every row comes from the resident lce_sa where the LCE image is resident, else from a whole-range locate as in ensure_text: the same bytes either way.
+// Two passes over the rows (pgx_walk_kernels.hip): marks, then -- behind popcounts and the scan -- the nodes.  Throws like ensure_text.
+void walk_directory(const uint64_t *bits, uint64_t n_blocks, DevBuf &counts, uint64_t *dir, DevBuf &scan_tmp, hipStream_t s) {
+    counts.ensure(n_blocks * 8);
+    hipLaunchKernelGGL(pgx_walk_popc_kernel, dim3((unsigned)std::min<uint64_t>((n_blocks + 255) / 256, 2048)), dim3(256), 0, s, bits, n_blocks, counts.as<uint64_t>());
+    HIPCHECK(hipGetLastError());
+    scan_excl(1, counts.p, n_blocks, 0, dir, scan_tmp, s);
+}
+
+static std::mutex g_walk_mutex;
+void ensure_walk(pgx_index *h, pgx_device_image *d) {
+    std::lock_guard<std::mutex> lock(g_walk_mutex);
+    if (d->has_walk) return;
+    if (!h->has_rank) throw Error(PGX_ERR_ARG, "walk image: index opened without an r-index");
+    if (!h->has_tags) throw Error(PGX_ERR_UNSUPPORTED, "walk image: index opened without a tag array, and the walk is recovered from the tags");
+    locate_check_supported(h, "walk image");
+    if (h->from_image && !h->loc.built)
+        throw Error(PGX_ERR_UNSUPPORTED, "walk image: the image file was saved without the locate image (--no-locate), and the walk is recovered through it");
+    const uint64_t n = d->img.n;
+    if (n >= (1ull << 32) - (1ull << 20))
+        throw Error(PGX_ERR_UNSUPPORTED, "walk image: the BWT has " + std::to_string(n) + " symbols, the image holds fewer than 2^32 - 2^20");
+    const uint32_t span_lo = h->img.consts.tag_span_lo;
+    if (!span_lo) throw Error(PGX_ERR_UNSUPPORTED, "walk image: the image file was saved before the span of the tag runs was kept; save it again from the index and tag files");
+    const auto t_begin = std::chrono::steady_clock::now();
+    ensure_text(h, d);
+    const uint64_t n_seq = d->text_n_seq, ml = h->meta.max_length;
+    // the runs end with the last row (pgx_image.h "WHICH RUN HOLDS ROW i"): in front of row n_seq lie `head` rows, mod 2^32 like span_lo
+    const uint32_t head = span_lo - 1u - (uint32_t)(n - n_seq);
+    if (head >= (1u << 25))
+        throw Error(PGX_ERR_FORMAT, "walk image: the tags do not belong to this index: their runs cover fewer rows than the " + std::to_string(n - n_seq) + " the index has behind its endmarkers");
+    const int64_t delta = (int64_t)head - (int64_t)n_seq;
+    bool from_lce = false;
+    {
+        std::lock_guard<std::mutex> lce_lock(g_lce_mutex);
+        from_lce = d->lce_state == 1 && d->img.lce_sa && d->lce_seq_start.p && d->lce_n_seq == n_seq;
+    }
+    const uint64_t n_blocks = n / PGX_WALK_BLOCK_BITS + 1, n_words = n_blocks * PGX_WALK_BLOCK_WORDS;
+    auto check_free = [&](uint64_t need, const char *what) {
+        size_t mem_free = 0, mem_total = 0;
+        if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); throw Error(PGX_ERR_HIP, "walk image: hipMemGetInfo failed"); }
+        if ((uint64_t)mem_free < need)
+            throw Error(PGX_ERR_NOMEM, std::string("walk image: ") + what + " takes " + std::to_string(need) + " bytes of device memory, " + std::to_string(mem_free) + " are free");
+    };
+    // the suffix array as the locate kernels write it (8 n, only without a resident LCE image), the marks, the directory and its counts, the scan's scratch
+    check_free((from_lce ? 0 : 8 * n + 128) + n_words * 8 + (n_blocks + 1) * 16 + (1ull << 20), "building it");
+    DevBuf vals, bits, dir, nodes, counts, scan_tmp, bad;
+    auto drop = [&]() { vals.release(); bits.release(); dir.release(); nodes.release(); counts.release(); scan_tmp.release(); bad.release(); };
+    uint64_t V = 0;
+    try {
+        const uint32_t *sa32 = nullptr;
+        const uint64_t *sa64 = nullptr;
+        if (from_lce) sa32 = d->lce_sa.as<uint32_t>();
+        else {
+            pgx_device_image *dl = locate_image(h, d->device);
+            if (!dl->loc.n || dl->loc.n != n) throw Error(PGX_ERR_UNSUPPORTED, "walk image: the locate image does not cover the BWT");
+            const uint64_t first = 0, last = n - 1;
+            std::vector<uint64_t> off;
+            uint64_t nv = 0;
+            locate_core(h, dl, &first, &last, 1, 0, off, vals, nv);
+            if (nv != n) throw Error(PGX_ERR_UNSUPPORTED, "walk image: the suffix array is incomplete");
+            sa64 = vals.as<uint64_t>();
+        }
+        const uint64_t *seq_start = d->text_seq_start.as<uint64_t>();
+        const uint64_t rows = n - n_seq;
+        const unsigned grid_rows = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((rows + 255) / 256, 1u << 20));
+        bits.ensure(n_words * 8); dir.ensure((n_blocks + 1) * 8); bad.ensure(16);
+        HIPCHECK(hipMemsetAsync(bits.p, 0, n_words * 8, nullptr));
+        HIPCHECK(hipMemsetAsync(bad.p, 0, 8, nullptr));
+        HIPCHECK(hipMemsetAsync(bad.as<uint8_t>() + 8, 0xFF, 8, nullptr));
+        hipLaunchKernelGGL(pgx_walk_mark_kernel, dim3(grid_rows), dim3(256), 0, nullptr, d->img, sa32, sa64, ml, seq_start, n_seq, n, delta, bits.as<uint32_t>(),
+                           bad.as<unsigned long long>());
+        HIPCHECK(hipGetLastError());
+        walk_directory(bits.as<uint64_t>(), n_blocks, counts, dir.as<uint64_t>(), scan_tmp, nullptr);
+        PgxWalkImage w{bits.as<uint64_t>(), dir.as<uint64_t>(), nullptr, n, n_words, n_blocks, 0};
+        hipLaunchKernelGGL(pgx_walk_check_kernel, dim3(grid_for(n_seq, 256)), dim3(256), 0, nullptr, w, seq_start, n_seq, 1u, bad.as<unsigned long long>() + 1);
+        HIPCHECK(hipGetLastError());
+        uint64_t hb[2] = {0, 0};
+        HIPCHECK(hipMemcpy(hb, bad.p, 16, hipMemcpyDeviceToHost));
+        if (hb[0]) throw Error(PGX_ERR_UNSUPPORTED, "walk image: suffix array values outside the collection");
+        if (hb[1] != ~0ull)
+            throw Error(PGX_ERR_FORMAT, "walk image: the tags do not belong to this index: the first position of sequence " + std::to_string(hb[1]) + " does not start a node visit");
+        HIPCHECK(hipMemcpy(&V, dir.as<uint64_t>() + n_blocks, 8, hipMemcpyDeviceToHost));
+        check_free((V ? V : 1) * 8, "the node of every visit");
+        nodes.ensure((V ? V : 1) * 8);
+        w.nodes = nodes.as<uint64_t>(); w.n_visits = V;
+        hipLaunchKernelGGL(pgx_walk_nodes_kernel, dim3(grid_rows), dim3(256), 0, nullptr, d->img, w, sa32, sa64, ml, seq_start, n_seq, n, delta, nodes.as<uint64_t>());
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipDeviceSynchronize());
+        d->walk = w;
+    } catch (...) { (void)hipGetLastError(); drop(); throw; }
+    d->walk_bits = bits; bits = DevBuf();
+    d->walk_dir = dir; dir = DevBuf();
+    d->walk_nodes = nodes; nodes = DevBuf();
+    d->has_walk = true;
+    drop();
+    if (std::getenv("PGX_IMAGE_TIMING")) // (scripts/read_walk_bench.py; the TEXT image's build is inside when this call built it)
+        std::fprintf(stderr, "[pgx] walk image (%s route): %.3f ms wall; %llu bytes (%llu marks + directory, %llu visits)\n", from_lce ? "lce" : "locate",
+                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(),
+                     (unsigned long long)(n_words * 8 + (n_blocks + 1) * 8 + V * 8), (unsigned long long)(n_words * 8 + (n_blocks + 1) * 8), (unsigned long long)V);
+}
+
+extern "C" pgx_status pgx_index_paths(pgx_index *h, int device, uint64_t *path_offsets, uint64_t n_seq_cap, uint64_t *path_nodes, uint32_t *visit_length, uint64_t cap) {
+    PGX_GUARD_BEGIN
+    if (!h || !path_offsets) throw Error(PGX_ERR_ARG, "pgx_index_paths: null argument");
+    pgx_device_image *d = device_image(h, device);
+    ensure_walk(h, d);
+    const uint64_t n_seq = d->text_n_seq, V = d->walk.n_visits;
+    if (n_seq_cap < n_seq) throw Error(PGX_ERR_ARG, "pgx_index_paths: the index has " + std::to_string(n_seq) + " sequences, n_seq_cap is " + std::to_string(n_seq_cap));
+    // the position of every visit comes down once; offsets and lengths follow on the host (an inspection call, not a stage)
+    std::vector<uint64_t> hs(n_seq + 1), pos(V);
+    HIPCHECK(hipMemcpy(hs.data(), d->text_seq_start.p, (n_seq + 1) * 8, hipMemcpyDeviceToHost));
+    if (V) {
+        DevBuf dpos;
+        try {
+            dpos.ensure(V * 8);
+            hipLaunchKernelGGL(pgx_walk_positions_kernel, dim3((unsigned)std::min<uint64_t>((d->walk.n_words + 255) / 256, 1u << 20)), dim3(256), 0, nullptr, d->walk, dpos.as<uint64_t>());
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipMemcpy(pos.data(), dpos.p, V * 8, hipMemcpyDeviceToHost));
+        } catch (...) { dpos.release(); throw; }
+        dpos.release();
+    }
+    uint64_t k = 0;
+    for (uint64_t q = 0; q < n_seq; q++) {
+        path_offsets[q] = k;
+        while (k < V && pos[k] < hs[q + 1]) k++;
+    }
+    path_offsets[n_seq] = k;
+    if (!path_nodes && !visit_length) return PGX_OK;
+    if (cap < V) throw Error(PGX_ERR_NOMEM, "pgx_index_paths: the index has " + std::to_string(V) + " visits, cap is " + std::to_string(cap));
+    if (path_nodes && V) HIPCHECK(hipMemcpy(path_nodes, d->walk_nodes.p, V * 8, hipMemcpyDeviceToHost));
+    if (visit_length)
+        for (uint64_t q = 0; q < n_seq; q++)
+            for (uint64_t j = path_offsets[q]; j < path_offsets[q + 1]; j++)
+                visit_length[j] = (uint32_t)((j + 1 < path_offsets[q + 1] ? pos[j + 1] : hs[q + 1] - 1) - pos[j]);
     return PGX_OK;
     PGX_GUARD_END
 }

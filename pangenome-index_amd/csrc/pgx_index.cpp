@@ -911,6 +911,7 @@ void build_tag_image(const TagFile &tf, HostImage &img) {
     }
     c.has_tags = 1;
     c.n_tag_runs = nr;
+    c.tag_span_lo = (uint32_t)tf.bwt_intervals.size;
     uint64_t span = tf.bwt_intervals.size ? tf.bwt_intervals.size : 1;
     uint32_t shift = 0;
     while (shift < 40 && ((span >> (shift + 1)) + 2) >= 2 * (nr + 1)) shift++;

@@ -67,6 +67,9 @@ struct pgx_device_image {
     DevBuf text4, text_seq_start;                  // TEXT image (ensure_text), built on its first use: 4-bit symbols; n_seq + 1 text positions
     uint64_t text_n_seq = 0;
     bool has_text = false;
+    DevBuf walk_bits, walk_dir, walk_nodes;        // WALK image (ensure_walk), built on its first use: marks, rank directory, node << 1 | rev of every visit
+    PgxWalkImage walk{};
+    bool has_walk = false;
     DevBuf lit_bstart, lit_cum, lit_runs, lit_roff, lit_tabs; // literal count image (quirk 3), uploaded on first use
     PgxLitImage lit{};
     bool has_lit = false;
@@ -81,6 +84,9 @@ pgx_device_image *locate_image(pgx_index *h, int device);
 pgx_device_image *literal_image(pgx_index *h, int device);
 void ensure_lce(pgx_index *h, pgx_device_image *d);
 void ensure_text(pgx_index *h, pgx_device_image *d); // throws where the image cannot be built (include/pgx.h pgx_index_text)
+void ensure_walk(pgx_index *h, pgx_device_image *d); // builds the TEXT image too; throws where it cannot be built (include/pgx.h "read walk")
+// the rank directory of a WALK image over n_blocks blocks of marks: dir[n_blocks + 1] on stream s (counts: n_blocks u64 of scratch)
+void walk_directory(const uint64_t *bits, uint64_t n_blocks, DevBuf &counts, uint64_t *dir, DevBuf &scan_tmp, hipStream_t s);
 // the section sum of an image file over n_bytes of device memory (16-byte aligned), added to *sum on stream s (pgx_image_sum_kernels.hip)
 void launch_image_sum(const void *data, uint64_t n_bytes, unsigned long long *sum, hipStream_t s);
 
@@ -217,6 +223,25 @@ struct AlignWork {
         for (auto &e : ev)
             if (e) (void)hipEventDestroy(e);
         ev.clear();
+        valid = false;
+    }
+};
+
+// pgx_batch_read_walk's buffers (grow-only, its own) and its result; pgx_read_walk_arrays uses one of its own
+struct WalkWork {
+    DevBuf recs, count, first, step_off, steps, scan_tmp;
+    HostBuf h_recs, h_step_off, h_steps;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool valid = false;
+    uint32_t flags = 0;
+    uint64_t n_reads = 0, n_steps = 0;
+    float ms = 0;
+    void release() {
+        DevBuf *all[] = {&recs, &count, &first, &step_off, &steps, &scan_tmp};
+        for (DevBuf *d : all) d->release();
+        h_recs.release(); h_step_off.release(); h_steps.release();
+        for (auto &e : ev)
+            if (e) { (void)hipEventDestroy(e); e = nullptr; }
         valid = false;
     }
 };

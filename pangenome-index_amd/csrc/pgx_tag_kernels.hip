@@ -20,21 +20,7 @@
 
 #include "pgx_device.h"
 
-// run start r: from the interleaved (start, value) array when the image has one -- the locate kernel then finds the run's value in the
-// cache line its search ended in (three random lines per MEM -> two)
-#define PGX_TSTART(img, r) ((img).tpair ? (img).tpair[(r)].x : (img).tstart[(r)])
-// rank_1(bwt_intervals, x + 1) = number of run starts <= x  (src/tag_arrays.cpp:857-858)
-__device__ __forceinline__ uint64_t pgx_tag_rank(const PgxDevImage &img, uint64_t x) {
-    const uint64_t nr = img.n_tag_runs;
-    uint64_t di = x >> img.tag_dir_shift;
-    if (di + 1 >= img.tag_dir_entries) return nr; // beyond bwt_intervals.size(): all ones
-    uint64_t lo = img.tdir[di], hi = img.tdir[di + 1];
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (PGX_TSTART(img, mid) <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+// (PGX_TSTART and pgx_tag_rank: pgx_device.h, shared with pgx_walk_kernels.hip)
 
 // Tag runs by bucket (round 3): the locate kernel is two to three dependent random lines per MEM through tdir and tpair (directory entry, the pair the
 // search ends at, sometimes a neighbour) -- 1.24 ms for 18.8 M MEMs at chr22 scale, at the rate random lines reach.  A bucket is the 2^shift BWT positions

@@ -155,6 +155,16 @@ class ReadAligns(C.Structure):  # pgx_read_aligns: host pointers (pgx_batch_alig
                 ("scratch_bytes", u64), ("ms_align", C.c_float), ("ms_forward", C.c_float), ("ms_trace", C.c_float), ("reserved2", u32)]
 
 
+WALK_STEPS = 1  # pgx_batch_read_walk / pgx_read_walk_arrays flag
+WALK_DTYPE = np.dtype([("path_len", "<u8"), ("path_start", "<u8"), ("path_end", "<u8"), ("n_steps", "<u4"), ("seq", "<u4")])  # pgx_read_walk, 32 bytes
+assert WALK_DTYPE.itemsize == 32
+
+
+class ReadWalks(C.Structure):  # pgx_read_walks: host pointers (pgx_batch_walked) or device pointers (pgx_batch_device_walked)
+    _fields_ = [("n_reads", u64), ("n_steps", u64), ("flags", u32), ("reserved", u32), ("reads", p), ("step_offsets", p), ("steps", p), ("ms_walk", C.c_float),
+                ("reserved2", u32)]
+
+
 class DeviceArray:
     """a device buffer owned by a batch, exposed through __cuda_array_interface__ (zero copy: torch.as_tensor(a, device="cuda"));
     64-bit unsigned values are presented as int64"""
@@ -307,6 +317,11 @@ def lib():
     L.pgx_batch_aligned.argtypes = [p, C.POINTER(ReadAligns)]
     L.pgx_batch_device_aligned.argtypes = [p, C.POINTER(ReadAligns)]
     L.pgx_read_align_arrays.argtypes = [C.c_int, p, p, u64, p, p, u64, p, p, u32, u32, p, p, p, u64]
+    L.pgx_batch_read_walk.argtypes = [p, u32, p]
+    L.pgx_batch_walked.argtypes = [p, C.POINTER(ReadWalks)]
+    L.pgx_batch_device_walked.argtypes = [p, C.POINTER(ReadWalks)]
+    L.pgx_index_paths.argtypes = [p, C.c_int, p, u64, p, p, u64]
+    L.pgx_read_walk_arrays.argtypes = [C.c_int, p, u64, p, p, p, u64, p, p, p, u32, p, p, p, u64]
     L.pgx_batch_result_compact.argtypes = [p, C.POINTER(CompactResult)]
     L.pgx_compact_expand.argtypes = [C.POINTER(CompactResult), u64, u64, p, p, p, p, p]
     L.pgx_compact_bound.argtypes = [u64, u64, u64, u32]
@@ -629,6 +644,16 @@ class Index:
         buf = np.zeros(int(inf.bwt_size), dtype=np.uint8)
         _check(self.L.pgx_index_text(self.h, device, lens.ctypes.data, len(lens), buf.ctypes.data, len(buf)))
         return lens, buf.tobytes()
+
+    def paths(self, device=0):
+        """pgx_index_paths: (path_offsets uint64[n_sequences + 1], path_nodes uint64[V] as node << 1 | rev, visit_length uint32[V]): the node list of
+        every sequence, recovered on the device from the index and its tags alone (builds the walk image on first use)"""
+        offs = np.zeros(int(self.info().n_sequences) + 1, dtype=np.uint64)
+        _check(self.L.pgx_index_paths(self.h, device, offs.ctypes.data, len(offs) - 1, None, None, 0))
+        v = int(offs[-1])
+        nodes, lens = np.zeros(max(v, 1), dtype=np.uint64), np.zeros(max(v, 1), dtype=np.uint32)
+        _check(self.L.pgx_index_paths(self.h, device, offs.ctypes.data, len(offs) - 1, nodes.ctypes.data, lens.ctypes.data, v))
+        return offs, nodes[:v], lens[:v]
 
     def lce_view(self, which, nbytes, device=0):
         """the device's LCE image (which = 30 suffix array, 31 text, 32 line flags, 33 common prefixes) as bytes; zeros where the index has none"""
@@ -1014,6 +1039,42 @@ def read_align_arrays(device, text, seq_offsets, reads, read_offsets, cand_seq, 
     return res
 
 
+def read_walk_arrays(device, seq_offsets, visit_offsets, visit_nodes, visit_length, seq, text_start, text_end, flags=0, steps_cap=None, out=None):
+    """pgx_read_walk_arrays: the walk kernels on stated path tables (sequence q = the visits [visit_offsets[q], visit_offsets[q + 1]) with nodes
+    visit_nodes uint64 and lengths visit_length uint32; read r = [text_start[r], text_end[r]) of sequence seq[r], NO_SEQUENCE 0xFFFFFFFF for none):
+    dict(reads WALK_DTYPE[n_reads], and with WALK_STEPS step_offsets uint64[n_reads + 1] and steps uint64[n_steps], else None).  steps_cap: the
+    capacity handed to the library (default: enough for any stretches on these tables); out: a dict of arrays to write into (tests)"""
+    seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+    visit_offsets = np.ascontiguousarray(visit_offsets, dtype=np.uint64)
+    visit_nodes = np.ascontiguousarray(visit_nodes, dtype=np.uint64)
+    visit_length = np.ascontiguousarray(visit_length, dtype=np.uint32)
+    seq = np.ascontiguousarray(seq, dtype=np.uint32)
+    text_start = np.ascontiguousarray(text_start, dtype=np.uint64)
+    text_end = np.ascontiguousarray(text_end, dtype=np.uint64)
+    n, n_seq = len(seq), len(seq_offsets) - 1
+    if len(text_start) != n or len(text_end) != n or len(visit_offsets) != n_seq + 1 or len(visit_nodes) != len(visit_length):
+        raise ValueError("read_walk_arrays: array lengths disagree")
+    lst = bool(flags & WALK_STEPS)
+    if steps_cap is None:  # (a stretch of L symbols meets at most L visits)
+        cap = int(np.maximum(text_end.astype(np.int64) - text_start.astype(np.int64), 0).sum()) if n else 0
+    else:
+        cap = int(steps_cap)
+    res = dict(out) if out else {}
+    if "reads" not in res:
+        res["reads"] = np.zeros(n, dtype=WALK_DTYPE)
+    if "step_offsets" not in res:
+        res["step_offsets"] = np.zeros(n + 1, dtype=np.uint64) if lst else None
+    if "steps" not in res:
+        res["steps"] = np.zeros(max(cap, 1), dtype=np.uint64) if lst else None
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().pgx_read_walk_arrays(device, seq_offsets.ctypes.data, n_seq, visit_offsets.ctypes.data, visit_nodes.ctypes.data, visit_length.ctypes.data, n,
+                                      seq.ctypes.data, text_start.ctypes.data, text_end.ctypes.data, flags, ptr(res["reads"]), ptr(res["step_offsets"]),
+                                      ptr(res["steps"]), cap))
+    if lst:
+        res["steps"] = res["steps"][: int(res["step_offsets"][-1])]
+    return res
+
+
 def find_mems_sharded(index, devices, reads_cat, offsets, min_len, min_occ, tags=False):
     """pgx_find_mems_sharded: contiguous read slices, slice i on devices[i]; returns the per-slice result dicts in slice order"""
     reads_cat = np.ascontiguousarray(reads_cat, dtype=np.uint8)
@@ -1387,6 +1448,37 @@ class Batch:
         out["reads"] = DeviceArray(r.reads, (n, 8), self)
         out["op_offsets"] = DeviceArray(r.op_offsets, (n + 1,), self) if r.op_offsets else None
         out["ops"] = DeviceArray(r.ops, (k,), self, "<u4") if r.ops else None
+        return out
+
+    def read_walk(self, flags=0, stream=None):
+        """pgx_batch_read_walk along the stretches of the last read_align, then walked()"""
+        _check(self.L.pgx_batch_read_walk(self.b, flags, stream))
+        return self.walked()
+
+    def _walked(self, fn):
+        r = ReadWalks()
+        _check(fn(self.b, C.byref(r)))
+        return r, dict(n_reads=int(r.n_reads), n_steps=int(r.n_steps), flags=int(r.flags), ms_walk=float(r.ms_walk))
+
+    def walked(self):
+        """the last walk result as numpy arrays: reads WALK_DTYPE[n_reads]; with WALK_STEPS step_offsets uint64[n_reads + 1] and steps uint64[n_steps]
+        (None without), with n_reads, n_steps, flags, ms_walk"""
+        r, out = self._walked(self.L.pgx_batch_walked)
+        n, k = out["n_reads"], out["n_steps"]
+        out["reads"] = np.frombuffer((C.c_char * (n * 32)).from_address(r.reads), dtype=WALK_DTYPE).copy() if n else np.zeros(0, WALK_DTYPE)
+        out["step_offsets"] = _u64_array(C.cast(r.step_offsets, C.POINTER(u64)), n + 1) if r.step_offsets else None
+        out["steps"] = (_u64_array(C.cast(r.steps, C.POINTER(u64)), k) if k else np.zeros(0, np.uint64)) if r.step_offsets else None
+        return out
+
+    def device_walked(self):
+        """the same as device arrays (valid until the next run / upload / read_walk / free): reads int64[n_reads, 4] (the 32-byte records as words),
+        step_offsets int64[n_reads + 1], steps int64[n_steps]"""
+        r, out = self._walked(self.L.pgx_batch_device_walked)
+        n, k = out["n_reads"], out["n_steps"]
+        out["device"] = True
+        out["reads"] = DeviceArray(r.reads, (n, 4), self)
+        out["step_offsets"] = DeviceArray(r.step_offsets, (n + 1,), self) if r.step_offsets else None
+        out["steps"] = DeviceArray(r.steps, (k,), self) if r.steps else None
         return out
 
     def free(self):

@@ -24,6 +24,9 @@
 //                 --align FILE (one line per read: the banded alignment with gaps at the verify winner and its CIGAR, pgx_batch_read_align; runs the
 //                 place and verify stages itself when they are not requested, with --place-max, --verify-max and --verify-mismatch as there; stdout
 //                 and stderr stay as they are), --align-band W (0 .. 31, default 8), --align-only (no MEM text, like --verify-only)
+//                 --gaf FILE (one GAF line per read: the alignment as a walk through the graph, pgx_batch_read_walk; runs the place, verify and align
+//                 stages itself when they are not requested, with their options as there; stdout and stderr stay as they are), --gaf-only (no MEM
+//                 text, like --align-only)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -156,6 +159,7 @@ struct Done {
     std::string places; // --place: the lines of this batch
     std::string verifies; // --verify: the lines of this batch
     std::string aligns; // --align: the lines of this batch
+    std::string gaf; // --gaf: the lines of this batch
     std::string error;
 };
 
@@ -337,6 +341,44 @@ static void format_aligns(const pgx_read_align *recs, const uint64_t *op_off, co
     out.resize((size_t)(p - &out[0]));
 }
 
+// --gaf: one GAF line per read of a batch, appended to out, from the align records with their operations and the walk records with their steps; len[i] =
+// bytes of read i.  A read without steps prints its number, its length, * in columns 3 to 11 and 255.  The S operations stay out of cg:Z: columns 3 and 4 state them.
+static void format_gaf(const pgx_read_align *recs, const uint64_t *op_off, const uint32_t *ops, const pgx_read_walk *walks, const uint64_t *step_off, const uint64_t *steps,
+                       const uint64_t *read_off, size_t n, uint64_t first_seq, std::string &out) {
+    out.resize(n * (13 * 21 + 40) + (size_t)(op_off[n] - op_off[0]) * 11 + (size_t)(step_off[n] - step_off[0]) * 21);
+    char *p = &out[0];
+    for (size_t i = 0; i < n; i++) {
+        const pgx_read_align &x = recs[i];
+        const pgx_read_walk &w = walks[i];
+        const uint64_t len = read_off[i + 1] - read_off[i];
+        p = put_u64(p, first_seq + i + 1); *p++ = '\t';
+        p = put_u64(p, len);
+        if (w.n_steps == 0) {
+            for (int k = 0; k < 9; k++) { *p++ = '\t'; *p++ = '*'; }
+            p = put_str(p, "\t255\n");
+            continue;
+        }
+        *p++ = '\t'; p = put_u64(p, x.clip_lo);
+        *p++ = '\t'; p = put_u64(p, len - x.clip_hi);
+        p = put_str(p, "\t+\t");
+        for (uint64_t o = step_off[i]; o < step_off[i + 1]; o++) { *p++ = (steps[o] & 1) ? '<' : '>'; p = put_u64(p, steps[o] >> 1); }
+        const uint64_t f[5] = {w.path_len, w.path_start, w.path_end, x.n_match, (uint64_t)x.n_match + x.n_mismatch + x.n_ins + x.n_del};
+        for (uint64_t v : f) { *p++ = '\t'; p = put_u64(p, v); }
+        p = put_str(p, "\t255\tNM:i:"); p = put_u64(p, x.edits);
+        p = put_str(p, "\ths:i:"); p = put_u64(p, x.seq);
+        p = put_str(p, "\tho:i:"); p = put_u64(p, x.text_start);
+        p = put_str(p, "\tcg:Z:");
+        for (uint64_t o = op_off[i]; o < op_off[i + 1]; o++) {
+            const uint32_t op = ops[o] & 15u;
+            if (op == PGX_ALIGN_OP_S) continue;
+            p = put_u64(p, ops[o] >> 4);
+            *p++ = op == PGX_ALIGN_OP_I ? 'I' : (op == PGX_ALIGN_OP_D ? 'D' : (op == PGX_ALIGN_OP_EQ ? '=' : 'X'));
+        }
+        *p++ = '\n';
+    }
+    out.resize((size_t)(p - &out[0]));
+}
+
 static int usage() {
     std::cerr << "usage: find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ>"
                  " [--device N | --gpus N | --devices a,b,..] [--streams W] [--mode compat|strict] [--batch N]"
@@ -345,7 +387,8 @@ static int usage() {
                  " [--hits FILE [--hits-max K] [--hits-only (not with --locate)]]"
                  " [--place FILE [--place-max K] [--place-only (not with --locate)]]"
                  " [--verify FILE [--verify-max C] [--verify-mismatch P] [--verify-only (not with --locate)]]"
-                 " [--align FILE [--align-band W (0 .. 31)] [--align-only (not with --locate)]]" << std::endl;
+                 " [--align FILE [--align-band W (0 .. 31)] [--align-only (not with --locate)]]"
+                 " [--gaf FILE [--gaf-only (not with --locate)]]" << std::endl;
     return EXIT_FAILURE;
 }
 
@@ -376,6 +419,8 @@ int main(int argc, char **argv) {
     std::string align_file;     // --align: the gapped alignments of every batch go to this file
     uint32_t align_band = 8;
     bool align_band_given = false, align_only = false;
+    std::string gaf_file;       // --gaf: the graph walks of every batch go to this file, one GAF line per read
+    bool gaf_only = false;
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -474,20 +519,25 @@ int main(int argc, char **argv) {
             align_band_given = true;
         }
         else if (a == "--align-only") align_only = true;
+        else if (a == "--gaf") { gaf_file = next(); if (gaf_file.empty()) { std::cerr << "--gaf: a file name" << std::endl; return EXIT_FAILURE; } }
+        else if (a == "--gaf-only") gaf_only = true;
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
     if ((hits_max_given || hits_only) && hits_file.empty()) return usage();
     if (hits_only && locate_mode) { std::cerr << "--hits-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if ((place_max_given || place_only) && place_file.empty()) return usage();
     if (place_only && locate_mode) { std::cerr << "--place-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
-    if ((verify_only && verify_file.empty()) || (verify_opt_given && verify_file.empty() && align_file.empty())) return usage();
+    if ((verify_only && verify_file.empty()) || (verify_opt_given && verify_file.empty() && align_file.empty() && gaf_file.empty())) return usage();
     if (verify_only && locate_mode) { std::cerr << "--verify-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
-    if ((align_band_given || align_only) && align_file.empty()) return usage();
+    if ((align_only && align_file.empty()) || (align_band_given && align_file.empty() && gaf_file.empty())) return usage();
+    if (gaf_only && gaf_file.empty()) return usage();
+    if (gaf_only && locate_mode) { std::cerr << "--gaf-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if (align_only && locate_mode) { std::cerr << "--align-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     const bool want_hits = !hits_file.empty(), want_places = !place_file.empty(), want_verify = !verify_file.empty(), want_align = !align_file.empty();
-    const bool run_verify = want_verify || want_align; // (--align runs the verify stage itself)
+    const bool want_gaf = !gaf_file.empty(), run_align = want_align || want_gaf; // (--gaf runs the align stage itself)
+    const bool run_verify = want_verify || run_align; // (--align runs the verify stage itself)
     const uint32_t place_flags = run_verify && verify_max > 1 ? PGX_PLACE_LIST : 0u; // (the candidates beyond the first come from the list)
-    const bool no_text = hits_only || place_only || verify_only || align_only; // (either one: no tag stage, no download of result arrays, stdout empty)
+    const bool no_text = hits_only || place_only || verify_only || align_only || gaf_only; // (either one: no tag stage, no download of result arrays, stdout empty)
     if (batch_reads == 0) batch_reads = 1;
     if (locate_max && !locate_mode) { std::cerr << "--locate-max needs --locate" << std::endl; return EXIT_FAILURE; }
 
@@ -500,14 +550,16 @@ int main(int argc, char **argv) {
         if (!rin) { std::cerr << "Cannot open r-index: " << r_index_file << std::endl; std::exit(EXIT_FAILURE); } // :30
     }
     const bool from_image = is_image_file(r_index_file.c_str());
-    if (!from_image) {
+    // --gaf with "-" for the tags of a .ri: the index opens without tags and the walk stage's own refusal ends the run below, before any batch
+    const bool gaf_no_tags = !from_image && !gaf_file.empty() && tag_array_index == "-";
+    if (!from_image && !gaf_no_tags) {
         std::ifstream tin(tag_array_index, std::ios::binary);
         if (!tin) { std::cerr << "Cannot open tag array: " << tag_array_index << std::endl; std::exit(EXIT_FAILURE); }
     }
     pgx_index *h = nullptr;
     if (from_image) {
         if (open_image_index(r_index_file.c_str(), tag_array_index.c_str(), mode_given, mode, &h)) return EXIT_FAILURE;
-    } else if (pgx_index_open(r_index_file.c_str(), tag_array_index.c_str(), tfmt, mode, &h) != PGX_OK) {
+    } else if (pgx_index_open(r_index_file.c_str(), gaf_no_tags ? nullptr : tag_array_index.c_str(), tfmt, mode, &h) != PGX_OK) {
         std::cerr << pgx_last_error() << std::endl; // reference: uncaught sdsl::simple_sds::InvalidData
         return EXIT_FAILURE;
     }
@@ -566,7 +618,7 @@ int main(int argc, char **argv) {
         std::fwrite(PLACE_HEADER, 1, sizeof PLACE_HEADER - 1, place_fp);
     }
     // --verify: the same question for the text image (what --place asks, and a collection of 2^32 - 2^20 symbols or more)
-    std::FILE *verify_fp = nullptr, *align_fp = nullptr;
+    std::FILE *verify_fp = nullptr, *align_fp = nullptr, *gaf_fp = nullptr;
     if (run_verify) {
         static const uint8_t probe_read[4] = {'A', 'C', 'G', 'T'};
         static const uint64_t probe_offs[2] = {0, 4};
@@ -579,12 +631,13 @@ int main(int argc, char **argv) {
             if (st == PGX_OK) st = pgx_batch_locate(pb, 0, place_max, nullptr);
             if (st == PGX_OK) st = pgx_batch_read_place(pb, place_flags, nullptr);
             if (st == PGX_OK) st = pgx_batch_read_verify(pb, verify_max, verify_penalty, 0, nullptr);
-            if (st == PGX_OK && want_align) st = pgx_batch_read_align(pb, align_band, PGX_ALIGN_CIGAR, nullptr);
+            if (st == PGX_OK && run_align) st = pgx_batch_read_align(pb, align_band, PGX_ALIGN_CIGAR, nullptr);
+            if (st == PGX_OK && want_gaf) st = pgx_batch_read_walk(pb, PGX_WALK_STEPS, nullptr); // (the walk image: an index without tags ends here)
             if (st != PGX_OK) msg = pgx_last_error();
             pgx_batch_free(pb);
         }
         if (st != PGX_OK) {
-            std::cerr << msg << (st != PGX_ERR_UNSUPPORTED ? "" : (want_verify ? " (find_mems --verify)" : " (find_mems --align)")) << std::endl;
+            std::cerr << msg << (st != PGX_ERR_UNSUPPORTED ? "" : (want_verify ? " (find_mems --verify)" : (want_align ? " (find_mems --align)" : " (find_mems --gaf)"))) << std::endl;
             if (hits_fp) std::fclose(hits_fp);
             if (place_fp) std::fclose(place_fp);
             return EXIT_FAILURE;
@@ -598,6 +651,10 @@ int main(int argc, char **argv) {
             align_fp = std::fopen(align_file.c_str(), "wb");
             if (!align_fp) { std::cerr << "Cannot open align file: " << align_file << std::endl; return EXIT_FAILURE; }
             std::fwrite(ALIGN_HEADER, 1, sizeof ALIGN_HEADER - 1, align_fp);
+        }
+        if (want_gaf) {
+            gaf_fp = std::fopen(gaf_file.c_str(), "wb");
+            if (!gaf_fp) { std::cerr << "Cannot open gaf file: " << gaf_file << std::endl; return EXIT_FAILURE; }
         }
     }
 
@@ -875,7 +932,7 @@ int main(int argc, char **argv) {
             std::vector<pgx_read_align> align_recs; // --align: the 64-byte records and the operations, at the winners of the verify stage above
             std::vector<uint64_t> align_op_off;
             std::vector<uint32_t> align_ops;
-            if (st == PGX_OK && want_align) {
+            if (st == PGX_OK && run_align) {
                 st = pgx_batch_read_align(b, align_band, PGX_ALIGN_CIGAR, nullptr);
                 pgx_read_aligns ra;
                 if (st == PGX_OK) st = pgx_batch_aligned(b, &ra);
@@ -883,6 +940,21 @@ int main(int argc, char **argv) {
                     align_recs.assign(ra.reads, ra.reads + ra.n_reads);
                     align_op_off.assign(ra.op_offsets, ra.op_offsets + ra.n_reads + 1);
                     align_ops.assign(ra.ops, ra.ops + ra.n_ops);
+                }
+            }
+            std::vector<pgx_read_walk> walk_recs; // --gaf: the 32-byte records and the steps, along the stretches of the align stage above; the reads' lengths
+            std::vector<uint64_t> walk_step_off, walk_steps, walk_read_off;
+            if (st == PGX_OK && want_gaf) {
+                st = pgx_batch_read_walk(b, PGX_WALK_STEPS, nullptr);
+                pgx_read_walks rw;
+                if (st == PGX_OK) st = pgx_batch_walked(b, &rw);
+                if (st == PGX_OK) {
+                    walk_recs.assign(rw.reads, rw.reads + rw.n_reads);
+                    walk_step_off.assign(rw.step_offsets, rw.step_offsets + rw.n_reads + 1);
+                    walk_steps.assign(rw.steps, rw.steps + rw.n_steps);
+                    walk_read_off.resize(rw.n_reads + 1);
+                    pgx_reads_info ri;
+                    st = pgx_batch_reads(b, &ri, walk_read_off.data(), walk_read_off.size(), nullptr, 0);
                 }
             }
             if (format_device || no_text) {
@@ -930,6 +1002,9 @@ int main(int argc, char **argv) {
                 if (want_hits) format_hits(hit_recs.data(), hit_recs.size(), j->first_seq, d->hits);
                 if (want_places) format_places(place_recs.data(), place_recs.size(), j->first_seq, d->places);
                 if (want_verify) format_verifies(verify_recs.data(), verify_recs.size(), j->first_seq, d->verifies);
+                if (want_gaf && !walk_read_off.empty())
+                    format_gaf(align_recs.data(), align_op_off.data(), align_ops.data(), walk_recs.data(), walk_step_off.data(), walk_steps.data(), walk_read_off.data(),
+                               walk_recs.size(), j->first_seq, d->gaf);
                 if (want_align && !align_op_off.empty()) format_aligns(align_recs.data(), align_op_off.data(), align_ops.data(), align_recs.size(), j->first_seq, d->aligns);
                 if (format_device && !no_text) {
                     // the text of the batch from the device, handed to the writer where it is
@@ -1031,6 +1106,7 @@ int main(int argc, char **argv) {
         if (place_fp && !d->places.empty()) std::fwrite(d->places.data(), 1, d->places.size(), place_fp);
         if (verify_fp && !d->verifies.empty()) std::fwrite(d->verifies.data(), 1, d->verifies.size(), verify_fp);
         if (align_fp && !d->aligns.empty()) std::fwrite(d->aligns.data(), 1, d->aligns.size(), align_fp);
+        if (gaf_fp && !d->gaf.empty()) std::fwrite(d->gaf.data(), 1, d->gaf.size(), gaf_fp);
         ns_write += now_ns() - tw0;
         total_mem_time += d->mem_s;
         total_tag_time += d->tag_s;
@@ -1056,6 +1132,7 @@ int main(int argc, char **argv) {
     if (place_fp && (std::fclose(place_fp) != 0) && error.empty()) error = "Cannot write place file: " + place_file;
     if (verify_fp && (std::fclose(verify_fp) != 0) && error.empty()) error = "Cannot write verify file: " + verify_file;
     if (align_fp && (std::fclose(align_fp) != 0) && error.empty()) error = "Cannot write align file: " + align_file;
+    if (gaf_fp && (std::fclose(gaf_fp) != 0) && error.empty()) error = "Cannot write gaf file: " + gaf_file;
     if (!error.empty()) {
         std::cerr << error << std::endl;
         return EXIT_FAILURE;
