@@ -1,5 +1,6 @@
-// pgx_batch.hip -- the pgx_batch object: uploads, pgx_batch_run, results, pgx_batch_locate, pgx_batch_read_hits, pgx_batch_read_place,
-// pgx_batch_read_verify, pgx_batch_read_align, pgx_batch_read_walk.
+// pgx_batch.hip -- the pgx_batch object (create, free, the uploads), pgx_batch_run with its stages and kernel tables, and the plain results.
+// The other result forms are in pgx_batch_forms.hip, pgx_batch_locate in pgx_batch_locate.hip, the read stages (hits, place, verify, align, walk)
+// in pgx_read_stages.hip; pgx_batch_internal.hpp is what they share.
 //
 // Pipeline of pgx_batch_run (one HIP stream, results stay on the device):
 //   scan(cap)      -> slot offsets (worst-case MEMs per read: min(len, len - min_len + 1)); the slot buffer
@@ -15,104 +16,16 @@
 #include <string>
 #include <thread>
 
-#include "pgx_runtime_internal.hpp"
+#include "pgx_batch_internal.hpp"
 
 // ------------------------------------------------------------------------------------------
-struct pgx_chunk { uint64_t r0, r1, slot_base, slots; }; // consecutive reads sharing one pass over the slot buffer
-
-// the compact result form (pgx_batch_result_compact; pgx_compact_encode uses one of its own): grow-only like the other result buffers
-struct CompactWork {
-    DevBuf sizes, tab, bytes, scan_tmp; // padded bytes per block; block_offsets | block_first_mem | block_first_pos; the stream
-    HostBuf h_tab, h_bytes;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the sizing kernel + scan, around the fill kernel
-    void release() {
-        DevBuf *all[] = {&sizes, &tab, &bytes, &scan_tmp};
-        for (DevBuf *d : all) d->release();
-        h_tab.release(); h_bytes.release();
-        for (auto &e : ev)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    }
-};
-
-// the text output (pgx_batch_format; pgx_format_result uses one of its own): grow-only like the other result buffers
-struct FormatWork {
-    // lengths and their scans per level: positions (plen -> pcum), located values (vlen -> vcum), MEMs (mlen -> mcum), reads (rlen -> roff = read_offsets;
-    // elen -> eoff for the stderr lines); pbase / vbase: where a MEM's lists start (pgx_format_fill_mems_kernel); the text and the stderr lines
-    DevBuf plen, pcum, vlen, vcum, mlen, mcum, rlen, roff, elen, eoff, pbase, vbase, text, etext, scan_tmp;
-    // the host side, twice: pgx_batch_format alternates between the two sets, so the text of one call outlives the next call (a writer thread may
-    // still be writing it); h_roff: read_offsets, and behind them the total of the stderr lines
-    HostBuf h_roff[2], h_text[2], h_etext[2];
-    int cur = 0; // the set the last call filled
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // around the length pass, around the fill pass
-    void release() {
-        DevBuf *all[] = {&plen, &pcum, &vlen, &vcum, &mlen, &mcum, &rlen, &roff, &elen, &eoff, &pbase, &vbase, &text, &etext, &scan_tmp};
-        for (DevBuf *d : all) d->release();
-        for (int i = 0; i < 2; i++) { h_roff[i].release(); h_text[i].release(); h_etext[i].release(); }
-        for (auto &e : ev)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    }
-};
-
-struct pgx_batch {
-    pgx_index *h = nullptr;
-    pgx_device_image *dimg = nullptr;
-    int device = 0;
-    hipStream_t own = nullptr; // non-blocking stream of this batch: its copies, and its kernels when the caller names no stream
-    // second stream: the dense2 kernel over the reads with a byte outside A C G T, while the two-step kernel runs (pgx_classify_reads_kernel)
-    hipStream_t side = nullptr;
-    hipEvent_t ev_side[2] = {nullptr, nullptr};
-    bool class_valid = false, class_ok = false; // read_flags / side_list / side_count describe the uploaded reads (ok: few enough such reads to list)
-    uint64_t side_reads_est = 0;                 // about how many reads the second-stream launch serves (sizes its grid)
-    uint64_t n_reads = 0, read_bytes = 0;
-    HostBuf h_off[2];                // rebased host copy of the offsets (chunk planning; pinned: its upload runs at link speed), and the one being filled
-    int h_off_cur = 0;
-    const uint64_t *h_offsets() const { return h_off[h_off_cur].as<uint64_t>(); }
-    std::vector<pgx_chunk> chunks;   // plan of the last run (reused while min_len / budget are unchanged)
-    bool plan_valid = false, slot_off_valid = false;
-    uint64_t slot_off_min_len = 0;
-    uint64_t plan_min_len = 0, plan_budget = 0;
-    DevBuf reads, offsets;
-    // run state
-    DevBuf slot_off, slots, mem_count, mem_off, mems, scan_tmp, counters, heavy_list, heavy_scratch, read_flags, side_list, side_count, packed, ovf_base;
-    DevBuf up_side_ids, up_side_off, up_side_bytes; // pgx_batch_upload_packed: the listed reads as they arrive
-    DevBuf fx_text, fx_tiles, fx_tile_base, fx_lines, fx_contrib, fx_rec, fx_out_off, fx_rec_idx, fx_offs, fx_scal, fx_scan_tmp; // pgx_batch_upload_text
-    std::vector<uint64_t> h_side_off;
-    hipEvent_t ev_up[2] = {nullptr, nullptr};        // around the device passes of an upload
-    float ms_upload_passes = 0;                      // device time of the passes this upload needed before its first find_mems launch (pgx_timing.ms_per_upload adds the run's own)
-    uint64_t last_ovf_used = 0; // arena slots the last run handed out (sizes the next arena)
-    uint64_t max_read_len = 0; // longest read of the upload (sizes the LDS columns of the packed pairs kernel)
-    TagWork tw;
-    LocWork lw; // pgx_batch_locate
-    CompactWork cw; // pgx_batch_result_compact
-    FormatWork fw;  // pgx_batch_format
-    HitsWork hw;    // pgx_batch_read_hits
-    PlaceWork pw;   // pgx_batch_read_place
-    VerifyWork vw;  // pgx_batch_read_verify
-    AlignWork aw;   // pgx_batch_read_align
-    WalkWork ww;    // pgx_batch_read_walk
-    uint64_t n_mems = 0, n_positions = 0, n_ext = 0, n_tag_overflow = 0;
-    bool ran = false, ran_tags = false;
-    // speculative sizing (pgx_batch_run): what the last run with these parameters produced
-    bool shape_valid = false;
-    uint64_t shape_reads = 0, shape_min_len = 0, shape_min_occ = 0, last_mems = 0;
-    bool shape_tags = false;
-    uint32_t spec_runs = 0, spec_fallbacks = 0;
-    // host copies
-    HostBuf h_mem_off, h_mems, h_run_nums, h_pos_off, h_positions;
-    // timing
-    hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // [8]: behind the first find_mems launch; [9]: before it, behind the passes a fresh upload needs
-    bool timed = false;
-    pgx_timing timing{};
-};
-
 static void batch_release(pgx_batch *b) {
     if (!b) return;
     if (hipSetDevice(b->device) == hipSuccess) {
-        DevBuf *all[] = {&b->reads, &b->offsets, &b->slot_off, &b->slots, &b->mem_count, &b->mem_off, &b->mems, &b->scan_tmp,
-                         &b->counters, &b->heavy_list, &b->heavy_scratch, &b->read_flags, &b->side_list, &b->side_count, &b->packed, &b->ovf_base,
-                         &b->up_side_ids, &b->up_side_off, &b->up_side_bytes, &b->fx_text, &b->fx_tiles, &b->fx_tile_base, &b->fx_lines,
-                         &b->fx_contrib, &b->fx_rec, &b->fx_out_off, &b->fx_rec_idx, &b->fx_offs, &b->fx_scal, &b->fx_scan_tmp};
-        for (DevBuf *d : all) d->release();
+        release_all({&b->reads, &b->offsets, &b->slot_off, &b->slots, &b->mem_count, &b->mem_off, &b->mems, &b->scan_tmp,
+                     &b->counters, &b->heavy_list, &b->heavy_scratch, &b->read_flags, &b->side_list, &b->side_count, &b->packed, &b->ovf_base,
+                     &b->up_side_ids, &b->up_side_off, &b->up_side_bytes, &b->fx_text, &b->fx_tiles, &b->fx_tile_base, &b->fx_lines,
+                     &b->fx_contrib, &b->fx_rec, &b->fx_out_off, &b->fx_rec_idx, &b->fx_offs, &b->fx_scal, &b->fx_scan_tmp});
         b->tw.release();
         b->lw.release();
         b->cw.release();
@@ -122,16 +35,12 @@ static void batch_release(pgx_batch *b) {
         b->vw.release();
         b->aw.release();
         b->ww.release();
-        HostBuf *hb[] = {&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]};
-        for (HostBuf *x : hb) x->release();
-        for (auto &e : b->ev)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        release_all({&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]});
+        destroy_events(b->ev);
         if (b->own) { (void)hipStreamDestroy(b->own); b->own = nullptr; }
         if (b->side) { (void)hipStreamDestroy(b->side); b->side = nullptr; }
-        for (auto &e : b->ev_side)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        for (auto &e : b->ev_up)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        destroy_events(b->ev_side);
+        destroy_events(b->ev_up);
     }
     delete b;
 }
@@ -1066,7 +975,7 @@ extern "C" pgx_status pgx_batch_run(pgx_batch *b, uint64_t min_len, uint64_t min
     RoctxRange range("pgx_batch_run");
     if (!b) throw Error(PGX_ERR_ARG, "pgx_batch_run: null batch");
     use_device(b->device);
-    RunCtx r{b, stream ? (hipStream_t)stream : b->own, read_run_knobs(), b->dimg->img, b->n_reads, min_len, min_occ, (flags & PGX_RUN_TAGS) != 0};
+    RunCtx r{b, batch_stream(b, stream), read_run_knobs(), b->dimg->img, b->n_reads, min_len, min_occ, (flags & PGX_RUN_TAGS) != 0};
     // seeds need min_len >= their depth (no stage of a shorter search has room for one): the shallower table serves searches below the depth of the first
     PgxDevImage &img = r.img;
     if (img.seed_k_main && min_len < img.seed_k_main && img.seed_k_small && min_len >= img.seed_k_small) { img.seed = img.seed_small; img.seed_k = img.seed_k_small; }
@@ -1170,1839 +1079,6 @@ extern "C" pgx_status pgx_batch_result(pgx_batch *b, pgx_result *out) {
 }
 
 // ------------------------------------------------------------------------------------------
-// compact result form (pgx_compact_kernels.hip; the format: include/pgx.h "compact result"; the host decoder: pgx_compact.cpp)
-// Sizes every block, scans the sizes into block_offsets and brings the three tables to w.h_tab: the host waits for them here, their last entry
-// sizes the byte buffer.  Returns the size of the stream.
-static uint64_t compact_tables(CompactWork &w, const uint64_t *d_mem_off, const pgx_mem *d_mems, const uint64_t *d_run_nums, const uint64_t *d_pos_off,
-                               const uint64_t *d_positions, uint64_t n_reads, bool tags, bool timed, hipStream_t s) {
-    const uint64_t nb = (n_reads + PGX_COMPACT_BLOCK_READS - 1) / PGX_COMPACT_BLOCK_READS;
-    w.sizes.ensure((nb ? nb : 1) * 8);
-    w.tab.ensure(3 * (nb + 1) * 8);
-    w.h_tab.ensure(3 * (nb + 1) * 8);
-    uint64_t *bo = w.tab.as<uint64_t>(), *fm = bo + (nb + 1), *fp = fm + (nb + 1);
-    if (timed) {
-        for (auto &e : w.ev)
-            if (!e) HIPCHECK(hipEventCreate(&e));
-        HIPCHECK(hipEventRecord(w.ev[0], s));
-    }
-    hipLaunchKernelGGL(pgx_compact_size_kernel, dim3(grid_for(nb + 1, 4)), dim3(256), 0, s, d_mem_off, d_mems, d_run_nums, d_pos_off, d_positions, n_reads, nb,
-                       tags ? 1 : 0, w.sizes.as<uint64_t>(), fm, fp);
-    HIPCHECK(hipGetLastError());
-    scan_excl(1, w.sizes.p, nb, 0, bo, w.scan_tmp, s);
-    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
-    HIPCHECK(hipMemcpyAsync(w.h_tab.p, w.tab.p, 3 * (nb + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    return w.h_tab.as<uint64_t>()[nb];
-}
-
-// the stream itself into w.bytes (grown to `total` first); async on s
-static void compact_fill(CompactWork &w, const uint64_t *d_mem_off, const pgx_mem *d_mems, const uint64_t *d_run_nums, const uint64_t *d_pos_off,
-                         const uint64_t *d_positions, uint64_t n_reads, bool tags, bool timed, uint64_t total, hipStream_t s) {
-    const uint64_t nb = (n_reads + PGX_COMPACT_BLOCK_READS - 1) / PGX_COMPACT_BLOCK_READS;
-    w.bytes.ensure(total ? total : 8);
-    if (timed) HIPCHECK(hipEventRecord(w.ev[2], s));
-    if (nb) {
-        // PGX_COMPACT_STAGE=1 (read per call): the fill kernel that stages its bytes in LDS and stores 8-byte words; the same stream either way
-        const char *e = std::getenv("PGX_COMPACT_STAGE");
-        const bool staged = e && e[0] == '1' && e[1] == 0;
-        hipLaunchKernelGGL(staged ? pgx_compact_fill_staged_kernel : pgx_compact_fill_kernel, dim3(grid_for(nb, 4)), dim3(256), 0, s, d_mem_off, d_mems, d_run_nums, d_pos_off, d_positions, n_reads, nb,
-                           tags ? 1 : 0, (const uint64_t *)w.tab.as<uint64_t>(), w.bytes.as<uint8_t>());
-        HIPCHECK(hipGetLastError());
-    }
-    if (timed) HIPCHECK(hipEventRecord(w.ev[3], s));
-}
-
-static float compact_ms(CompactWork &w) { // (behind the synchronisation that follows compact_fill)
-    float a = 0, c = 0;
-    HIPCHECK(hipEventElapsedTime(&a, w.ev[0], w.ev[1]));
-    HIPCHECK(hipEventElapsedTime(&c, w.ev[2], w.ev[3]));
-    return a + c;
-}
-
-extern "C" pgx_status pgx_batch_result_compact(pgx_batch *b, pgx_compact_result *out) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_batch_result_compact");
-    checked_device_count();
-    if (!b || !out || !b->ran) throw Error(PGX_ERR_ARG, "pgx_batch_result_compact: batch has not been run");
-    use_device(b->device);
-    CompactWork &w = b->cw;
-    hipStream_t s = b->own; // (the run itself completed inside pgx_batch_run, on whatever stream it used)
-    const bool tags = b->ran_tags, timed = b->timed;
-    const uint64_t n = b->n_reads, nb = (n + PGX_COMPACT_BLOCK_READS - 1) / PGX_COMPACT_BLOCK_READS;
-    const uint64_t *run_nums = tags ? b->tw.run_nums.as<uint64_t>() : nullptr, *pos_off = tags ? b->tw.pos_off.as<uint64_t>() : nullptr;
-    const uint64_t *positions = tags ? b->tw.positions.as<uint64_t>() : nullptr;
-    const uint64_t total = compact_tables(w, b->mem_off.as<uint64_t>(), b->mems.as<pgx_mem>(), run_nums, pos_off, positions, n, tags, timed, s);
-    compact_fill(w, b->mem_off.as<uint64_t>(), b->mems.as<pgx_mem>(), run_nums, pos_off, positions, n, tags, timed, total, s);
-    w.h_bytes.ensure(total ? total : 8);
-    if (total) HIPCHECK(hipMemcpyAsync(w.h_bytes.p, w.bytes.p, total, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    std::memset(out, 0, sizeof *out);
-    out->n_reads = n;
-    out->n_mems = b->n_mems;
-    out->n_extensions = b->n_ext;
-    if (tags) {
-        out->n_positions = b->n_positions;
-        out->n_tag_overflow = b->n_tag_overflow;
-        out->flags = PGX_COMPACT_TAGS;
-    }
-    out->block_reads = PGX_COMPACT_BLOCK_READS;
-    out->n_blocks = nb;
-    out->n_bytes = total;
-    out->block_offsets = w.h_tab.as<uint64_t>();
-    out->block_first_mem = out->block_offsets + (nb + 1);
-    out->block_first_pos = out->block_first_mem + (nb + 1);
-    out->bytes = w.h_bytes.as<uint8_t>();
-    out->ms_encode = timed ? compact_ms(w) : 0;
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_compact_encode(int device, const pgx_result *in, uint8_t *bytes, uint64_t bytes_cap, uint64_t *block_offsets,
-                                         uint64_t *block_first_mem, uint64_t *block_first_pos, uint64_t *n_bytes) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_compact_encode");
-    use_device(device);
-    if (!in || !in->mem_offsets || (in->n_mems && !in->mems) || (bytes_cap && !bytes) || !block_offsets || !block_first_mem || !block_first_pos || !n_bytes)
-        throw Error(PGX_ERR_ARG, "pgx_compact_encode: null argument");
-    const bool tags = in->pos_offsets != nullptr;
-    const uint64_t n = in->n_reads, m = in->n_mems, np = tags ? in->n_positions : 0;
-    if (tags && ((m && !in->tag_run_counts) || (np && !in->positions))) throw Error(PGX_ERR_ARG, "pgx_compact_encode: pos_offsets without tag_run_counts / positions");
-    auto check_csr = [](const uint64_t *off, uint64_t cnt, uint64_t last, const char *name) { // the kernels index the arrays by these
-        bool ok = off[0] == 0 && off[cnt] == last;
-        for (uint64_t i = 0; ok && i < cnt; i++) ok = off[i] <= off[i + 1];
-        if (!ok) throw Error(PGX_ERR_ARG, std::string("pgx_compact_encode: ") + name + " must start at 0, never decrease and end at the count of what it indexes");
-    };
-    check_csr(in->mem_offsets, n, m, "mem_offsets");
-    if (tags) check_csr(in->pos_offsets, m, np, "pos_offsets");
-    struct Work { // device copies of the input + the encoder's buffers, released on every way out
-        DevBuf mem_off, mems, run_nums, pos_off, positions;
-        CompactWork w;
-        ~Work() {
-            DevBuf *all[] = {&mem_off, &mems, &run_nums, &pos_off, &positions};
-            for (DevBuf *d : all) d->release();
-            w.release();
-        }
-    } k;
-    upload(k.mem_off, in->mem_offsets, (n + 1) * 8);
-    upload(k.mems, in->mems, m * sizeof(pgx_mem));
-    if (tags) {
-        upload(k.run_nums, in->tag_run_counts, m * 8);
-        upload(k.pos_off, in->pos_offsets, (m + 1) * 8);
-        upload(k.positions, in->positions, np * 8);
-    }
-    hipStream_t s = nullptr;
-    const uint64_t nb = (n + PGX_COMPACT_BLOCK_READS - 1) / PGX_COMPACT_BLOCK_READS;
-    const uint64_t total = compact_tables(k.w, k.mem_off.as<uint64_t>(), k.mems.as<pgx_mem>(), k.run_nums.as<uint64_t>(), k.pos_off.as<uint64_t>(),
-                                          k.positions.as<uint64_t>(), n, tags, false, s);
-    *n_bytes = total;
-    const uint64_t *t = k.w.h_tab.as<uint64_t>();
-    std::memcpy(block_offsets, t, (nb + 1) * 8);
-    std::memcpy(block_first_mem, t + (nb + 1), (nb + 1) * 8);
-    std::memcpy(block_first_pos, t + 2 * (nb + 1), (nb + 1) * 8);
-    if (total > bytes_cap)
-        throw Error(PGX_ERR_NOMEM, "pgx_compact_encode: the stream takes " + std::to_string(total) + " bytes, bytes_cap is " + std::to_string(bytes_cap));
-    compact_fill(k.w, k.mem_off.as<uint64_t>(), k.mems.as<pgx_mem>(), k.run_nums.as<uint64_t>(), k.pos_off.as<uint64_t>(), k.positions.as<uint64_t>(), n, tags,
-                 false, total, s);
-    if (total) HIPCHECK(hipMemcpyAsync(bytes, k.w.bytes.p, total, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-// ------------------------------------------------------------------------------------------
-// text output (pgx_format_kernels.hip; the grammar: include/pgx.h "text output")
-struct FormatIn { // a result on the device, and what pgx_format_params adds
-    const uint64_t *mem_off, *pos_off, *positions, *loc_off, *values;
-    const pgx_mem *mems;
-    uint64_t n_reads, n_mems, n_positions, n_values, first_seq, max_length;
-    uint32_t flags;
-    bool locate() const { return (flags & (PGX_FORMAT_LOCATE_POSITIONS | PGX_FORMAT_LOCATE_SEQS)) != 0; }
-    PgxFormatArgs args() const { return PgxFormatArgs{mem_off, mems, pos_off, loc_off, n_reads, n_mems, first_seq, flags}; }
-    uint64_t value_divisor() const { return (flags & PGX_FORMAT_LOCATE_POSITIONS) ? max_length : 0; } // (0: the values print as they are)
-};
-
-// what both entry points refuse in a pgx_format_params, said with or without a device
-static void format_check_params(const pgx_format_params *p, const char *who) {
-    if (!p) throw Error(PGX_ERR_ARG, std::string(who) + ": null argument");
-    if (p->flags & ~(PGX_FORMAT_STDERR | PGX_FORMAT_LOCATE_POSITIONS | PGX_FORMAT_LOCATE_SEQS)) throw Error(PGX_ERR_ARG, std::string(who) + ": unknown flag");
-    if (p->reserved) throw Error(PGX_ERR_ARG, std::string(who) + ": reserved must be 0");
-    if ((p->flags & PGX_FORMAT_LOCATE_POSITIONS) && (p->flags & PGX_FORMAT_LOCATE_SEQS))
-        throw Error(PGX_ERR_ARG, std::string(who) + ": PGX_FORMAT_LOCATE_POSITIONS and PGX_FORMAT_LOCATE_SEQS exclude each other");
-}
-
-// The length pass: every level's lengths and scans, then read_offsets (and the total of the stderr lines behind them) to w.h_roff.  The host waits
-// here: the totals size the text buffers.
-static void format_lengths(FormatWork &w, const FormatIn &in, bool timed, hipStream_t s, uint64_t &n_bytes, uint64_t &n_err_bytes) {
-    const uint64_t n = in.n_reads, m = in.n_mems, np = in.n_positions, nv = in.locate() ? in.n_values : 0;
-    const bool err = (in.flags & PGX_FORMAT_STDERR) != 0;
-    w.plen.ensure(np ? np : 1); w.pcum.ensure((np + 1) * 8);
-    if (in.locate()) { w.vlen.ensure(nv ? nv : 1); w.vcum.ensure((nv + 1) * 8); }
-    w.mlen.ensure((m ? m : 1) * 8); w.mcum.ensure((m + 1) * 8);
-    w.rlen.ensure((n ? n : 1) * 8); w.roff.ensure((n + 1) * 8);
-    if (err) { w.elen.ensure(n ? n : 1); w.eoff.ensure((n + 1) * 8); }
-    HostBuf &h_roff = w.h_roff[w.cur];
-    h_roff.ensure((n + 2) * 8);
-    if (timed) {
-        for (auto &e : w.ev)
-            if (!e) HIPCHECK(hipEventCreate(&e));
-        HIPCHECK(hipEventRecord(w.ev[0], s));
-    }
-    if (np) hipLaunchKernelGGL(pgx_format_item_len_kernel, dim3(grid_for(np, 256)), dim3(256), 0, s, in.positions, np, (uint64_t)0, w.plen.as<uint8_t>());
-    scan_excl(4, w.plen.p, np, 0, w.pcum.as<uint64_t>(), w.scan_tmp, s);
-    if (in.locate()) {
-        if (nv) hipLaunchKernelGGL(pgx_format_item_len_kernel, dim3(grid_for(nv, 256)), dim3(256), 0, s, in.values, nv, in.value_divisor(), w.vlen.as<uint8_t>());
-        scan_excl(4, w.vlen.p, nv, 0, w.vcum.as<uint64_t>(), w.scan_tmp, s);
-    }
-    const uint64_t *vcum = in.locate() ? w.vcum.as<uint64_t>() : nullptr;
-    if (m) hipLaunchKernelGGL(pgx_format_mem_len_kernel, dim3(grid_for(m, 256)), dim3(256), 0, s, in.args(), (const uint64_t *)w.pcum.as<uint64_t>(), vcum, w.mlen.as<uint64_t>());
-    scan_excl(1, w.mlen.p, m, 0, w.mcum.as<uint64_t>(), w.scan_tmp, s);
-    if (n) hipLaunchKernelGGL(pgx_format_read_len_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, in.args(), (const uint64_t *)w.mcum.as<uint64_t>(), w.rlen.as<uint64_t>(),
-                              err ? w.elen.as<uint8_t>() : nullptr);
-    HIPCHECK(hipGetLastError());
-    scan_excl(1, w.rlen.p, n, 0, w.roff.as<uint64_t>(), w.scan_tmp, s);
-    if (err) scan_excl(4, w.elen.p, n, 0, w.eoff.as<uint64_t>(), w.scan_tmp, s);
-    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
-    uint64_t *h = h_roff.as<uint64_t>();
-    h[n + 1] = 0;
-    HIPCHECK(hipMemcpyAsync(h, w.roff.p, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (err) HIPCHECK(hipMemcpyAsync(h + n + 1, w.eoff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    n_bytes = h[n];
-    n_err_bytes = h[n + 1];
-}
-
-// The fill pass into w.text / w.etext (grown to the totals first); async on s.  Every byte of text[0 .. n_bytes) is written by exactly one lane.
-static void format_fill(FormatWork &w, const FormatIn &in, bool timed, hipStream_t s, uint64_t n_bytes, uint64_t n_err_bytes) {
-    const uint64_t n = in.n_reads, m = in.n_mems, np = in.n_positions, nv = in.locate() ? in.n_values : 0;
-    const bool err = (in.flags & PGX_FORMAT_STDERR) != 0;
-    w.text.ensure(n_bytes ? n_bytes : 8);
-    if (err) w.etext.ensure(n_err_bytes ? n_err_bytes : 8);
-    w.pbase.ensure((m ? m : 1) * 8);
-    if (in.locate()) w.vbase.ensure((m ? m : 1) * 8);
-    char *text = w.text.as<char>();
-    const uint64_t *roff = w.roff.as<uint64_t>(), *pcum = w.pcum.as<uint64_t>(), *vcum = in.locate() ? w.vcum.as<uint64_t>() : nullptr;
-    if (timed) HIPCHECK(hipEventRecord(w.ev[2], s));
-    if (n) hipLaunchKernelGGL(pgx_format_fill_reads_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, in.args(), roff, err ? (const uint64_t *)w.eoff.as<uint64_t>() : nullptr, text,
-                              err ? w.etext.as<char>() : nullptr);
-    if (m) hipLaunchKernelGGL(pgx_format_fill_mems_kernel, dim3(grid_for(m, 256)), dim3(256), 0, s, in.args(), roff, (const uint64_t *)w.mcum.as<uint64_t>(), pcum, vcum, text,
-                              w.pbase.as<uint64_t>(), in.locate() ? w.vbase.as<uint64_t>() : nullptr);
-    if (np) hipLaunchKernelGGL(pgx_format_fill_items_kernel, dim3(grid_for(np, 256)), dim3(256), 0, s, in.positions, np, in.pos_off, m, pcum, (const uint64_t *)w.pbase.as<uint64_t>(),
-                               (uint64_t)0, text);
-    if (nv) hipLaunchKernelGGL(pgx_format_fill_items_kernel, dim3(grid_for(nv, 256)), dim3(256), 0, s, in.values, nv, in.loc_off, m, vcum, (const uint64_t *)w.vbase.as<uint64_t>(),
-                               in.value_divisor(), text);
-    HIPCHECK(hipGetLastError());
-    if (timed) HIPCHECK(hipEventRecord(w.ev[3], s));
-}
-
-static float format_ms(FormatWork &w) { // (behind the synchronisation that follows format_fill)
-    float a = 0, c = 0;
-    HIPCHECK(hipEventElapsedTime(&a, w.ev[0], w.ev[1]));
-    HIPCHECK(hipEventElapsedTime(&c, w.ev[2], w.ev[3]));
-    return a + c;
-}
-
-extern "C" pgx_status pgx_batch_format(pgx_batch *b, const pgx_format_params *p, pgx_text *out) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_batch_format");
-    checked_device_count();
-    if (!b || !out) throw Error(PGX_ERR_ARG, "pgx_batch_format: null argument");
-    format_check_params(p, "pgx_batch_format");
-    if (!b->ran) throw Error(PGX_ERR_ARG, "pgx_batch_format: batch has not been run");
-    if (!b->ran_tags) throw Error(PGX_ERR_ARG, "pgx_batch_format: the run had no PGX_RUN_TAGS (the text holds the positions of every MEM)");
-    FormatIn in{};
-    in.flags = p->flags;
-    if (in.locate()) { // the last locate must be of the form the flag prints
-        const LocWork &lw = b->lw;
-        const uint32_t want = (p->flags & PGX_FORMAT_LOCATE_SEQS) ? (PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE) : 0u;
-        if (!lw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_format: a locate flag without a completed pgx_batch_locate");
-        if (lw.flags != want || lw.n_mems != b->n_mems)
-            throw Error(PGX_ERR_ARG, "pgx_batch_format: the last pgx_batch_locate ran with flags " + std::to_string(lw.flags) + ", the locate flag given prints the result of flags " +
-                                         std::to_string(want));
-        in.loc_off = lw.d_off;
-        in.values = lw.vals.as<uint64_t>();
-        in.n_values = lw.n_values;
-    }
-    use_device(b->device);
-    FormatWork &w = b->fw;
-    hipStream_t s = b->own; // (the run and the locate completed inside their calls, on whatever stream they used)
-    const bool timed = b->timed, err = (p->flags & PGX_FORMAT_STDERR) != 0;
-    in.mem_off = b->mem_off.as<uint64_t>();
-    in.mems = b->mems.as<pgx_mem>();
-    in.pos_off = b->tw.pos_off.as<uint64_t>();
-    in.positions = b->tw.positions.as<uint64_t>();
-    in.n_reads = b->n_reads; in.n_mems = b->n_mems; in.n_positions = b->n_positions;
-    in.first_seq = p->first_seq;
-    in.max_length = p->max_length ? p->max_length : b->h->meta.max_length ? b->h->meta.max_length : 1;
-    uint64_t n_bytes = 0, n_err = 0;
-    w.cur ^= 1; // (the set of the call before stays as it is)
-    HostBuf &h_text = w.h_text[w.cur], &h_etext = w.h_etext[w.cur];
-    format_lengths(w, in, timed, s, n_bytes, n_err);
-    format_fill(w, in, timed, s, n_bytes, n_err);
-    h_text.ensure(n_bytes ? n_bytes : 8);
-    if (n_bytes) HIPCHECK(hipMemcpyAsync(h_text.p, w.text.p, n_bytes, hipMemcpyDeviceToHost, s));
-    if (err) {
-        h_etext.ensure(n_err ? n_err : 8);
-        if (n_err) HIPCHECK(hipMemcpyAsync(h_etext.p, w.etext.p, n_err, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHECK(hipStreamSynchronize(s));
-    std::memset(out, 0, sizeof *out);
-    out->n_reads = in.n_reads;
-    out->n_bytes = n_bytes;
-    out->n_err_bytes = n_err;
-    out->read_offsets = w.h_roff[w.cur].as<uint64_t>();
-    out->text = h_text.as<char>();
-    out->err_text = err ? h_etext.as<char>() : nullptr;
-    out->ms_format = timed ? format_ms(w) : 0;
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_format_result(int device, const pgx_result *in_, const pgx_locations *loc, const pgx_format_params *p, char *text, uint64_t text_cap,
-                                        uint64_t *read_offsets, uint64_t *n_bytes, char *err_text, uint64_t err_cap, uint64_t *n_err_bytes) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_format_result");
-    // everything the arguments alone decide comes first: said with or without a device
-    format_check_params(p, "pgx_format_result");
-    const bool err = (p->flags & PGX_FORMAT_STDERR) != 0, locate = (p->flags & (PGX_FORMAT_LOCATE_POSITIONS | PGX_FORMAT_LOCATE_SEQS)) != 0;
-    if (!in_ || !in_->mem_offsets || (in_->n_mems && !in_->mems) || !in_->pos_offsets || (in_->n_positions && !in_->positions) || (text_cap && !text) || !read_offsets ||
-        !n_bytes || !n_err_bytes || (err && err_cap && !err_text))
-        throw Error(PGX_ERR_ARG, "pgx_format_result: null argument (pos_offsets included: the text holds the positions of every MEM)");
-    const uint64_t n = in_->n_reads, m = in_->n_mems, np = in_->n_positions;
-    if (locate && (!loc || !loc->loc_offsets || (loc->n_values && !loc->values))) throw Error(PGX_ERR_ARG, "pgx_format_result: a locate flag without loc");
-    if (locate && loc->n_mems != m) throw Error(PGX_ERR_ARG, "pgx_format_result: loc->n_mems differs from in->n_mems");
-    if ((p->flags & PGX_FORMAT_LOCATE_POSITIONS) && !p->max_length) throw Error(PGX_ERR_ARG, "pgx_format_result: PGX_FORMAT_LOCATE_POSITIONS needs max_length");
-    auto check_csr = [](const uint64_t *off, uint64_t cnt, uint64_t last, const char *name) { // the kernels index the arrays by these
-        bool ok = off[0] == 0 && off[cnt] == last;
-        for (uint64_t i = 0; ok && i < cnt; i++) ok = off[i] <= off[i + 1];
-        if (!ok) throw Error(PGX_ERR_ARG, std::string("pgx_format_result: ") + name + " must start at 0, never decrease and end at the count of what it indexes");
-    };
-    check_csr(in_->mem_offsets, n, m, "mem_offsets");
-    check_csr(in_->pos_offsets, m, np, "pos_offsets");
-    if (locate) check_csr(loc->loc_offsets, m, loc->n_values, "loc_offsets");
-    *n_bytes = *n_err_bytes = 0;
-    use_device(device);
-    struct Work { // device copies of the input + the formatter's buffers, released on every way out
-        DevBuf mem_off, mems, pos_off, positions, loc_off, values;
-        FormatWork w;
-        ~Work() {
-            DevBuf *all[] = {&mem_off, &mems, &pos_off, &positions, &loc_off, &values};
-            for (DevBuf *d : all) d->release();
-            w.release();
-        }
-    } k;
-    upload(k.mem_off, in_->mem_offsets, (n + 1) * 8);
-    upload(k.mems, in_->mems, m * sizeof(pgx_mem));
-    upload(k.pos_off, in_->pos_offsets, (m + 1) * 8);
-    upload(k.positions, in_->positions, np * 8);
-    FormatIn in{};
-    in.flags = p->flags;
-    if (locate) {
-        upload(k.loc_off, loc->loc_offsets, (m + 1) * 8);
-        upload(k.values, loc->values, loc->n_values * 8);
-        in.loc_off = k.loc_off.as<uint64_t>();
-        in.values = k.values.as<uint64_t>();
-        in.n_values = loc->n_values;
-    }
-    in.mem_off = k.mem_off.as<uint64_t>();
-    in.mems = k.mems.as<pgx_mem>();
-    in.pos_off = k.pos_off.as<uint64_t>();
-    in.positions = k.positions.as<uint64_t>();
-    in.n_reads = n; in.n_mems = m; in.n_positions = np;
-    in.first_seq = p->first_seq;
-    in.max_length = p->max_length;
-    hipStream_t s = nullptr;
-    uint64_t total = 0, total_err = 0;
-    format_lengths(k.w, in, false, s, total, total_err);
-    *n_bytes = total;
-    *n_err_bytes = total_err;
-    std::memcpy(read_offsets, k.w.h_roff[k.w.cur].as<uint64_t>(), (n + 1) * 8);
-    if (total > text_cap) throw Error(PGX_ERR_NOMEM, "pgx_format_result: the text takes " + std::to_string(total) + " bytes, text_cap is " + std::to_string(text_cap));
-    if (err && total_err > err_cap)
-        throw Error(PGX_ERR_NOMEM, "pgx_format_result: the stderr lines take " + std::to_string(total_err) + " bytes, err_cap is " + std::to_string(err_cap));
-    format_fill(k.w, in, false, s, total, total_err);
-    if (total) HIPCHECK(hipMemcpyAsync(text, k.w.text.p, total, hipMemcpyDeviceToHost, s));
-    if (err && total_err) HIPCHECK(hipMemcpyAsync(err_text, k.w.etext.p, total_err, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-// ------------------------------------------------------------------------------------------
-// pgx_batch_locate (pgx_mem_locate_kernels.hip): the occurrences of the last run's MEMs, on the device
-// values one pass of the intermediate buffer may hold: PGX_LOCATE_BUDGET_MB (fractions allowed), default a quarter of free device memory
-static uint64_t locate_budget_values() {
-    uint64_t bytes = 0;
-    if (const char *e = std::getenv("PGX_LOCATE_BUDGET_MB")) {
-        const double mb = std::strtod(e, nullptr);
-        if (mb > 0) bytes = (uint64_t)(mb * 1048576.0);
-    }
-    if (!bytes) {
-        size_t mem_free = 0, mem_total = 0;
-        if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); mem_free = 1ull << 30; }
-        bytes = mem_free / 4;
-    }
-    return std::max<uint64_t>(bytes / 8, 1);
-}
-
-// PGX_LOCATE_SETS=0 (read per call): PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE by the segmented sort even where the sequence sets would serve it
-static bool locate_sets_enabled() {
-    const char *e = std::getenv("PGX_LOCATE_SETS");
-    return !(e && e[0] == '0' && e[1] == 0);
-}
-
-extern "C" pgx_status pgx_batch_locate(pgx_batch *b, uint32_t flags, uint64_t max_occ, void *stream) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_batch_locate");
-    if ((flags & PGX_LOCATE_SEQ_SETS) && (flags & (PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE))) // (a contradiction in the call itself: said with or without a device)
-        throw Error(PGX_ERR_ARG, "pgx_batch_locate: PGX_LOCATE_SEQ_SETS goes with PGX_LOCATE_CHAINS alone");
-    checked_device_count();
-    if (!b) throw Error(PGX_ERR_ARG, "pgx_batch_locate: null batch");
-    if (flags & ~(PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE | PGX_LOCATE_CHAINS | PGX_LOCATE_SEQ_SETS)) throw Error(PGX_ERR_ARG, "pgx_batch_locate: unknown flag");
-    if (!b->ran) throw Error(PGX_ERR_ARG, "pgx_batch_locate: batch has not been run");
-    LocWork &w = b->lw;
-    w.valid = false;
-    locate_check_supported(b->h, "pgx_batch_locate");
-    use_device(b->device);
-    pgx_device_image *d = locate_image(b->h, b->device);
-    hipStream_t s = stream ? (hipStream_t)stream : b->own;
-    const uint64_t n = b->n_mems, bwt_n = d->loc.n;
-    const bool sets_form = (flags & PGX_LOCATE_SEQ_SETS) != 0;
-    const bool seq_ids = sets_form || (flags & PGX_LOCATE_SEQ_IDS) != 0, uniq = (flags & PGX_LOCATE_UNIQUE) != 0;
-    // sequence sets: the result itself (PGX_LOCATE_SEQ_SETS), or what the sorted unique sequence ids are expanded from (routed) in place of the sort
-    const uint64_t n_seq = b->h->meta.n_sequences();
-    const uint64_t W = (n_seq + 63) / 64;
-    const bool sets_fit = W >= 1 && W <= PGX_ML_SET_WORDS_MAX;
-    if (sets_form && !sets_fit)
-        throw Error(PGX_ERR_UNSUPPORTED, "pgx_batch_locate: PGX_LOCATE_SEQ_SETS serves at most " + std::to_string(64 * PGX_ML_SET_WORDS_MAX) + " sequences, the index has " +
-                                             std::to_string(n_seq));
-    const bool routed = !sets_form && seq_ids && uniq && sets_fit && locate_sets_enabled();
-    const bool build_sets = sets_form || routed, sort_uniq = uniq && !routed;
-    // the resident suffix array: the LCE image in text coordinates and its sequence starts (built from this very locate image's chains)
-    const bool resident = !(flags & PGX_LOCATE_CHAINS) && d->lce_state == 1 && d->img.lce_sa && d->lce_seq_start.p && d->lce_n_seq && d->img.n == bwt_n;
-    const bool timed = b->timed;
-    if (timed) {
-        for (auto &e : w.ev)
-            if (!e) HIPCHECK(hipEventCreate(&e));
-        HIPCHECK(hipEventRecord(w.ev[0], s));
-    }
-    // 1. plan: counts (cap, range checks), ranges, not-located total; value offsets
-    //    ctr: [0] wave list [1] workgroup list [2] scratch total [3] unique values of a pass [4] not located [5] values [6..7] cut
-    w.cnt.ensure((n ? n : 1) * 8); w.qs.ensure((n ? n : 1) * 8); w.qe.ensure((n ? n : 1) * 8); w.voff.ensure((n + 1) * 8); w.ctr.ensure(64);
-    unsigned long long *ctr = w.ctr.as<unsigned long long>();
-    HIPCHECK(hipMemsetAsync(w.ctr.p, 0, 64, s));
-    if (n) {
-        hipLaunchKernelGGL(pgx_ml_plan_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const pgx_mem *)b->mems.as<pgx_mem>(), n, bwt_n, max_occ,
-                           w.cnt.as<uint64_t>(), w.qs.as<uint64_t>(), w.qe.as<uint64_t>(), ctr + 4);
-        HIPCHECK(hipGetLastError());
-    }
-    scan_excl(1, w.cnt.p, n, 0, w.voff.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 5));
-    uint64_t tot[2];
-    read_scalars(tot, ctr + 4, 16, s);
-    const uint64_t n_not = tot[0], V = tot[1];
-    const uint64_t *voff = w.voff.as<uint64_t>();
-    // 2. passes over consecutive MEMs whose values fit the budget (one pass unless the batch exceeds it)
-    const uint64_t budget = locate_budget_values();
-    if (sets_form) { // the result: n x W words, cleared once; loc_offsets[m] = m * W
-        w.vals.ensure((n ? n * W : 1) * 8); w.uoff.ensure((n + 1) * 8);
-        if (n) HIPCHECK(hipMemsetAsync(w.vals.p, 0, n * W * 8, s));
-        hipLaunchKernelGGL(pgx_ml_stride_kernel, dim3(grid_for(n + 1, 256)), dim3(256), 0, s, w.uoff.as<uint64_t>(), n + 1, W);
-        HIPCHECK(hipGetLastError());
-    } else if (!uniq) w.vals.ensure((V ? V : 1) * 8); // (the values are written in place: no intermediate buffer)
-    else { w.ucount.ensure((n ? n : 1) * 8); w.uoff.ensure((n + 1) * 8); }
-    // the values of a pass need a buffer unless they are written in place or go straight from the resident suffix array into the sets
-    const bool value_buffer = sort_uniq || (build_sets && !resident);
-    const uint64_t set_mems = std::max<uint64_t>(budget / (W ? W : 1), 1); // MEMs whose sets fit the budget (routed: the set array is intermediate too)
-    uint64_t U = 0; // unique values of the passes so far
-    for (uint64_t m0 = 0, o0 = 0; m0 < n;) {
-        uint64_t m1 = n, o1 = V;
-        const bool by_values = !(build_sets && resident) && V - o0 > budget;
-        const uint64_t m_lim = routed && n - m0 > set_mems ? m0 + set_mems : n;
-        if (by_values || m_lim < n) {
-            hipLaunchKernelGGL(pgx_ml_cut_kernel, dim3(1), dim3(64), 0, s, voff, m_lim, m0, by_values ? budget : V, reinterpret_cast<uint64_t *>(ctr + 6));
-            HIPCHECK(hipGetLastError());
-            uint64_t c[2];
-            read_scalars(c, ctr + 6, 16, s);
-            m1 = c[0]; o1 = c[1];
-        }
-        const uint64_t np = m1 - m0, nv = o1 - o0;
-        if (value_buffer) w.gbuf.ensure((nv ? nv : 1) * 8);
-        uint64_t *dst = value_buffer ? w.gbuf.as<uint64_t>() : w.vals.as<uint64_t>() + o0; // value o of the batch goes to dst[o - o0]
-        unsigned long long *sets = nullptr; // the pass's sets: MEM m at sets[(m - m0) * W ..)
-        if (sets_form) sets = w.vals.as<unsigned long long>() + m0 * W;
-        else if (routed) {
-            w.sets.ensure(np * W * 8);
-            sets = w.sets.as<unsigned long long>();
-            HIPCHECK(hipMemsetAsync(sets, 0, np * W * 8, s));
-        }
-        if (nv && resident && build_sets) {
-            hipLaunchKernelGGL(pgx_ml_sets_kernel, dim3(grid_for(nv, PGX_ML_SPAN)), dim3(256), 0, s, (const pgx_mem *)b->mems.as<pgx_mem>(), voff, m0, m1, o0, nv,
-                               (const uint32_t *)d->img.lce_sa, bwt_n, (const uint64_t *)d->lce_seq_start.as<uint64_t>(), d->lce_n_seq, (uint32_t)W, sets);
-            HIPCHECK(hipGetLastError());
-        } else if (nv && resident) {
-            hipLaunchKernelGGL(pgx_ml_gather_kernel, dim3(grid_for(nv, PGX_ML_SPAN)), dim3(256), 0, s, (const pgx_mem *)b->mems.as<pgx_mem>(), voff, m0, m1, o0, nv,
-                               (const uint32_t *)d->img.lce_sa, bwt_n, (const uint64_t *)d->lce_seq_start.as<uint64_t>(), d->lce_n_seq, d->loc.max_length,
-                               seq_ids ? 1 : 0, dst);
-            HIPCHECK(hipGetLastError());
-        } else if (nv) { // the sample chains of pgx_locate_batch, from the device ranges
-            w.run0.ensure(np * 8); w.npieces.ensure(np * 8); w.poff.ensure((np + 1) * 8);
-            const uint64_t *qs = w.qs.as<uint64_t>() + m0, *qe = w.qe.as<uint64_t>() + m0;
-            hipLaunchKernelGGL(pgx_locate_plan_kernel, dim3(grid_for(np, 256)), dim3(256), 0, s, d->loc, qs, qe, np, w.run0.as<uint64_t>(), w.npieces.as<uint64_t>());
-            HIPCHECK(hipGetLastError());
-            scan_excl(1, w.npieces.p, np, 0, w.poff.as<uint64_t>(), w.scan_tmp, s);
-            const uint64_t n_pieces = read_u64(w.poff.as<uint64_t>() + np, s);
-            if (n_pieces) {
-                hipLaunchKernelGGL(pgx_locate_walk_kernel, dim3(grid_for(n_pieces, 256)), dim3(256), 0, s, d->loc, qs, qe, np, (const uint64_t *)w.run0.as<uint64_t>(),
-                                   (const uint64_t *)w.poff.as<uint64_t>(), n_pieces, voff + m0, o0, seq_ids ? 1 : 0, dst);
-                HIPCHECK(hipGetLastError());
-                if (build_sets) { // the pass's sequence ids -> bits
-                    hipLaunchKernelGGL(pgx_ml_sets_ids_kernel, dim3(grid_for(nv, PGX_ML_SPAN)), dim3(256), 0, s, voff, m0, m1, o0, nv, (const uint64_t *)dst, (uint32_t)W,
-                                       sets);
-                    HIPCHECK(hipGetLastError());
-                }
-            }
-        }
-        if (routed) { // the sets as ascending ids behind the passes before: sorted and unique by construction
-            uint32_t Wp = 1;
-            while (Wp < W) Wp <<= 1;
-            uint64_t *ucount = w.ucount.as<uint64_t>() + m0;
-            w.uloc.ensure((np + 1) * 8);
-            hipLaunchKernelGGL(pgx_ml_set_count_kernel, dim3(grid_for(np * Wp, 256)), dim3(256), 0, s, (const unsigned long long *)sets, np, (uint32_t)W, Wp, ucount);
-            HIPCHECK(hipGetLastError());
-            scan_excl(1, ucount, np, 0, w.uloc.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 3));
-            const uint64_t Up = read_u64(reinterpret_cast<const uint64_t *>(ctr + 3), s);
-            w.vals.ensure_keep((U + Up ? U + Up : 1) * 8, U * 8); // (the stream is idle here: the read-back above synchronised it)
-            if (Up) {
-                hipLaunchKernelGGL(pgx_ml_set_expand_kernel, dim3(grid_for(np, 4)), dim3(256), 0, s, (const unsigned long long *)sets, np, (uint32_t)W,
-                                   (const uint64_t *)w.uloc.as<uint64_t>(), w.vals.as<uint64_t>() + U);
-                HIPCHECK(hipGetLastError());
-            }
-            U += Up;
-        }
-        if (sort_uniq) { // segmented sort-unique with the tag stage's kernels, size-class lists built on the device, then compaction behind the passes before
-            w.seg.ensure((np + 1) * 8); w.lists.ensure(2 * np * 8); w.need.ensure(np * 8); w.soff.ensure((np + 1) * 8); w.uloc.ensure((np + 1) * 8);
-            uint64_t *seg = w.seg.as<uint64_t>(), *wave_list = w.lists.as<uint64_t>(), *wg_list = wave_list + np, *ucount = w.ucount.as<uint64_t>() + m0;
-            const uint64_t *cnt = w.cnt.as<uint64_t>() + m0;
-            HIPCHECK(hipMemsetAsync(w.ctr.p, 0, 32, s));
-            hipLaunchKernelGGL(pgx_ml_classify_kernel, dim3(grid_for(np + 1, 256)), dim3(256), 0, s, cnt, voff + m0, np, seg, wave_list, wg_list,
-                               w.need.as<uint64_t>(), ucount, ctr);
-            HIPCHECK(hipGetLastError());
-            scan_excl(1, w.need.p, np, 0, w.soff.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 2));
-            uint64_t c[3];
-            read_scalars(c, ctr, 24, s);
-            const uint64_t n_wave = c[0], n_wg = c[1], S = c[2];
-            if (n_wave)
-                hipLaunchKernelGGL(pgx_tag_sort_unique_kernel<PgxTagDense>, dim3(grid_for(n_wave, 4)), dim3(256), 0, s, PgxTagDense{wave_list, cnt, seg}, n_wave,
-                                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, w.gbuf.as<uint64_t>(), ucount);
-            if (n_wg) {
-                w.scratch.ensure((S ? S : 1) * 8);
-                HIPCHECK(hipFuncSetAttribute((const void *)pgx_tag_sort_large_kernel<PgxTagDense>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PGX_SORT_WG_LDS_CAP * 8)));
-                hipLaunchKernelGGL(pgx_tag_sort_large_kernel<PgxTagDense>, dim3(grid_for(n_wg, 1)), dim3(1024), (size_t)PGX_SORT_WG_LDS_CAP * 8, s, PgxTagDense{wg_list, cnt, seg},
-                                   n_wg, (const uint64_t *)nullptr, (const uint64_t *)nullptr, w.gbuf.as<uint64_t>(), w.scratch.as<uint64_t>(),
-                                   (const uint64_t *)w.soff.as<uint64_t>(), ucount);
-            }
-            HIPCHECK(hipGetLastError());
-            scan_excl(1, ucount, np, 0, w.uloc.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 3));
-            const uint64_t Up = read_u64(reinterpret_cast<const uint64_t *>(ctr + 3), s);
-            w.vals.ensure_keep((U + Up ? U + Up : 1) * 8, U * 8); // (the stream is idle here: the read-back above synchronised it)
-            if (Up) {
-                hipLaunchKernelGGL(pgx_tag_compact_kernel<PgxTagDense>, dim3(grid_for(np, 16)), dim3(256), 0, s, PgxTagDense{nullptr, nullptr, seg}, np,
-                                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, (const uint64_t *)ucount, (const uint64_t *)w.gbuf.as<uint64_t>(),
-                                   (const uint64_t *)w.uloc.as<uint64_t>(), w.vals.as<uint64_t>() + U, ~0ull);
-                HIPCHECK(hipGetLastError());
-            }
-            U += Up;
-        }
-        m0 = m1; o0 = o1;
-    }
-    if (uniq) scan_excl(1, w.ucount.p, n, 0, w.uoff.as<uint64_t>(), w.scan_tmp, s);
-    w.vals.ensure(8);
-    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
-    HIPCHECK(hipStreamSynchronize(s));
-    w.ms = 0;
-    if (timed) HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
-    w.d_off = uniq || sets_form ? w.uoff.as<uint64_t>() : voff;
-    w.n_mems = n;
-    w.n_values = sets_form ? n * W : uniq ? U : V;
-    w.n_not_located = n_not;
-    w.flags = flags & (PGX_LOCATE_SEQ_IDS | PGX_LOCATE_UNIQUE | PGX_LOCATE_SEQ_SETS);
-    w.set_words = build_sets ? (uint32_t)W : 0;
-    w.resident = resident;
-    w.valid = true;
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-static void locations_header(const pgx_batch *b, pgx_locations *out) {
-    const LocWork &w = b->lw;
-    std::memset(out, 0, sizeof *out);
-    out->n_mems = w.n_mems;
-    out->n_values = w.n_values;
-    out->n_not_located = w.n_not_located;
-    out->flags = w.flags;
-    out->resident = w.resident ? 1u : 0u;
-    out->ms_locate = w.ms;
-    out->set_words = w.set_words;
-}
-
-extern "C" pgx_status pgx_batch_device_locations(pgx_batch *b, pgx_locations *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->lw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_locations: batch has no locate result");
-    locations_header(b, out);
-    out->loc_offsets = b->lw.d_off;
-    out->values = b->lw.vals.as<uint64_t>();
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_batch_locations(pgx_batch *b, pgx_locations *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->lw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_locations: batch has no locate result");
-    use_device(b->device);
-    LocWork &w = b->lw;
-    w.h_off.ensure((w.n_mems + 1) * 8);
-    w.h_vals.ensure((w.n_values ? w.n_values : 1) * 8);
-    HIPCHECK(hipMemcpyAsync(w.h_off.p, w.d_off, (w.n_mems + 1) * 8, hipMemcpyDeviceToHost, b->own));
-    if (w.n_values) HIPCHECK(hipMemcpyAsync(w.h_vals.p, w.vals.p, w.n_values * 8, hipMemcpyDeviceToHost, b->own));
-    HIPCHECK(hipStreamSynchronize(b->own)); // (the locate itself completed inside pgx_batch_locate, on whatever stream it used)
-    locations_header(b, out);
-    out->loc_offsets = w.h_off.as<uint64_t>();
-    out->values = w.h_vals.as<uint64_t>();
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-// ------------------------------------------------------------------------------------------
-// read hits (pgx_hits_kernels.hip; the definitions: include/pgx.h "read hits")
-static const uint32_t HITS_FLAGS = PGX_HITS_BEST_SETS | PGX_HITS_SCORES;
-
-// log2 of the lanes a read takes (Sp: the power of two >= n_seq, 64 with more than one word column); refuses what one launch cannot hold
-static uint32_t hits_lane_shift(uint64_t n_reads, uint64_t n_seq, uint32_t W, const char *who) {
-    uint32_t sp_shift = 0;
-    while (W == 1 && (1ull << sp_shift) < n_seq) sp_shift++;
-    if (W > 1) sp_shift = 6;
-    // (a grid holds fewer than 2^32 threads: a larger launch would lose reads without an error)
-    if (n_reads > (((1ull << 32) - PGX_HITS_THREADS) >> sp_shift))
-        throw Error(PGX_ERR_UNSUPPORTED, std::string(who) + ": " + std::to_string(n_reads) + " reads at " + std::to_string(1u << sp_shift) +
-                                             " lanes a read exceed the 2^32 threads of one launch: score the reads in smaller batches");
-    return sp_shift;
-}
-
-// the one launch: sizes the outputs the flags ask for and enqueues the kernel on s (sets: n_mems x W words on the device)
-static void hits_launch(HitsWork &w, const uint64_t *mem_off, const pgx_mem *mems, const uint64_t *sets, uint64_t n_reads, uint64_t n_mems, uint64_t n_seq, uint32_t W,
-                        uint32_t flags, hipStream_t s) {
-    const uint32_t sp_shift = hits_lane_shift(n_reads, n_seq, W, "read hits");
-    w.hits.ensure((n_reads ? n_reads : 1) * sizeof(pgx_read_hit));
-    if (flags & PGX_HITS_BEST_SETS) w.best_sets.ensure((n_reads ? n_reads * W : 1) * 8);
-    if (flags & PGX_HITS_SCORES) w.scores.ensure((n_reads ? n_reads * n_seq : 1) * 4);
-    if (!n_reads) return;
-    unsigned long long *best = (flags & PGX_HITS_BEST_SETS) ? w.best_sets.as<unsigned long long>() : nullptr;
-    uint32_t *scores = (flags & PGX_HITS_SCORES) ? w.scores.as<uint32_t>() : nullptr;
-    const unsigned long long *dsets = reinterpret_cast<const unsigned long long *>(sets);
-    if (W == 1) { // Sp lanes a read
-        hipLaunchKernelGGL(pgx_read_hits_kernel, dim3(grid_for(n_reads, PGX_HITS_THREADS >> sp_shift)), dim3(PGX_HITS_THREADS), 0, s, mem_off, mems, dsets, n_reads, n_mems,
-                           n_seq, sp_shift, flags, w.hits.as<pgx_read_hit>(), best, scores);
-    } else // a wave a read
-        hipLaunchKernelGGL(pgx_read_hits_wide_kernel, dim3(grid_for(n_reads, PGX_HITS_THREADS / 64)), dim3(PGX_HITS_THREADS), 0, s, mem_off, mems, dsets, n_reads, n_mems,
-                           n_seq, W, flags, w.hits.as<pgx_read_hit>(), best, scores);
-    HIPCHECK(hipGetLastError());
-}
-
-extern "C" pgx_status pgx_batch_read_hits(pgx_batch *b, uint32_t flags, void *stream) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_batch_read_hits");
-    checked_device_count();
-    if (!b) throw Error(PGX_ERR_ARG, "pgx_batch_read_hits: null batch");
-    HitsWork &w = b->hw;
-    w.valid = false;
-    if (flags & ~HITS_FLAGS) throw Error(PGX_ERR_ARG, "pgx_batch_read_hits: unknown flag");
-    if (!b->ran) throw Error(PGX_ERR_ARG, "pgx_batch_read_hits: batch has not been run");
-    const LocWork &lw = b->lw;
-    if (!lw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_read_hits: needs a completed pgx_batch_locate(PGX_LOCATE_SEQ_SETS), the batch has no locate result");
-    if (lw.flags != PGX_LOCATE_SEQ_SETS || lw.n_mems != b->n_mems || !lw.set_words)
-        throw Error(PGX_ERR_ARG, "pgx_batch_read_hits: needs a completed pgx_batch_locate(PGX_LOCATE_SEQ_SETS), the last pgx_batch_locate ran with flags " +
-                                     std::to_string(lw.flags));
-    use_device(b->device);
-    hipStream_t s = stream ? (hipStream_t)stream : b->own;
-    const uint64_t n = b->n_reads, n_seq = b->h->meta.n_sequences();
-    const uint32_t W = lw.set_words;
-    (void)hits_lane_shift(n, n_seq, W, "pgx_batch_read_hits");
-    if (flags & PGX_HITS_SCORES) {
-        size_t mem_free = 0, mem_total = 0;
-        if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); mem_free = 1ull << 30; }
-        const uint64_t need = n * n_seq * 4;
-        if (need > mem_free / 4)
-            throw Error(PGX_ERR_NOMEM, "pgx_batch_read_hits: PGX_HITS_SCORES takes " + std::to_string(need) + " bytes, a quarter of the free device memory is " +
-                                           std::to_string(mem_free / 4));
-    }
-    const bool timed = b->timed;
-    if (timed) {
-        for (auto &e : w.ev)
-            if (!e) HIPCHECK(hipEventCreate(&e));
-        HIPCHECK(hipEventRecord(w.ev[0], s));
-    }
-    hits_launch(w, b->mem_off.as<uint64_t>(), b->mems.as<pgx_mem>(), lw.vals.as<uint64_t>(), n, b->n_mems, n_seq, W, flags, s);
-    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
-    HIPCHECK(hipStreamSynchronize(s));
-    w.ms = 0;
-    if (timed) HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
-    w.flags = flags;
-    w.set_words = W;
-    w.n_reads = n;
-    w.n_seq = n_seq;
-    w.valid = true;
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-static void hits_header(const pgx_batch *b, pgx_read_hits *out) {
-    const HitsWork &w = b->hw;
-    std::memset(out, 0, sizeof *out);
-    out->n_reads = w.n_reads;
-    out->n_seq = w.n_seq;
-    out->set_words = w.set_words;
-    out->flags = w.flags;
-    out->ms_hits = w.ms;
-}
-
-extern "C" pgx_status pgx_batch_device_hits(pgx_batch *b, pgx_read_hits *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->hw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_hits: batch has no hits result");
-    const HitsWork &w = b->hw;
-    hits_header(b, out);
-    out->hits = w.hits.as<pgx_read_hit>();
-    out->best_sets = (w.flags & PGX_HITS_BEST_SETS) ? w.best_sets.as<uint64_t>() : nullptr;
-    out->scores = (w.flags & PGX_HITS_SCORES) ? w.scores.as<uint32_t>() : nullptr;
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_batch_hits(pgx_batch *b, pgx_read_hits *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->hw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_hits: batch has no hits result");
-    use_device(b->device);
-    HitsWork &w = b->hw;
-    const uint64_t n = w.n_reads;
-    const bool best = (w.flags & PGX_HITS_BEST_SETS) != 0, scores = (w.flags & PGX_HITS_SCORES) != 0;
-    w.h_hits.ensure((n ? n : 1) * sizeof(pgx_read_hit));
-    if (n) HIPCHECK(hipMemcpyAsync(w.h_hits.p, w.hits.p, n * sizeof(pgx_read_hit), hipMemcpyDeviceToHost, b->own));
-    if (best) {
-        w.h_best_sets.ensure((n ? n * w.set_words : 1) * 8);
-        if (n) HIPCHECK(hipMemcpyAsync(w.h_best_sets.p, w.best_sets.p, n * w.set_words * 8, hipMemcpyDeviceToHost, b->own));
-    }
-    if (scores) {
-        w.h_scores.ensure((n ? n * w.n_seq : 1) * 4);
-        if (n) HIPCHECK(hipMemcpyAsync(w.h_scores.p, w.scores.p, n * w.n_seq * 4, hipMemcpyDeviceToHost, b->own));
-    }
-    HIPCHECK(hipStreamSynchronize(b->own)); // (the kernel completed inside pgx_batch_read_hits, on whatever stream it used)
-    hits_header(b, out);
-    out->hits = w.h_hits.as<pgx_read_hit>();
-    out->best_sets = best ? w.h_best_sets.as<uint64_t>() : nullptr;
-    out->scores = scores ? w.h_scores.as<uint32_t>() : nullptr;
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_read_hits_arrays(int device, const uint64_t *mem_offsets, uint64_t n_reads, const pgx_mem *mems, const uint64_t *sets, uint32_t set_words,
-                                           uint64_t n_seq, uint32_t flags, pgx_read_hit *hits, uint64_t *best_sets, uint32_t *scores) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_read_hits_arrays");
-    checked_device_count();
-    if (flags & ~HITS_FLAGS) throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: unknown flag");
-    if (set_words < 1 || set_words > PGX_ML_SET_WORDS_MAX || n_seq == 0 || (n_seq + 63) / 64 != set_words)
-        throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: set_words must be ceil(n_seq / 64) and 1 .. " + std::to_string(PGX_ML_SET_WORDS_MAX) + ", got set_words " +
-                                     std::to_string(set_words) + " for n_seq " + std::to_string(n_seq));
-    if (!mem_offsets || (n_reads && !hits) || ((flags & PGX_HITS_BEST_SETS) && n_reads && !best_sets) || ((flags & PGX_HITS_SCORES) && n_reads && !scores))
-        throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: null argument");
-    (void)hits_lane_shift(n_reads, n_seq, set_words, "pgx_read_hits_arrays"); // (before the arrays are read)
-    bool ok = mem_offsets[0] == 0;
-    for (uint64_t i = 0; ok && i < n_reads; i++) ok = mem_offsets[i] <= mem_offsets[i + 1];
-    if (!ok) throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: mem_offsets must start at 0 and never decrease");
-    const uint64_t m = mem_offsets[n_reads];
-    if (m && (!mems || !sets)) throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: null argument");
-    use_device(device);
-    struct Work { // device copies of the input + the stage's buffers, released on every way out
-        DevBuf mem_off, mems, sets;
-        HitsWork w;
-        ~Work() {
-            DevBuf *all[] = {&mem_off, &mems, &sets};
-            for (DevBuf *d : all) d->release();
-            w.release();
-        }
-    } k;
-    upload(k.mem_off, mem_offsets, (n_reads + 1) * 8);
-    upload(k.mems, mems, m * sizeof(pgx_mem));
-    upload(k.sets, sets, m * set_words * 8);
-    hipStream_t s = nullptr;
-    if (n_reads) { // the precondition, before anything is written
-        k.w.bad.ensure(8);
-        HIPCHECK(hipMemsetAsync(k.w.bad.p, 0xFF, 8, s));
-        hipLaunchKernelGGL(pgx_read_hits_check_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, s, (const uint64_t *)k.mem_off.as<uint64_t>(),
-                           (const pgx_mem *)k.mems.as<pgx_mem>(), n_reads, m, k.w.bad.as<unsigned long long>());
-        HIPCHECK(hipGetLastError());
-        const uint64_t bad = read_u64(k.w.bad.as<uint64_t>(), s);
-        if (bad != ~0ull) throw Error(PGX_ERR_ARG, "pgx_read_hits_arrays: the MEM starts of read " + std::to_string(bad) + " do not ascend strictly");
-    }
-    hits_launch(k.w, k.mem_off.as<uint64_t>(), k.mems.as<pgx_mem>(), k.sets.as<uint64_t>(), n_reads, m, n_seq, set_words, flags, s);
-    if (n_reads) {
-        HIPCHECK(hipMemcpyAsync(hits, k.w.hits.p, n_reads * sizeof(pgx_read_hit), hipMemcpyDeviceToHost, s));
-        if (flags & PGX_HITS_BEST_SETS) HIPCHECK(hipMemcpyAsync(best_sets, k.w.best_sets.p, n_reads * set_words * 8, hipMemcpyDeviceToHost, s));
-        if (flags & PGX_HITS_SCORES) HIPCHECK(hipMemcpyAsync(scores, k.w.scores.p, n_reads * n_seq * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHECK(hipStreamSynchronize(s));
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-// ------------------------------------------------------------------------------------------
-// read placement (pgx_place_kernels.hip; the definitions: include/pgx.h "read placement")
-static const uint32_t PLACE_FLAGS = PGX_PLACE_LIST;
-// reads, MEMs or keys one launch takes at a thread an item or fewer: a grid holds fewer than 2^32 threads, and a larger one would lose items without an error
-static const uint64_t PLACE_LAUNCH_ITEMS = 1ull << 31;
-
-// keys one pass may hold: PGX_PLACE_BUDGET_MB (read per call, fractions allowed), default a quarter of the free device memory
-static uint64_t place_budget_keys(size_t mem_free) {
-    uint64_t bytes = 0;
-    if (const char *e = std::getenv("PGX_PLACE_BUDGET_MB")) {
-        const double mb = std::strtod(e, nullptr);
-        if (mb > 0) bytes = (uint64_t)(mb * 1048576.0);
-    }
-    if (!bytes) bytes = mem_free / 4;
-    return std::min<uint64_t>(std::max<uint64_t>(bytes / 8, 1), PLACE_LAUNCH_ITEMS);
-}
-
-static uint32_t place_bits(unsigned __int128 v) {
-    uint32_t b = 0;
-    while (v) { b++; v >>= 1; }
-    return b;
-}
-
-// log2 of the lanes a read of the sweep takes: the power of two >= twice the mean anchors a read of the pass, 4 .. 64 (a longer read takes more
-// steps).  PGX_PLACE_LANES (tests; 1 .. 64, rounded up to a power of two) fixes it.  Results never depend on it.
-static uint32_t place_lane_shift(uint64_t keys, uint64_t reads) {
-    uint64_t want = reads ? 2 * ((keys + reads - 1) / reads) : 4;
-    want = std::min<uint64_t>(std::max<uint64_t>(want, 4), 64);
-    if (const char *e = std::getenv("PGX_PLACE_LANES")) {
-        const long v = std::strtol(e, nullptr, 10);
-        if (v >= 1 && v <= 64) want = (uint64_t)v;
-    }
-    uint32_t sh = 0;
-    while ((1ull << sh) < want) sh++;
-    return sh;
-}
-
-static size_t free_device_memory() {
-    size_t mem_free = 0, mem_total = 0;
-    if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); mem_free = 1ull << 30; }
-    return mem_free;
-}
-
-// The stage on device arrays, enqueued on s (synchronised where a size is read back): w.recs, and with PGX_PLACE_LIST w.place_off / w.places.
-// loc_off: n_mems + 1 value offsets, values: n_values.  Refuses before a result buffer is written.
-static void place_core(PlaceWork &w, const uint64_t *mem_off, const pgx_mem *mems, const uint64_t *loc_off, const uint64_t *values, uint64_t n, uint64_t n_mems,
-                       uint64_t n_values, uint64_t n_seq, uint64_t L, uint32_t flags, size_t mem_free, hipStream_t s, const std::string &who) {
-    if (n >= PLACE_LAUNCH_ITEMS || n_mems >= PLACE_LAUNCH_ITEMS)
-        throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n) + " reads with " + std::to_string(n_mems) + " MEMs exceed the " + std::to_string(PLACE_LAUNCH_ITEMS) +
-                                             " one launch holds: place the reads in smaller batches");
-    const bool list = (flags & PGX_PLACE_LIST) != 0;
-    // 1. plan: the anchors of every read, the first MEM of every MEM's read, the maxima of the key layout
-    //    ctr: [0] most MEMs of a read [1] largest MEM start [2] aoff[n] [3] aoff[0]; later [0] wave list [1] workgroup list [2] scratch total [3] placements of a pass [6..7] cut
-    w.aoff.ensure((n + 1) * 8); w.acnt.ensure((n ? n : 1) * 8); w.mfirst.ensure((n_mems ? n_mems : 1) * 8); w.ctr.ensure(64);
-    unsigned long long *ctr = w.ctr.as<unsigned long long>();
-    HIPCHECK(hipMemsetAsync(w.ctr.p, 0, 64, s));
-    hipLaunchKernelGGL(pgx_place_plan_kernel, dim3(grid_for(n + 1, 256)), dim3(256), 0, s, mem_off, loc_off, mems, n, n_mems, n_values, w.aoff.as<uint64_t>(),
-                       w.acnt.as<uint64_t>(), ctr);
-    if (n_mems) hipLaunchKernelGGL(pgx_place_first_kernel, dim3(grid_for(n_mems, 256)), dim3(256), 0, s, mem_off, n, n_mems, w.mfirst.as<uint64_t>());
-    HIPCHECK(hipGetLastError());
-    uint64_t c[4];
-    read_scalars(c, ctr, 32, s);
-    const uint64_t most_mems = c[0], bias = c[1], a_end = c[2], a_begin = std::min(c[3], c[2]);
-    const uint32_t ordinal_bits = place_bits(most_mems ? most_mems - 1 : 0);
-    const uint64_t span = L + bias;
-    const uint32_t group_bits = span < L ? 65u : place_bits((unsigned __int128)n_seq * span);
-    if (group_bits + ordinal_bits > 64)
-        throw Error(PGX_ERR_UNSUPPORTED, who + ": a key needs " + std::to_string(group_bits) + " bits for sequence and diagonal (" + std::to_string(n_seq) + " sequences x (max_length " +
-                                             std::to_string(L) + " + largest MEM start " + std::to_string(bias) + ")) and " + std::to_string(ordinal_bits) +
-                                             " bits for the MEM of a read (most MEMs of a read: " + std::to_string(most_mems) + "), 64 are available");
-    const uint64_t budget = place_budget_keys(mem_free);
-    const uint64_t *aoff = w.aoff.as<uint64_t>(), *acnt = w.acnt.as<uint64_t>();
-    w.recs.ensure((n ? n : 1) * sizeof(pgx_read_place)); w.pcount.ensure((n ? n : 1) * 8);
-    // 2. passes over consecutive whole reads whose keys fit the budget (one pass unless the batch exceeds it)
-    uint64_t U = 0; // placements listed by the passes so far
-    uint32_t passes = 0;
-    for (uint64_t r0 = 0, o0 = a_begin; r0 < n;) {
-        uint64_t r1 = n, o1 = a_end;
-        if (a_end - o0 > budget) {
-            hipLaunchKernelGGL(pgx_ml_cut_kernel, dim3(1), dim3(64), 0, s, aoff, n, r0, budget, reinterpret_cast<uint64_t *>(ctr + 6));
-            HIPCHECK(hipGetLastError());
-            uint64_t cut[2];
-            read_scalars(cut, ctr + 6, 16, s);
-            r1 = cut[0]; o1 = cut[1];
-            if (o1 - o0 > budget) // (the cut is a read at least)
-                throw Error(PGX_ERR_NOMEM, who + ": read " + std::to_string(r0) + " has " + std::to_string(o1 - o0) + " anchors, the keys of a pass hold " + std::to_string(budget) +
-                                               " (PGX_PLACE_BUDGET_MB)");
-        }
-        const uint64_t np = r1 - r0, nk = o1 - o0;
-        passes++;
-        // keys, then the segmented sort of the tag stage: a read is a segment, the size-class lists are built on the device
-        w.keys.ensure((nk ? nk : 1) * 8);
-        w.seg.ensure((np + 1) * 8); w.lists.ensure(2 * np * 8); w.need.ensure(np * 8); w.soff.ensure((np + 1) * 8); w.ucount.ensure(np * 8);
-        uint64_t *keys = w.keys.as<uint64_t>(), *seg = w.seg.as<uint64_t>(), *wave_list = w.lists.as<uint64_t>(), *wg_list = wave_list + np, *ucount = w.ucount.as<uint64_t>();
-        if (nk) {
-            hipLaunchKernelGGL(pgx_place_keys_kernel, dim3(grid_for(nk, PGX_ML_SPAN)), dim3(256), 0, s, mems, loc_off, (const uint64_t *)w.mfirst.as<uint64_t>(), values,
-                               (uint64_t)0, n_mems, o0, nk, L, span, bias, ordinal_bits, keys);
-            HIPCHECK(hipGetLastError());
-        }
-        HIPCHECK(hipMemsetAsync(w.ctr.p, 0, 32, s));
-        hipLaunchKernelGGL(pgx_ml_classify_kernel, dim3(grid_for(np + 1, 256)), dim3(256), 0, s, acnt + r0, aoff + r0, np, seg, wave_list, wg_list, w.need.as<uint64_t>(),
-                           ucount, ctr);
-        HIPCHECK(hipGetLastError());
-        scan_excl(1, w.need.p, np, 0, w.soff.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 2));
-        uint64_t lc[3];
-        read_scalars(lc, ctr, 24, s);
-        const uint64_t n_wave = lc[0], n_wg = lc[1], S = lc[2];
-        if (n_wave)
-            hipLaunchKernelGGL(pgx_tag_sort_unique_kernel<PgxTagDense>, dim3(grid_for(n_wave, 4)), dim3(256), 0, s, PgxTagDense{wave_list, acnt + r0, seg}, n_wave,
-                               (const uint64_t *)nullptr, (const uint64_t *)nullptr, keys, ucount);
-        if (n_wg) {
-            w.scratch.ensure((S ? S : 1) * 8);
-            HIPCHECK(hipFuncSetAttribute((const void *)pgx_tag_sort_large_kernel<PgxTagDense>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PGX_SORT_WG_LDS_CAP * 8)));
-            hipLaunchKernelGGL(pgx_tag_sort_large_kernel<PgxTagDense>, dim3(grid_for(n_wg, 1)), dim3(1024), (size_t)PGX_SORT_WG_LDS_CAP * 8, s,
-                               PgxTagDense{wg_list, acnt + r0, seg}, n_wg, (const uint64_t *)nullptr, (const uint64_t *)nullptr, keys, w.scratch.as<uint64_t>(),
-                               (const uint64_t *)w.soff.as<uint64_t>(), ucount);
-        }
-        HIPCHECK(hipGetLastError());
-        // the sweep, in launches of fewer than 2^32 threads
-        const uint32_t g_shift = place_lane_shift(nk, np);
-        const uint64_t per_launch = PLACE_LAUNCH_ITEMS >> g_shift;
-        auto sweep = [&](bool fill, const uint64_t *list_off, pgx_placement *places) {
-            for (uint64_t q0 = 0; q0 < np; q0 += per_launch) {
-                const uint64_t nr = std::min(per_launch, np - q0);
-                const dim3 grid(grid_for(nr, PGX_PLACE_THREADS >> g_shift)), block(PGX_PLACE_THREADS);
-                if (fill)
-                    hipLaunchKernelGGL(pgx_place_sweep_kernel<true>, grid, block, 0, s, mem_off, mems, loc_off, acnt, (const uint64_t *)keys, (const uint64_t *)seg,
-                                       (const uint64_t *)ucount, r0, r0 + q0, nr, n_mems, span, bias, ordinal_bits, g_shift, w.recs.as<pgx_read_place>(),
-                                       w.pcount.as<uint64_t>(), list_off, places);
-                else
-                    hipLaunchKernelGGL(pgx_place_sweep_kernel<false>, grid, block, 0, s, mem_off, mems, loc_off, acnt, (const uint64_t *)keys, (const uint64_t *)seg,
-                                       (const uint64_t *)ucount, r0, r0 + q0, nr, n_mems, span, bias, ordinal_bits, g_shift, w.recs.as<pgx_read_place>(),
-                                       w.pcount.as<uint64_t>(), list_off, places);
-                HIPCHECK(hipGetLastError());
-            }
-        };
-        sweep(false, nullptr, nullptr);
-        if (list) { // the pass's counts -> offsets behind the passes before, then the same walk writes the placements
-            w.loff.ensure((np + 1) * 8);
-            scan_excl(1, w.pcount.as<uint64_t>() + r0, np, 0, w.loff.as<uint64_t>(), w.scan_tmp, s, reinterpret_cast<uint64_t *>(ctr + 3));
-            const uint64_t Up = read_u64(reinterpret_cast<const uint64_t *>(ctr + 3), s);
-            if ((U + Up) > (mem_free / 4) / sizeof(pgx_placement))
-                throw Error(PGX_ERR_NOMEM, who + ": PGX_PLACE_LIST takes at least " + std::to_string((U + Up) * sizeof(pgx_placement)) +
-                                               " bytes, a quarter of the free device memory is " + std::to_string(mem_free / 4));
-            w.places.ensure_keep((U + Up ? U + Up : 1) * sizeof(pgx_placement), U * sizeof(pgx_placement)); // (the stream is idle here: the read-back above synchronised it)
-            if (Up) sweep(true, w.loff.as<uint64_t>(), w.places.as<pgx_placement>() + U);
-            U += Up;
-        }
-        r0 = r1; o0 = o1;
-    }
-    if (list) {
-        w.place_off.ensure((n + 1) * 8);
-        w.places.ensure(sizeof(pgx_placement));
-        scan_excl(1, w.pcount.p, n, 0, w.place_off.as<uint64_t>(), w.scan_tmp, s);
-    }
-    w.flags = flags;
-    w.n_reads = n;
-    w.n_anchors = a_end - a_begin;
-    w.n_places = U;
-    w.n_passes = passes;
-}
-
-extern "C" pgx_status pgx_batch_read_place(pgx_batch *b, uint32_t flags, void *stream) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_batch_read_place");
-    checked_device_count();
-    if (!b) throw Error(PGX_ERR_ARG, "pgx_batch_read_place: null batch");
-    // (what is refused here leaves an earlier place result as it was)
-    if (flags & ~PLACE_FLAGS) throw Error(PGX_ERR_ARG, "pgx_batch_read_place: unknown flag");
-    if (!b->ran) throw Error(PGX_ERR_ARG, "pgx_batch_read_place: batch has not been run");
-    const LocWork &lw = b->lw;
-    if (!lw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_read_place: needs a completed pgx_batch_locate(flags = 0), the batch has no locate result");
-    if (lw.flags != 0 || lw.n_mems != b->n_mems)
-        throw Error(PGX_ERR_ARG, "pgx_batch_read_place: needs a completed pgx_batch_locate(flags = 0), the last pgx_batch_locate ran with flags " + std::to_string(lw.flags));
-    use_device(b->device);
-    pgx_device_image *d = locate_image(b->h, b->device);
-    hipStream_t s = stream ? (hipStream_t)stream : b->own;
-    PlaceWork &w = b->pw;
-    w.valid = false;
-    const size_t mem_free = free_device_memory();
-    const bool timed = b->timed;
-    if (timed) {
-        for (auto &e : w.ev)
-            if (!e) HIPCHECK(hipEventCreate(&e));
-        HIPCHECK(hipEventRecord(w.ev[0], s));
-    }
-    place_core(w, b->mem_off.as<uint64_t>(), b->mems.as<pgx_mem>(), lw.d_off, lw.vals.as<uint64_t>(), b->n_reads, b->n_mems, lw.n_values, b->h->meta.n_sequences(),
-               d->loc.max_length, flags, mem_free, s, "pgx_batch_read_place");
-    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
-    HIPCHECK(hipStreamSynchronize(s));
-    w.ms = 0;
-    if (timed) HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
-    w.valid = true;
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-static void places_header(const pgx_batch *b, pgx_read_places *out) {
-    const PlaceWork &w = b->pw;
-    std::memset(out, 0, sizeof *out);
-    out->n_reads = w.n_reads;
-    out->n_anchors = w.n_anchors;
-    out->n_places = w.n_places;
-    out->flags = w.flags;
-    out->n_passes = w.n_passes;
-    out->ms_place = w.ms;
-}
-
-extern "C" pgx_status pgx_batch_device_places(pgx_batch *b, pgx_read_places *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->pw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_places: batch has no place result");
-    const PlaceWork &w = b->pw;
-    places_header(b, out);
-    out->reads = w.recs.as<pgx_read_place>();
-    if (w.flags & PGX_PLACE_LIST) {
-        out->place_offsets = w.place_off.as<uint64_t>();
-        out->places = w.places.as<pgx_placement>();
-    }
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_batch_places(pgx_batch *b, pgx_read_places *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->pw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_places: batch has no place result");
-    use_device(b->device);
-    PlaceWork &w = b->pw;
-    const uint64_t n = w.n_reads;
-    const bool list = (w.flags & PGX_PLACE_LIST) != 0;
-    w.h_recs.ensure((n ? n : 1) * sizeof(pgx_read_place));
-    if (n) HIPCHECK(hipMemcpyAsync(w.h_recs.p, w.recs.p, n * sizeof(pgx_read_place), hipMemcpyDeviceToHost, b->own));
-    if (list) {
-        w.h_place_off.ensure((n + 1) * 8);
-        w.h_places.ensure((w.n_places ? w.n_places : 1) * sizeof(pgx_placement));
-        HIPCHECK(hipMemcpyAsync(w.h_place_off.p, w.place_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, b->own));
-        if (w.n_places) HIPCHECK(hipMemcpyAsync(w.h_places.p, w.places.p, w.n_places * sizeof(pgx_placement), hipMemcpyDeviceToHost, b->own));
-    }
-    HIPCHECK(hipStreamSynchronize(b->own)); // (the stage completed inside pgx_batch_read_place, on whatever stream it used)
-    places_header(b, out);
-    out->reads = w.h_recs.as<pgx_read_place>();
-    if (list) {
-        out->place_offsets = w.h_place_off.as<uint64_t>();
-        out->places = w.h_places.as<pgx_placement>();
-    }
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_read_place_arrays(int device, const uint64_t *mem_offsets, uint64_t n_reads, const pgx_mem *mems, const uint64_t *loc_offsets,
-                                            const uint64_t *values, uint64_t n_seq, uint64_t max_length, uint32_t flags, pgx_read_place *out,
-                                            uint64_t *place_offsets, pgx_placement *places, uint64_t places_cap) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_read_place_arrays");
-    checked_device_count();
-    if (flags & ~PLACE_FLAGS) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: unknown flag");
-    if (n_seq == 0 || max_length == 0) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: n_seq and max_length must be positive");
-    const bool list = (flags & PGX_PLACE_LIST) != 0;
-    if (!mem_offsets || !loc_offsets || (n_reads && !out) || (list && (!place_offsets || (places_cap && !places))))
-        throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: null argument");
-    if (mem_offsets[0] != 0) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: mem_offsets must start at 0");
-    for (uint64_t i = 0; i < n_reads; i++)
-        if (mem_offsets[i] > mem_offsets[i + 1])
-            throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: mem_offsets decrease at read " + std::to_string(i));
-    const uint64_t m = mem_offsets[n_reads];
-    if (loc_offsets[0] != 0) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: loc_offsets must start at 0");
-    for (uint64_t r = 0; r < n_reads; r++)
-        for (uint64_t i = mem_offsets[r]; i < mem_offsets[r + 1]; i++)
-            if (loc_offsets[i] > loc_offsets[i + 1])
-                throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: loc_offsets decrease at MEM " + std::to_string(i) + " of read " + std::to_string(r));
-    const uint64_t nv = loc_offsets[m];
-    if ((m && !mems) || (nv && !values)) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: null argument");
-    use_device(device);
-    struct Work { // device copies of the input + the stage's buffers, released on every way out
-        DevBuf mem_off, mems, loc_off, values;
-        PlaceWork w;
-        ~Work() {
-            DevBuf *all[] = {&mem_off, &mems, &loc_off, &values};
-            for (DevBuf *d : all) d->release();
-            w.release();
-        }
-    } k;
-    const size_t mem_free = free_device_memory();
-    upload(k.mem_off, mem_offsets, (n_reads + 1) * 8);
-    upload(k.mems, mems, m * sizeof(pgx_mem));
-    upload(k.loc_off, loc_offsets, (m + 1) * 8);
-    upload(k.values, values, nv * 8);
-    hipStream_t s = nullptr;
-    if (n_reads) { // the preconditions, before anything is written
-        if (n_reads >= PLACE_LAUNCH_ITEMS || nv >= (1ull << 32) - 256)
-            throw Error(PGX_ERR_UNSUPPORTED, "pgx_read_place_arrays: " + std::to_string(n_reads) + " reads with " + std::to_string(nv) + " values exceed one checking launch");
-        k.w.bad.ensure(8);
-        HIPCHECK(hipMemsetAsync(k.w.bad.p, 0xFF, 8, s));
-        hipLaunchKernelGGL(pgx_read_hits_check_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, s, (const uint64_t *)k.mem_off.as<uint64_t>(),
-                           (const pgx_mem *)k.mems.as<pgx_mem>(), n_reads, m, k.w.bad.as<unsigned long long>());
-        HIPCHECK(hipGetLastError());
-        uint64_t bad = read_u64(k.w.bad.as<uint64_t>(), s);
-        if (bad != ~0ull) throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: the MEM starts of read " + std::to_string(bad) + " do not ascend strictly");
-        if (nv) { // (a read's anchors: loc_offsets at its first MEM, what the plan kernel computes too)
-            std::vector<uint64_t> h_aoff(n_reads + 1);
-            for (uint64_t r = 0; r <= n_reads; r++) h_aoff[r] = loc_offsets[mem_offsets[r]];
-            upload(k.w.aoff, h_aoff.data(), (n_reads + 1) * 8);
-            hipLaunchKernelGGL(pgx_place_check_values_kernel, dim3(grid_for(nv, 256)), dim3(256), 0, s, (const uint64_t *)k.values.as<uint64_t>(), nv, max_length, n_seq,
-                               (const uint64_t *)k.w.aoff.as<uint64_t>(), n_reads, k.w.bad.as<unsigned long long>());
-            HIPCHECK(hipGetLastError());
-            bad = read_u64(k.w.bad.as<uint64_t>(), s);
-            if (bad != ~0ull)
-                throw Error(PGX_ERR_ARG, "pgx_read_place_arrays: read " + std::to_string(bad) + " has a value whose sequence is not below n_seq " + std::to_string(n_seq));
-        }
-    }
-    place_core(k.w, k.mem_off.as<uint64_t>(), k.mems.as<pgx_mem>(), k.loc_off.as<uint64_t>(), k.values.as<uint64_t>(), n_reads, m, nv, n_seq, max_length, flags, mem_free, s,
-               "pgx_read_place_arrays");
-    if (list && k.w.n_places > places_cap)
-        throw Error(PGX_ERR_NOMEM, "pgx_read_place_arrays: the list holds " + std::to_string(k.w.n_places) + " placements, places_cap is " + std::to_string(places_cap));
-    if (n_reads) HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, n_reads * sizeof(pgx_read_place), hipMemcpyDeviceToHost, s));
-    if (list) {
-        HIPCHECK(hipMemcpyAsync(place_offsets, k.w.place_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (k.w.n_places) HIPCHECK(hipMemcpyAsync(places, k.w.places.p, k.w.n_places * sizeof(pgx_placement), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHECK(hipStreamSynchronize(s));
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-// ------------------------------------------------------------------------------------------
-// read verify (pgx_verify_kernels.hip; the definitions: include/pgx.h "read verify")
-static const uint32_t VERIFY_FLAGS = PGX_VERIFY_LIST;
-
-static void verify_check_args(const std::string &who, uint32_t penalty, uint32_t flags) {
-    if (flags & ~VERIFY_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
-    if (penalty == 0 || penalty > PGX_VERIFY_MAX_PENALTY)
-        throw Error(PGX_ERR_ARG, who + ": mismatch_penalty " + std::to_string(penalty) + " is outside 1 .. " + std::to_string(PGX_VERIFY_MAX_PENALTY));
-}
-
-// The stage on device arrays, enqueued on s: the candidates w.cand_off / cand_seq / cand_diag / cand_read (n_cands of them) -> w.cands, w.recs.
-// reads: read_bytes bytes, read_off: n + 1 offsets into them.  Every buffer was sized by the caller's checks; nothing is read back.
-static void verify_core(VerifyWork &w, const uint32_t *text4, const uint64_t *seq_start, uint32_t endmark, const uint8_t *reads, uint64_t read_bytes, const uint64_t *read_off,
-                        uint64_t n, uint64_t n_cands, uint32_t penalty, hipStream_t s) {
-    const uint64_t n_rw = (read_bytes + 7) / 8 + 1;
-    w.rcode.ensure(n_rw * 4);
-    w.cands.ensure((n_cands ? n_cands : 1) * sizeof(pgx_read_verify));
-    w.recs.ensure((n ? n : 1) * sizeof(pgx_read_verify));
-    // the reads at the text's symbol width, once per read whatever the number of its candidates
-    hipLaunchKernelGGL(pgx_verify_code_kernel, dim3((unsigned)std::min<uint64_t>((n_rw + 255) / 256, 1u << 20)), dim3(256), 0, s, reads, read_bytes, n_rw, w.rcode.as<uint32_t>());
-    if (n_cands)
-        hipLaunchKernelGGL(pgx_verify_kernel, dim3(grid_for(n_cands, PGX_VERIFY_THREADS)), dim3(PGX_VERIFY_THREADS), 0, s, text4, seq_start, endmark,
-                           (const uint32_t *)w.rcode.as<uint32_t>(), read_off, (const uint64_t *)w.cand_off.as<uint64_t>(), (const uint64_t *)w.cand_read.as<uint64_t>(),
-                           (const uint32_t *)w.cand_seq.as<uint32_t>(), (const int64_t *)w.cand_diag.as<int64_t>(), n_cands, penalty, w.cands.as<pgx_read_verify>());
-    if (n)
-        hipLaunchKernelGGL(pgx_verify_reduce_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const pgx_read_verify *)w.cands.as<pgx_read_verify>(),
-                           (const uint64_t *)w.cand_off.as<uint64_t>(), n, w.recs.as<pgx_read_verify>());
-    HIPCHECK(hipGetLastError());
-}
-
-extern "C" pgx_status pgx_batch_read_verify(pgx_batch *b, uint32_t max_cand, uint32_t mismatch_penalty, uint32_t flags, void *stream) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_batch_read_verify");
-    checked_device_count();
-    const std::string who = "pgx_batch_read_verify";
-    if (!b) throw Error(PGX_ERR_ARG, who + ": null batch");
-    // (what is refused here leaves an earlier verify result as it was)
-    verify_check_args(who, mismatch_penalty, flags);
-    if (max_cand < 1 || max_cand > PGX_VERIFY_MAX_CAND) throw Error(PGX_ERR_ARG, who + ": max_cand " + std::to_string(max_cand) + " is outside 1 .. " + std::to_string(PGX_VERIFY_MAX_CAND));
-    if (!b->ran) throw Error(PGX_ERR_ARG, who + ": batch has not been run");
-    PlaceWork &pw = b->pw;
-    if (!pw.valid || pw.n_reads != b->n_reads) throw Error(PGX_ERR_ARG, who + ": needs a completed pgx_batch_read_place, the batch has no place result");
-    if (max_cand > 1 && !(pw.flags & PGX_PLACE_LIST))
-        throw Error(PGX_ERR_ARG, who + ": max_cand " + std::to_string(max_cand) + " needs a place result made with PGX_PLACE_LIST, the last pgx_batch_read_place ran without it");
-    if (b->max_read_len >= (1ull << 31)) throw Error(PGX_ERR_UNSUPPORTED, who + ": a read of " + std::to_string(b->max_read_len) + " bytes; the records hold read positions below 2^31");
-    const uint64_t n = b->n_reads;
-    if (n >= PLACE_LAUNCH_ITEMS) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n) + " reads exceed one launch");
-    use_device(b->device);
-    pgx_device_image *d = device_image(b->h, b->device);
-    ensure_text(b->h, d); // (throws where the index has no text image, before anything of the batch changes)
-    hipStream_t s = stream ? (hipStream_t)stream : b->own;
-    VerifyWork &w = b->vw;
-    w.valid = false;
-    const bool timed = b->timed;
-    if (timed) {
-        for (auto &e : w.ev)
-            if (!e) HIPCHECK(hipEventCreate(&e));
-        HIPCHECK(hipEventRecord(w.ev[0], s));
-    }
-    // the candidates: counted, scanned, filled
-    const bool from_list = max_cand > 1;
-    const pgx_read_place *recs = pw.recs.as<pgx_read_place>();
-    const uint64_t *place_off = from_list ? pw.place_off.as<uint64_t>() : nullptr;
-    const pgx_placement *places = from_list ? pw.places.as<pgx_placement>() : nullptr;
-    w.count.ensure((n ? n : 1) * 8);
-    w.cand_off.ensure((n + 1) * 8);
-    uint64_t n_cands = 0;
-    if (n) {
-        hipLaunchKernelGGL(pgx_verify_choose_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, recs, place_off, places, n, max_cand, w.count.as<uint64_t>(),
-                           (const uint64_t *)nullptr, (uint32_t *)nullptr, (int64_t *)nullptr);
-        HIPCHECK(hipGetLastError());
-        scan_excl(1, w.count.p, n, 0, w.cand_off.as<uint64_t>(), w.scan_tmp, s);
-        n_cands = read_u64(w.cand_off.as<uint64_t>() + n, s);
-    } else HIPCHECK(hipMemsetAsync(w.cand_off.p, 0, 8, s));
-    if (n_cands >= PLACE_LAUNCH_ITEMS) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_cands) + " candidates exceed one launch; lower max_cand");
-    {
-        const uint64_t need = n_cands * (sizeof(pgx_read_verify) + 20) + n * sizeof(pgx_read_verify) + b->read_bytes / 2;
-        const size_t mem_free = free_device_memory();
-        if (need > w.cands.cap + w.recs.cap + w.rcode.cap && need - (w.cands.cap + w.recs.cap + w.rcode.cap) > mem_free)
-            throw Error(PGX_ERR_NOMEM, who + ": " + std::to_string(n_cands) + " candidates take " + std::to_string(need) + " bytes of device memory, " + std::to_string(mem_free) + " are free");
-    }
-    w.cand_seq.ensure((n_cands ? n_cands : 1) * 4);
-    w.cand_diag.ensure((n_cands ? n_cands : 1) * 8);
-    w.cand_read.ensure((n_cands ? n_cands : 1) * 8);
-    if (n_cands) {
-        hipLaunchKernelGGL(pgx_verify_choose_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, recs, place_off, places, n, max_cand, w.count.as<uint64_t>(),
-                           (const uint64_t *)w.cand_off.as<uint64_t>(), w.cand_seq.as<uint32_t>(), w.cand_diag.as<int64_t>());
-        hipLaunchKernelGGL(pgx_verify_owner_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const uint64_t *)w.cand_off.as<uint64_t>(), n, n_cands, w.cand_read.as<uint64_t>());
-        HIPCHECK(hipGetLastError());
-    }
-    verify_core(w, d->text4.as<uint32_t>(), d->text_seq_start.as<uint64_t>(), 1u, b->reads.as<uint8_t>(), b->read_bytes, b->offsets.as<uint64_t>(), n, n_cands, mismatch_penalty, s);
-    if (timed) HIPCHECK(hipEventRecord(w.ev[1], s));
-    HIPCHECK(hipStreamSynchronize(s));
-    w.ms = 0;
-    if (timed) HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
-    w.n_reads = n; w.n_cands = n_cands; w.flags = flags; w.max_cand = max_cand; w.penalty = mismatch_penalty;
-    w.valid = true;
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-static void verified_header(const pgx_batch *b, pgx_read_verifies *out) {
-    const VerifyWork &w = b->vw;
-    std::memset(out, 0, sizeof *out);
-    out->n_reads = w.n_reads;
-    out->n_cands = w.n_cands;
-    out->flags = w.flags;
-    out->max_cand = w.max_cand;
-    out->mismatch_penalty = w.penalty;
-    out->ms_verify = w.ms;
-}
-
-extern "C" pgx_status pgx_batch_device_verified(pgx_batch *b, pgx_read_verifies *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->vw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_verified: batch has no verify result");
-    const VerifyWork &w = b->vw;
-    verified_header(b, out);
-    out->reads = w.recs.as<pgx_read_verify>();
-    if (w.flags & PGX_VERIFY_LIST) {
-        out->cand_offsets = w.cand_off.as<uint64_t>();
-        out->cands = w.cands.as<pgx_read_verify>();
-    }
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_batch_verified(pgx_batch *b, pgx_read_verifies *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->vw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_verified: batch has no verify result");
-    use_device(b->device);
-    VerifyWork &w = b->vw;
-    const uint64_t n = w.n_reads;
-    const bool list = (w.flags & PGX_VERIFY_LIST) != 0;
-    w.h_recs.ensure((n ? n : 1) * sizeof(pgx_read_verify));
-    if (n) HIPCHECK(hipMemcpyAsync(w.h_recs.p, w.recs.p, n * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, b->own));
-    if (list) {
-        w.h_cand_off.ensure((n + 1) * 8);
-        w.h_cands.ensure((w.n_cands ? w.n_cands : 1) * sizeof(pgx_read_verify));
-        HIPCHECK(hipMemcpyAsync(w.h_cand_off.p, w.cand_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, b->own));
-        if (w.n_cands) HIPCHECK(hipMemcpyAsync(w.h_cands.p, w.cands.p, w.n_cands * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, b->own));
-    }
-    HIPCHECK(hipStreamSynchronize(b->own)); // (the stage completed inside pgx_batch_read_verify, on whatever stream it used)
-    verified_header(b, out);
-    out->reads = w.h_recs.as<pgx_read_verify>();
-    if (list) {
-        out->cand_offsets = w.h_cand_off.as<uint64_t>();
-        out->cands = w.h_cands.as<pgx_read_verify>();
-    }
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_read_verify_arrays(int device, const uint8_t *text, const uint64_t *seq_offsets, uint64_t n_seq, const uint8_t *reads,
-                                             const uint64_t *read_offsets, uint64_t n_reads, const uint64_t *cand_offsets, const uint32_t *cand_seq,
-                                             const int64_t *cand_diag, uint32_t mismatch_penalty, uint32_t flags, pgx_read_verify *out,
-                                             uint64_t *list_offsets, pgx_read_verify *list, uint64_t list_cap) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_read_verify_arrays");
-    checked_device_count();
-    const std::string who = "pgx_read_verify_arrays";
-    verify_check_args(who, mismatch_penalty, flags);
-    const bool want_list = (flags & PGX_VERIFY_LIST) != 0;
-    if (!seq_offsets || !read_offsets || !cand_offsets || (n_reads && !out) || (want_list && (!list_offsets || (list_cap && !list))))
-        throw Error(PGX_ERR_ARG, who + ": null argument");
-    auto check_offsets = [&](const uint64_t *o, uint64_t k, const char *name, const char *item) {
-        if (o[0] != 0) throw Error(PGX_ERR_ARG, who + ": " + name + " must start at 0");
-        for (uint64_t i = 0; i < k; i++)
-            if (o[i] > o[i + 1]) throw Error(PGX_ERR_ARG, who + ": " + name + " decrease at " + item + " " + std::to_string(i));
-    };
-    check_offsets(seq_offsets, n_seq, "seq_offsets", "sequence");
-    check_offsets(read_offsets, n_reads, "read_offsets", "read");
-    check_offsets(cand_offsets, n_reads, "cand_offsets", "read");
-    const uint64_t n_text = seq_offsets[n_seq], read_bytes = read_offsets[n_reads], n_cands = cand_offsets[n_reads];
-    if ((n_text && !text) || (read_bytes && !reads) || (n_cands && (!cand_seq || !cand_diag))) throw Error(PGX_ERR_ARG, who + ": null argument");
-    if (n_text >= (1ull << 32) - (1ull << 20)) throw Error(PGX_ERR_UNSUPPORTED, who + ": a text of " + std::to_string(n_text) + " symbols, the image holds fewer than 2^32 - 2^20");
-    for (uint64_t i = 0; i < n_text; i++) {
-        const uint8_t c = text[i];
-        if (c != '\n' && c != 'A' && c != 'C' && c != 'G' && c != 'N' && c != 'T')
-            throw Error(PGX_ERR_UNSUPPORTED, who + ": text byte " + std::to_string((unsigned)c) + " at offset " + std::to_string(i) + " is none of \\n A C G N T");
-    }
-    for (uint64_t r = 0; r < n_reads; r++)
-        if (read_offsets[r + 1] - read_offsets[r] >= (1ull << 31))
-            throw Error(PGX_ERR_UNSUPPORTED, who + ": read " + std::to_string(r) + " has " + std::to_string(read_offsets[r + 1] - read_offsets[r]) + " bytes; the records hold read positions below 2^31");
-    if (n_reads >= PLACE_LAUNCH_ITEMS || n_cands >= PLACE_LAUNCH_ITEMS)
-        throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_reads) + " reads with " + std::to_string(n_cands) + " candidates exceed one launch");
-    if (want_list && n_cands > list_cap)
-        throw Error(PGX_ERR_NOMEM, who + ": the list holds " + std::to_string(n_cands) + " candidates, list_cap is " + std::to_string(list_cap));
-    use_device(device);
-    struct Work { // device copies of the input + the stage's buffers, released on every way out
-        DevBuf text8, text4, seq_off, reads, read_off;
-        VerifyWork w;
-        ~Work() {
-            DevBuf *all[] = {&text8, &text4, &seq_off, &reads, &read_off};
-            for (DevBuf *d : all) d->release();
-            w.release();
-        }
-    } k;
-    hipStream_t s = nullptr;
-    const uint64_t n_words = (n_text + 7) / 8 + PGX_TEXT_PAD_WORDS;
-    upload(k.text8, text, n_text);
-    upload(k.seq_off, seq_offsets, (n_seq + 1) * 8);
-    upload(k.reads, reads, read_bytes);
-    upload(k.read_off, read_offsets, (n_reads + 1) * 8);
-    upload(k.w.cand_off, cand_offsets, (n_reads + 1) * 8);
-    upload(k.w.cand_seq, cand_seq, n_cands * 4);
-    upload(k.w.cand_diag, cand_diag, n_cands * 8);
-    k.w.cand_read.ensure((n_cands ? n_cands : 1) * 8);
-    if (n_cands) { // the preconditions, before anything is written
-        hipLaunchKernelGGL(pgx_verify_owner_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, s, (const uint64_t *)k.w.cand_off.as<uint64_t>(), n_reads, n_cands,
-                           k.w.cand_read.as<uint64_t>());
-        k.w.bad.ensure(8);
-        HIPCHECK(hipMemsetAsync(k.w.bad.p, 0xFF, 8, s));
-        hipLaunchKernelGGL(pgx_verify_check_kernel, dim3(grid_for(n_cands, 256)), dim3(256), 0, s, (const uint64_t *)k.w.cand_read.as<uint64_t>(),
-                           (const uint32_t *)k.w.cand_seq.as<uint32_t>(), n_cands, n_seq, k.w.bad.as<unsigned long long>());
-        HIPCHECK(hipGetLastError());
-        const uint64_t bad = read_u64(k.w.bad.as<uint64_t>(), s);
-        if (bad != ~0ull) throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(bad) + " has a candidate whose sequence is not below n_seq " + std::to_string(n_seq));
-    }
-    k.text4.ensure(n_words * 4);
-    hipLaunchKernelGGL(pgx_text_pack_kernel, dim3((unsigned)std::min<uint64_t>((n_words + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint8_t *)k.text8.as<uint8_t>(), n_text, n_words,
-                       1u, k.text4.as<uint32_t>());
-    HIPCHECK(hipGetLastError());
-    verify_core(k.w, k.text4.as<uint32_t>(), k.seq_off.as<uint64_t>(), 0u, k.reads.as<uint8_t>(), read_bytes, k.read_off.as<uint64_t>(), n_reads, n_cands, mismatch_penalty, s);
-    if (n_reads) HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, n_reads * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, s));
-    if (want_list) {
-        HIPCHECK(hipMemcpyAsync(list_offsets, k.w.cand_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (n_cands) HIPCHECK(hipMemcpyAsync(list, k.w.cands.p, n_cands * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHECK(hipStreamSynchronize(s));
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-// ------------------------------------------------------------------------------------------
-// read align (pgx_align_kernels.hip; the definitions: include/pgx.h "read align")
-static const uint32_t ALIGN_FLAGS = PGX_ALIGN_CIGAR;
-static const uint64_t ALIGN_MAX_READ = 1ull << 28; // an operation's length has 28 bits
-
-static void align_check_args(const std::string &who, uint32_t band, uint32_t flags) {
-    if (flags & ~ALIGN_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
-    if (band > PGX_ALIGN_MAX_BAND) throw Error(PGX_ERR_ARG, who + ": band " + std::to_string(band) + " is outside 0 .. " + std::to_string(PGX_ALIGN_MAX_BAND));
-}
-
-// bytes of direction planes one pass may hold: PGX_ALIGN_BUDGET_MB (read per call, fractions allowed), default a quarter of the free device memory
-static uint64_t align_budget_bytes(size_t mem_free) {
-    uint64_t bytes = 0;
-    if (const char *e = std::getenv("PGX_ALIGN_BUDGET_MB")) {
-        const double mb = std::strtod(e, nullptr);
-        if (mb > 0) bytes = (uint64_t)(mb * 1048576.0);
-    }
-    if (!bytes) bytes = mem_free / 4;
-    return std::max<uint64_t>(bytes, 16);
-}
-
-struct AlignPass { uint64_t r0, r1, bytes; };
-
-// The passes over consecutive whole reads whose planes fit the budget, from the host's read offsets: a read of len bytes takes len rows of
-// row_bytes, rounded up to 16 (pgx_align_need_kernel computes the same on the device).  Throws before anything is launched.
-static std::vector<AlignPass> align_plan(const uint64_t *h_read_off, uint64_t n, uint32_t row_bytes, uint64_t budget, const std::string &who) {
-    std::vector<AlignPass> passes;
-    AlignPass cur{0, 0, 0};
-    for (uint64_t r = 0; r < n; r++) {
-        const uint64_t len = h_read_off[r + 1] - h_read_off[r];
-        if (len >= ALIGN_MAX_READ) throw Error(PGX_ERR_UNSUPPORTED, who + ": read " + std::to_string(r) + " has " + std::to_string(len) + " bytes; an operation's length is below 2^28");
-        const uint64_t need = (len * row_bytes + 15) & ~15ull;
-        if (need > budget)
-            throw Error(PGX_ERR_NOMEM, who + ": read " + std::to_string(r) + " needs " + std::to_string(need) + " bytes of direction planes, a pass holds " + std::to_string(budget) +
-                                           " (PGX_ALIGN_BUDGET_MB)");
-        if (cur.bytes + need > budget) { passes.push_back(cur); cur = AlignPass{r, r, 0}; }
-        cur.bytes += need;
-        cur.r1 = r + 1;
-    }
-    if (cur.r1 > cur.r0) passes.push_back(cur);
-    return passes;
-}
-
-template <int LG>
-static void align_launch_forward(const uint32_t *text4, const uint64_t *seq_start, uint32_t endmark, const uint32_t *rcode, const uint64_t *read_off, const AlignWork &w,
-                                 const AlignPass &p, uint32_t band, hipStream_t s) {
-    hipLaunchKernelGGL(pgx_align_forward_kernel<LG>, dim3(grid_for(p.r1 - p.r0, PGX_ALIGN_THREADS >> LG)), dim3(PGX_ALIGN_THREADS), 0, s, text4, seq_start, endmark, rcode, read_off,
-                       (const uint32_t *)w.cand_seq.as<uint32_t>(), (const int64_t *)w.cand_diag.as<int64_t>(), p.r0, p.r1, band, (const uint64_t *)w.plane_off.as<uint64_t>(),
-                       w.planes.as<uint8_t>(), w.fwd.as<uint2>());
-}
-
-// The stage on device arrays, enqueued on s (synchronised where the number of operations is read back): w.cand_seq / w.cand_diag (n of each) -> w.recs,
-// w.op_off and, with PGX_ALIGN_CIGAR, w.ops.  rcode: the reads coded by pgx_verify_code_kernel.  The plan was made by the caller: nothing here refuses.
-// With one pass the planes stay in place between the counting walk and the writing walk; with more, the forward kernel runs again before the writing walk.
-static void align_core(AlignWork &w, const uint32_t *text4, const uint64_t *seq_start, uint32_t endmark, const uint32_t *rcode, const uint64_t *read_off, uint64_t n,
-                       const std::vector<AlignPass> &plan, uint32_t band, uint32_t flags, bool timed, hipStream_t s) {
-    uint32_t lg = 0;
-    while ((1u << lg) < 2 * band + 1) lg++;
-    const uint32_t row_bytes = std::max(1u << lg, 8u) / 4;
-    uint64_t scratch = 16;
-    for (const AlignPass &p : plan) scratch = std::max(scratch, p.bytes);
-    w.recs.ensure((n ? n : 1) * sizeof(pgx_read_align));
-    w.need.ensure((n ? n : 1) * 8); w.plane_off.ensure((n + 1) * 8); w.fwd.ensure((n ? n : 1) * sizeof(uint2));
-    w.count.ensure((n ? n : 1) * 8); w.op_off.ensure((n + 1) * 8);
-    w.planes.ensure(scratch);
-    size_t n_ev = 2;
-    auto stamp = [&]() { // the next event of the call, recorded on s
-        if (!timed) return;
-        if (w.ev.size() <= n_ev) w.ev.resize(n_ev + 1, nullptr);
-        if (!w.ev[n_ev]) HIPCHECK(hipEventCreate(&w.ev[n_ev]));
-        HIPCHECK(hipEventRecord(w.ev[n_ev++], s));
-    };
-    std::vector<int> kinds; // of every pair of events: 0 forward, 1 trace
-    auto forward = [&](const AlignPass &p) {
-        stamp();
-        switch (lg) {
-        case 0: align_launch_forward<0>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
-        case 1: align_launch_forward<1>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
-        case 2: align_launch_forward<2>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
-        case 3: align_launch_forward<3>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
-        case 4: align_launch_forward<4>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
-        case 5: align_launch_forward<5>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
-        default: align_launch_forward<6>(text4, seq_start, endmark, rcode, read_off, w, p, band, s); break;
-        }
-        stamp();
-        kinds.push_back(0);
-    };
-    auto trace = [&](const AlignPass &p, uint32_t write) {
-        stamp();
-        hipLaunchKernelGGL(pgx_align_trace_kernel, dim3(grid_for(p.r1 - p.r0, 256)), dim3(256), 0, s, seq_start, endmark, read_off, (const uint32_t *)w.cand_seq.as<uint32_t>(),
-                           (const int64_t *)w.cand_diag.as<int64_t>(), p.r0, p.r1, band, row_bytes, (const uint64_t *)w.plane_off.as<uint64_t>(),
-                           (const uint8_t *)w.planes.as<uint8_t>(), (const uint2 *)w.fwd.as<uint2>(), write, w.recs.as<pgx_read_align>(), w.count.as<uint64_t>(),
-                           (const uint64_t *)w.op_off.as<uint64_t>(), w.ops.as<uint32_t>());
-        stamp();
-        kinds.push_back(1);
-    };
-    uint64_t n_ops = 0;
-    if (n) {
-        hipLaunchKernelGGL(pgx_align_need_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, read_off, n, row_bytes, w.need.as<uint64_t>());
-        HIPCHECK(hipGetLastError());
-        scan_excl(1, w.need.p, n, 0, w.plane_off.as<uint64_t>(), w.scan_tmp, s);
-        for (const AlignPass &p : plan) { forward(p); trace(p, 0); }
-        HIPCHECK(hipGetLastError());
-        scan_excl(1, w.count.p, n, 0, w.op_off.as<uint64_t>(), w.scan_tmp, s);
-        n_ops = read_u64(w.op_off.as<uint64_t>() + n, s);
-    } else HIPCHECK(hipMemsetAsync(w.op_off.p, 0, 8, s));
-    if ((flags & PGX_ALIGN_CIGAR) && n_ops) {
-        w.ops.ensure(n_ops * 4);
-        for (const AlignPass &p : plan) {
-            if (plan.size() > 1) forward(p);
-            trace(p, 1);
-        }
-        HIPCHECK(hipGetLastError());
-    }
-    HIPCHECK(hipStreamSynchronize(s));
-    w.ms_forward = w.ms_trace = 0;
-    for (size_t i = 0; timed && i < kinds.size(); i++) {
-        float ms = 0;
-        HIPCHECK(hipEventElapsedTime(&ms, w.ev[2 + 2 * i], w.ev[3 + 2 * i]));
-        (kinds[i] ? w.ms_trace : w.ms_forward) += ms;
-    }
-    w.n_reads = n; w.n_ops = n_ops; w.flags = flags; w.band = band; w.passes = (uint32_t)plan.size(); w.scratch_bytes = plan.empty() ? 0 : scratch;
-}
-
-extern "C" pgx_status pgx_batch_read_align(pgx_batch *b, uint32_t band, uint32_t flags, void *stream) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_batch_read_align");
-    checked_device_count();
-    const std::string who = "pgx_batch_read_align";
-    if (!b) throw Error(PGX_ERR_ARG, who + ": null batch");
-    // (what is refused here leaves an earlier align result as it was)
-    align_check_args(who, band, flags);
-    if (!b->ran) throw Error(PGX_ERR_ARG, who + ": batch has not been run");
-    VerifyWork &vw = b->vw;
-    if (!vw.valid || vw.n_reads != b->n_reads) throw Error(PGX_ERR_ARG, who + ": needs a completed pgx_batch_read_verify, the batch has no verify result");
-    const uint64_t n = b->n_reads;
-    if (n >= PLACE_LAUNCH_ITEMS) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n) + " reads exceed one launch");
-    use_device(b->device);
-    pgx_device_image *d = device_image(b->h, b->device);
-    ensure_text(b->h, d); // (built by the verify stage)
-    uint32_t lg = 0;
-    while ((1u << lg) < 2 * band + 1) lg++;
-    const std::vector<AlignPass> plan = align_plan(b->h_offsets(), n, std::max(1u << lg, 8u) / 4, align_budget_bytes(free_device_memory()), who);
-    hipStream_t s = stream ? (hipStream_t)stream : b->own;
-    AlignWork &w = b->aw;
-    w.valid = false;
-    const bool timed = b->timed;
-    if (timed) {
-        if (w.ev.size() < 2) w.ev.resize(2, nullptr);
-        for (int i = 0; i < 2; i++)
-            if (!w.ev[i]) HIPCHECK(hipEventCreate(&w.ev[i]));
-        HIPCHECK(hipEventRecord(w.ev[0], s));
-    }
-    w.cand_seq.ensure((n ? n : 1) * 4); w.cand_diag.ensure((n ? n : 1) * 8);
-    if (n) {
-        hipLaunchKernelGGL(pgx_align_cand_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const pgx_read_verify *)vw.recs.as<pgx_read_verify>(), n, w.cand_seq.as<uint32_t>(),
-                           w.cand_diag.as<int64_t>());
-        HIPCHECK(hipGetLastError());
-    }
-    // (the reads were coded by the verify call for all of its candidates: vw.rcode describes this run's reads)
-    align_core(w, d->text4.as<uint32_t>(), d->text_seq_start.as<uint64_t>(), 1u, (const uint32_t *)vw.rcode.as<uint32_t>(), b->offsets.as<uint64_t>(), n, plan, band, flags, timed, s);
-    w.ms = 0;
-    if (timed) {
-        HIPCHECK(hipEventRecord(w.ev[1], s));
-        HIPCHECK(hipStreamSynchronize(s));
-        HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
-    }
-    w.valid = true;
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-static void aligned_header(const pgx_batch *b, pgx_read_aligns *out) {
-    const AlignWork &w = b->aw;
-    std::memset(out, 0, sizeof *out);
-    out->n_reads = w.n_reads;
-    out->n_ops = w.n_ops;
-    out->flags = w.flags;
-    out->band = w.band;
-    out->passes = w.passes;
-    out->scratch_bytes = w.scratch_bytes;
-    out->ms_align = w.ms;
-    out->ms_forward = w.ms_forward;
-    out->ms_trace = w.ms_trace;
-}
-
-extern "C" pgx_status pgx_batch_device_aligned(pgx_batch *b, pgx_read_aligns *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->aw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_aligned: batch has no align result");
-    const AlignWork &w = b->aw;
-    aligned_header(b, out);
-    out->reads = w.recs.as<pgx_read_align>();
-    if (w.flags & PGX_ALIGN_CIGAR) {
-        out->op_offsets = w.op_off.as<uint64_t>();
-        out->ops = w.ops.as<uint32_t>();
-    }
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_batch_aligned(pgx_batch *b, pgx_read_aligns *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->aw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_aligned: batch has no align result");
-    use_device(b->device);
-    AlignWork &w = b->aw;
-    const uint64_t n = w.n_reads;
-    const bool list = (w.flags & PGX_ALIGN_CIGAR) != 0;
-    w.h_recs.ensure((n ? n : 1) * sizeof(pgx_read_align));
-    if (n) HIPCHECK(hipMemcpyAsync(w.h_recs.p, w.recs.p, n * sizeof(pgx_read_align), hipMemcpyDeviceToHost, b->own));
-    if (list) {
-        w.h_op_off.ensure((n + 1) * 8);
-        w.h_ops.ensure((w.n_ops ? w.n_ops : 1) * 4);
-        HIPCHECK(hipMemcpyAsync(w.h_op_off.p, w.op_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, b->own));
-        if (w.n_ops) HIPCHECK(hipMemcpyAsync(w.h_ops.p, w.ops.p, w.n_ops * 4, hipMemcpyDeviceToHost, b->own));
-    }
-    HIPCHECK(hipStreamSynchronize(b->own)); // (the stage completed inside pgx_batch_read_align, on whatever stream it used)
-    aligned_header(b, out);
-    out->reads = w.h_recs.as<pgx_read_align>();
-    if (list) {
-        out->op_offsets = w.h_op_off.as<uint64_t>();
-        out->ops = w.h_ops.as<uint32_t>();
-    }
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_read_align_arrays(int device, const uint8_t *text, const uint64_t *seq_offsets, uint64_t n_seq, const uint8_t *reads,
-                                            const uint64_t *read_offsets, uint64_t n_reads, const uint32_t *cand_seq, const int64_t *cand_diag, uint32_t band,
-                                            uint32_t flags, pgx_read_align *out, uint64_t *op_offsets, uint32_t *ops, uint64_t ops_cap) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_read_align_arrays");
-    checked_device_count();
-    const std::string who = "pgx_read_align_arrays";
-    align_check_args(who, band, flags);
-    const bool want_ops = (flags & PGX_ALIGN_CIGAR) != 0;
-    if (!seq_offsets || !read_offsets || (n_reads && (!out || !cand_seq || !cand_diag)) || (want_ops && (!op_offsets || (ops_cap && !ops))))
-        throw Error(PGX_ERR_ARG, who + ": null argument");
-    auto check_offsets = [&](const uint64_t *o, uint64_t k, const char *name, const char *item) {
-        if (o[0] != 0) throw Error(PGX_ERR_ARG, who + ": " + name + " must start at 0");
-        for (uint64_t i = 0; i < k; i++)
-            if (o[i] > o[i + 1]) throw Error(PGX_ERR_ARG, who + ": " + name + " decrease at " + item + " " + std::to_string(i));
-    };
-    check_offsets(seq_offsets, n_seq, "seq_offsets", "sequence");
-    check_offsets(read_offsets, n_reads, "read_offsets", "read");
-    const uint64_t n_text = seq_offsets[n_seq], read_bytes = read_offsets[n_reads];
-    if ((n_text && !text) || (read_bytes && !reads)) throw Error(PGX_ERR_ARG, who + ": null argument");
-    if (n_text >= (1ull << 32) - (1ull << 20)) throw Error(PGX_ERR_UNSUPPORTED, who + ": a text of " + std::to_string(n_text) + " symbols, the image holds fewer than 2^32 - 2^20");
-    for (uint64_t i = 0; i < n_text; i++) {
-        const uint8_t c = text[i];
-        if (c != '\n' && c != 'A' && c != 'C' && c != 'G' && c != 'N' && c != 'T')
-            throw Error(PGX_ERR_UNSUPPORTED, who + ": text byte " + std::to_string((unsigned)c) + " at offset " + std::to_string(i) + " is none of \\n A C G N T");
-    }
-    for (uint64_t r = 0; r < n_reads; r++)
-        if (cand_seq[r] != PGX_NO_SEQUENCE && cand_seq[r] >= n_seq)
-            throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " has a candidate whose sequence is not below n_seq " + std::to_string(n_seq));
-    if (n_reads >= PLACE_LAUNCH_ITEMS) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_reads) + " reads exceed one launch");
-    use_device(device);
-    uint32_t lg = 0;
-    while ((1u << lg) < 2 * band + 1) lg++;
-    const std::vector<AlignPass> plan = align_plan(read_offsets, n_reads, std::max(1u << lg, 8u) / 4, align_budget_bytes(free_device_memory()), who);
-    struct Work { // device copies of the input + the stage's buffers, released on every way out
-        DevBuf text8, text4, seq_off, reads, read_off;
-        AlignWork w;
-        ~Work() {
-            DevBuf *all[] = {&text8, &text4, &seq_off, &reads, &read_off};
-            for (DevBuf *d : all) d->release();
-            w.release();
-        }
-    } k;
-    hipStream_t s = nullptr;
-    const uint64_t n_words = (n_text + 7) / 8 + PGX_TEXT_PAD_WORDS, n_rw = (read_bytes + 7) / 8 + 1;
-    upload(k.text8, text, n_text);
-    upload(k.seq_off, seq_offsets, (n_seq + 1) * 8);
-    upload(k.reads, reads, read_bytes);
-    upload(k.read_off, read_offsets, (n_reads + 1) * 8);
-    upload(k.w.cand_seq, cand_seq, n_reads * 4);
-    upload(k.w.cand_diag, cand_diag, n_reads * 8);
-    k.text4.ensure(n_words * 4);
-    k.w.rcode.ensure(n_rw * 4);
-    hipLaunchKernelGGL(pgx_text_pack_kernel, dim3((unsigned)std::min<uint64_t>((n_words + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint8_t *)k.text8.as<uint8_t>(), n_text, n_words,
-                       1u, k.text4.as<uint32_t>());
-    hipLaunchKernelGGL(pgx_verify_code_kernel, dim3((unsigned)std::min<uint64_t>((n_rw + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint8_t *)k.reads.as<uint8_t>(), read_bytes, n_rw,
-                       k.w.rcode.as<uint32_t>());
-    HIPCHECK(hipGetLastError());
-    align_core(k.w, k.text4.as<uint32_t>(), k.seq_off.as<uint64_t>(), 0u, (const uint32_t *)k.w.rcode.as<uint32_t>(), k.read_off.as<uint64_t>(), n_reads, plan, band, flags, false, s);
-    if (want_ops && k.w.n_ops > ops_cap)
-        throw Error(PGX_ERR_NOMEM, who + ": the list holds " + std::to_string(k.w.n_ops) + " operations, ops_cap is " + std::to_string(ops_cap));
-    if (n_reads) HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, n_reads * sizeof(pgx_read_align), hipMemcpyDeviceToHost, s));
-    if (want_ops) {
-        HIPCHECK(hipMemcpyAsync(op_offsets, k.w.op_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (k.w.n_ops) HIPCHECK(hipMemcpyAsync(ops, k.w.ops.p, k.w.n_ops * 4, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHECK(hipStreamSynchronize(s));
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-// ------------------------------------------------------------------------------------------
-// read walk (pgx_walk_kernels.hip; the definitions: include/pgx.h "read walk")
-static const uint32_t WALK_FLAGS = PGX_WALK_STEPS;
-
-// The stage on device arrays, enqueued on s (synchronised where the number of steps is read back): the align records, or seq / text_start / text_end
-// (n of each), -> w.recs, w.step_off and, with PGX_WALK_STEPS, w.steps.  Nothing here refuses.
-static void walk_core(WalkWork &w, const PgxWalkImage &img, const uint64_t *seq_start, uint32_t endmark, uint64_t n_seq, const pgx_read_align *recs, const uint32_t *seq,
-                      const uint64_t *text_start, const uint64_t *text_end, uint64_t n, uint32_t flags, hipStream_t s) {
-    w.recs.ensure((n ? n : 1) * sizeof(pgx_read_walk));
-    w.count.ensure((n ? n : 1) * 8); w.first.ensure((n ? n : 1) * 8); w.step_off.ensure((n + 1) * 8);
-    uint64_t n_steps = 0;
-    if (n) {
-        hipLaunchKernelGGL(pgx_walk_count_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, img, seq_start, endmark, n_seq, recs, seq, text_start, text_end, n,
-                           w.recs.as<pgx_read_walk>(), w.count.as<uint64_t>(), w.first.as<uint64_t>());
-        HIPCHECK(hipGetLastError());
-        scan_excl(1, w.count.p, n, 0, w.step_off.as<uint64_t>(), w.scan_tmp, s);
-        n_steps = read_u64(w.step_off.as<uint64_t>() + n, s); // (the stage's one read-back)
-    } else HIPCHECK(hipMemsetAsync(w.step_off.p, 0, 8, s));
-    if ((flags & PGX_WALK_STEPS) && n_steps) {
-        w.steps.ensure(n_steps * 8);
-        hipLaunchKernelGGL(pgx_walk_fill_kernel, dim3(grid_for(n, 256 / PGX_WALK_FILL_LANES)), dim3(256), 0, s, img, (const uint64_t *)w.count.as<uint64_t>(),
-                           (const uint64_t *)w.first.as<uint64_t>(), (const uint64_t *)w.step_off.as<uint64_t>(), n, w.steps.as<uint64_t>());
-        HIPCHECK(hipGetLastError());
-    }
-    HIPCHECK(hipStreamSynchronize(s));
-    w.n_reads = n; w.n_steps = n_steps; w.flags = flags;
-}
-
-extern "C" pgx_status pgx_batch_read_walk(pgx_batch *b, uint32_t flags, void *stream) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_batch_read_walk");
-    checked_device_count();
-    const std::string who = "pgx_batch_read_walk";
-    if (!b) throw Error(PGX_ERR_ARG, who + ": null batch");
-    // (what is refused here leaves an earlier walk result as it was)
-    if (flags & ~WALK_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
-    if (!b->ran) throw Error(PGX_ERR_ARG, who + ": batch has not been run");
-    AlignWork &aw = b->aw;
-    if (!aw.valid || aw.n_reads != b->n_reads) throw Error(PGX_ERR_ARG, who + ": needs a completed pgx_batch_read_align, the batch has no align result");
-    const uint64_t n = b->n_reads;
-    if (n >= PLACE_LAUNCH_ITEMS / PGX_WALK_FILL_LANES) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n) + " reads exceed one launch");
-    use_device(b->device);
-    pgx_device_image *d = device_image(b->h, b->device);
-    ensure_walk(b->h, d); // (throws before anything of the batch changes)
-    hipStream_t s = stream ? (hipStream_t)stream : b->own;
-    WalkWork &w = b->ww;
-    w.valid = false;
-    const bool timed = b->timed;
-    if (timed) {
-        for (auto &e : w.ev)
-            if (!e) HIPCHECK(hipEventCreate(&e));
-        HIPCHECK(hipEventRecord(w.ev[0], s));
-    }
-    walk_core(w, d->walk, d->text_seq_start.as<uint64_t>(), 1u, d->text_n_seq, (const pgx_read_align *)aw.recs.as<pgx_read_align>(), nullptr, nullptr, nullptr, n, flags, s);
-    w.ms = 0;
-    if (timed) {
-        HIPCHECK(hipEventRecord(w.ev[1], s));
-        HIPCHECK(hipStreamSynchronize(s));
-        HIPCHECK(hipEventElapsedTime(&w.ms, w.ev[0], w.ev[1]));
-    }
-    w.valid = true;
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-static void walked_header(const pgx_batch *b, pgx_read_walks *out) {
-    const WalkWork &w = b->ww;
-    std::memset(out, 0, sizeof *out);
-    out->n_reads = w.n_reads;
-    out->n_steps = w.n_steps;
-    out->flags = w.flags;
-    out->ms_walk = w.ms;
-}
-
-extern "C" pgx_status pgx_batch_device_walked(pgx_batch *b, pgx_read_walks *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->ww.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_walked: batch has no walk result");
-    const WalkWork &w = b->ww;
-    walked_header(b, out);
-    out->reads = w.recs.as<pgx_read_walk>();
-    if (w.flags & PGX_WALK_STEPS) {
-        out->step_offsets = w.step_off.as<uint64_t>();
-        out->steps = w.steps.as<uint64_t>();
-    }
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_batch_walked(pgx_batch *b, pgx_read_walks *out) {
-    PGX_GUARD_BEGIN
-    if (!b || !out || !b->ww.valid) throw Error(PGX_ERR_ARG, "pgx_batch_walked: batch has no walk result");
-    use_device(b->device);
-    WalkWork &w = b->ww;
-    const uint64_t n = w.n_reads;
-    const bool list = (w.flags & PGX_WALK_STEPS) != 0;
-    w.h_recs.ensure((n ? n : 1) * sizeof(pgx_read_walk));
-    if (n) HIPCHECK(hipMemcpyAsync(w.h_recs.p, w.recs.p, n * sizeof(pgx_read_walk), hipMemcpyDeviceToHost, b->own));
-    if (list) {
-        w.h_step_off.ensure((n + 1) * 8);
-        w.h_steps.ensure((w.n_steps ? w.n_steps : 1) * 8);
-        HIPCHECK(hipMemcpyAsync(w.h_step_off.p, w.step_off.p, (n + 1) * 8, hipMemcpyDeviceToHost, b->own));
-        if (w.n_steps) HIPCHECK(hipMemcpyAsync(w.h_steps.p, w.steps.p, w.n_steps * 8, hipMemcpyDeviceToHost, b->own));
-    }
-    HIPCHECK(hipStreamSynchronize(b->own)); // (the stage completed inside pgx_batch_read_walk, on whatever stream it used)
-    walked_header(b, out);
-    out->reads = w.h_recs.as<pgx_read_walk>();
-    if (list) {
-        out->step_offsets = w.h_step_off.as<uint64_t>();
-        out->steps = w.h_steps.as<uint64_t>();
-    }
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
-extern "C" pgx_status pgx_read_walk_arrays(int device, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
-                                           const uint32_t *visit_length, uint64_t n_reads, const uint32_t *seq, const uint64_t *text_start, const uint64_t *text_end,
-                                           uint32_t flags, pgx_read_walk *out, uint64_t *step_offsets, uint64_t *steps, uint64_t steps_cap) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_read_walk_arrays");
-    checked_device_count();
-    const std::string who = "pgx_read_walk_arrays";
-    if (flags & ~WALK_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
-    const bool want_steps = (flags & PGX_WALK_STEPS) != 0;
-    if (!seq_offsets || !visit_offsets || (n_reads && (!out || !seq || !text_start || !text_end)) || (want_steps && (!step_offsets || (steps_cap && !steps))))
-        throw Error(PGX_ERR_ARG, who + ": null argument");
-    auto check_offsets = [&](const uint64_t *o, uint64_t k, const char *name) {
-        if (o[0] != 0) throw Error(PGX_ERR_ARG, who + ": " + name + " must start at 0");
-        for (uint64_t i = 0; i < k; i++)
-            if (o[i] > o[i + 1]) throw Error(PGX_ERR_ARG, who + ": " + name + " decrease at sequence " + std::to_string(i));
-    };
-    check_offsets(seq_offsets, n_seq, "seq_offsets");
-    check_offsets(visit_offsets, n_seq, "visit_offsets");
-    const uint64_t n_text = seq_offsets[n_seq], V = visit_offsets[n_seq];
-    if (V && (!visit_nodes || !visit_length)) throw Error(PGX_ERR_ARG, who + ": null argument");
-    if (n_text >= (1ull << 32) - (1ull << 20)) throw Error(PGX_ERR_UNSUPPORTED, who + ": a text of " + std::to_string(n_text) + " symbols, the image holds fewer than 2^32 - 2^20");
-    std::vector<uint64_t> marks(V);
-    for (uint64_t q = 0; q < n_seq; q++) {
-        uint64_t p = seq_offsets[q];
-        for (uint64_t k = visit_offsets[q]; k < visit_offsets[q + 1]; k++) {
-            if (visit_length[k] == 0 || visit_length[k] > PGX_WALK_MAX_VISIT)
-                throw Error(PGX_ERR_ARG, who + ": visit " + std::to_string(k) + " of sequence " + std::to_string(q) + " has length " + std::to_string(visit_length[k]) + ", outside 1 .. 1024");
-            marks[k] = p;
-            p += visit_length[k];
-        }
-        if (p != seq_offsets[q + 1])
-            throw Error(PGX_ERR_ARG, who + ": the visits of sequence " + std::to_string(q) + " sum to " + std::to_string(p - seq_offsets[q]) + " symbols, the sequence has " +
-                                         std::to_string(seq_offsets[q + 1] - seq_offsets[q]));
-    }
-    for (uint64_t r = 0; r < n_reads; r++) {
-        if (seq[r] == PGX_NO_SEQUENCE) continue;
-        if (seq[r] >= n_seq) throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " names a sequence that is not below n_seq " + std::to_string(n_seq));
-        const uint64_t ls = seq_offsets[(uint64_t)seq[r] + 1] - seq_offsets[seq[r]];
-        if (text_start[r] > text_end[r] || text_end[r] > ls)
-            throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " has the stretch [" + std::to_string(text_start[r]) + ", " + std::to_string(text_end[r]) +
-                                         "), its sequence has " + std::to_string(ls) + " symbols");
-    }
-    if (n_reads >= PLACE_LAUNCH_ITEMS / PGX_WALK_FILL_LANES) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_reads) + " reads exceed one launch");
-    use_device(device);
-    struct Work { // device copies of the input, the image + the stage's buffers, released on every way out
-        DevBuf seq_off, marks, bits, dir, nodes, counts, seq, ts, te;
-        WalkWork w;
-        ~Work() {
-            DevBuf *all[] = {&seq_off, &marks, &bits, &dir, &nodes, &counts, &seq, &ts, &te};
-            for (DevBuf *d : all) d->release();
-            w.release();
-        }
-    } k;
-    hipStream_t s = nullptr;
-    const uint64_t n_blocks = n_text / PGX_WALK_BLOCK_BITS + 1, n_words = n_blocks * PGX_WALK_BLOCK_WORDS;
-    upload(k.seq_off, seq_offsets, (n_seq + 1) * 8);
-    upload(k.marks, marks.data(), V * 8);
-    upload(k.nodes, visit_nodes, V * 8);
-    upload(k.seq, seq, n_reads * 4);
-    upload(k.ts, text_start, n_reads * 8);
-    upload(k.te, text_end, n_reads * 8);
-    k.bits.ensure(n_words * 8); k.dir.ensure((n_blocks + 1) * 8);
-    HIPCHECK(hipMemsetAsync(k.bits.p, 0, n_words * 8, s));
-    if (V) {
-        hipLaunchKernelGGL(pgx_walk_set_kernel, dim3((unsigned)std::min<uint64_t>((V + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint64_t *)k.marks.as<uint64_t>(), V, k.bits.as<uint32_t>());
-        HIPCHECK(hipGetLastError());
-    }
-    walk_directory(k.bits.as<uint64_t>(), n_blocks, k.counts, k.dir.as<uint64_t>(), k.w.scan_tmp, s);
-    const PgxWalkImage img{k.bits.as<uint64_t>(), k.dir.as<uint64_t>(), k.nodes.as<uint64_t>(), n_text, n_words, n_blocks, V};
-    walk_core(k.w, img, k.seq_off.as<uint64_t>(), 0u, n_seq, nullptr, (const uint32_t *)k.seq.as<uint32_t>(), (const uint64_t *)k.ts.as<uint64_t>(),
-              (const uint64_t *)k.te.as<uint64_t>(), n_reads, flags, s);
-    if (want_steps && k.w.n_steps > steps_cap)
-        throw Error(PGX_ERR_NOMEM, who + ": the list holds " + std::to_string(k.w.n_steps) + " steps, steps_cap is " + std::to_string(steps_cap));
-    if (n_reads) HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, n_reads * sizeof(pgx_read_walk), hipMemcpyDeviceToHost, s));
-    if (want_steps) {
-        HIPCHECK(hipMemcpyAsync(step_offsets, k.w.step_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (k.w.n_steps) HIPCHECK(hipMemcpyAsync(steps, k.w.steps.p, k.w.n_steps * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHECK(hipStreamSynchronize(s));
-    return PGX_OK;
-    PGX_GUARD_END
-}
-
 extern "C" pgx_status pgx_find_mems_batch(pgx_index *h, int device, const uint8_t *reads, const uint64_t *offsets,
                                           uint64_t n_reads, uint64_t min_len, uint64_t min_occ, uint32_t flags,
                                           pgx_batch **batch_out, pgx_result *result_out) {

@@ -1,5 +1,5 @@
 // pgx_compact.cpp -- host side of the compact result form (include/pgx.h "compact result"): pgx_compact_expand, pgx_compact_bound.
-// No device, no HIP: the encoder is pgx_compact_kernels.hip, its host glue is in pgx_batch.hip.
+// No device, no HIP: the encoder is pgx_compact_kernels.hip, its host glue is in pgx_batch_forms.hip.
 #include <new>
 #include <string>
 

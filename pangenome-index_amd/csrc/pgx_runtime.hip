@@ -1,7 +1,8 @@
 // pgx_runtime.hip -- the small things behind the C ABI that every host unit of the runtime uses: device selection, pinned host memory,
 // roctx, the device-wide exclusive scan and the scalar read-back; the r-index locate entry points; and the per-call entry points
-// (rank, extend, count, lf, find_mems_function, tag_query).  The device images are in pgx_images.hip, the batch pipeline in pgx_batch.hip,
-// merge_tags / build_tags in pgx_tools.hip; pgx_runtime_internal.hpp is what they share.
+// (rank, extend, count, lf, find_mems_function, tag_query).  The device images are in pgx_images.hip, the batch pipeline in pgx_batch.hip
+// (its other result forms, its locate and the read stages in pgx_batch_forms.hip, pgx_batch_locate.hip, pgx_read_stages.hip), merge_tags / build_tags
+// in pgx_tools.hip; pgx_runtime_internal.hpp is what they share.
 #include <dlfcn.h>
 
 #include <string>

@@ -1,5 +1,5 @@
-// pgx_runtime_internal.hpp -- what the host units of the runtime share (pgx_runtime.hip, pgx_images.hip, pgx_batch.hip, pgx_tools.hip):
-// roctx ranges, the small launch helpers, the device image of an index, the tag stage and the work buffers of the batch.
+// pgx_runtime_internal.hpp -- what the host units of the runtime share (pgx_runtime.hip, pgx_images.hip, pgx_tools.hip, and through
+// pgx_batch_internal.hpp the units of the batch): roctx ranges, the small launch helpers, the device image of an index and the tag stage.
 // Nothing here is part of the C ABI, and nothing is exported from libpgx.so.
 #pragma once
 
@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <vector>
 
 #include "pgx_device.h"
@@ -112,6 +113,14 @@ inline unsigned grid_for(uint64_t n, unsigned per_block) {
     return (unsigned)g;
 }
 
+// what every release() is made of: the buffers of a brace list, the events of an array or a vector (destroyed and forgotten)
+inline void release_all(std::initializer_list<DevBuf *> bufs) { for (DevBuf *d : bufs) d->release(); }
+inline void release_all(std::initializer_list<HostBuf *> bufs) { for (HostBuf *h : bufs) h->release(); }
+template <class Events> void destroy_events(Events &ev) {
+    for (auto &e : ev)
+        if (e) { (void)hipEventDestroy(e); e = nullptr; }
+}
+
 // ------------------------------------------------------------------------------------------
 // tag pipeline shared by pgx_batch_run and pgx_tag_query_batch
 // per query: run_nums (a result array) and uval (pgx_tag_locate_kernel); per list entry: a record (PgxTagRec).  need / scratch_off / scratch: global
@@ -124,125 +133,7 @@ struct TagWork {
     uint64_t last_G = 0, last_P = 0, last_small = 0, last_big = 0, last_large = 0, last_largest = 0, last_rep = 0, last_dup = 0;
     bool have_last = false;
     void release() {
-        DevBuf *all[] = {&run_nums, &uval, &gbuf, &need, &scratch_off, &scratch, &pos_off, &positions, &small_recs, &big_recs, &large_recs,
-                         &scan_tmp, &dedup, &dd_table};
-        for (DevBuf *d : all) d->release();
-    }
-};
-
-// pgx_batch_locate's buffers (grow-only, kept with the batch like its other result buffers) and its result
-struct LocWork {
-    DevBuf cnt, qs, qe, voff, uoff, vals, gbuf, run0, npieces, poff, seg, lists, need, soff, scratch, ucount, uloc, ctr, scan_tmp, sets;
-    HostBuf h_off, h_vals;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool valid = false, resident = false;
-    uint32_t flags = 0, set_words = 0; // set_words: W when the call built sequence sets (the set form, or the unique ids expanded from them)
-    uint64_t n_mems = 0, n_values = 0, n_not_located = 0;
-    const uint64_t *d_off = nullptr; // voff, or uoff with PGX_LOCATE_UNIQUE / PGX_LOCATE_SEQ_SETS
-    float ms = 0;
-    void release() {
-        DevBuf *all[] = {&cnt, &qs, &qe, &voff, &uoff, &vals, &gbuf, &run0, &npieces, &poff, &seg, &lists, &need, &soff, &scratch, &ucount, &uloc, &ctr, &scan_tmp, &sets};
-        for (DevBuf *d : all) d->release();
-        h_off.release(); h_vals.release();
-        for (auto &e : ev)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        valid = false;
-    }
-};
-
-// pgx_batch_read_hits' buffers (grow-only) and its result; pgx_read_hits_arrays uses one of its own
-struct HitsWork {
-    DevBuf hits, best_sets, scores, bad;
-    HostBuf h_hits, h_best_sets, h_scores;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool valid = false;
-    uint32_t flags = 0, set_words = 0;
-    uint64_t n_reads = 0, n_seq = 0;
-    float ms = 0;
-    void release() {
-        DevBuf *all[] = {&hits, &best_sets, &scores, &bad};
-        for (DevBuf *d : all) d->release();
-        h_hits.release(); h_best_sets.release(); h_scores.release();
-        for (auto &e : ev)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        valid = false;
-    }
-};
-
-// pgx_batch_read_place's buffers (grow-only, its own: a later locate leaves them alone) and its result; pgx_read_place_arrays uses one of its own
-struct PlaceWork {
-    DevBuf recs, pcount, place_off, places, aoff, acnt, mfirst, keys, seg, lists, need, soff, scratch, ucount, loff, ctr, scan_tmp, bad;
-    HostBuf h_recs, h_place_off, h_places;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool valid = false;
-    uint32_t flags = 0, n_passes = 0;
-    uint64_t n_reads = 0, n_anchors = 0, n_places = 0;
-    float ms = 0;
-    void release() {
-        DevBuf *all[] = {&recs, &pcount, &place_off, &places, &aoff, &acnt, &mfirst, &keys, &seg, &lists, &need, &soff, &scratch, &ucount, &loff, &ctr, &scan_tmp, &bad};
-        for (DevBuf *d : all) d->release();
-        h_recs.release(); h_place_off.release(); h_places.release();
-        for (auto &e : ev)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        valid = false;
-    }
-};
-
-// pgx_batch_read_verify's buffers (grow-only, its own: a later locate leaves them alone) and its result; pgx_read_verify_arrays uses one of its own
-struct VerifyWork {
-    DevBuf recs, count, cand_off, cand_seq, cand_diag, cand_read, cands, rcode, scan_tmp, bad;
-    HostBuf h_recs, h_cand_off, h_cands;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool valid = false;
-    uint32_t flags = 0, max_cand = 0, penalty = 0;
-    uint64_t n_reads = 0, n_cands = 0;
-    float ms = 0;
-    void release() {
-        DevBuf *all[] = {&recs, &count, &cand_off, &cand_seq, &cand_diag, &cand_read, &cands, &rcode, &scan_tmp, &bad};
-        for (DevBuf *d : all) d->release();
-        h_recs.release(); h_cand_off.release(); h_cands.release();
-        for (auto &e : ev)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        valid = false;
-    }
-};
-
-// pgx_batch_read_align's buffers (grow-only, its own) and its result; pgx_read_align_arrays uses one of its own
-struct AlignWork {
-    DevBuf recs, cand_seq, cand_diag, need, plane_off, planes, fwd, count, op_off, ops, rcode, scan_tmp;
-    HostBuf h_recs, h_op_off, h_ops;
-    std::vector<hipEvent_t> ev; // [0], [1]: around the call; then a pair a launch of the forward and of the trace kernel
-    bool valid = false;
-    uint32_t flags = 0, band = 0, passes = 0;
-    uint64_t n_reads = 0, n_ops = 0, scratch_bytes = 0;
-    float ms = 0, ms_forward = 0, ms_trace = 0;
-    void release() {
-        DevBuf *all[] = {&recs, &cand_seq, &cand_diag, &need, &plane_off, &planes, &fwd, &count, &op_off, &ops, &rcode, &scan_tmp};
-        for (DevBuf *d : all) d->release();
-        h_recs.release(); h_op_off.release(); h_ops.release();
-        for (auto &e : ev)
-            if (e) (void)hipEventDestroy(e);
-        ev.clear();
-        valid = false;
-    }
-};
-
-// pgx_batch_read_walk's buffers (grow-only, its own) and its result; pgx_read_walk_arrays uses one of its own
-struct WalkWork {
-    DevBuf recs, count, first, step_off, steps, scan_tmp;
-    HostBuf h_recs, h_step_off, h_steps;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool valid = false;
-    uint32_t flags = 0;
-    uint64_t n_reads = 0, n_steps = 0;
-    float ms = 0;
-    void release() {
-        DevBuf *all[] = {&recs, &count, &first, &step_off, &steps, &scan_tmp};
-        for (DevBuf *d : all) d->release();
-        h_recs.release(); h_step_off.release(); h_steps.release();
-        for (auto &e : ev)
-            if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        valid = false;
+        release_all({&run_nums, &uval, &gbuf, &need, &scratch_off, &scratch, &pos_off, &positions, &small_recs, &big_recs, &large_recs, &scan_tmp, &dedup, &dd_table});
     }
 };
 
