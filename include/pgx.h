@@ -837,6 +837,7 @@ pgx_status pgx_read_place_arrays(int device, const uint64_t *mem_offsets, uint64
  *   56 cand_index                the winner's ordinal among the candidates (in the list: this candidate's ordinal)
  *   60 n_tied                    candidates that equal the winner in (seg_score, matches), the winner included (in the list: 0)
  * PGX_VERIFY_LIST adds cand_offsets[n_reads + 1] and one such record per candidate, in candidate order.
+ * A pgx_batch_read_mates call with PGX_MATES_ELECT rewrites the winner records of the batch with the candidates the pairs chose ("read mates").
  * Reads of 2^31 bytes or more are PGX_ERR_UNSUPPORTED. */
 #define PGX_VERIFY_LIST 1u
 #define PGX_VERIFY_MAX_CAND 64u
@@ -884,6 +885,91 @@ pgx_status pgx_read_verify_arrays(int device, const uint8_t *text, const uint64_
                                   const uint64_t *read_offsets, uint64_t n_reads, const uint64_t *cand_offsets, const uint32_t *cand_seq,
                                   const int64_t *cand_diag, uint32_t mismatch_penalty, uint32_t flags, pgx_read_verify *out,
                                   uint64_t *list_offsets, pgx_read_verify *list, uint64_t list_cap);
+
+/* ---- read mates: the two reads of a pair choose their placements together, on the device --------------------------------------------
+ * Short reads come in pairs: two reads from the two ends of one fragment, facing each other, a few hundred bases apart.  A read that lies
+ * inside an exact repeat ties between the copies in place and in verify; its mate, placed uniquely nearby, settles it.  This stage looks
+ * at the verify candidates of both mates and lets the pair choose.  It sits between verify and align and reads nothing but verify's list.
+ *
+ * DEFINITIONS.  Reads 2k and 2k + 1 of a batch are mates A and B of pair k.  Read r has the candidates of the verify list, in candidate
+ * order, each with (seq, diag, seg_score, matches).  Sequence q has L[q] symbols, without its endmarker.
+ *   twins        the index is twinned iff n_seq is even and L[2p] == L[2p + 1] for every p: a collection that holds path p forward as
+ *                sequence 2p and reversed as 2p + 1 (gbz_extract -b).  A forward / reverse pair lands on twin sequences.
+ *   compatible   candidate i of A and candidate j of B are compatible iff seq_i ^ 1 == seq_j and frag_min <= frag <= frag_max, with
+ *                frag = L[seq_i] - diag_i - diag_j, signed 64-bit and symmetric in A and B (|diag| stays below 2^62).  For the fragment
+ *                [f, f + I) of path p, A its first la bases on 2p at diag f, B the reverse complement of its last lb bases on 2p + 1 at
+ *                diag L - f - I, this is frag = I; a fragment from the other strand swaps the roles and gives the same value.
+ *   solo winner  verify's WINNER rule recomputed from the list (largest seg_score, then most matches, then the first), not read from the
+ *                winner records: a second call on the same verify result gives the same answer after an election.
+ *   best pair    the compatible pair with the largest seg_score_i + seg_score_j, then the largest matches_i + matches_j, then the
+ *                smallest i, then the smallest j.  n_compatible counts the compatible pairs, n_best those that equal the best in both
+ *                sums, next_score is the largest score sum of a compatible pair below the best one's, 0 if there is none.  Sums are
+ *                formed and compared in 64 bits; a stored sum is held at 2^32 - 1 (verify's own records cannot reach it).
+ *   PROPER       with the unpaired penalty U: a compatible pair exists and pair_score + U >= solo_score, in 64 bits.  The solo winners
+ *                always score at least as much as any pair; U is what a user pays in seg_score to keep the mates together.  A PROPER
+ *                pair chooses the best pair's candidates; without PROPER each mate keeps its solo winner.
+ * Like place's and verify's reductions the best pair is a monoid -- (best key (score sum, matches sum, i, j), the count of pairs equal to
+ * it in both sums, the best score sum below it, the count of all) merges associatively and commutatively --, so a kernel may split the
+ * i x j grid any way it likes.
+ * pgx_read_mates (64 bytes, little endian, one per pair):
+ *    0 frag i64          frag of the best pair when one is compatible, else 0
+ *    8 pair_score u32    seg_score sum of the best compatible pair         12 solo_score u32    seg_score sum of the two solo winners
+ *   16 cand_a u32        ordinal of the chosen candidate of A: the best pair's if PROPER, else the solo winner's; 0 for a mate without one
+ *   20 cand_b u32        the same for B
+ *   24 solo_a  28 solo_b u32   ordinals of the solo winners (0 without a candidate)
+ *   32 n_compatible  36 n_best  40 next_score u32   see above
+ *   44 pair_matches u32  matches sum of the best compatible pair
+ *   48 seq_a  52 seq_b u32    sequence of the chosen candidate; PGX_NO_SEQUENCE without one
+ *   56 flags u32         PGX_MATES_PROPER, _COMPATIBLE, _HAS_A, _HAS_B (the mate has a candidate), _MOVED_A, _MOVED_B (chosen != solo)
+ *   60 reserved u32      0
+ * PGX_MATES_ELECT makes the chosen candidates the winners: the verify winner record of every read is overwritten with the list record of
+ * its chosen candidate, n_cand set to the read's candidate count, cand_index to the chosen ordinal and n_tied to the number of the read's
+ * candidates that equal the chosen one in (seg_score, matches), the chosen one included.  Reads whose chosen candidate is their solo
+ * winner get the bytes they had.  pgx_batch_read_align and pgx_batch_read_walk then work on the elected winners.  Without the flag the
+ * verify result is untouched. */
+#define PGX_MATES_ELECT 1u
+#define PGX_MATES_PROPER 1u     /* bits of pgx_read_mates.flags */
+#define PGX_MATES_COMPATIBLE 2u
+#define PGX_MATES_HAS_A 4u
+#define PGX_MATES_HAS_B 8u
+#define PGX_MATES_MOVED_A 16u
+#define PGX_MATES_MOVED_B 32u
+typedef struct {
+    int64_t frag;
+    uint32_t pair_score, solo_score, cand_a, cand_b, solo_a, solo_b, n_compatible, n_best, next_score, pair_matches, seq_a, seq_b, flags, reserved;
+} pgx_read_mates;
+typedef struct {
+    uint64_t n_pairs;
+    uint64_t n_proper, n_compatible, n_moved_a, n_moved_b; /* pairs with the flag, summed on the device */
+    int64_t frag_min, frag_max;   /* what the call ran with */
+    uint32_t flags;               /* PGX_MATES_ELECT or 0 */
+    uint32_t penalty;
+    const pgx_read_mates *pairs;  /* n_pairs */
+    float ms_mates;               /* device time of the call when the run had PGX_RUN_TIMING, else 0 */
+    uint32_t reserved;
+} pgx_read_mates_result;
+/* Whether the index is twinned (see above): *first_bad is 2^64 - 1 if it is, else the first p with L[2p] != L[2p + 1], or n_seq / 2 when
+ * n_seq is odd.  Builds the text image on `device` if it is not built (errors as pgx_index_text). */
+pgx_status pgx_index_twinned(pgx_index *h, int device, uint64_t *first_bad);
+/* Pairs the reads of the last run from the list of the last pgx_batch_read_verify, which must be this run's and made with
+ * PGX_VERIFY_LIST.  PGX_ERR_ARG with nothing changed, naming what was found: no such verify result, an unknown flag, frag_min > frag_max,
+ * an odd read count.  PGX_ERR_UNSUPPORTED naming the first p that breaks it when the index is not twinned.  A pair takes the smallest
+ * power of two of lanes that is at least the verify call's max_cand (PGX_MATES_LANES in the environment, read per call, 1 .. 64, raises
+ * it; results never depend on it).  Runs on `stream` (NULL = the batch's own), complete on return.  Buffers grow only and are the stage's
+ * own: the result stays valid until the next run, upload, pgx_batch_read_mates or free of the batch, and a later pgx_batch_locate of any
+ * form leaves it valid. */
+pgx_status pgx_batch_read_mates(pgx_batch *b, int64_t frag_min, int64_t frag_max, uint32_t penalty, uint32_t flags, void *stream);
+/* Host copy of the last mates result (a pinned buffer owned by the batch) / the same as a device pointer.  PGX_ERR_ARG when there is none. */
+pgx_status pgx_batch_mated(pgx_batch *b, pgx_read_mates_result *out);
+pgx_status pgx_batch_device_mated(pgx_batch *b, pgx_read_mates_result *out);
+/* The same kernel on stated lists (how shapes no index produces are tested): seq_lengths[n_seq]; cand_offsets[n_reads + 1] into cands, list
+ * records of pgx_read_verify of which seq, diag, seg_score and matches are read (and all 64 bytes copied with PGX_MATES_ELECT).  `out`
+ * takes n_reads / 2 records; `winners` takes n_reads records with PGX_MATES_ELECT and may be NULL without it.  PGX_ERR_ARG with nothing
+ * written, the first offender named: an unknown flag, frag_min > frag_max, an odd n_seq, unequal twin lengths, offsets that do not start
+ * at 0 or decrease, more than 64 candidates for a read, a seq >= n_seq, an odd n_reads.  PGX_ERR_NO_DEVICE without a GPU. */
+pgx_status pgx_read_mates_arrays(int device, const uint64_t *seq_lengths, uint64_t n_seq, uint64_t n_reads, const uint64_t *cand_offsets,
+                                 const pgx_read_verify *cands, int64_t frag_min, int64_t frag_max, uint32_t penalty, uint32_t flags,
+                                 pgx_read_mates *out, pgx_read_verify *winners);
 
 /* ---- read align: every read aligned with gaps at its verified placement, on the device -------------------------------------------
  * Verify knows only substitutions: a read with a one-base insertion or deletion places on two neighbouring diagonals, each covering part of

@@ -33,6 +33,7 @@ static void batch_release(pgx_batch *b) {
         b->hw.release();
         b->pw.release();
         b->vw.release();
+        b->mw.release();
         b->aw.release();
         b->ww.release();
         release_all({&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]});
@@ -57,6 +58,7 @@ static void batch_reset_for_upload(pgx_batch *b, uint64_t n_reads, uint64_t max_
     b->hw.valid = false;
     b->pw.valid = false;
     b->vw.valid = false;
+    b->mw.valid = false;
     b->aw.valid = false;
     b->ww.valid = false;
     b->plan_valid = false;
@@ -987,6 +989,7 @@ extern "C" pgx_status pgx_batch_run(pgx_batch *b, uint64_t min_len, uint64_t min
     b->hw.valid = false; // (and so do the hits)
     b->pw.valid = false; // (and the places)
     b->vw.valid = false; // (and what was verified at them)
+    b->mw.valid = false; // (and paired from that)
     b->aw.valid = false; // (and aligned there)
     b->ww.valid = false; // (and walked through the graph)
     b->n_mems = b->n_positions = b->n_ext = b->n_tag_overflow = 0;

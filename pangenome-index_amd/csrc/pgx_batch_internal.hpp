@@ -113,6 +113,22 @@ struct VerifyWork {
     }
 };
 
+// pgx_batch_read_mates' buffers (grow-only, its own) and its result; pgx_read_mates_arrays uses one of its own
+struct MatesWork {
+    DevBuf recs, ctr; // ctr: the four counters
+    HostBuf h_recs;
+    StageTimer timer;
+    bool valid = false;
+    uint32_t flags = 0, penalty = 0;
+    int64_t frag_min = 0, frag_max = 0;
+    uint64_t n_pairs = 0, counters[4] = {0, 0, 0, 0}; // pairs PROPER, COMPATIBLE, with A moved, with B moved
+    float ms = 0;
+    void release() {
+        release_all({&recs, &ctr});
+        release_all({&h_recs}); timer.release(); valid = false;
+    }
+};
+
 // pgx_batch_read_align's buffers (grow-only, its own) and its result; pgx_read_align_arrays uses one of its own
 struct AlignWork {
     DevBuf recs, cand_seq, cand_diag, need, plane_off, planes, fwd, count, op_off, ops, rcode, scan_tmp;
@@ -210,6 +226,7 @@ struct pgx_batch {
     HitsWork hw;    // pgx_batch_read_hits
     PlaceWork pw;   // pgx_batch_read_place
     VerifyWork vw;  // pgx_batch_read_verify
+    MatesWork mw;   // pgx_batch_read_mates
     AlignWork aw;   // pgx_batch_read_align
     WalkWork ww;    // pgx_batch_read_walk
     uint64_t n_mems = 0, n_positions = 0, n_ext = 0, n_tag_overflow = 0;

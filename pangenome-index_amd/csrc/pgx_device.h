@@ -426,6 +426,14 @@ __global__ void pgx_verify_kernel(const uint32_t *text4, const uint64_t *seq_sta
                                   uint32_t penalty, pgx_read_verify *out);
 __global__ void pgx_verify_reduce_kernel(const pgx_read_verify *cands, const uint64_t *cand_off, uint64_t n_reads, pgx_read_verify *out);
 
+// ---- pgx_mates_kernels.hip: read mates (pgx_batch_read_mates, pgx_read_mates_arrays)
+#define PGX_MATES_THREADS 256
+// 2^g_shift lanes a pair, at least the candidates of either mate; sequence q has seq_start[q + 1] - seq_start[q] - endmark symbols; winners: NULL without
+// PGX_MATES_ELECT; counters: pairs PROPER, COMPATIBLE, with A moved, with B moved (added to)
+__global__ void pgx_mates_kernel(const uint64_t *seq_start, uint32_t endmark, const uint64_t *cand_off, const pgx_read_verify *cands, uint64_t n_pairs, uint32_t g_shift,
+                                 int64_t frag_min, int64_t frag_max, uint32_t penalty, uint32_t flags, pgx_read_mates *out, pgx_read_verify *winners,
+                                 unsigned long long *counters);
+
 // ---- pgx_align_kernels.hip: read align (pgx_batch_read_align, pgx_read_align_arrays)
 #define PGX_ALIGN_THREADS 256
 __global__ void pgx_align_cand_kernel(const pgx_read_verify *recs, uint64_t n_reads, uint32_t *cand_seq, int64_t *cand_diag);

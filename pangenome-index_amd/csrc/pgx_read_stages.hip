@@ -1,4 +1,4 @@
-// pgx_read_stages.hip -- the read stages behind a run: hits, place, verify, align, walk.  Each is a core on device arrays with two entry points, one on
+// pgx_read_stages.hip -- the read stages behind a run: hits, place, verify, mates, align, walk.  Each is a core on device arrays with two entry points, one on
 // the batch (pgx_batch_read_X with its results pgx_batch_device_X / pgx_batch_X) and one on host arrays (pgx_read_X_arrays), and what they share comes first.
 // A batch entry point clears its `valid` only behind its last refusal, so that what it refuses leaves the result before as it was (hits differs: see there).
 #include <string>
@@ -707,6 +707,202 @@ extern "C" pgx_status pgx_read_verify_arrays(int device, const uint8_t *text, co
     verify_core(k.w, k.text4.as<uint32_t>(), k.seq_off.as<uint64_t>(), 0u, k.reads.as<uint8_t>(), read_bytes, k.read_off.as<uint64_t>(), n_reads, n_cands, mismatch_penalty, s);
     k.w.n_reads = n_reads; k.w.n_cands = n_cands; k.w.flags = flags;
     download_result(k.w.result(), out, list_offsets, list, s);
+    HIPCHECK(hipStreamSynchronize(s));
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// read mates (pgx_mates_kernels.hip; the definitions: include/pgx.h "read mates")
+static const uint32_t MATES_FLAGS = PGX_MATES_ELECT;
+
+static void mates_check_args(const std::string &who, int64_t frag_min, int64_t frag_max, uint32_t flags) {
+    if (flags & ~MATES_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
+    if (frag_min > frag_max) throw Error(PGX_ERR_ARG, who + ": frag_min " + std::to_string(frag_min) + " exceeds frag_max " + std::to_string(frag_max));
+}
+
+// the first p with L[2p] != L[2p + 1] (n_seq / 2 for an odd n_seq), ~0 when the collection is twinned; start: n_seq + 1 offsets
+// (with an endmarker behind every sequence or with none: both sides of a comparison carry it)
+static uint64_t first_untwinned(const uint64_t *start, uint64_t n_seq) {
+    for (uint64_t p = 0; 2 * p + 1 < n_seq; p++)
+        if (start[2 * p + 1] - start[2 * p] != start[2 * p + 2] - start[2 * p + 1]) return p;
+    return (n_seq & 1) ? n_seq / 2 : ~0ull;
+}
+
+bool index_twinned(pgx_device_image *d, uint64_t *first_bad) {
+    if (!d->twin_state) {
+        std::vector<uint64_t> start(d->text_n_seq + 1);
+        HIPCHECK(hipMemcpy(start.data(), d->text_seq_start.p, start.size() * 8, hipMemcpyDeviceToHost));
+        d->twin_bad = first_untwinned(start.data(), d->text_n_seq);
+        d->twin_state = d->twin_bad == ~0ull ? 1 : 2;
+    }
+    if (first_bad) *first_bad = d->twin_bad;
+    return d->twin_state == 1;
+}
+
+extern "C" pgx_status pgx_index_twinned(pgx_index *h, int device, uint64_t *first_bad) {
+    PGX_GUARD_BEGIN
+    checked_device_count();
+    if (!h || !first_bad) throw Error(PGX_ERR_ARG, "pgx_index_twinned: null argument");
+    use_device(device);
+    pgx_device_image *d = device_image(h, device);
+    ensure_text(h, d);
+    (void)index_twinned(d, first_bad);
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// log2 of the lanes a pair takes: the power of two >= max_cand, and >= PGX_MATES_LANES (tests; 1 .. 64, read per call).  Results never depend on it.
+// Refuses the pairs one launch cannot hold.
+static uint32_t mates_lane_shift(uint64_t n_pairs, uint64_t max_cand, const std::string &who) {
+    uint64_t want = std::max<uint64_t>(max_cand, 1);
+    if (const char *e = std::getenv("PGX_MATES_LANES")) {
+        const long v = std::strtol(e, nullptr, 10);
+        if (v >= 1 && v <= 64) want = std::max<uint64_t>(want, (uint64_t)v);
+    }
+    uint32_t sh = 0;
+    while ((1ull << sh) < want) sh++;
+    if (n_pairs >= (PLACE_LAUNCH_ITEMS >> sh)) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_pairs) + " pairs at " + std::to_string(1u << sh) + " lanes a pair exceed one launch");
+    return sh;
+}
+
+// The stage on device arrays, enqueued on s, the four counters read back behind it (synchronises s): w.recs, w.counters; winners: with PGX_MATES_ELECT.
+// No list is longer than max_cand <= 64.  Refuses a launch that is too large (the batch entry point has asked before it clears its result).
+static void mates_core(MatesWork &w, const uint64_t *seq_start, uint32_t endmark, const uint64_t *cand_off, const pgx_read_verify *cands, uint64_t n_pairs, uint64_t max_cand,
+                       int64_t frag_min, int64_t frag_max, uint32_t penalty, uint32_t flags, pgx_read_verify *winners, hipStream_t s, const std::string &who) {
+    const uint32_t g_shift = mates_lane_shift(n_pairs, max_cand, who);
+    w.recs.ensure((n_pairs ? n_pairs : 1) * sizeof(pgx_read_mates));
+    w.ctr.ensure(32);
+    HIPCHECK(hipMemsetAsync(w.ctr.p, 0, 32, s));
+    if (n_pairs) {
+        hipLaunchKernelGGL(pgx_mates_kernel, dim3(grid_for(n_pairs, PGX_MATES_THREADS >> g_shift)), dim3(PGX_MATES_THREADS), 0, s, seq_start, endmark, cand_off, cands, n_pairs,
+                           g_shift, frag_min, frag_max, penalty, flags, w.recs.as<pgx_read_mates>(), winners, w.ctr.as<unsigned long long>());
+        HIPCHECK(hipGetLastError());
+    }
+    w.n_pairs = n_pairs; w.flags = flags; w.penalty = penalty; w.frag_min = frag_min; w.frag_max = frag_max;
+}
+
+extern "C" pgx_status pgx_batch_read_mates(pgx_batch *b, int64_t frag_min, int64_t frag_max, uint32_t penalty, uint32_t flags, void *stream) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_read_mates");
+    checked_device_count();
+    const std::string who = "pgx_batch_read_mates";
+    if (!b) throw Error(PGX_ERR_ARG, who + ": null batch");
+    // (what is refused here leaves an earlier mates result and the verify result as they were)
+    mates_check_args(who, frag_min, frag_max, flags);
+    if (!b->ran) throw Error(PGX_ERR_ARG, who + ": batch has not been run");
+    VerifyWork &vw = b->vw;
+    if (!vw.valid || vw.n_reads != b->n_reads) throw Error(PGX_ERR_ARG, who + ": needs a completed pgx_batch_read_verify(PGX_VERIFY_LIST), the batch has no verify result");
+    if (!(vw.flags & PGX_VERIFY_LIST))
+        throw Error(PGX_ERR_ARG, who + ": needs a verify result made with PGX_VERIFY_LIST, the last pgx_batch_read_verify ran with flags " + std::to_string(vw.flags));
+    const uint64_t n = b->n_reads;
+    if (n & 1) throw Error(PGX_ERR_ARG, who + ": " + std::to_string(n) + " reads, an odd number: reads 2k and 2k + 1 are the mates of pair k");
+    use_device(b->device);
+    pgx_device_image *d = device_image(b->h, b->device);
+    ensure_text(b->h, d); // (built by the verify call)
+    uint64_t bad = 0;
+    if (!index_twinned(d, &bad))
+        throw Error(PGX_ERR_UNSUPPORTED, who + ": the index is not twinned, " +
+                                             ((d->text_n_seq & 1) && bad == d->text_n_seq / 2 ? "it has an odd number of sequences (" + std::to_string(d->text_n_seq) + ")"
+                                                                                                : "sequences " + std::to_string(2 * bad) + " and " + std::to_string(2 * bad + 1) +
+                                                                                                      " (p = " + std::to_string(bad) + ") differ in length") +
+                                             ": mates need a collection with every path forward and reversed (gbz_extract -b)");
+    (void)mates_lane_shift(n / 2, vw.max_cand, who); // (the last refusal: what is refused leaves an earlier mates result as it was)
+    hipStream_t s = batch_stream(b, stream);
+    MatesWork &w = b->mw;
+    w.valid = false;
+    w.timer.begin(b->timed, s);
+    mates_core(w, d->text_seq_start.as<uint64_t>(), 1u, vw.cand_off.as<uint64_t>(), vw.cands.as<pgx_read_verify>(), n / 2, vw.max_cand, frag_min, frag_max, penalty, flags,
+               (flags & PGX_MATES_ELECT) ? vw.recs.as<pgx_read_verify>() : nullptr, s, who);
+    w.ms = w.timer.end(s);
+    read_scalars(w.counters, w.ctr.p, 32, s); // (waits for the kernel: the call is complete on return)
+    w.valid = true;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+static void mated_header(const pgx_batch *b, pgx_read_mates_result *out) {
+    const MatesWork &w = b->mw;
+    std::memset(out, 0, sizeof *out);
+    out->n_pairs = w.n_pairs;
+    out->n_proper = w.counters[0]; out->n_compatible = w.counters[1]; out->n_moved_a = w.counters[2]; out->n_moved_b = w.counters[3];
+    out->frag_min = w.frag_min; out->frag_max = w.frag_max;
+    out->flags = w.flags;
+    out->penalty = w.penalty;
+    out->ms_mates = w.ms;
+}
+
+extern "C" pgx_status pgx_batch_device_mated(pgx_batch *b, pgx_read_mates_result *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->mw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_mated: batch has no mates result");
+    mated_header(b, out);
+    out->pairs = b->mw.recs.as<pgx_read_mates>();
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_batch_mated(pgx_batch *b, pgx_read_mates_result *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->mw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_mated: batch has no mates result");
+    use_device(b->device);
+    MatesWork &w = b->mw;
+    w.h_recs.ensure((w.n_pairs ? w.n_pairs : 1) * sizeof(pgx_read_mates));
+    if (w.n_pairs) HIPCHECK(hipMemcpyAsync(w.h_recs.p, w.recs.p, w.n_pairs * sizeof(pgx_read_mates), hipMemcpyDeviceToHost, b->own));
+    HIPCHECK(hipStreamSynchronize(b->own)); // (the kernel completed inside pgx_batch_read_mates, on whatever stream it used)
+    mated_header(b, out);
+    out->pairs = w.h_recs.as<pgx_read_mates>();
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_read_mates_arrays(int device, const uint64_t *seq_lengths, uint64_t n_seq, uint64_t n_reads, const uint64_t *cand_offsets, const pgx_read_verify *cands,
+                                            int64_t frag_min, int64_t frag_max, uint32_t penalty, uint32_t flags, pgx_read_mates *out, pgx_read_verify *winners) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_read_mates_arrays");
+    checked_device_count();
+    const std::string who = "pgx_read_mates_arrays";
+    mates_check_args(who, frag_min, frag_max, flags);
+    const bool elect = (flags & PGX_MATES_ELECT) != 0;
+    if ((n_seq && !seq_lengths) || !cand_offsets || (n_reads && (!out || (elect && !winners)))) throw Error(PGX_ERR_ARG, who + ": null argument");
+    if (n_seq & 1) throw Error(PGX_ERR_ARG, who + ": n_seq " + std::to_string(n_seq) + " is odd: sequences 2p and 2p + 1 are twins");
+    if (n_seq >= (1ull << 32) - 1) throw Error(PGX_ERR_ARG, who + ": n_seq " + std::to_string(n_seq) + " does not fit a record's seq");
+    std::vector<uint64_t> start(n_seq + 1, 0);
+    for (uint64_t q = 0; q < n_seq; q++) start[q + 1] = start[q] + seq_lengths[q];
+    if (const uint64_t bad = first_untwinned(start.data(), n_seq); bad != ~0ull)
+        throw Error(PGX_ERR_ARG, who + ": sequences " + std::to_string(2 * bad) + " and " + std::to_string(2 * bad + 1) + " (p = " + std::to_string(bad) + ") have the lengths " +
+                                     std::to_string(seq_lengths[2 * bad]) + " and " + std::to_string(seq_lengths[2 * bad + 1]) + ": twins have one length");
+    check_offsets(who, cand_offsets, n_reads, "cand_offsets", "read");
+    uint64_t max_cand = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t c = cand_offsets[r + 1] - cand_offsets[r];
+        if (c > PGX_VERIFY_MAX_CAND) throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " has " + std::to_string(c) + " candidates, more than " + std::to_string(PGX_VERIFY_MAX_CAND));
+        max_cand = std::max(max_cand, c);
+    }
+    const uint64_t n_cands = cand_offsets[n_reads];
+    if (n_cands && !cands) throw Error(PGX_ERR_ARG, who + ": null argument");
+    for (uint64_t r = 0; r < n_reads; r++)
+        for (uint64_t c = cand_offsets[r]; c < cand_offsets[r + 1]; c++)
+            if (cands[c].seq >= n_seq)
+                throw Error(PGX_ERR_ARG, who + ": candidate " + std::to_string(c - cand_offsets[r]) + " of read " + std::to_string(r) + " has seq " + std::to_string(cands[c].seq) +
+                                             ", not below n_seq " + std::to_string(n_seq));
+    if (n_reads & 1) throw Error(PGX_ERR_ARG, who + ": n_reads " + std::to_string(n_reads) + " is odd: reads 2k and 2k + 1 are the mates of pair k");
+    use_device(device);
+    struct MatesInput { // device copies of the input + the stage's buffers, released on every way out
+        DevBuf seq_start, cand_off, cands, winners;
+        MatesWork w;
+        ~MatesInput() { release_all({&seq_start, &cand_off, &cands, &winners}); w.release(); }
+    } k;
+    hipStream_t s = nullptr;
+    upload(k.seq_start, start.data(), (n_seq + 1) * 8);
+    upload(k.cand_off, cand_offsets, (n_reads + 1) * 8);
+    upload(k.cands, cands, n_cands * sizeof(pgx_read_verify));
+    if (elect) k.winners.ensure((n_reads ? n_reads : 1) * sizeof(pgx_read_verify));
+    mates_core(k.w, k.seq_start.as<uint64_t>(), 0u, k.cand_off.as<uint64_t>(), k.cands.as<pgx_read_verify>(), n_reads / 2, max_cand, frag_min, frag_max, penalty, flags,
+               elect ? k.winners.as<pgx_read_verify>() : nullptr, s, who);
+    if (n_reads) {
+        HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, (n_reads / 2) * sizeof(pgx_read_mates), hipMemcpyDeviceToHost, s));
+        if (elect) HIPCHECK(hipMemcpyAsync(winners, k.winners.p, n_reads * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, s));
+    }
     HIPCHECK(hipStreamSynchronize(s));
     return PGX_OK;
     PGX_GUARD_END

@@ -68,6 +68,8 @@ struct pgx_device_image {
     DevBuf text4, text_seq_start;                  // TEXT image (ensure_text), built on its first use: 4-bit symbols; n_seq + 1 text positions
     uint64_t text_n_seq = 0;
     bool has_text = false;
+    int twin_state = 0;                            // index_twinned: 0 not looked at, 1 twinned, 2 not (twin_bad: the first p with L[2p] != L[2p + 1])
+    uint64_t twin_bad = 0;
     DevBuf walk_bits, walk_dir, walk_nodes;        // WALK image (ensure_walk), built on its first use: marks, rank directory, node << 1 | rev of every visit
     PgxWalkImage walk{};
     bool has_walk = false;
@@ -85,6 +87,8 @@ pgx_device_image *locate_image(pgx_index *h, int device);
 pgx_device_image *literal_image(pgx_index *h, int device);
 void ensure_lce(pgx_index *h, pgx_device_image *d);
 void ensure_text(pgx_index *h, pgx_device_image *d); // throws where the image cannot be built (include/pgx.h pgx_index_text)
+// whether the collection holds every sequence next to a twin of its length (include/pgx.h "read mates"); needs the TEXT image; *first_bad as pgx_index_twinned
+bool index_twinned(pgx_device_image *d, uint64_t *first_bad);
 void ensure_walk(pgx_index *h, pgx_device_image *d); // builds the TEXT image too; throws where it cannot be built (include/pgx.h "read walk")
 // the rank directory of a WALK image over n_blocks blocks of marks: dir[n_blocks + 1] on stream s (counts: n_blocks u64 of scratch)
 void walk_directory(const uint64_t *bits, uint64_t n_blocks, DevBuf &counts, uint64_t *dir, DevBuf &scan_tmp, hipStream_t s);

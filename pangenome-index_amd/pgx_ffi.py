@@ -138,6 +138,19 @@ class ReadVerifies(C.Structure):  # pgx_read_verifies: host pointers (pgx_batch_
                 ("cand_offsets", p), ("cands", p), ("ms_verify", C.c_float), ("reserved2", u32)]
 
 
+MATES_ELECT = 1  # pgx_batch_read_mates / pgx_read_mates_arrays flag
+MATES_PROPER, MATES_COMPATIBLE, MATES_HAS_A, MATES_HAS_B, MATES_MOVED_A, MATES_MOVED_B = 1, 2, 4, 8, 16, 32  # bits of a record's flags
+MATES_DTYPE = np.dtype([("frag", "<i8"), ("pair_score", "<u4"), ("solo_score", "<u4"), ("cand_a", "<u4"), ("cand_b", "<u4"), ("solo_a", "<u4"), ("solo_b", "<u4"),
+                        ("n_compatible", "<u4"), ("n_best", "<u4"), ("next_score", "<u4"), ("pair_matches", "<u4"), ("seq_a", "<u4"), ("seq_b", "<u4"),
+                        ("flags", "<u4"), ("reserved", "<u4")])  # pgx_read_mates, 64 bytes
+assert MATES_DTYPE.itemsize == 64
+
+
+class ReadMatesResult(C.Structure):  # pgx_read_mates_result: a host pointer (pgx_batch_mated) or a device pointer (pgx_batch_device_mated)
+    _fields_ = [("n_pairs", u64), ("n_proper", u64), ("n_compatible", u64), ("n_moved_a", u64), ("n_moved_b", u64), ("frag_min", C.c_int64), ("frag_max", C.c_int64),
+                ("flags", u32), ("penalty", u32), ("pairs", p), ("ms_mates", C.c_float), ("reserved", u32)]
+
+
 ALIGN_CIGAR = 1  # pgx_batch_read_align / pgx_read_align_arrays flag
 ALIGN_DTYPE = np.dtype([("diag", "<i8"), ("text_start", "<u8"), ("text_end", "<u8"), ("seq", "<u4"), ("clip_lo", "<u4"), ("clip_hi", "<u4"), ("edits", "<u4"),
                         ("n_match", "<u4"), ("n_mismatch", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4"), ("n_ops", "<u4"), ("band_hit", "<u4")])  # pgx_read_align, 64 bytes
@@ -317,6 +330,11 @@ def lib():
     L.pgx_batch_aligned.argtypes = [p, C.POINTER(ReadAligns)]
     L.pgx_batch_device_aligned.argtypes = [p, C.POINTER(ReadAligns)]
     L.pgx_read_align_arrays.argtypes = [C.c_int, p, p, u64, p, p, u64, p, p, u32, u32, p, p, p, u64]
+    L.pgx_index_twinned.argtypes = [p, C.c_int, C.POINTER(u64)]
+    L.pgx_batch_read_mates.argtypes = [p, C.c_int64, C.c_int64, u32, u32, p]
+    L.pgx_batch_mated.argtypes = [p, C.POINTER(ReadMatesResult)]
+    L.pgx_batch_device_mated.argtypes = [p, C.POINTER(ReadMatesResult)]
+    L.pgx_read_mates_arrays.argtypes = [C.c_int, p, u64, u64, p, p, C.c_int64, C.c_int64, u32, u32, p, p]
     L.pgx_batch_read_walk.argtypes = [p, u32, p]
     L.pgx_batch_walked.argtypes = [p, C.POINTER(ReadWalks)]
     L.pgx_batch_device_walked.argtypes = [p, C.POINTER(ReadWalks)]
@@ -644,6 +662,12 @@ class Index:
         buf = np.zeros(int(inf.bwt_size), dtype=np.uint8)
         _check(self.L.pgx_index_text(self.h, device, lens.ctypes.data, len(lens), buf.ctypes.data, len(buf)))
         return lens, buf.tobytes()
+
+    def twinned(self, device=0):
+        """pgx_index_twinned: None when every sequence 2p has a twin 2p + 1 of its length (what read_mates needs), else the first p without"""
+        bad = u64(0)
+        _check(self.L.pgx_index_twinned(self.h, device, C.byref(bad)))
+        return None if bad.value == 2 ** 64 - 1 else int(bad.value)
 
     def paths(self, device=0):
         """pgx_index_paths: (path_offsets uint64[n_sequences + 1], path_nodes uint64[V] as node << 1 | rev, visit_length uint32[V]): the node list of
@@ -1005,6 +1029,25 @@ def read_verify_arrays(device, text, seq_offsets, reads, read_offsets, cand_offs
                                         cand_seq.ctypes.data, cand_diag.ctypes.data, penalty, flags, ptr(res["reads"]), ptr(res["cand_offsets"]), ptr(res["cands"]), cap))
     if lst:
         res["cands"] = res["cands"][: int(res["cand_offsets"][-1])]
+    return res
+
+
+def read_mates_arrays(device, seq_lengths, cand_offsets, cands, frag_min, frag_max, penalty, flags=0, n_reads=None, out=None):
+    """pgx_read_mates_arrays: the mates kernel on stated lists (seq_lengths uint64[n_seq]; the candidates of read r at [cand_offsets[r],
+    cand_offsets[r + 1]) of cands VERIFY_DTYPE, of which seq, diag, seg_score and matches count): dict(pairs MATES_DTYPE[n_reads / 2], and with
+    MATES_ELECT winners VERIFY_DTYPE[n_reads], else None).  n_reads: default len(cand_offsets) - 1; out: a dict of arrays to write into (tests)"""
+    seq_lengths = np.ascontiguousarray(seq_lengths, dtype=np.uint64)
+    cand_offsets = np.ascontiguousarray(cand_offsets, dtype=np.uint64)
+    cands = np.ascontiguousarray(cands, dtype=VERIFY_DTYPE)
+    n = len(cand_offsets) - 1 if n_reads is None else int(n_reads)
+    res = dict(out) if out else {}
+    if "pairs" not in res:
+        res["pairs"] = np.zeros(n // 2, dtype=MATES_DTYPE)
+    if "winners" not in res:
+        res["winners"] = np.zeros(n, dtype=VERIFY_DTYPE) if flags & MATES_ELECT else None
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().pgx_read_mates_arrays(device, seq_lengths.ctypes.data, len(seq_lengths), n, cand_offsets.ctypes.data, cands.ctypes.data, frag_min, frag_max, penalty, flags,
+                                       ptr(res["pairs"]), ptr(res["winners"])))
     return res
 
 
@@ -1416,6 +1459,32 @@ class Batch:
         out["reads"] = DeviceArray(r.reads, (n, 8), self)
         out["cand_offsets"] = DeviceArray(r.cand_offsets, (n + 1,), self) if r.cand_offsets else None
         out["cands"] = DeviceArray(r.cands, (k, 8), self) if r.cands else None
+        return out
+
+    def read_mates(self, frag_min, frag_max, penalty, flags=0, stream=None):
+        """pgx_batch_read_mates on the list of the last read_verify (made with VERIFY_LIST), then mated(); with MATES_ELECT the chosen candidates
+        become the verify winners"""
+        _check(self.L.pgx_batch_read_mates(self.b, frag_min, frag_max, penalty, flags, stream))
+        return self.mated()
+
+    def _mated(self, fn):
+        r = ReadMatesResult()
+        _check(fn(self.b, C.byref(r)))
+        return r, dict(n_pairs=int(r.n_pairs), n_proper=int(r.n_proper), n_compatible=int(r.n_compatible), n_moved_a=int(r.n_moved_a), n_moved_b=int(r.n_moved_b),
+                       frag_min=int(r.frag_min), frag_max=int(r.frag_max), flags=int(r.flags), penalty=int(r.penalty), ms_mates=float(r.ms_mates))
+
+    def mated(self):
+        """the last mates result: pairs MATES_DTYPE[n_pairs], with n_pairs, the four counters, frag_min, frag_max, flags, penalty, ms_mates"""
+        r, out = self._mated(self.L.pgx_batch_mated)
+        k = out["n_pairs"]
+        out["pairs"] = np.frombuffer((C.c_char * (k * 64)).from_address(r.pairs), dtype=MATES_DTYPE).copy() if k else np.zeros(0, MATES_DTYPE)
+        return out
+
+    def device_mated(self):
+        """the same with pairs as a device array (valid until the next run / upload / read_mates / free): int64[n_pairs, 8], the 64-byte records as words"""
+        r, out = self._mated(self.L.pgx_batch_device_mated)
+        out["device"] = True
+        out["pairs"] = DeviceArray(r.pairs, (out["n_pairs"], 8), self)
         return out
 
     def read_align(self, band=8, flags=0, stream=None):

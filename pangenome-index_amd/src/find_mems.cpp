@@ -27,6 +27,11 @@
 //                 --gaf FILE (one GAF line per read: the alignment as a walk through the graph, pgx_batch_read_walk; runs the place, verify and align
 //                 stages itself when they are not requested, with their options as there; stdout and stderr stay as they are), --gaf-only (no MEM
 //                 text, like --align-only)
+//                 --paired (the reads file is interleaved: records 2k and 2k + 1 are mates, in every --reads-format; an odd record count ends the run
+//                 with status 1; every batch holds whole pairs; runs place with its list, verify with its list -- --verify-max defaults to 16 --
+//                 and pgx_batch_read_mates with PGX_MATES_ELECT, so that --verify, --align and --gaf report the winners the pairs elected),
+//                 --frag-min A (default 0), --frag-max B (default 1000), --mates-penalty U (default 2 * (P + 1), P of --verify-mismatch),
+//                 --mates FILE (one line per pair), --mates-only (no MEM text, like --verify-only)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -160,6 +165,7 @@ struct Done {
     std::string verifies; // --verify: the lines of this batch
     std::string aligns; // --align: the lines of this batch
     std::string gaf; // --gaf: the lines of this batch
+    std::string mates; // --mates: the lines of this batch's pairs
     std::string error;
 };
 
@@ -316,6 +322,34 @@ static void format_verifies(const pgx_read_verify *recs, size_t n, uint64_t firs
     out.resize((size_t)(p - &out[0]));
 }
 
+// --mates: the lines of pairs [0, n) of a batch whose first read is first_seq (even), appended to out; frag prints as * without a compatible pair,
+// seq_a / seq_b as * for a mate without a candidate
+static const char MATES_HEADER[] = "#pair\tread_a\tread_b\tproper\tfrag\tpair_score\tsolo_score\tcand_a\tcand_b\tseq_a\tseq_b\tn_compatible\tn_best\tnext\tmoved_a\tmoved_b\n";
+static void format_mates(const pgx_read_mates *recs, size_t n, uint64_t first_seq, std::string &out) {
+    out.resize(n * (16 * 21));
+    char *p = &out[0];
+    for (size_t k = 0; k < n; k++) {
+        const pgx_read_mates &x = recs[k];
+        p = put_u64(p, first_seq / 2 + k + 1); *p++ = '\t';
+        p = put_u64(p, first_seq + 2 * k + 1); *p++ = '\t';
+        p = put_u64(p, first_seq + 2 * k + 2); *p++ = '\t';
+        *p++ = (x.flags & PGX_MATES_PROPER) ? '1' : '0'; *p++ = '\t';
+        if (!(x.flags & PGX_MATES_COMPATIBLE)) *p++ = '*';
+        else if (x.frag < 0) { *p++ = '-'; p = put_u64(p, 0 - (uint64_t)x.frag); }
+        else p = put_u64(p, (uint64_t)x.frag);
+        const uint32_t f[4] = {x.pair_score, x.solo_score, x.cand_a, x.cand_b};
+        for (uint32_t v : f) { *p++ = '\t'; p = put_u64(p, v); }
+        const uint32_t q[2] = {x.seq_a, x.seq_b};
+        for (uint32_t v : q) { *p++ = '\t'; if (v == PGX_NO_SEQUENCE) *p++ = '*'; else p = put_u64(p, v); }
+        const uint32_t g[3] = {x.n_compatible, x.n_best, x.next_score};
+        for (uint32_t v : g) { *p++ = '\t'; p = put_u64(p, v); }
+        *p++ = '\t'; *p++ = (x.flags & PGX_MATES_MOVED_A) ? '1' : '0';
+        *p++ = '\t'; *p++ = (x.flags & PGX_MATES_MOVED_B) ? '1' : '0';
+        *p++ = '\n';
+    }
+    out.resize((size_t)(p - &out[0]));
+}
+
 // --align: the lines of reads [0, n) of a batch, appended to out; seq, start, end and cigar print as * when the read has no candidate
 static const char ALIGN_HEADER[] = "#read\tseq\tstart\tend\tclip_lo\tclip_hi\tedits\tmatches\tmismatches\tins\tdel\tband_hit\tcigar\n";
 static void format_aligns(const pgx_read_align *recs, const uint64_t *op_off, const uint32_t *ops, size_t n, uint64_t first_seq, std::string &out) {
@@ -388,7 +422,8 @@ static int usage() {
                  " [--place FILE [--place-max K] [--place-only (not with --locate)]]"
                  " [--verify FILE [--verify-max C] [--verify-mismatch P] [--verify-only (not with --locate)]]"
                  " [--align FILE [--align-band W (0 .. 31)] [--align-only (not with --locate)]]"
-                 " [--gaf FILE [--gaf-only (not with --locate)]]" << std::endl;
+                 " [--gaf FILE [--gaf-only (not with --locate)]]"
+                 " [--paired [--frag-min A] [--frag-max B] [--mates-penalty U] [--mates FILE [--mates-only (not with --locate)]]]" << std::endl;
     return EXIT_FAILURE;
 }
 
@@ -421,6 +456,11 @@ int main(int argc, char **argv) {
     bool align_band_given = false, align_only = false;
     std::string gaf_file;       // --gaf: the graph walks of every batch go to this file, one GAF line per read
     bool gaf_only = false;
+    bool paired = false;        // --paired: records 2k and 2k + 1 of the reads file are mates; the mates stage elects the verify winners
+    std::string mates_file;     // --mates: the pair records of every batch go to this file
+    int64_t frag_min = 0, frag_max = 1000;
+    uint64_t mates_penalty = 0;
+    bool mates_opt_given = false, mates_penalty_given = false, mates_only = false, verify_max_given = false;
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -506,6 +546,7 @@ int main(int argc, char **argv) {
             if (!endp || *endp || errno || k < 1 || k > top) { std::cerr << a << ": a number in 1 .. " << top << std::endl; return EXIT_FAILURE; }
             (a == "--verify-max" ? verify_max : verify_penalty) = (uint32_t)k;
             verify_opt_given = true;
+            if (a == "--verify-max") verify_max_given = true;
         }
         else if (a == "--verify-only") verify_only = true;
         else if (a == "--align") { align_file = next(); if (align_file.empty()) { std::cerr << "--align: a file name" << std::endl; return EXIT_FAILURE; } }
@@ -521,13 +562,40 @@ int main(int argc, char **argv) {
         else if (a == "--align-only") align_only = true;
         else if (a == "--gaf") { gaf_file = next(); if (gaf_file.empty()) { std::cerr << "--gaf: a file name" << std::endl; return EXIT_FAILURE; } }
         else if (a == "--gaf-only") gaf_only = true;
+        else if (a == "--paired") paired = true;
+        else if (a == "--mates") { mates_file = next(); if (mates_file.empty()) { std::cerr << "--mates: a file name" << std::endl; return EXIT_FAILURE; } }
+        else if (a == "--mates-only") mates_only = true;
+        else if (a == "--frag-min" || a == "--frag-max") {
+            const std::string v = next();
+            char *endp = nullptr;
+            errno = 0;
+            const long long k = v.empty() ? 0 : std::strtoll(v.c_str(), &endp, 10);
+            if (!endp || *endp || errno) { std::cerr << a << ": a fragment length (a signed number)" << std::endl; return EXIT_FAILURE; }
+            (a == "--frag-min" ? frag_min : frag_max) = (int64_t)k;
+            mates_opt_given = true;
+        }
+        else if (a == "--mates-penalty") {
+            const std::string v = next();
+            char *endp = nullptr;
+            errno = 0;
+            const unsigned long long k = v.empty() || v[0] == '-' ? 0 : std::strtoull(v.c_str(), &endp, 10);
+            if (!endp || *endp || errno || k > 0xFFFFFFFFull) { std::cerr << a << ": a number in 0 .. 4294967295" << std::endl; return EXIT_FAILURE; }
+            mates_penalty = k;
+            mates_opt_given = mates_penalty_given = true;
+        }
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
+    if ((!mates_file.empty() || mates_only || mates_opt_given) && !paired) return usage(); // (the mates options belong to --paired)
+    if (mates_only && mates_file.empty()) return usage();
+    if (mates_only && locate_mode) { std::cerr << "--mates-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
+    if (paired && frag_min > frag_max) { std::cerr << "--frag-min " << frag_min << " exceeds --frag-max " << frag_max << std::endl; return EXIT_FAILURE; }
+    if (paired && !verify_max_given) verify_max = 16; // (a pair chooses among candidates: one a read leaves it nothing to choose)
+    if (paired && !mates_penalty_given) mates_penalty = 2ull * (verify_penalty + 1); // two substitutions' worth of seg_score: each costs a match and P
     if ((hits_max_given || hits_only) && hits_file.empty()) return usage();
     if (hits_only && locate_mode) { std::cerr << "--hits-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if ((place_max_given || place_only) && place_file.empty()) return usage();
     if (place_only && locate_mode) { std::cerr << "--place-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
-    if ((verify_only && verify_file.empty()) || (verify_opt_given && verify_file.empty() && align_file.empty() && gaf_file.empty())) return usage();
+    if ((verify_only && verify_file.empty()) || (verify_opt_given && verify_file.empty() && align_file.empty() && gaf_file.empty() && !paired)) return usage();
     if (verify_only && locate_mode) { std::cerr << "--verify-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if ((align_only && align_file.empty()) || (align_band_given && align_file.empty() && gaf_file.empty())) return usage();
     if (gaf_only && gaf_file.empty()) return usage();
@@ -535,9 +603,11 @@ int main(int argc, char **argv) {
     if (align_only && locate_mode) { std::cerr << "--align-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     const bool want_hits = !hits_file.empty(), want_places = !place_file.empty(), want_verify = !verify_file.empty(), want_align = !align_file.empty();
     const bool want_gaf = !gaf_file.empty(), run_align = want_align || want_gaf; // (--gaf runs the align stage itself)
-    const bool run_verify = want_verify || run_align; // (--align runs the verify stage itself)
-    const uint32_t place_flags = run_verify && verify_max > 1 ? PGX_PLACE_LIST : 0u; // (the candidates beyond the first come from the list)
-    const bool no_text = hits_only || place_only || verify_only || align_only || gaf_only; // (either one: no tag stage, no download of result arrays, stdout empty)
+    const bool want_mates = !mates_file.empty();
+    const bool run_verify = want_verify || run_align || paired; // (--align runs the verify stage itself; --paired elects its winners)
+    const uint32_t place_flags = run_verify && (verify_max > 1 || paired) ? PGX_PLACE_LIST : 0u; // (the candidates beyond the first come from the list)
+    const uint32_t verify_flags = paired ? PGX_VERIFY_LIST : 0u;                                 // (the mates stage reads the candidates of both mates)
+    const bool no_text = hits_only || place_only || verify_only || align_only || gaf_only || mates_only; // (either one: no tag stage, no download of result arrays, stdout empty)
     if (batch_reads == 0) batch_reads = 1;
     if (locate_max && !locate_mode) { std::cerr << "--locate-max needs --locate" << std::endl; return EXIT_FAILURE; }
 
@@ -618,26 +688,38 @@ int main(int argc, char **argv) {
         std::fwrite(PLACE_HEADER, 1, sizeof PLACE_HEADER - 1, place_fp);
     }
     // --verify: the same question for the text image (what --place asks, and a collection of 2^32 - 2^20 symbols or more)
-    std::FILE *verify_fp = nullptr, *align_fp = nullptr, *gaf_fp = nullptr;
+    std::FILE *verify_fp = nullptr, *align_fp = nullptr, *gaf_fp = nullptr, *mates_fp = nullptr;
     if (run_verify) {
         static const uint8_t probe_read[4] = {'A', 'C', 'G', 'T'};
         static const uint64_t probe_offs[2] = {0, 4};
         pgx_status st = PGX_OK;
         std::string msg;
+        bool twin_refused = false;
         for (size_t i = 0; st == PGX_OK && i < devices.size(); i++) { // (the text image of every device is built here, before any batch)
             pgx_batch *pb = nullptr;
             st = pgx_batch_create(h, devices[i], probe_read, probe_offs, 1, &pb);
             if (st == PGX_OK) st = pgx_batch_run(pb, mem_length, min_occ, 0, nullptr);
             if (st == PGX_OK) st = pgx_batch_locate(pb, 0, place_max, nullptr);
             if (st == PGX_OK) st = pgx_batch_read_place(pb, place_flags, nullptr);
-            if (st == PGX_OK) st = pgx_batch_read_verify(pb, verify_max, verify_penalty, 0, nullptr);
+            if (st == PGX_OK) st = pgx_batch_read_verify(pb, verify_max, verify_penalty, verify_flags, nullptr);
+            if (st == PGX_OK && paired) { // (a probe of one read is no pair: ask the index itself)
+                uint64_t bad = 0;
+                st = pgx_index_twinned(h, devices[i], &bad);
+                if (st == PGX_OK && bad != ~0ull) {
+                    msg = "find_mems --paired: the index is not twinned (p = " + std::to_string(bad) + "): mates need a collection with every path forward as sequence 2p and reversed as 2p + 1 (gbz_extract -b)";
+                    twin_refused = true;
+                    st = PGX_ERR_UNSUPPORTED;
+                }
+            }
             if (st == PGX_OK && run_align) st = pgx_batch_read_align(pb, align_band, PGX_ALIGN_CIGAR, nullptr);
             if (st == PGX_OK && want_gaf) st = pgx_batch_read_walk(pb, PGX_WALK_STEPS, nullptr); // (the walk image: an index without tags ends here)
-            if (st != PGX_OK) msg = pgx_last_error();
+            if (st != PGX_OK && !twin_refused) msg = pgx_last_error();
             pgx_batch_free(pb);
         }
         if (st != PGX_OK) {
-            std::cerr << msg << (st != PGX_ERR_UNSUPPORTED ? "" : (want_verify ? " (find_mems --verify)" : (want_align ? " (find_mems --align)" : " (find_mems --gaf)"))) << std::endl;
+            std::cerr << msg
+                      << (st != PGX_ERR_UNSUPPORTED || twin_refused ? "" : (want_verify ? " (find_mems --verify)" : (want_align ? " (find_mems --align)" : (want_gaf ? " (find_mems --gaf)" : " (find_mems --paired)"))))
+                      << std::endl;
             if (hits_fp) std::fclose(hits_fp);
             if (place_fp) std::fclose(place_fp);
             return EXIT_FAILURE;
@@ -655,6 +737,11 @@ int main(int argc, char **argv) {
         if (want_gaf) {
             gaf_fp = std::fopen(gaf_file.c_str(), "wb");
             if (!gaf_fp) { std::cerr << "Cannot open gaf file: " << gaf_file << std::endl; return EXIT_FAILURE; }
+        }
+        if (want_mates) {
+            mates_fp = std::fopen(mates_file.c_str(), "wb");
+            if (!mates_fp) { std::cerr << "Cannot open mates file: " << mates_file << std::endl; return EXIT_FAILURE; }
+            std::fwrite(MATES_HEADER, 1, sizeof MATES_HEADER - 1, mates_fp);
         }
     }
 
@@ -719,7 +806,7 @@ int main(int argc, char **argv) {
         const double per_line = lines ? (double)probe / (double)lines : rfmt == PGX_READS_LINES ? 152.0 : (double)std::max<size_t>(probe, 1);
         const size_t want = (size_t)std::max(1.0, per_line * (double)batch_reads);
         size_t at = 0;
-        while (at < mf.n) {
+        while (!paired && at < mf.n) {
             size_t end = std::min(mf.n, at + want);
             if (end < mf.n && dev_parse) {
                 uint64_t cut = mf.n;
@@ -731,6 +818,39 @@ int main(int argc, char **argv) {
             }
             ranges.emplace_back(at, end);
             at = end;
+        }
+        if (paired) {
+            // --paired: every range holds whole pairs.  The cutter walks the file line by line, counts records while it cuts -- a non-empty line of a line
+            // file, four lines of FASTQ (empty lines between records skipped), a '>' at a line start of FASTA -- and ends a range where a record ends,
+            // the range holds an even number of them and at least `want` bytes.  Every cut lies where a record starts, so the device parser and
+            // pgx_fastx_cut see whole records.
+            const char *p = mf.p, *const stop = mf.p + mf.n;
+            size_t in_range = 0, total = 0, fq_lines = 0;
+            bool fa_open = false; // FASTA: a record has started and has not ended
+            auto record_ends = [&](size_t e) { // a record ends at byte e
+                in_range++; total++;
+                if (in_range % 2 == 0 && e - at >= want) { ranges.emplace_back(at, e); at = e; in_range = 0; }
+            };
+            while (p < stop) {
+                const char *nl = static_cast<const char *>(std::memchr(p, '\n', (size_t)(stop - p)));
+                const char *next = nl ? nl + 1 : stop;
+                const size_t len = (size_t)((nl ? nl : stop) - p);
+                if (rfmt == PGX_READS_LINES) { if (len) record_ends((size_t)(next - mf.p)); }
+                else if (rfmt == PGX_READS_FASTQ) {
+                    if (fq_lines || len) fq_lines++;
+                    if (fq_lines == 4) { fq_lines = 0; record_ends((size_t)(next - mf.p)); }
+                } else if (len && *p == '>') {
+                    if (fa_open) record_ends((size_t)(p - mf.p));
+                    fa_open = true;
+                }
+                p = next;
+            }
+            if (fa_open || fq_lines) { in_range++; total++; } // the last record of a FASTA file, a FASTQ record cut short (the parser says what is wrong with it)
+            if (at < mf.n) ranges.emplace_back(at, mf.n);
+            if (total % 2) {
+                std::cerr << "find_mems --paired: " << reads_file << " holds " << total << " records, an odd number: records 2k and 2k + 1 are the mates of pair k" << std::endl;
+                return EXIT_FAILURE;
+            }
         }
     }
     n_jobs = ranges.size();
@@ -922,9 +1042,16 @@ int main(int argc, char **argv) {
                 if (st == PGX_OK && want_places) st = pgx_batch_places(b, &rp2);
                 if (st == PGX_OK && want_places) place_recs.assign(rp2.reads, rp2.reads + rp2.n_reads);
             }
+            std::vector<pgx_read_mates> mate_recs;    // --mates: the 64-byte records of the batch's pairs
             std::vector<pgx_read_verify> verify_recs; // --verify: the 64-byte records, at the candidates of the place stage above
             if (st == PGX_OK && run_verify) {
-                st = pgx_batch_read_verify(b, verify_max, verify_penalty, 0, nullptr);
+                st = pgx_batch_read_verify(b, verify_max, verify_penalty, verify_flags, nullptr);
+                if (st == PGX_OK && paired) { // the pairs choose: the elected winners are what --verify, --align and --gaf report below
+                    st = pgx_batch_read_mates(b, frag_min, frag_max, (uint32_t)mates_penalty, PGX_MATES_ELECT, nullptr);
+                    pgx_read_mates_result rm;
+                    if (st == PGX_OK && want_mates) st = pgx_batch_mated(b, &rm);
+                    if (st == PGX_OK && want_mates) mate_recs.assign(rm.pairs, rm.pairs + rm.n_pairs);
+                }
                 pgx_read_verifies rv;
                 if (st == PGX_OK && want_verify) st = pgx_batch_verified(b, &rv);
                 if (st == PGX_OK && want_verify) verify_recs.assign(rv.reads, rv.reads + rv.n_reads);
@@ -1002,6 +1129,7 @@ int main(int argc, char **argv) {
                 if (want_hits) format_hits(hit_recs.data(), hit_recs.size(), j->first_seq, d->hits);
                 if (want_places) format_places(place_recs.data(), place_recs.size(), j->first_seq, d->places);
                 if (want_verify) format_verifies(verify_recs.data(), verify_recs.size(), j->first_seq, d->verifies);
+                if (want_mates) format_mates(mate_recs.data(), mate_recs.size(), j->first_seq, d->mates);
                 if (want_gaf && !walk_read_off.empty())
                     format_gaf(align_recs.data(), align_op_off.data(), align_ops.data(), walk_recs.data(), walk_step_off.data(), walk_steps.data(), walk_read_off.data(),
                                walk_recs.size(), j->first_seq, d->gaf);
@@ -1107,6 +1235,7 @@ int main(int argc, char **argv) {
         if (verify_fp && !d->verifies.empty()) std::fwrite(d->verifies.data(), 1, d->verifies.size(), verify_fp);
         if (align_fp && !d->aligns.empty()) std::fwrite(d->aligns.data(), 1, d->aligns.size(), align_fp);
         if (gaf_fp && !d->gaf.empty()) std::fwrite(d->gaf.data(), 1, d->gaf.size(), gaf_fp);
+        if (mates_fp && !d->mates.empty()) std::fwrite(d->mates.data(), 1, d->mates.size(), mates_fp);
         ns_write += now_ns() - tw0;
         total_mem_time += d->mem_s;
         total_tag_time += d->tag_s;
@@ -1133,6 +1262,7 @@ int main(int argc, char **argv) {
     if (verify_fp && (std::fclose(verify_fp) != 0) && error.empty()) error = "Cannot write verify file: " + verify_file;
     if (align_fp && (std::fclose(align_fp) != 0) && error.empty()) error = "Cannot write align file: " + align_file;
     if (gaf_fp && (std::fclose(gaf_fp) != 0) && error.empty()) error = "Cannot write gaf file: " + gaf_file;
+    if (mates_fp && (std::fclose(mates_fp) != 0) && error.empty()) error = "Cannot write mates file: " + mates_file;
     if (!error.empty()) {
         std::cerr << error << std::endl;
         return EXIT_FAILURE;
