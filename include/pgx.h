@@ -971,6 +971,87 @@ pgx_status pgx_read_mates_arrays(int device, const uint64_t *seq_lengths, uint64
                                  const pgx_read_verify *cands, int64_t frag_min, int64_t frag_max, uint32_t penalty, uint32_t flags,
                                  pgx_read_mates *out, pgx_read_verify *winners);
 
+/* ---- read rescue: the unplaced mate of a pair searched for next to the placed one, on the device --------------------------------------
+ * pgx_batch_read_mates chooses among the candidates place produced, and a read has one only where a MEM of min_len was located.  A mate
+ * with a substitution every ten bases, or one whose MEMs the place or run limits cut away, has none near its truth.  Its mate usually sits
+ * uniquely, and the pair's geometry says where to look: on the twin sequence, inside a window of frag_max - frag_min + 1 diagonals.  This
+ * stage scores every diagonal of that window against the read.  It sits between verify and mates.
+ *
+ * DEFINITIONS.  Reads 2k and 2k + 1 are the mates of pair k; verify's list (PGX_VERIFY_LIST) gives every read its candidates; L[q] is the
+ * length of sequence q without its endmarker; P is the mismatch penalty of the verify call; "compatible", "solo winner" and frag are those
+ * of "read mates" under the frag_min and frag_max of this call.
+ *   target       read t with mate a is a target iff the pair has no compatible candidate pair, a has at least one candidate and t has
+ *                fewer than PGX_VERIFY_MAX_CAND.  A read with PGX_VERIFY_MAX_CAND candidates in such a pair gets PGX_RESCUE_FULL and is
+ *                no target.  Both reads of a pair may be targets.
+ *   anchors      of a target: the candidates of a that equal a's solo winner in (seg_score, matches), in candidate order, the first
+ *                max_anchors of them, 1 <= max_anchors <= PGX_RESCUE_MAX_ANCHORS.
+ *   task (t, anchor i)   the sequence is s = seq_i ^ 1; the window is the diagonals d with frag_min <= L[s] - diag_i - d <= frag_max,
+ *                clipped to those on which the read overlaps the sequence, -(len_t - 1) <= d <= L[s] - 1; empty for len_t == 0, and a
+ *                task may be empty.  All of it signed 64-bit (|diag| stays below 2^62).
+ *   score of a diagonal   verify's seg_score and matches of read t at (s, d), with the same P and the same match rule.
+ *   best diagonal   of a target, over all its tasks: the largest seg_score, then the most matches, then the smallest anchor ordinal,
+ *                then the smallest d.  n_diags counts the diagonals scored, n_best those that equal the best in (seg_score, matches),
+ *                held at 2^32 - 1; next_score is the largest seg_score strictly below the best one's, 0 if there is none.
+ *   RESCUED      n_diags > 0 and the best seg_score >= min_score, min_score >= 1.
+ * The best diagonal is a monoid like the best pair of "read mates", so a kernel may split windows and tasks as it likes.
+ * pgx_read_rescue (64 bytes, little endian, one per read):
+ *    0 diag i64          the best diagonal; 0 without one
+ *    8 n_diags u64       diagonals scored over all tasks of the read
+ *   16 seq u32           sequence of the best diagonal; PGX_NO_SEQUENCE for a read that is no target and for a target with n_diags == 0
+ *   20 flags u32         PGX_RESCUE_TARGET, _RESCUED, _FULL
+ *   24 anchor u32        ordinal, in the mate's list, of the anchor whose task holds the best diagonal
+ *   28 n_anchors u32     anchors (= tasks) of the target
+ *   32 seg_score  36 matches u32   of the best diagonal
+ *   40 n_best  44 next_score u32   see above
+ *   48 reserved u32[4]   0
+ * A read that is no target has every field but seq (and the flag FULL) 0.
+ * PGX_RESCUE_MERGE appends the best diagonal of every RESCUED target to its list as its last candidate: the record is byte for byte what
+ * verify writes for that read at (seq, diag), with n_cand = cand_index = its ordinal and n_tied = 0.  cand_offsets and n_cands are
+ * rebuilt, every winner record is recomputed by verify's WINNER rule (a target without a candidate now has a winner), and an earlier mates
+ * result of the run becomes invalid.  The verify result's reported max_cand stays, though a list may now hold max_cand + 1 <= 64
+ * entries.  Without the flag the verify result is untouched.  A verify result takes one merge: a second rescue call on it is PGX_ERR_ARG. */
+#define PGX_RESCUE_MERGE 1u
+#define PGX_RESCUE_TARGET 1u     /* bits of pgx_read_rescue.flags */
+#define PGX_RESCUE_RESCUED 2u
+#define PGX_RESCUE_FULL 4u
+#define PGX_RESCUE_MAX_ANCHORS 8u
+#define PGX_RESCUE_MAX_WINDOW 65536
+typedef struct {
+    int64_t diag;
+    uint64_t n_diags;
+    uint32_t seq, flags, anchor, n_anchors, seg_score, matches, n_best, next_score, reserved[4];
+} pgx_read_rescue;
+typedef struct {
+    uint64_t n_reads;
+    uint64_t n_targets, n_rescued, n_full, n_tasks, n_diags; /* summed on the device */
+    int64_t frag_min, frag_max;     /* what the call ran with */
+    uint32_t min_score, max_anchors, flags, mismatch_penalty;
+    const pgx_read_rescue *reads;   /* n_reads */
+    float ms_rescue;                /* device time of the call when the run had PGX_RUN_TIMING, else 0 */
+    uint32_t reserved;
+} pgx_read_rescue_result;
+/* Rescues the reads of the last run from the list of the last pgx_batch_read_verify, which must be this run's and made with
+ * PGX_VERIFY_LIST.  PGX_ERR_ARG with nothing changed, naming what was found: no such verify result, one that was already merged, an
+ * unknown flag, frag_min > frag_max, frag_max - frag_min >= PGX_RESCUE_MAX_WINDOW, min_score 0, max_anchors outside 1 .. 8, an odd read
+ * count.  PGX_ERR_UNSUPPORTED when the index is not twinned (the first p named) or the tasks exceed one launch.  Runs on `stream` (NULL =
+ * the batch's own), complete on return.  Buffers grow only and are the stage's own: the result stays valid until the next run, upload,
+ * pgx_batch_read_rescue or free of the batch. */
+pgx_status pgx_batch_read_rescue(pgx_batch *b, int64_t frag_min, int64_t frag_max, uint32_t min_score, uint32_t max_anchors, uint32_t flags,
+                                 void *stream);
+/* Host copy of the last rescue result (a pinned buffer owned by the batch) / the same as a device pointer.  PGX_ERR_ARG when there is none. */
+pgx_status pgx_batch_rescued(pgx_batch *b, pgx_read_rescue_result *out);
+pgx_status pgx_batch_device_rescued(pgx_batch *b, pgx_read_rescue_result *out);
+/* The same kernels on host arrays: text, sequences and reads as in pgx_read_verify_arrays (no endmarkers), the lists as in
+ * pgx_read_mates_arrays.  `out` takes n_reads records.  With PGX_RESCUE_MERGE list_offsets takes n_reads + 1 entries, list up to list_cap
+ * records (PGX_ERR_NOMEM with the needed count when the merged list is longer) and winners n_reads records; all three may be NULL without
+ * the flag.  Refuses, with nothing written and the first offender named, what pgx_read_verify_arrays and pgx_read_mates_arrays refuse for
+ * the same inputs, and the arguments pgx_batch_read_rescue refuses.  PGX_ERR_NO_DEVICE without a GPU. */
+pgx_status pgx_read_rescue_arrays(int device, const uint8_t *text, const uint64_t *seq_offsets, uint64_t n_seq, const uint8_t *reads,
+                                  const uint64_t *read_offsets, uint64_t n_reads, const uint64_t *cand_offsets, const pgx_read_verify *cands,
+                                  int64_t frag_min, int64_t frag_max, uint32_t mismatch_penalty, uint32_t min_score, uint32_t max_anchors,
+                                  uint32_t flags, pgx_read_rescue *out, uint64_t *list_offsets, pgx_read_verify *list, uint64_t list_cap,
+                                  pgx_read_verify *winners);
+
 /* ---- read align: every read aligned with gaps at its verified placement, on the device -------------------------------------------
  * Verify knows only substitutions: a read with a one-base insertion or deletion places on two neighbouring diagonals, each covering part of
  * it, and the winner reads as "half the read matches, then a wall of mismatches".  This stage computes the banded unit-cost alignment of the

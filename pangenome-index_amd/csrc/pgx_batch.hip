@@ -33,6 +33,7 @@ static void batch_release(pgx_batch *b) {
         b->hw.release();
         b->pw.release();
         b->vw.release();
+        b->rw.release();
         b->mw.release();
         b->aw.release();
         b->ww.release();
@@ -58,6 +59,7 @@ static void batch_reset_for_upload(pgx_batch *b, uint64_t n_reads, uint64_t max_
     b->hw.valid = false;
     b->pw.valid = false;
     b->vw.valid = false;
+    b->rw.valid = false;
     b->mw.valid = false;
     b->aw.valid = false;
     b->ww.valid = false;
@@ -989,6 +991,7 @@ extern "C" pgx_status pgx_batch_run(pgx_batch *b, uint64_t min_len, uint64_t min
     b->hw.valid = false; // (and so do the hits)
     b->pw.valid = false; // (and the places)
     b->vw.valid = false; // (and what was verified at them)
+    b->rw.valid = false; // (and rescued next to it)
     b->mw.valid = false; // (and paired from that)
     b->aw.valid = false; // (and aligned there)
     b->ww.valid = false; // (and walked through the graph)

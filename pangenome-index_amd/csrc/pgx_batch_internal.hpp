@@ -104,6 +104,8 @@ struct VerifyWork {
     StageTimer timer;
     bool valid = false;
     uint32_t flags = 0, max_cand = 0, penalty = 0;
+    uint32_t max_list = 0; // the longest list: max_cand, or max_cand + 1 <= 64 behind a merge of pgx_batch_read_rescue (sizes the lane group of mates)
+    bool merged = false;   // a rescue call has appended its candidates: cand_seq / cand_diag / cand_read describe the list before it
     uint64_t n_reads = 0, n_cands = 0;
     float ms = 0;
     StageResult result() const { return {n_reads, recs.p, sizeof(pgx_read_verify), (flags & PGX_VERIFY_LIST) != 0, cand_off.p, n_cands, cands.p, sizeof(pgx_read_verify)}; }
@@ -125,6 +127,27 @@ struct MatesWork {
     float ms = 0;
     void release() {
         release_all({&recs, &ctr});
+        release_all({&h_recs}); timer.release(); valid = false;
+    }
+};
+
+// pgx_batch_read_rescue's buffers (grow-only, its own) and its result; pgx_read_rescue_arrays uses one of its own
+struct RescueWork {
+    MatesWork mates; // the pair records under this call's frag bounds, without ELECT: n_compatible and the solo winners are read from them
+    DevBuf recs, task_count, task_off, tasks, best, ctr, scan_tmp;
+    // MERGE: the rescued reads' flags and slots, their candidate arrays and verified records, the new list (swapped with the verify result's)
+    DevBuf rescued, res_off, cand_read, cand_seq, cand_diag, fake_off, res_cands, new_count, new_off, new_cands;
+    HostBuf h_recs;
+    StageTimer timer;
+    bool valid = false;
+    uint32_t flags = 0, min_score = 0, max_anchors = 0, penalty = 0;
+    int64_t frag_min = 0, frag_max = 0;
+    uint64_t n_reads = 0, counters[5] = {0, 0, 0, 0, 0}; // targets, rescued, full, tasks, diagonals
+    float ms = 0;
+    void release() {
+        mates.release();
+        release_all({&recs, &task_count, &task_off, &tasks, &best, &ctr, &scan_tmp, &rescued, &res_off, &cand_read, &cand_seq, &cand_diag, &fake_off, &res_cands, &new_count,
+                     &new_off, &new_cands});
         release_all({&h_recs}); timer.release(); valid = false;
     }
 };
@@ -226,6 +249,7 @@ struct pgx_batch {
     HitsWork hw;    // pgx_batch_read_hits
     PlaceWork pw;   // pgx_batch_read_place
     VerifyWork vw;  // pgx_batch_read_verify
+    RescueWork rw;  // pgx_batch_read_rescue
     MatesWork mw;   // pgx_batch_read_mates
     AlignWork aw;   // pgx_batch_read_align
     WalkWork ww;    // pgx_batch_read_walk

@@ -434,6 +434,40 @@ __global__ void pgx_mates_kernel(const uint64_t *seq_start, uint32_t endmark, co
                                  int64_t frag_min, int64_t frag_max, uint32_t penalty, uint32_t flags, pgx_read_mates *out, pgx_read_verify *winners,
                                  unsigned long long *counters);
 
+// ---- pgx_rescue_kernels.hip: read rescue (pgx_batch_read_rescue, pgx_read_rescue_arrays)
+#define PGX_RESCUE_THREADS 256
+// a task: read t on sequence seq over the diagonals [d_lo, d_hi] (empty: d_hi < d_lo), and what the scan found there (PgxRescueBest, n == 0: nothing)
+struct PgxRescueTask {
+    int64_t d_lo, d_hi;
+    uint64_t read;
+    uint32_t seq, anchor;
+};
+struct PgxRescueBest {
+    int64_t d;          // the smallest diagonal that holds (score, matches)
+    uint32_t score, matches;
+    uint32_t next;      // the largest score below `score` (0: none)
+    uint32_t n_best, n; // a task scores at most 2^31 + 2^32 diagonals only in theory: its window holds at most PGX_RESCUE_MAX_WINDOW
+    uint32_t pad;
+};
+// tasks == nullptr: task_count[t] = anchors of read t (0: no target); else the tasks of read t behind task_off[t].  mates: the pair records of
+// pgx_mates_kernel under the same frag bounds (n_compatible is read).
+__global__ void pgx_rescue_targets_kernel(const uint64_t *seq_start, uint32_t endmark, const uint64_t *read_off, const uint64_t *cand_off, const pgx_read_verify *cands,
+                                          const pgx_read_mates *mates, uint64_t n_reads, int64_t frag_min, int64_t frag_max, uint32_t max_anchors, uint64_t *task_count,
+                                          const uint64_t *task_off, PgxRescueTask *tasks);
+// a wave a task, a lane a diagonal
+__global__ void pgx_rescue_scan_kernel(const uint32_t *text4, const uint64_t *seq_start, uint32_t endmark, const uint32_t *rcode, const uint64_t *read_off,
+                                       const PgxRescueTask *tasks, uint64_t n_tasks, uint32_t penalty, PgxRescueBest *best);
+// a thread a read: its record from its tasks; counters: targets, rescued, full, tasks, diagonals (added to); rescued: NULL, or 1 where RESCUED else 0
+__global__ void pgx_rescue_reduce_kernel(const uint64_t *cand_off, const pgx_read_mates *mates, const uint64_t *task_count, const uint64_t *task_off,
+                                         const PgxRescueTask *tasks, const PgxRescueBest *best, uint64_t n_reads, uint32_t min_score, pgx_read_rescue *out,
+                                         uint64_t *rescued, unsigned long long *counters);
+// MERGE: the candidate arrays of the rescued reads (slot res_off[t]) for pgx_verify_kernel; fake_off[t] makes its n_cand the list ordinal
+__global__ void pgx_rescue_cands_kernel(const pgx_read_rescue *recs, const uint64_t *cand_off, const uint64_t *rescued, const uint64_t *res_off, uint64_t n_reads,
+                                        uint64_t *cand_read, uint32_t *cand_seq, int64_t *cand_diag, uint64_t *fake_off, uint64_t *new_count);
+// MERGE: the list rebuilt, a thread a record: the n_old old ones (owner: old_read) and the n_res rescued ones (owner: res_read), each behind new_off
+__global__ void pgx_rescue_copy_kernel(const pgx_read_verify *old_cands, const uint64_t *old_off, const uint64_t *old_read, uint64_t n_old, const pgx_read_verify *res_cands,
+                                       const uint64_t *res_read, uint64_t n_res, const uint64_t *new_off, pgx_read_verify *out);
+
 // ---- pgx_align_kernels.hip: read align (pgx_batch_read_align, pgx_read_align_arrays)
 #define PGX_ALIGN_THREADS 256
 __global__ void pgx_align_cand_kernel(const pgx_read_verify *recs, uint64_t n_reads, uint32_t *cand_seq, int64_t *cand_diag);

@@ -1,4 +1,4 @@
-// pgx_read_stages.hip -- the read stages behind a run: hits, place, verify, mates, align, walk.  Each is a core on device arrays with two entry points, one on
+// pgx_read_stages.hip -- the read stages behind a run: hits, place, verify, rescue, mates, align, walk.  Each is a core on device arrays with two entry points, one on
 // the batch (pgx_batch_read_X with its results pgx_batch_device_X / pgx_batch_X) and one on host arrays (pgx_read_X_arrays), and what they share comes first.
 // A batch entry point clears its `valid` only behind its last refusal, so that what it refuses leaves the result before as it was (hits differs: see there).
 #include <string>
@@ -609,6 +609,7 @@ extern "C" pgx_status pgx_batch_read_verify(pgx_batch *b, uint32_t max_cand, uin
     w.ms = w.timer.end(s);
     if (!b->timed) HIPCHECK(hipStreamSynchronize(s)); // (a timed call has waited in end(); verify_core, unlike align_core and walk_core, reads nothing back)
     w.n_reads = n; w.n_cands = n_cands; w.flags = flags; w.max_cand = max_cand; w.penalty = mismatch_penalty;
+    w.max_list = max_cand; w.merged = false;
     w.valid = true;
     return PGX_OK;
     PGX_GUARD_END
@@ -807,12 +808,12 @@ extern "C" pgx_status pgx_batch_read_mates(pgx_batch *b, int64_t frag_min, int64
                                                                                                 : "sequences " + std::to_string(2 * bad) + " and " + std::to_string(2 * bad + 1) +
                                                                                                       " (p = " + std::to_string(bad) + ") differ in length") +
                                              ": mates need a collection with every path forward and reversed (gbz_extract -b)");
-    (void)mates_lane_shift(n / 2, vw.max_cand, who); // (the last refusal: what is refused leaves an earlier mates result as it was)
+    (void)mates_lane_shift(n / 2, vw.max_list, who); // (the last refusal: what is refused leaves an earlier mates result as it was)
     hipStream_t s = batch_stream(b, stream);
     MatesWork &w = b->mw;
     w.valid = false;
     w.timer.begin(b->timed, s);
-    mates_core(w, d->text_seq_start.as<uint64_t>(), 1u, vw.cand_off.as<uint64_t>(), vw.cands.as<pgx_read_verify>(), n / 2, vw.max_cand, frag_min, frag_max, penalty, flags,
+    mates_core(w, d->text_seq_start.as<uint64_t>(), 1u, vw.cand_off.as<uint64_t>(), vw.cands.as<pgx_read_verify>(), n / 2, vw.max_list, frag_min, frag_max, penalty, flags,
                (flags & PGX_MATES_ELECT) ? vw.recs.as<pgx_read_verify>() : nullptr, s, who);
     w.ms = w.timer.end(s);
     read_scalars(w.counters, w.ctr.p, 32, s); // (waits for the kernel: the call is complete on return)
@@ -903,6 +904,283 @@ extern "C" pgx_status pgx_read_mates_arrays(int device, const uint64_t *seq_leng
         HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, (n_reads / 2) * sizeof(pgx_read_mates), hipMemcpyDeviceToHost, s));
         if (elect) HIPCHECK(hipMemcpyAsync(winners, k.winners.p, n_reads * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, s));
     }
+    HIPCHECK(hipStreamSynchronize(s));
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// read rescue (pgx_rescue_kernels.hip; the definitions: include/pgx.h "read rescue")
+static const uint32_t RESCUE_FLAGS = PGX_RESCUE_MERGE;
+static const uint64_t RESCUE_LAUNCH_TASKS = (1ull << 26) - 4; // a wave a task: fewer than 2^32 threads a launch
+
+static void rescue_check_args(const std::string &who, int64_t frag_min, int64_t frag_max, uint32_t min_score, uint32_t max_anchors, uint32_t flags) {
+    if (flags & ~RESCUE_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
+    if (frag_min > frag_max) throw Error(PGX_ERR_ARG, who + ": frag_min " + std::to_string(frag_min) + " exceeds frag_max " + std::to_string(frag_max));
+    if ((uint64_t)frag_max - (uint64_t)frag_min >= (uint64_t)PGX_RESCUE_MAX_WINDOW)
+        throw Error(PGX_ERR_ARG, who + ": frag_min " + std::to_string(frag_min) + " .. frag_max " + std::to_string(frag_max) + " is a window of more than " +
+                                     std::to_string(PGX_RESCUE_MAX_WINDOW) + " diagonals");
+    if (min_score == 0) throw Error(PGX_ERR_ARG, who + ": min_score 0: a rescued placement needs a match");
+    if (max_anchors < 1 || max_anchors > PGX_RESCUE_MAX_ANCHORS)
+        throw Error(PGX_ERR_ARG, who + ": max_anchors " + std::to_string(max_anchors) + " is outside 1 .. " + std::to_string(PGX_RESCUE_MAX_ANCHORS));
+}
+
+// what the stage reads, on the device: the text with its sequences, the coded reads, verify's list (no list longer than max_list <= 64)
+struct RescueInput {
+    const uint32_t *text4;
+    const uint64_t *seq_start;
+    uint32_t endmark;
+    const uint32_t *rcode;
+    const uint64_t *read_off, *cand_off;
+    const pgx_read_verify *cands;
+    uint64_t n_reads, n_cands, max_list;
+};
+
+// The stage on device arrays, enqueued on s: w.recs and w.counters.  Two scalars are read back (each synchronises s): the number of tasks, which sizes the
+// scan's launch and its buffers, and the counters.  Refuses the tasks one launch cannot hold, before anything of a result is written; *cleared is set
+// behind that refusal (the batch entry point drops its earlier result there).
+static void rescue_core(RescueWork &w, const RescueInput &in, int64_t frag_min, int64_t frag_max, uint32_t penalty, uint32_t min_score, uint32_t max_anchors, bool merge,
+                        hipStream_t s, const std::string &who, bool *cleared) {
+    const uint64_t n = in.n_reads;
+    w.recs.ensure((n ? n : 1) * sizeof(pgx_read_rescue));
+    w.ctr.ensure(40);
+    HIPCHECK(hipMemsetAsync(w.ctr.p, 0, 40, s));
+    uint64_t n_tasks = 0;
+    if (n) {
+        // compatible pairs and solo winners: the mates kernel itself, without an election, into records of the stage's own
+        mates_core(w.mates, in.seq_start, in.endmark, in.cand_off, in.cands, n / 2, in.max_list, frag_min, frag_max, 0u, 0u, nullptr, s, who);
+        // frag bounds beyond any L - diag - d (|diag| < 2^62, |d| < 2^32) select what +-(2^62 + 2^34) select, and those cannot overflow in the kernel
+        const int64_t lim = (1ll << 62) + (1ll << 34);
+        const int64_t fmin = std::min(std::max(frag_min, -lim), lim), fmax = std::min(std::max(frag_max, -lim), lim);
+        const pgx_read_mates *mrecs = w.mates.recs.as<pgx_read_mates>();
+        w.task_count.ensure(n * 8);
+        w.task_off.ensure((n + 1) * 8);
+        hipLaunchKernelGGL(pgx_rescue_targets_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, in.seq_start, in.endmark, in.read_off, in.cand_off, in.cands, mrecs, n, fmin, fmax,
+                           max_anchors, w.task_count.as<uint64_t>(), (const uint64_t *)nullptr, (PgxRescueTask *)nullptr);
+        HIPCHECK(hipGetLastError());
+        scan_excl(1, w.task_count.p, n, 0, w.task_off.as<uint64_t>(), w.scan_tmp, s);
+        n_tasks = read_u64(w.task_off.as<uint64_t>() + n, s);
+        if (n_tasks >= RESCUE_LAUNCH_TASKS)
+            throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_tasks) + " tasks at a wave a task exceed one launch: rescue the reads in smaller batches or lower max_anchors");
+        if (cleared) *cleared = true;
+        w.tasks.ensure((n_tasks ? n_tasks : 1) * sizeof(PgxRescueTask));
+        w.best.ensure((n_tasks ? n_tasks : 1) * sizeof(PgxRescueBest));
+        if (merge) w.rescued.ensure(n * 8);
+        if (n_tasks) {
+            hipLaunchKernelGGL(pgx_rescue_targets_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, in.seq_start, in.endmark, in.read_off, in.cand_off, in.cands, mrecs, n, fmin,
+                               fmax, max_anchors, w.task_count.as<uint64_t>(), (const uint64_t *)w.task_off.as<uint64_t>(), w.tasks.as<PgxRescueTask>());
+            hipLaunchKernelGGL(pgx_rescue_scan_kernel, dim3(grid_for(n_tasks, PGX_RESCUE_THREADS / 64)), dim3(PGX_RESCUE_THREADS), 0, s, in.text4, in.seq_start, in.endmark,
+                               in.rcode, in.read_off, (const PgxRescueTask *)w.tasks.as<PgxRescueTask>(), n_tasks, penalty, w.best.as<PgxRescueBest>());
+        }
+        hipLaunchKernelGGL(pgx_rescue_reduce_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, in.cand_off, mrecs, (const uint64_t *)w.task_count.as<uint64_t>(),
+                           (const uint64_t *)w.task_off.as<uint64_t>(), (const PgxRescueTask *)w.tasks.as<PgxRescueTask>(), (const PgxRescueBest *)w.best.as<PgxRescueBest>(), n,
+                           min_score, w.recs.as<pgx_read_rescue>(), merge ? w.rescued.as<uint64_t>() : nullptr, w.ctr.as<unsigned long long>());
+        HIPCHECK(hipGetLastError());
+    } else if (cleared) *cleared = true;
+    read_scalars(w.counters, w.ctr.p, 40, s);
+    w.n_reads = n; w.frag_min = frag_min; w.frag_max = frag_max; w.min_score = min_score; w.max_anchors = max_anchors; w.penalty = penalty;
+    w.flags = merge ? PGX_RESCUE_MERGE : 0u;
+}
+
+// MERGE on device arrays, enqueued on s behind rescue_core: w.new_off (n + 1) and w.new_cands (n_cands + rescued records), and the winners of every read by
+// the reduce kernel of verify.  old_read: the read of every candidate of the list.  Nothing is read back: the host knows the rescued count.
+static void rescue_merge_core(RescueWork &w, const RescueInput &in, const uint64_t *old_read, uint32_t penalty, pgx_read_verify *winners, hipStream_t s) {
+    const uint64_t n = in.n_reads, n_res = w.counters[1], n_new = in.n_cands + n_res;
+    w.new_off.ensure((n + 1) * 8);
+    w.new_cands.ensure((n_new ? n_new : 1) * sizeof(pgx_read_verify));
+    if (!n) { HIPCHECK(hipMemsetAsync(w.new_off.p, 0, 8, s)); return; }
+    w.res_off.ensure((n + 1) * 8);
+    w.new_count.ensure(n * 8);
+    w.fake_off.ensure(n * 8);
+    w.cand_read.ensure((n_res ? n_res : 1) * 8);
+    w.cand_seq.ensure((n_res ? n_res : 1) * 4);
+    w.cand_diag.ensure((n_res ? n_res : 1) * 8);
+    w.res_cands.ensure((n_res ? n_res : 1) * sizeof(pgx_read_verify));
+    scan_excl(1, w.rescued.p, n, 0, w.res_off.as<uint64_t>(), w.scan_tmp, s);
+    hipLaunchKernelGGL(pgx_rescue_cands_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const pgx_read_rescue *)w.recs.as<pgx_read_rescue>(), in.cand_off,
+                       (const uint64_t *)w.rescued.as<uint64_t>(), (const uint64_t *)w.res_off.as<uint64_t>(), n, w.cand_read.as<uint64_t>(), w.cand_seq.as<uint32_t>(),
+                       w.cand_diag.as<int64_t>(), w.fake_off.as<uint64_t>(), w.new_count.as<uint64_t>());
+    if (n_res) // the appended records: verify's own kernel at the rescued (seq, diag)
+        hipLaunchKernelGGL(pgx_verify_kernel, dim3(grid_for(n_res, PGX_VERIFY_THREADS)), dim3(PGX_VERIFY_THREADS), 0, s, in.text4, in.seq_start, in.endmark, in.rcode, in.read_off,
+                           (const uint64_t *)w.fake_off.as<uint64_t>(), (const uint64_t *)w.cand_read.as<uint64_t>(), (const uint32_t *)w.cand_seq.as<uint32_t>(),
+                           (const int64_t *)w.cand_diag.as<int64_t>(), n_res, penalty, w.res_cands.as<pgx_read_verify>());
+    HIPCHECK(hipGetLastError());
+    scan_excl(1, w.new_count.p, n, 0, w.new_off.as<uint64_t>(), w.scan_tmp, s);
+    if (n_new)
+        hipLaunchKernelGGL(pgx_rescue_copy_kernel, dim3(grid_for(n_new, 256)), dim3(256), 0, s, in.cands, in.cand_off, old_read, in.n_cands,
+                           (const pgx_read_verify *)w.res_cands.as<pgx_read_verify>(), (const uint64_t *)w.cand_read.as<uint64_t>(), n_res,
+                           (const uint64_t *)w.new_off.as<uint64_t>(), w.new_cands.as<pgx_read_verify>());
+    hipLaunchKernelGGL(pgx_verify_reduce_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const pgx_read_verify *)w.new_cands.as<pgx_read_verify>(),
+                       (const uint64_t *)w.new_off.as<uint64_t>(), n, winners);
+    HIPCHECK(hipGetLastError());
+}
+
+extern "C" pgx_status pgx_batch_read_rescue(pgx_batch *b, int64_t frag_min, int64_t frag_max, uint32_t min_score, uint32_t max_anchors, uint32_t flags, void *stream) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_read_rescue");
+    checked_device_count();
+    const std::string who = "pgx_batch_read_rescue";
+    if (!b) throw Error(PGX_ERR_ARG, who + ": null batch");
+    // (what is refused here leaves an earlier rescue result, the mates result and the verify result as they were)
+    rescue_check_args(who, frag_min, frag_max, min_score, max_anchors, flags);
+    if (!b->ran) throw Error(PGX_ERR_ARG, who + ": batch has not been run");
+    VerifyWork &vw = b->vw;
+    if (!vw.valid || vw.n_reads != b->n_reads) throw Error(PGX_ERR_ARG, who + ": needs a completed pgx_batch_read_verify(PGX_VERIFY_LIST), the batch has no verify result");
+    if (!(vw.flags & PGX_VERIFY_LIST))
+        throw Error(PGX_ERR_ARG, who + ": needs a verify result made with PGX_VERIFY_LIST, the last pgx_batch_read_verify ran with flags " + std::to_string(vw.flags));
+    if (vw.merged) throw Error(PGX_ERR_ARG, who + ": the verify result was already merged by an earlier call: a verify result takes one PGX_RESCUE_MERGE");
+    const uint64_t n = b->n_reads;
+    if (n & 1) throw Error(PGX_ERR_ARG, who + ": " + std::to_string(n) + " reads, an odd number: reads 2k and 2k + 1 are the mates of pair k");
+    use_device(b->device);
+    pgx_device_image *d = device_image(b->h, b->device);
+    ensure_text(b->h, d); // (built by the verify call)
+    uint64_t bad = 0;
+    if (!index_twinned(d, &bad))
+        throw Error(PGX_ERR_UNSUPPORTED, who + ": the index is not twinned, " +
+                                             ((d->text_n_seq & 1) && bad == d->text_n_seq / 2 ? "it has an odd number of sequences (" + std::to_string(d->text_n_seq) + ")"
+                                                                                                : "sequences " + std::to_string(2 * bad) + " and " + std::to_string(2 * bad + 1) +
+                                                                                                      " (p = " + std::to_string(bad) + ") differ in length") +
+                                             ": rescue needs a collection with every path forward and reversed (gbz_extract -b)");
+    (void)mates_lane_shift(n / 2, vw.max_list, who);
+    hipStream_t s = batch_stream(b, stream);
+    RescueWork &w = b->rw;
+    const bool merge = (flags & PGX_RESCUE_MERGE) != 0, was_valid = w.valid;
+    w.timer.begin(b->timed, s);
+    const RescueInput in{d->text4.as<uint32_t>(), d->text_seq_start.as<uint64_t>(), 1u, vw.rcode.as<uint32_t>(), b->offsets.as<uint64_t>(), vw.cand_off.as<uint64_t>(),
+                         vw.cands.as<pgx_read_verify>(), n, vw.n_cands, vw.max_list};
+    bool cleared = false;
+    w.valid = false;
+    try {
+        rescue_core(w, in, frag_min, frag_max, vw.penalty, min_score, max_anchors, merge, s, who, &cleared);
+    } catch (...) {
+        if (!cleared) w.valid = was_valid; // (the last refusal: the records of the result before were not touched)
+        throw;
+    }
+    if (merge) {
+        rescue_merge_core(w, in, vw.cand_read.as<uint64_t>(), vw.penalty, vw.recs.as<pgx_read_verify>(), s);
+        std::swap(vw.cands, w.new_cands);
+        std::swap(vw.cand_off, w.new_off);
+        vw.n_cands += w.counters[1];
+        vw.merged = true;
+        if (w.counters[1]) vw.max_list = std::min<uint32_t>(vw.max_cand + 1, PGX_VERIFY_MAX_CAND);
+        b->mw.valid = false; // (paired from the list before)
+    }
+    w.ms = w.timer.end(s);
+    if (!b->timed) HIPCHECK(hipStreamSynchronize(s));
+    w.valid = true;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+static void rescued_header(const pgx_batch *b, pgx_read_rescue_result *out) {
+    const RescueWork &w = b->rw;
+    std::memset(out, 0, sizeof *out);
+    out->n_reads = w.n_reads;
+    out->n_targets = w.counters[0]; out->n_rescued = w.counters[1]; out->n_full = w.counters[2]; out->n_tasks = w.counters[3]; out->n_diags = w.counters[4];
+    out->frag_min = w.frag_min; out->frag_max = w.frag_max;
+    out->min_score = w.min_score; out->max_anchors = w.max_anchors; out->flags = w.flags; out->mismatch_penalty = w.penalty;
+    out->ms_rescue = w.ms;
+}
+
+extern "C" pgx_status pgx_batch_device_rescued(pgx_batch *b, pgx_read_rescue_result *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->rw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_rescued: batch has no rescue result");
+    rescued_header(b, out);
+    out->reads = b->rw.recs.as<pgx_read_rescue>();
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_batch_rescued(pgx_batch *b, pgx_read_rescue_result *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->rw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_rescued: batch has no rescue result");
+    use_device(b->device);
+    RescueWork &w = b->rw;
+    w.h_recs.ensure((w.n_reads ? w.n_reads : 1) * sizeof(pgx_read_rescue));
+    if (w.n_reads) HIPCHECK(hipMemcpyAsync(w.h_recs.p, w.recs.p, w.n_reads * sizeof(pgx_read_rescue), hipMemcpyDeviceToHost, b->own));
+    HIPCHECK(hipStreamSynchronize(b->own)); // (the kernels completed inside pgx_batch_read_rescue, on whatever stream it used)
+    rescued_header(b, out);
+    out->reads = w.h_recs.as<pgx_read_rescue>();
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_read_rescue_arrays(int device, const uint8_t *text, const uint64_t *seq_offsets, uint64_t n_seq, const uint8_t *reads, const uint64_t *read_offsets,
+                                             uint64_t n_reads, const uint64_t *cand_offsets, const pgx_read_verify *cands, int64_t frag_min, int64_t frag_max,
+                                             uint32_t mismatch_penalty, uint32_t min_score, uint32_t max_anchors, uint32_t flags, pgx_read_rescue *out,
+                                             uint64_t *list_offsets, pgx_read_verify *list, uint64_t list_cap, pgx_read_verify *winners) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_read_rescue_arrays");
+    checked_device_count();
+    const std::string who = "pgx_read_rescue_arrays";
+    rescue_check_args(who, frag_min, frag_max, min_score, max_anchors, flags);
+    verify_check_args(who, mismatch_penalty, 0u);
+    const bool merge = (flags & PGX_RESCUE_MERGE) != 0;
+    if (!seq_offsets || !read_offsets || !cand_offsets || (n_reads && !out) || (merge && (!list_offsets || (list_cap && !list) || (n_reads && !winners))))
+        throw Error(PGX_ERR_ARG, who + ": null argument");
+    // what pgx_read_verify_arrays refuses
+    check_offsets(who, seq_offsets, n_seq, "seq_offsets", "sequence");
+    check_offsets(who, read_offsets, n_reads, "read_offsets", "read");
+    check_offsets(who, cand_offsets, n_reads, "cand_offsets", "read");
+    const uint64_t n_text = seq_offsets[n_seq], read_bytes = read_offsets[n_reads], n_cands = cand_offsets[n_reads];
+    if ((n_text && !text) || (read_bytes && !reads) || (n_cands && !cands)) throw Error(PGX_ERR_ARG, who + ": null argument");
+    check_text(who, text, n_text);
+    for (uint64_t r = 0; r < n_reads; r++)
+        if (read_offsets[r + 1] - read_offsets[r] >= (1ull << 31))
+            throw Error(PGX_ERR_UNSUPPORTED, who + ": read " + std::to_string(r) + " has " + std::to_string(read_offsets[r + 1] - read_offsets[r]) + " bytes; the records hold read positions below 2^31");
+    if (n_reads >= PLACE_LAUNCH_ITEMS || n_cands >= PLACE_LAUNCH_ITEMS)
+        throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_reads) + " reads with " + std::to_string(n_cands) + " candidates exceed one launch");
+    // what pgx_read_mates_arrays refuses
+    if (n_seq & 1) throw Error(PGX_ERR_ARG, who + ": n_seq " + std::to_string(n_seq) + " is odd: sequences 2p and 2p + 1 are twins");
+    if (n_seq >= (1ull << 32) - 1) throw Error(PGX_ERR_ARG, who + ": n_seq " + std::to_string(n_seq) + " does not fit a record's seq");
+    if (const uint64_t bad = first_untwinned(seq_offsets, n_seq); bad != ~0ull)
+        throw Error(PGX_ERR_ARG, who + ": sequences " + std::to_string(2 * bad) + " and " + std::to_string(2 * bad + 1) + " (p = " + std::to_string(bad) + ") have the lengths " +
+                                     std::to_string(seq_offsets[2 * bad + 1] - seq_offsets[2 * bad]) + " and " + std::to_string(seq_offsets[2 * bad + 2] - seq_offsets[2 * bad + 1]) +
+                                     ": twins have one length");
+    uint64_t max_cand = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t c = cand_offsets[r + 1] - cand_offsets[r];
+        if (c > PGX_VERIFY_MAX_CAND) throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " has " + std::to_string(c) + " candidates, more than " + std::to_string(PGX_VERIFY_MAX_CAND));
+        max_cand = std::max(max_cand, c);
+    }
+    for (uint64_t r = 0; r < n_reads; r++)
+        for (uint64_t c = cand_offsets[r]; c < cand_offsets[r + 1]; c++)
+            if (cands[c].seq >= n_seq)
+                throw Error(PGX_ERR_ARG, who + ": candidate " + std::to_string(c - cand_offsets[r]) + " of read " + std::to_string(r) + " has seq " + std::to_string(cands[c].seq) +
+                                             ", not below n_seq " + std::to_string(n_seq));
+    if (n_reads & 1) throw Error(PGX_ERR_ARG, who + ": n_reads " + std::to_string(n_reads) + " is odd: reads 2k and 2k + 1 are the mates of pair k");
+    use_device(device);
+    struct RescueArrays : TextInput { // device copies of the input + the stage's buffers, released on every way out
+        DevBuf cand_off, cands, rcode, old_read, winners;
+        RescueWork w;
+        ~RescueArrays() { release_all({&cand_off, &cands, &rcode, &old_read, &winners}); w.release(); }
+    } k;
+    hipStream_t s = nullptr;
+    (void)mates_lane_shift(n_reads / 2, max_cand, who);
+    k.upload(text, seq_offsets, n_seq, reads, read_offsets, n_reads);
+    upload(k.cand_off, cand_offsets, (n_reads + 1) * 8);
+    upload(k.cands, cands, n_cands * sizeof(pgx_read_verify));
+    k.pack(s);
+    code_reads(k.rcode, k.reads.as<uint8_t>(), read_bytes, s);
+    HIPCHECK(hipGetLastError());
+    const RescueInput in{k.text4.as<uint32_t>(), k.seq_off.as<uint64_t>(), 0u, k.rcode.as<uint32_t>(), k.read_off.as<uint64_t>(), k.cand_off.as<uint64_t>(),
+                         k.cands.as<pgx_read_verify>(), n_reads, n_cands, max_cand};
+    rescue_core(k.w, in, frag_min, frag_max, mismatch_penalty, min_score, max_anchors, merge, s, who, nullptr);
+    const uint64_t n_new = n_cands + k.w.counters[1];
+    if (merge && n_new > list_cap)
+        throw Error(PGX_ERR_NOMEM, who + ": the merged list holds " + std::to_string(n_new) + " candidates, list_cap is " + std::to_string(list_cap));
+    if (merge) {
+        k.old_read.ensure((n_cands ? n_cands : 1) * 8);
+        k.winners.ensure((n_reads ? n_reads : 1) * sizeof(pgx_read_verify));
+        if (n_cands)
+            hipLaunchKernelGGL(pgx_verify_owner_kernel, dim3(grid_for(n_reads, 256)), dim3(256), 0, s, (const uint64_t *)k.cand_off.as<uint64_t>(), n_reads, n_cands,
+                               k.old_read.as<uint64_t>());
+        rescue_merge_core(k.w, in, k.old_read.as<uint64_t>(), mismatch_penalty, k.winners.as<pgx_read_verify>(), s);
+        HIPCHECK(hipMemcpyAsync(list_offsets, k.w.new_off.p, (n_reads + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (n_new) HIPCHECK(hipMemcpyAsync(list, k.w.new_cands.p, n_new * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, s));
+        if (n_reads) HIPCHECK(hipMemcpyAsync(winners, k.winners.p, n_reads * sizeof(pgx_read_verify), hipMemcpyDeviceToHost, s));
+    }
+    if (n_reads) HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, n_reads * sizeof(pgx_read_rescue), hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     return PGX_OK;
     PGX_GUARD_END

@@ -151,6 +151,20 @@ class ReadMatesResult(C.Structure):  # pgx_read_mates_result: a host pointer (pg
                 ("flags", u32), ("penalty", u32), ("pairs", p), ("ms_mates", C.c_float), ("reserved", u32)]
 
 
+RESCUE_MERGE = 1  # pgx_batch_read_rescue / pgx_read_rescue_arrays flag
+RESCUE_TARGET, RESCUE_RESCUED, RESCUE_FULL = 1, 2, 4  # bits of a record's flags
+RESCUE_MAX_ANCHORS, RESCUE_MAX_WINDOW = 8, 65536
+RESCUE_DTYPE = np.dtype([("diag", "<i8"), ("n_diags", "<u8"), ("seq", "<u4"), ("flags", "<u4"), ("anchor", "<u4"), ("n_anchors", "<u4"), ("seg_score", "<u4"),
+                         ("matches", "<u4"), ("n_best", "<u4"), ("next_score", "<u4"), ("reserved", "<u4", (4,))])  # pgx_read_rescue, 64 bytes
+assert RESCUE_DTYPE.itemsize == 64
+
+
+class ReadRescueResult(C.Structure):  # pgx_read_rescue_result: a host pointer (pgx_batch_rescued) or a device pointer (pgx_batch_device_rescued)
+    _fields_ = [("n_reads", u64), ("n_targets", u64), ("n_rescued", u64), ("n_full", u64), ("n_tasks", u64), ("n_diags", u64), ("frag_min", C.c_int64),
+                ("frag_max", C.c_int64), ("min_score", u32), ("max_anchors", u32), ("flags", u32), ("mismatch_penalty", u32), ("reads", p), ("ms_rescue", C.c_float),
+                ("reserved", u32)]
+
+
 ALIGN_CIGAR = 1  # pgx_batch_read_align / pgx_read_align_arrays flag
 ALIGN_DTYPE = np.dtype([("diag", "<i8"), ("text_start", "<u8"), ("text_end", "<u8"), ("seq", "<u4"), ("clip_lo", "<u4"), ("clip_hi", "<u4"), ("edits", "<u4"),
                         ("n_match", "<u4"), ("n_mismatch", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4"), ("n_ops", "<u4"), ("band_hit", "<u4")])  # pgx_read_align, 64 bytes
@@ -335,6 +349,10 @@ def lib():
     L.pgx_batch_mated.argtypes = [p, C.POINTER(ReadMatesResult)]
     L.pgx_batch_device_mated.argtypes = [p, C.POINTER(ReadMatesResult)]
     L.pgx_read_mates_arrays.argtypes = [C.c_int, p, u64, u64, p, p, C.c_int64, C.c_int64, u32, u32, p, p]
+    L.pgx_batch_read_rescue.argtypes = [p, C.c_int64, C.c_int64, u32, u32, u32, p]
+    L.pgx_batch_rescued.argtypes = [p, C.POINTER(ReadRescueResult)]
+    L.pgx_batch_device_rescued.argtypes = [p, C.POINTER(ReadRescueResult)]
+    L.pgx_read_rescue_arrays.argtypes = [C.c_int, p, p, u64, p, p, u64, p, p, C.c_int64, C.c_int64, u32, u32, u32, u32, p, p, p, u64, p]
     L.pgx_batch_read_walk.argtypes = [p, u32, p]
     L.pgx_batch_walked.argtypes = [p, C.POINTER(ReadWalks)]
     L.pgx_batch_device_walked.argtypes = [p, C.POINTER(ReadWalks)]
@@ -1032,6 +1050,41 @@ def read_verify_arrays(device, text, seq_offsets, reads, read_offsets, cand_offs
     return res
 
 
+def read_rescue_arrays(device, text, seq_offsets, reads, read_offsets, cand_offsets, cands, frag_min, frag_max, penalty=4, min_score=1, max_anchors=2, flags=0,
+                       list_cap=None, out=None):
+    """pgx_read_rescue_arrays: the rescue kernels on host arrays (text, seq_offsets, reads, read_offsets as in read_verify_arrays; the list of read r at
+    [cand_offsets[r], cand_offsets[r + 1]) of cands VERIFY_DTYPE): dict(reads RESCUE_DTYPE[n_reads], and with RESCUE_MERGE cand_offsets uint64[n_reads + 1],
+    cands VERIFY_DTYPE (the merged list) and winners VERIFY_DTYPE[n_reads], else None).  list_cap: the capacity handed to the library (default: the list with
+    one more entry a read); out: a dict of arrays to write into (tests)"""
+    text = np.ascontiguousarray(text, dtype=np.uint8)
+    reads = np.ascontiguousarray(reads, dtype=np.uint8)
+    seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+    read_offsets = np.ascontiguousarray(read_offsets, dtype=np.uint64)
+    cand_offsets = np.ascontiguousarray(cand_offsets, dtype=np.uint64)
+    cands = np.ascontiguousarray(cands, dtype=VERIFY_DTYPE)
+    n, n_seq = len(read_offsets) - 1, len(seq_offsets) - 1
+    if len(cand_offsets) != n + 1:
+        raise ValueError("read_rescue_arrays: cand_offsets must have len(read_offsets) entries")
+    merge = bool(flags & RESCUE_MERGE)
+    cap = len(cands) + n if list_cap is None else int(list_cap)
+    res = dict(out) if out else {}
+    if "reads" not in res:
+        res["reads"] = np.zeros(n, dtype=RESCUE_DTYPE)
+    if "cand_offsets" not in res:
+        res["cand_offsets"] = np.zeros(n + 1, dtype=np.uint64) if merge else None
+    if "cands" not in res:
+        res["cands"] = np.zeros(max(cap, 1), dtype=VERIFY_DTYPE) if merge else None
+    if "winners" not in res:
+        res["winners"] = np.zeros(n, dtype=VERIFY_DTYPE) if merge else None
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().pgx_read_rescue_arrays(device, text.ctypes.data, seq_offsets.ctypes.data, n_seq, reads.ctypes.data, read_offsets.ctypes.data, n, cand_offsets.ctypes.data,
+                                        cands.ctypes.data, frag_min, frag_max, penalty, min_score, max_anchors, flags, ptr(res["reads"]), ptr(res["cand_offsets"]),
+                                        ptr(res["cands"]), cap, ptr(res["winners"])))
+    if merge:
+        res["cands"] = res["cands"][: int(res["cand_offsets"][-1])]
+    return res
+
+
 def read_mates_arrays(device, seq_lengths, cand_offsets, cands, frag_min, frag_max, penalty, flags=0, n_reads=None, out=None):
     """pgx_read_mates_arrays: the mates kernel on stated lists (seq_lengths uint64[n_seq]; the candidates of read r at [cand_offsets[r],
     cand_offsets[r + 1]) of cands VERIFY_DTYPE, of which seq, diag, seg_score and matches count): dict(pairs MATES_DTYPE[n_reads / 2], and with
@@ -1459,6 +1512,33 @@ class Batch:
         out["reads"] = DeviceArray(r.reads, (n, 8), self)
         out["cand_offsets"] = DeviceArray(r.cand_offsets, (n + 1,), self) if r.cand_offsets else None
         out["cands"] = DeviceArray(r.cands, (k, 8), self) if r.cands else None
+        return out
+
+    def read_rescue(self, frag_min, frag_max, min_score, max_anchors=2, flags=0, stream=None):
+        """pgx_batch_read_rescue on the list of the last read_verify (made with VERIFY_LIST), then rescued(); with RESCUE_MERGE every rescued read gains
+        its best diagonal as the last candidate of its list, and the winners are recomputed"""
+        _check(self.L.pgx_batch_read_rescue(self.b, frag_min, frag_max, min_score, max_anchors, flags, stream))
+        return self.rescued()
+
+    def _rescued(self, fn):
+        r = ReadRescueResult()
+        _check(fn(self.b, C.byref(r)))
+        return r, dict(n_reads=int(r.n_reads), n_targets=int(r.n_targets), n_rescued=int(r.n_rescued), n_full=int(r.n_full), n_tasks=int(r.n_tasks), n_diags=int(r.n_diags),
+                       frag_min=int(r.frag_min), frag_max=int(r.frag_max), min_score=int(r.min_score), max_anchors=int(r.max_anchors), flags=int(r.flags),
+                       mismatch_penalty=int(r.mismatch_penalty), ms_rescue=float(r.ms_rescue))
+
+    def rescued(self):
+        """the last rescue result: reads RESCUE_DTYPE[n_reads], with n_reads, the five counters, the parameters of the call and ms_rescue"""
+        r, out = self._rescued(self.L.pgx_batch_rescued)
+        k = out["n_reads"]
+        out["reads"] = np.frombuffer((C.c_char * (k * 64)).from_address(r.reads), dtype=RESCUE_DTYPE).copy() if k else np.zeros(0, RESCUE_DTYPE)
+        return out
+
+    def device_rescued(self):
+        """the same with reads as a device array (valid until the next run / upload / read_rescue / free): int64[n_reads, 8], the 64-byte records as words"""
+        r, out = self._rescued(self.L.pgx_batch_device_rescued)
+        out["device"] = True
+        out["reads"] = DeviceArray(r.reads, (out["n_reads"], 8), self)
         return out
 
     def read_mates(self, frag_min, frag_max, penalty, flags=0, stream=None):

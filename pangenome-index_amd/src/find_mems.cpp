@@ -32,6 +32,10 @@
 //                 and pgx_batch_read_mates with PGX_MATES_ELECT, so that --verify, --align and --gaf report the winners the pairs elected),
 //                 --frag-min A (default 0), --frag-max B (default 1000), --mates-penalty U (default 2 * (P + 1), P of --verify-mismatch),
 //                 --mates FILE (one line per pair), --mates-only (no MEM text, like --verify-only)
+//                 --rescue (with --paired: pgx_batch_read_rescue with PGX_RESCUE_MERGE between verify and mates, under the bounds of --frag-min /
+//                 --frag-max: a read without a placement near its placed mate is searched for on every diagonal of the window the mate names, and
+//                 what is found joins its candidates, so that mates, --verify, --align and --gaf see it), --rescue-min S (default min_mem_length),
+//                 --rescue-anchors R (1 .. 8, default 2), --rescued FILE (one line per read)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -166,6 +170,7 @@ struct Done {
     std::string aligns; // --align: the lines of this batch
     std::string gaf; // --gaf: the lines of this batch
     std::string mates; // --mates: the lines of this batch's pairs
+    std::string rescued; // --rescued: the lines of this batch
     std::string error;
 };
 
@@ -350,6 +355,32 @@ static void format_mates(const pgx_read_mates *recs, size_t n, uint64_t first_se
     out.resize((size_t)(p - &out[0]));
 }
 
+// --rescued: the lines of reads [0, n) of a batch whose first read is first_seq, appended to out; seq and pos (the diagonal) print as * for a read
+// that is no target and for a target whose windows were empty
+static const char RESCUED_HEADER[] = "#read\ttarget\tanchors\tdiags\tseq\tpos\tseg_score\tmatches\tn_best\tnext\trescued\n";
+static void format_rescued(const pgx_read_rescue *recs, size_t n, uint64_t first_seq, std::string &out) {
+    out.resize(n * (11 * 21));
+    char *p = &out[0];
+    for (size_t k = 0; k < n; k++) {
+        const pgx_read_rescue &x = recs[k];
+        p = put_u64(p, first_seq + k + 1); *p++ = '\t';
+        *p++ = (x.flags & PGX_RESCUE_TARGET) ? '1' : '0'; *p++ = '\t';
+        p = put_u64(p, x.n_anchors); *p++ = '\t';
+        p = put_u64(p, x.n_diags); *p++ = '\t';
+        if (x.seq == PGX_NO_SEQUENCE) { *p++ = '*'; *p++ = '\t'; *p++ = '*'; }
+        else {
+            p = put_u64(p, x.seq); *p++ = '\t';
+            if (x.diag < 0) { *p++ = '-'; p = put_u64(p, 0 - (uint64_t)x.diag); }
+            else p = put_u64(p, (uint64_t)x.diag);
+        }
+        const uint32_t f[4] = {x.seg_score, x.matches, x.n_best, x.next_score};
+        for (uint32_t v : f) { *p++ = '\t'; p = put_u64(p, v); }
+        *p++ = '\t'; *p++ = (x.flags & PGX_RESCUE_RESCUED) ? '1' : '0';
+        *p++ = '\n';
+    }
+    out.resize((size_t)(p - &out[0]));
+}
+
 // --align: the lines of reads [0, n) of a batch, appended to out; seq, start, end and cigar print as * when the read has no candidate
 static const char ALIGN_HEADER[] = "#read\tseq\tstart\tend\tclip_lo\tclip_hi\tedits\tmatches\tmismatches\tins\tdel\tband_hit\tcigar\n";
 static void format_aligns(const pgx_read_align *recs, const uint64_t *op_off, const uint32_t *ops, size_t n, uint64_t first_seq, std::string &out) {
@@ -423,7 +454,8 @@ static int usage() {
                  " [--verify FILE [--verify-max C] [--verify-mismatch P] [--verify-only (not with --locate)]]"
                  " [--align FILE [--align-band W (0 .. 31)] [--align-only (not with --locate)]]"
                  " [--gaf FILE [--gaf-only (not with --locate)]]"
-                 " [--paired [--frag-min A] [--frag-max B] [--mates-penalty U] [--mates FILE [--mates-only (not with --locate)]]]" << std::endl;
+                 " [--paired [--frag-min A] [--frag-max B] [--mates-penalty U] [--mates FILE [--mates-only (not with --locate)]]"
+                 " [--rescue [--rescue-min S] [--rescue-anchors R (1 .. 8)] [--rescued FILE]]]" << std::endl;
     return EXIT_FAILURE;
 }
 
@@ -461,6 +493,10 @@ int main(int argc, char **argv) {
     int64_t frag_min = 0, frag_max = 1000;
     uint64_t mates_penalty = 0;
     bool mates_opt_given = false, mates_penalty_given = false, mates_only = false, verify_max_given = false;
+    bool rescue = false;        // --rescue: pgx_batch_read_rescue with PGX_RESCUE_MERGE between verify and mates
+    std::string rescued_file;   // --rescued: the rescue records of every batch go to this file
+    uint64_t rescue_min = 0, rescue_anchors = 2;
+    bool rescue_opt_given = false, rescue_min_given = false;
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -583,7 +619,30 @@ int main(int argc, char **argv) {
             mates_penalty = k;
             mates_opt_given = mates_penalty_given = true;
         }
+        else if (a == "--rescue") rescue = true;
+        else if (a == "--rescued") { rescued_file = next(); if (rescued_file.empty()) { std::cerr << "--rescued: a file name" << std::endl; return EXIT_FAILURE; } }
+        else if (a == "--rescue-min" || a == "--rescue-anchors") {
+            const bool is_min = a == "--rescue-min";
+            const std::string v = next();
+            char *endp = nullptr;
+            errno = 0;
+            const unsigned long long k = v.empty() || v[0] == '-' ? 0 : std::strtoull(v.c_str(), &endp, 10);
+            if (!endp || *endp || errno || k < 1 || k > (is_min ? 0xFFFFFFFFull : (unsigned long long)PGX_RESCUE_MAX_ANCHORS)) {
+                std::cerr << a << (is_min ? ": a number in 1 .. 4294967295" : ": a number in 1 .. 8") << std::endl;
+                return EXIT_FAILURE;
+            }
+            (is_min ? rescue_min : rescue_anchors) = k;
+            rescue_opt_given = true;
+            if (is_min) rescue_min_given = true;
+        }
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
+    }
+    if (rescue && !paired) return usage();                                     // (the rescue options belong to --paired ...
+    if ((!rescued_file.empty() || rescue_opt_given) && !rescue) return usage(); // ... and its own to --rescue)
+    if (rescue && !rescue_min_given) rescue_min = mem_length ? std::min<uint64_t>(mem_length, 0xFFFFFFFFull) : 1; // (no less evidence than a placed read: a MEM of that length)
+    if (rescue && (uint64_t)frag_max - (uint64_t)frag_min >= (uint64_t)PGX_RESCUE_MAX_WINDOW && frag_min <= frag_max) {
+        std::cerr << "--rescue: --frag-min " << frag_min << " .. --frag-max " << frag_max << " is a window of more than " << PGX_RESCUE_MAX_WINDOW << " diagonals" << std::endl;
+        return EXIT_FAILURE;
     }
     if ((!mates_file.empty() || mates_only || mates_opt_given) && !paired) return usage(); // (the mates options belong to --paired)
     if (mates_only && mates_file.empty()) return usage();
@@ -603,7 +662,7 @@ int main(int argc, char **argv) {
     if (align_only && locate_mode) { std::cerr << "--align-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     const bool want_hits = !hits_file.empty(), want_places = !place_file.empty(), want_verify = !verify_file.empty(), want_align = !align_file.empty();
     const bool want_gaf = !gaf_file.empty(), run_align = want_align || want_gaf; // (--gaf runs the align stage itself)
-    const bool want_mates = !mates_file.empty();
+    const bool want_mates = !mates_file.empty(), want_rescued = !rescued_file.empty();
     const bool run_verify = want_verify || run_align || paired; // (--align runs the verify stage itself; --paired elects its winners)
     const uint32_t place_flags = run_verify && (verify_max > 1 || paired) ? PGX_PLACE_LIST : 0u; // (the candidates beyond the first come from the list)
     const uint32_t verify_flags = paired ? PGX_VERIFY_LIST : 0u;                                 // (the mates stage reads the candidates of both mates)
@@ -688,7 +747,7 @@ int main(int argc, char **argv) {
         std::fwrite(PLACE_HEADER, 1, sizeof PLACE_HEADER - 1, place_fp);
     }
     // --verify: the same question for the text image (what --place asks, and a collection of 2^32 - 2^20 symbols or more)
-    std::FILE *verify_fp = nullptr, *align_fp = nullptr, *gaf_fp = nullptr, *mates_fp = nullptr;
+    std::FILE *verify_fp = nullptr, *align_fp = nullptr, *gaf_fp = nullptr, *mates_fp = nullptr, *rescued_fp = nullptr;
     if (run_verify) {
         static const uint8_t probe_read[4] = {'A', 'C', 'G', 'T'};
         static const uint64_t probe_offs[2] = {0, 4};
@@ -742,6 +801,11 @@ int main(int argc, char **argv) {
             mates_fp = std::fopen(mates_file.c_str(), "wb");
             if (!mates_fp) { std::cerr << "Cannot open mates file: " << mates_file << std::endl; return EXIT_FAILURE; }
             std::fwrite(MATES_HEADER, 1, sizeof MATES_HEADER - 1, mates_fp);
+        }
+        if (want_rescued) {
+            rescued_fp = std::fopen(rescued_file.c_str(), "wb");
+            if (!rescued_fp) { std::cerr << "Cannot open rescued file: " << rescued_file << std::endl; return EXIT_FAILURE; }
+            std::fwrite(RESCUED_HEADER, 1, sizeof RESCUED_HEADER - 1, rescued_fp);
         }
     }
 
@@ -1043,9 +1107,16 @@ int main(int argc, char **argv) {
                 if (st == PGX_OK && want_places) place_recs.assign(rp2.reads, rp2.reads + rp2.n_reads);
             }
             std::vector<pgx_read_mates> mate_recs;    // --mates: the 64-byte records of the batch's pairs
+            std::vector<pgx_read_rescue> rescue_recs; // --rescued: the 64-byte records of the batch's reads
             std::vector<pgx_read_verify> verify_recs; // --verify: the 64-byte records, at the candidates of the place stage above
             if (st == PGX_OK && run_verify) {
                 st = pgx_batch_read_verify(b, verify_max, verify_penalty, verify_flags, nullptr);
+                if (st == PGX_OK && rescue) { // the unplaced mates are searched for and join the lists, before the pairs choose
+                    st = pgx_batch_read_rescue(b, frag_min, frag_max, (uint32_t)rescue_min, (uint32_t)rescue_anchors, PGX_RESCUE_MERGE, nullptr);
+                    pgx_read_rescue_result rr;
+                    if (st == PGX_OK && want_rescued) st = pgx_batch_rescued(b, &rr);
+                    if (st == PGX_OK && want_rescued) rescue_recs.assign(rr.reads, rr.reads + rr.n_reads);
+                }
                 if (st == PGX_OK && paired) { // the pairs choose: the elected winners are what --verify, --align and --gaf report below
                     st = pgx_batch_read_mates(b, frag_min, frag_max, (uint32_t)mates_penalty, PGX_MATES_ELECT, nullptr);
                     pgx_read_mates_result rm;
@@ -1130,6 +1201,7 @@ int main(int argc, char **argv) {
                 if (want_places) format_places(place_recs.data(), place_recs.size(), j->first_seq, d->places);
                 if (want_verify) format_verifies(verify_recs.data(), verify_recs.size(), j->first_seq, d->verifies);
                 if (want_mates) format_mates(mate_recs.data(), mate_recs.size(), j->first_seq, d->mates);
+                if (want_rescued) format_rescued(rescue_recs.data(), rescue_recs.size(), j->first_seq, d->rescued);
                 if (want_gaf && !walk_read_off.empty())
                     format_gaf(align_recs.data(), align_op_off.data(), align_ops.data(), walk_recs.data(), walk_step_off.data(), walk_steps.data(), walk_read_off.data(),
                                walk_recs.size(), j->first_seq, d->gaf);
@@ -1236,6 +1308,7 @@ int main(int argc, char **argv) {
         if (align_fp && !d->aligns.empty()) std::fwrite(d->aligns.data(), 1, d->aligns.size(), align_fp);
         if (gaf_fp && !d->gaf.empty()) std::fwrite(d->gaf.data(), 1, d->gaf.size(), gaf_fp);
         if (mates_fp && !d->mates.empty()) std::fwrite(d->mates.data(), 1, d->mates.size(), mates_fp);
+        if (rescued_fp && !d->rescued.empty()) std::fwrite(d->rescued.data(), 1, d->rescued.size(), rescued_fp);
         ns_write += now_ns() - tw0;
         total_mem_time += d->mem_s;
         total_tag_time += d->tag_s;
@@ -1263,6 +1336,7 @@ int main(int argc, char **argv) {
     if (align_fp && (std::fclose(align_fp) != 0) && error.empty()) error = "Cannot write align file: " + align_file;
     if (gaf_fp && (std::fclose(gaf_fp) != 0) && error.empty()) error = "Cannot write gaf file: " + gaf_file;
     if (mates_fp && (std::fclose(mates_fp) != 0) && error.empty()) error = "Cannot write mates file: " + mates_file;
+    if (rescued_fp && (std::fclose(rescued_fp) != 0) && error.empty()) error = "Cannot write rescued file: " + rescued_file;
     if (!error.empty()) {
         std::cerr << error << std::endl;
         return EXIT_FAILURE;
