@@ -1199,6 +1199,123 @@ pgx_status pgx_read_walk_arrays(int device, const uint64_t *seq_offsets, uint64_
                                 const uint32_t *visit_length, uint64_t n_reads, const uint32_t *seq, const uint64_t *text_start, const uint64_t *text_end,
                                 uint32_t flags, pgx_read_walk *out, uint64_t *step_offsets, uint64_t *steps, uint64_t steps_cap);
 
+/* ---- read mapq: how far to trust the placement of every read, on the device ----------------------------------------------------------
+ * Verify's n_tied counts haplotypes: a read that lies on eight haplotypes which agree over it has n_tied = 8 and one place in the graph.  This
+ * stage counts competing graph LOCI instead, treats the neighbouring diagonals of one sequence (a read with an indel) as one place, looks one
+ * coverage level below the candidates, and turns the evidence into a number from 0 to 60.  It sits behind verify (and rescue and mates where
+ * they run) and changes none of their results.  Everything is integer arithmetic.
+ *
+ * DEFINITIONS for read r.
+ *   entries      the candidates of r's verify list (PGX_VERIFY_LIST, possibly after a rescue merge) in list order, n_list of them, and behind
+ *                them the EXTRAS: the first min(max_extra, 64 - n_list) placements of r with cov == next_score > 0 (next_score of the place
+ *                record), in placement order, 0 <= max_extra <= 63.  The stage verifies the extras itself with the verify call's P; an extra's
+ *                record is what verify writes at that (seq, diag).  Extras only compete: they never become candidates or winners, and the
+ *                verify result is not touched.  With max_extra == 0 no place list is needed.  A read has at most 64 entries.
+ *   chosen       the entry whose ordinal is the cand_index of r's winner record (possibly after an election, PGX_MATES_ELECT).  A read whose
+ *                winner has seq == PGX_NO_SEQUENCE has no chosen entry: its record is 32 zero bytes.
+ *   anchor       a = seg_start of the chosen entry, a read position.
+ *   locus        of entry i: defined iff span_lo_i <= a < span_hi_i; then the pair (first step, path_start) that "read walk" gives for the
+ *                stretch [diag_i + a, diag_i + a + 1) of seq_i: the oriented node that holds the text position under the anchor and the
+ *                offset in it.  The 1024 cut of the walk's scans applies as it does there.
+ *   classes      two entries are in one class iff both loci are defined and equal; an entry without a locus is a class of its own.
+ *   adjacent     a class X other than the chosen's is adjacent iff some entry i of X and some entry j of the chosen's class have
+ *                seq_i == seq_j and 0 < |diag_i - diag_j| <= slack (signed 64-bit), 0 <= slack <= 1024; slack == 0: no class is adjacent.
+ *                Adjacent classes do not compete.  The classes that are neither the chosen's nor adjacent are the COMPETING classes.
+ *   score        of entry i: s_i = seg_score_i.  With PGX_MAPQ_PAIRED reads 2k and 2k + 1 are mates and the score is s_i + m_i in signed 64
+ *                bits, under frag_min, frag_max and U of the batch's mates result: m_i = 0 if the mate has no list candidate, else the larger of
+ *                (1) the largest seg_score_j over the mate's LIST candidates j compatible with i in the sense of "read mates" and (2)
+ *                solo_mate - U, solo_mate the seg_score of the mate's solo winner.  When the winners were elected under the same bounds and U,
+ *                the chosen entry has the largest score of its list, PROPER or not, for any U >= 0: a PROPER pair (i*, j*) has s_i* + s_j* >=
+ *                every compatible sum and >= solo_a + solo_b - U >= s_i + solo_b - U; without PROPER the chosen entry is the solo winner and
+ *                every compatible sum lies below solo_a + solo_b - U.
+ *   S_X, S_w, d_X   S_X is the largest score in class X, S_w the score of the chosen entry, d_X = max(0, S_w - S_X).  PGX_MAPQ_OUTSCORED: some
+ *                competing class has S_X > S_w (possible through extras and in the arrays route).
+ *   weights      T[k] = floor(65536 * 10^(-k / 10)), k = 0 .. 49 (PGX_MAPQ_T below).  A competing class weighs T[min(49, scale * d_X)], the
+ *                product in 64 bits, 1 <= scale <= 16 decibels per score unit.  The default 2 makes a mismatch (P + 1 = 5 units at the
+ *                default penalty) 10 dB: a model choice, not a measurement.
+ *   excess       E = the sum of the weights of the competing classes.  If the chosen entry is the candidate a rescue merge appended (the
+ *                read's rescue record has PGX_RESCUE_RESCUED, the verify result is merged and the chosen ordinal is the list's last), the
+ *                diagonals of the rescue window compete with it: (n_best - 1) * 65536 is added, and T[min(49, scale * (seg_score -
+ *                next_score))] when next_score > 0, all from the rescue record; PGX_MAPQ_RESCUED is set.  E is summed in 64 bits and stored
+ *                held at 2^32 - 1.
+ *   mapq         K[q] = floor(65536 * 10^(q / 10)), q = 0 .. 60 (PGX_MAPQ_K below).  mapq is the largest q in 0 .. 60 with
+ *                E * K[q] <= (E + 65536) * 65536: 10 log10 of (all weight) / (competing weight), cut at 60.  E may be held at 2^26 in the
+ *                comparison (mapq is 0 from E = 253 122 on, and no E, 2^26 included, makes the two sides equal: no K[q] - 65536 divides 2^32).  E = 0: 60; one exact tie (E = 65536): 3; two: 1; one competitor 10 / 20 dB
+ *                down (E = 6553 / 655): 10 / 20; E = T[48] = 1: 48.
+ * pgx_read_mapq (32 bytes, little endian, u32 each):
+ *    0 mapq          4 flags
+ *    8 n_entries     entries of the read                       12 n_loci        classes
+ *   16 n_with        entries in the chosen's class or in an adjacent class
+ *   20 n_competing   competing classes                         24 best_other    largest competing S_X held to [0, 2^32 - 1]; 0 without one
+ *   28 excess        E held at 2^32 - 1
+ * flags: PGX_MAPQ_HAS (a chosen entry), _LOCUS (the chosen's locus is defined), _PAIRED (the paired scores were used and the mate has a list
+ * candidate), _RESCUED, _OUTSCORED, and _CAPPED: some competitors may be unseen -- the list holds at least the verify call's max_cand entries,
+ * or (max_extra > 0) more next-level placements exist than extras were taken.  The arrays route never sets _CAPPED. */
+#define PGX_MAPQ_PAIRED 4u     /* a flag of the call and a bit of pgx_read_mapq.flags */
+#define PGX_MAPQ_HAS 1u        /* bits of pgx_read_mapq.flags */
+#define PGX_MAPQ_LOCUS 2u
+#define PGX_MAPQ_RESCUED 8u
+#define PGX_MAPQ_CAPPED 16u
+#define PGX_MAPQ_OUTSCORED 32u
+#define PGX_MAPQ_MAX_ENTRIES 64u
+#define PGX_MAPQ_MAX_SCALE 16u
+#define PGX_MAPQ_MAX_SLACK 1024u
+#define PGX_MAPQ_MAX_EXTRA 63u
+#define PGX_MAPQ_NO_CHOSEN 0xFFFFFFFFu
+#define PGX_MAPQ_T { \
+    65536, 52057, 41350, 32845, 26090, 20724, 16461, 13076, 10386, 8250, \
+    6553, 5205, 4135, 3284, 2609, 2072, 1646, 1307, 1038, 825, \
+    655, 520, 413, 328, 260, 207, 164, 130, 103, 82, \
+    65, 52, 41, 32, 26, 20, 16, 13, 10, 8, \
+    6, 5, 4, 3, 2, 2, 1, 1, 1, 0 }
+#define PGX_MAPQ_K { \
+    65536, 82504, 103867, 130761, 164618, 207243, 260903, 328458, 413504, 520570, \
+    655360, 825049, 1038675, 1307615, 1646189, 2072430, 2609035, 3284580, 4135042, 5205709, \
+    6553600, 8250493, 10386756, 13076151, 16461898, 20724302, 26090351, 32845806, 41350420, 52057095, \
+    65536000, 82504935, 103867560, 130761511, 164618989, 207243028, 260903515, 328458065, 413504205, 520570951, \
+    655360000, 825049357, 1038675602, 1307615110, 1646189891, 2072430287, 2609035152, 3284580654, 4135042052, 5205709519, \
+    6553600000, 8250493578, 10386756026, 13076151107, 16461898917, 20724302873, 26090351529, 32845806542, 41350420527, 52057095190, \
+    65536000000 }
+typedef struct {
+    uint32_t mapq, flags, n_entries, n_loci, n_with, n_competing, best_other, excess;
+} pgx_read_mapq;
+typedef struct {
+    uint64_t n_reads;
+    uint64_t n_has, n_unique, n_capped, sum_mapq; /* reads with PGX_MAPQ_HAS, of them with E == 0, reads with PGX_MAPQ_CAPPED, the sum of mapq: summed on the device */
+    uint64_t n_extras;              /* extras verified over all reads */
+    uint32_t scale, slack, max_extra, flags; /* what the call ran with */
+    const pgx_read_mapq *records;   /* n_reads */
+    float ms_mapq;                  /* device time of the call when the run had PGX_RUN_TIMING, else 0 (the walk image's build is not in it) */
+    uint32_t reserved;
+} pgx_read_mapqs;
+/* The mapping qualities of the reads of the last run from the list and the winners of the last pgx_batch_read_verify, which must be this run's
+ * and made with PGX_VERIFY_LIST.  With max_extra > 0 it also needs a place result of this run made with PGX_PLACE_LIST; with PGX_MAPQ_PAIRED
+ * a mates result made on the current verify result and an even read count.  The rescue terms are added when the batch holds a rescue result
+ * whose merge made the current list (a merged list takes no further pgx_batch_read_rescue call, with or without PGX_RESCUE_MERGE, so that
+ * result stays the batch's until the next verify call).  PGX_ERR_ARG with nothing changed, naming what was found: no such result, scale outside 1 .. 16,
+ * slack > 1024, max_extra > 63, an unknown flag.  Builds the WALK image on first use, with the refusals of pgx_batch_read_walk.  A read takes
+ * the smallest power of two of lanes that holds the longest entry list (PGX_MAPQ_LANES in the environment, read per call, 1 .. 64, raises it;
+ * results never depend on it).  Runs on `stream` (NULL = the batch's own), complete on return.  Buffers grow only and are the stage's own: the
+ * result stays valid until the next run, upload, pgx_batch_read_verify, pgx_batch_read_rescue, pgx_batch_read_mates, pgx_batch_read_mapq or
+ * free of the batch; a later pgx_batch_locate of any form leaves it valid. */
+pgx_status pgx_batch_read_mapq(pgx_batch *b, uint32_t scale, uint32_t slack, uint32_t max_extra, uint32_t flags, void *stream);
+/* Host copy of the last mapq result (a pinned buffer owned by the batch) / the same as a device pointer.  PGX_ERR_ARG when there is none. */
+pgx_status pgx_batch_mapqs(pgx_batch *b, pgx_read_mapqs *out);
+pgx_status pgx_batch_device_mapqs(pgx_batch *b, pgx_read_mapqs *out);
+/* The same kernel on stated tables (how shapes no index produces are tested): the path tables of pgx_read_walk_arrays; read r has the entries
+ * [entry_offsets[r], entry_offsets[r + 1]), pgx_read_verify records of which seq, diag, span_lo, span_hi, seg_start, seg_score and matches are
+ * read; chosen[r] is an ordinal or PGX_MAPQ_NO_CHOSEN; list_len[r] says how many leading entries are list candidates, the rest are extras
+ * (NULL: all are list candidates); rescue (NULL: none) holds a pgx_read_rescue record per read, and a read whose record has PGX_RESCUE_RESCUED
+ * and whose chosen entry is its last list candidate takes the rescue terms.  frag_min, frag_max and penalty (U) are read under
+ * PGX_MAPQ_PAIRED only.  `out` takes n_reads records.  PGX_ERR_ARG with nothing written, the first offender named: whatever
+ * pgx_read_walk_arrays and pgx_read_mates_arrays refuse for the same tables (offsets, visit lengths, under PGX_MAPQ_PAIRED frag_min > frag_max,
+ * an odd n_seq and unequal twins), a seq >= n_seq, a span that leaves its sequence, more than 64 entries, a list_len above the entry count, a
+ * chosen >= list_len, scale, slack or a flag outside their ranges, an odd n_reads under PGX_MAPQ_PAIRED.  PGX_ERR_NO_DEVICE without a GPU. */
+pgx_status pgx_read_mapq_arrays(int device, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
+                                const uint32_t *visit_length, uint64_t n_reads, const uint64_t *entry_offsets, const pgx_read_verify *entries,
+                                const uint32_t *chosen, const pgx_read_rescue *rescue, int64_t frag_min, int64_t frag_max, uint32_t penalty,
+                                const uint32_t *list_len, uint32_t scale, uint32_t slack, uint32_t flags, pgx_read_mapq *out);
+
 /* ---- compact result: the result of a run as a byte stream, encoded on the device, expanded on the host ---------------------
  * What pgx_batch_result downloads is six dense uint64 arrays (8 bytes per read, 48 per MEM, 8 per graph position), nearly all of
  * them zero bits.  The compact form carries the same values and is expanded to the same pgx_result; only it crosses the link.

@@ -37,6 +37,7 @@ static void batch_release(pgx_batch *b) {
         b->mw.release();
         b->aw.release();
         b->ww.release();
+        b->qw.release();
         release_all({&b->h_mem_off, &b->h_mems, &b->h_run_nums, &b->h_pos_off, &b->h_positions, &b->h_off[0], &b->h_off[1]});
         destroy_events(b->ev);
         if (b->own) { (void)hipStreamDestroy(b->own); b->own = nullptr; }
@@ -63,6 +64,7 @@ static void batch_reset_for_upload(pgx_batch *b, uint64_t n_reads, uint64_t max_
     b->mw.valid = false;
     b->aw.valid = false;
     b->ww.valid = false;
+    b->qw.valid = false;
     b->plan_valid = false;
     b->slot_off_valid = false;
     b->class_valid = false;
@@ -995,6 +997,7 @@ extern "C" pgx_status pgx_batch_run(pgx_batch *b, uint64_t min_len, uint64_t min
     b->mw.valid = false; // (and paired from that)
     b->aw.valid = false; // (and aligned there)
     b->ww.valid = false; // (and walked through the graph)
+    b->qw.valid = false; // (and the qualities of the placements)
     b->n_mems = b->n_positions = b->n_ext = b->n_tag_overflow = 0;
     std::memset(&b->timing, 0, sizeof b->timing);
     bool force_worst = false;

@@ -106,6 +106,7 @@ struct VerifyWork {
     uint32_t flags = 0, max_cand = 0, penalty = 0;
     uint32_t max_list = 0; // the longest list: max_cand, or max_cand + 1 <= 64 behind a merge of pgx_batch_read_rescue (sizes the lane group of mates)
     bool merged = false;   // a rescue call has appended its candidates: cand_seq / cand_diag / cand_read describe the list before it
+    uint64_t gen = 0;      // counts the verify calls and merges of the batch: what was made from the list says which list it was (MatesWork.verify_gen)
     uint64_t n_reads = 0, n_cands = 0;
     float ms = 0;
     StageResult result() const { return {n_reads, recs.p, sizeof(pgx_read_verify), (flags & PGX_VERIFY_LIST) != 0, cand_off.p, n_cands, cands.p, sizeof(pgx_read_verify)}; }
@@ -124,6 +125,7 @@ struct MatesWork {
     uint32_t flags = 0, penalty = 0;
     int64_t frag_min = 0, frag_max = 0;
     uint64_t n_pairs = 0, counters[4] = {0, 0, 0, 0}; // pairs PROPER, COMPATIBLE, with A moved, with B moved
+    uint64_t verify_gen = 0; // VerifyWork.gen of the list the pairs were made from (pgx_batch_read_mapq asks)
     float ms = 0;
     void release() {
         release_all({&recs, &ctr});
@@ -182,6 +184,23 @@ struct WalkWork {
     void release() {
         release_all({&recs, &count, &first, &step_off, &steps, &scan_tmp});
         release_all({&h_recs, &h_step_off, &h_steps}); timer.release(); valid = false;
+    }
+};
+
+// pgx_batch_read_mapq's buffers (grow-only, its own) and its result; pgx_read_mapq_arrays uses one of its own
+struct MapqWork {
+    DevBuf recs, ctr; // ctr: the four counters
+    // the extras: their counts and offsets, whether a read has more than were taken, the candidate arrays pgx_verify_kernel takes, their verified records
+    DevBuf count, extra_off, more, cand_seq, cand_diag, cand_read, extras, scan_tmp;
+    HostBuf h_recs;
+    StageTimer timer;
+    bool valid = false;
+    uint32_t scale = 0, slack = 0, max_extra = 0, flags = 0;
+    uint64_t n_reads = 0, n_extras = 0, counters[4] = {0, 0, 0, 0}; // reads with HAS, of them with E == 0, reads CAPPED, the sum of mapq
+    float ms = 0;
+    void release() {
+        release_all({&recs, &ctr, &count, &extra_off, &more, &cand_seq, &cand_diag, &cand_read, &extras, &scan_tmp});
+        release_all({&h_recs}); timer.release(); valid = false;
     }
 };
 
@@ -253,6 +272,7 @@ struct pgx_batch {
     MatesWork mw;   // pgx_batch_read_mates
     AlignWork aw;   // pgx_batch_read_align
     WalkWork ww;    // pgx_batch_read_walk
+    MapqWork qw;    // pgx_batch_read_mapq
     uint64_t n_mems = 0, n_positions = 0, n_ext = 0, n_tag_overflow = 0;
     bool ran = false, ran_tags = false;
     // speculative sizing (pgx_batch_run): what the last run with these parameters produced

@@ -501,6 +501,35 @@ __global__ void pgx_walk_count_kernel(PgxWalkImage w, const uint64_t *seq_start,
                                       const uint64_t *text_start, const uint64_t *text_end, uint64_t n_reads, pgx_read_walk *out, uint64_t *n_steps, uint64_t *first);
 __global__ void pgx_walk_fill_kernel(PgxWalkImage w, const uint64_t *n_steps, const uint64_t *first, const uint64_t *step_off, uint64_t n_reads, uint64_t *steps);
 
+// ---- pgx_mapq_kernels.hip: read mapq (pgx_batch_read_mapq, pgx_read_mapq_arrays)
+#define PGX_MAPQ_THREADS 256
+// The entries of read r: recs_a[off_a[r] .. off_a[r + 1]), then (off_b != NULL) recs_b[off_b[r] .. off_b[r + 1]); the first list_len[r] of them (NULL: those
+// of recs_a) are list candidates, the rest extras.  The chosen ordinal: the winner record's cand_index (winners != NULL), or chosen[r].
+struct PgxMapqArgs {
+    PgxWalkImage walk;
+    const uint64_t *seq_start; // n_seq + 1; sequence q has seq_start[q + 1] - seq_start[q] - endmark symbols
+    const uint64_t *off_a, *off_b;
+    const pgx_read_verify *recs_a, *recs_b;
+    const uint32_t *list_len;
+    const pgx_read_verify *winners;
+    const uint32_t *chosen;
+    const pgx_read_rescue *rescue; // NULL: no rescue terms
+    const uint32_t *more;          // NULL, or per read: more next-level placements exist than extras were taken (PGX_MAPQ_CAPPED)
+    int64_t frag_min, frag_max;    // PAIRED
+    uint64_t n_reads;
+    uint32_t endmark, g_shift, scale, slack, penalty;
+    uint32_t max_cand;             // 0, or PGX_MAPQ_CAPPED from this many list candidates on
+    pgx_read_mapq *out;
+    unsigned long long *counters;  // reads with HAS, of them with E == 0, reads CAPPED, the sum of mapq (added to)
+};
+// count[r] / more[r] (cand_seq == NULL), or the extras of read r behind extra_off[r]
+__global__ void pgx_mapq_choose_extras_kernel(const pgx_read_place *recs, const uint64_t *place_off, const pgx_placement *places, const uint64_t *cand_off,
+                                              uint64_t n_reads, uint32_t max_extra, uint64_t *count, uint32_t *more, const uint64_t *extra_off, uint32_t *cand_seq,
+                                              int64_t *cand_diag);
+// 2^g_shift lanes a read (PAIRED: a pair of mates), at least the entries of any read
+template <bool PAIRED>
+__global__ void pgx_mapq_kernel(PgxMapqArgs a);
+
 // literal count image: COMPAT count_encoded / LF_encoded on an encoded index without N, block by block as the
 // reference's rankAt_encoded (src/r-index.cpp:570-590) sees it -- true cumulative counts, run scan one varint late
 struct PgxLitImage {

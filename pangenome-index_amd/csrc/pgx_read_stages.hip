@@ -1,4 +1,4 @@
-// pgx_read_stages.hip -- the read stages behind a run: hits, place, verify, rescue, mates, align, walk.  Each is a core on device arrays with two entry points, one on
+// pgx_read_stages.hip -- the read stages behind a run: hits, place, verify, rescue, mates, align, walk, mapq.  Each is a core on device arrays with two entry points, one on
 // the batch (pgx_batch_read_X with its results pgx_batch_device_X / pgx_batch_X) and one on host arrays (pgx_read_X_arrays), and what they share comes first.
 // A batch entry point clears its `valid` only behind its last refusal, so that what it refuses leaves the result before as it was (hits differs: see there).
 #include <string>
@@ -573,6 +573,8 @@ extern "C" pgx_status pgx_batch_read_verify(pgx_batch *b, uint32_t max_cand, uin
     hipStream_t s = batch_stream(b, stream);
     VerifyWork &w = b->vw;
     w.valid = false;
+    b->qw.valid = false; // (the qualities belong to the list before)
+    w.gen++;
     w.timer.begin(b->timed, s);
     // the candidates: counted, scanned, filled
     const bool from_list = max_cand > 1;
@@ -812,6 +814,8 @@ extern "C" pgx_status pgx_batch_read_mates(pgx_batch *b, int64_t frag_min, int64
     hipStream_t s = batch_stream(b, stream);
     MatesWork &w = b->mw;
     w.valid = false;
+    b->qw.valid = false; // (the qualities were made before this call, and an election moves the winners)
+    w.verify_gen = vw.gen;
     w.timer.begin(b->timed, s);
     mates_core(w, d->text_seq_start.as<uint64_t>(), 1u, vw.cand_off.as<uint64_t>(), vw.cands.as<pgx_read_verify>(), n / 2, vw.max_list, frag_min, frag_max, penalty, flags,
                (flags & PGX_MATES_ELECT) ? vw.recs.as<pgx_read_verify>() : nullptr, s, who);
@@ -1050,10 +1054,12 @@ extern "C" pgx_status pgx_batch_read_rescue(pgx_batch *b, int64_t frag_min, int6
                          vw.cands.as<pgx_read_verify>(), n, vw.n_cands, vw.max_list};
     bool cleared = false;
     w.valid = false;
+    const bool mapq_was_valid = b->qw.valid;
+    b->qw.valid = false; // (the qualities were made before this call)
     try {
         rescue_core(w, in, frag_min, frag_max, vw.penalty, min_score, max_anchors, merge, s, who, &cleared);
     } catch (...) {
-        if (!cleared) w.valid = was_valid; // (the last refusal: the records of the result before were not touched)
+        if (!cleared) { w.valid = was_valid; b->qw.valid = mapq_was_valid; } // (the last refusal: the records of the result before were not touched)
         throw;
     }
     if (merge) {
@@ -1062,6 +1068,7 @@ extern "C" pgx_status pgx_batch_read_rescue(pgx_batch *b, int64_t frag_min, int6
         std::swap(vw.cand_off, w.new_off);
         vw.n_cands += w.counters[1];
         vw.merged = true;
+        vw.gen++;
         if (w.counters[1]) vw.max_list = std::min<uint32_t>(vw.max_cand + 1, PGX_VERIFY_MAX_CAND);
         b->mw.valid = false; // (paired from the list before)
     }
@@ -1531,17 +1538,10 @@ extern "C" pgx_status pgx_batch_walked(pgx_batch *b, pgx_read_walks *out) {
     PGX_GUARD_END
 }
 
-extern "C" pgx_status pgx_read_walk_arrays(int device, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
-                                           const uint32_t *visit_length, uint64_t n_reads, const uint32_t *seq, const uint64_t *text_start, const uint64_t *text_end,
-                                           uint32_t flags, pgx_read_walk *out, uint64_t *step_offsets, uint64_t *steps, uint64_t steps_cap) {
-    PGX_GUARD_BEGIN
-    RoctxRange range("pgx_read_walk_arrays");
-    checked_device_count();
-    const std::string who = "pgx_read_walk_arrays";
-    if (flags & ~WALK_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
-    const bool want_steps = (flags & PGX_WALK_STEPS) != 0;
-    if (!seq_offsets || !visit_offsets || (n_reads && (!out || !seq || !text_start || !text_end)) || (want_steps && (!step_offsets || (steps_cap && !steps))))
-        throw Error(PGX_ERR_ARG, who + ": null argument");
+// What the _arrays entry points that take path tables (walk, mapq) ask of them, and the text position of every visit: sequence q is seq_offsets[q] ..
+// seq_offsets[q + 1] and consists of the visits [visit_offsets[q], visit_offsets[q + 1]).
+static std::vector<uint64_t> walk_table_marks(const std::string &who, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
+                                              const uint32_t *visit_length) {
     check_offsets(who, seq_offsets, n_seq, "seq_offsets", "sequence");
     check_offsets(who, visit_offsets, n_seq, "visit_offsets", "sequence");
     const uint64_t n_text = seq_offsets[n_seq], V = visit_offsets[n_seq];
@@ -1560,6 +1560,44 @@ extern "C" pgx_status pgx_read_walk_arrays(int device, const uint64_t *seq_offse
             throw Error(PGX_ERR_ARG, who + ": the visits of sequence " + std::to_string(q) + " sum to " + std::to_string(p - seq_offsets[q]) + " symbols, the sequence has " +
                                          std::to_string(seq_offsets[q + 1] - seq_offsets[q]));
     }
+    return marks;
+}
+
+// the WALK image of stated path tables on the device (null stream), released on every way out
+namespace {
+struct WalkTables {
+    DevBuf seq_off, marks, bits, dir, nodes, counts, scan_tmp;
+    ~WalkTables() { release_all({&seq_off, &marks, &bits, &dir, &nodes, &counts, &scan_tmp}); }
+    PgxWalkImage build(const uint64_t *seq_offsets, uint64_t n_seq, const std::vector<uint64_t> &m, const uint64_t *visit_nodes, hipStream_t s) {
+        const uint64_t n_text = seq_offsets[n_seq], V = m.size();
+        const uint64_t n_blocks = n_text / PGX_WALK_BLOCK_BITS + 1, n_words = n_blocks * PGX_WALK_BLOCK_WORDS;
+        upload(seq_off, seq_offsets, (n_seq + 1) * 8);
+        upload(marks, m.data(), V * 8);
+        upload(nodes, visit_nodes, V * 8);
+        bits.ensure(n_words * 8); dir.ensure((n_blocks + 1) * 8);
+        HIPCHECK(hipMemsetAsync(bits.p, 0, n_words * 8, s));
+        if (V) {
+            hipLaunchKernelGGL(pgx_walk_set_kernel, dim3((unsigned)std::min<uint64_t>((V + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint64_t *)marks.as<uint64_t>(), V, bits.as<uint32_t>());
+            HIPCHECK(hipGetLastError());
+        }
+        walk_directory(bits.as<uint64_t>(), n_blocks, counts, dir.as<uint64_t>(), scan_tmp, s);
+        return PgxWalkImage{bits.as<uint64_t>(), dir.as<uint64_t>(), nodes.as<uint64_t>(), n_text, n_words, n_blocks, V};
+    }
+};
+} // namespace
+
+extern "C" pgx_status pgx_read_walk_arrays(int device, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
+                                           const uint32_t *visit_length, uint64_t n_reads, const uint32_t *seq, const uint64_t *text_start, const uint64_t *text_end,
+                                           uint32_t flags, pgx_read_walk *out, uint64_t *step_offsets, uint64_t *steps, uint64_t steps_cap) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_read_walk_arrays");
+    checked_device_count();
+    const std::string who = "pgx_read_walk_arrays";
+    if (flags & ~WALK_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
+    const bool want_steps = (flags & PGX_WALK_STEPS) != 0;
+    if (!seq_offsets || !visit_offsets || (n_reads && (!out || !seq || !text_start || !text_end)) || (want_steps && (!step_offsets || (steps_cap && !steps))))
+        throw Error(PGX_ERR_ARG, who + ": null argument");
+    const std::vector<uint64_t> marks = walk_table_marks(who, seq_offsets, n_seq, visit_offsets, visit_nodes, visit_length);
     for (uint64_t r = 0; r < n_reads; r++) {
         if (seq[r] == PGX_NO_SEQUENCE) continue;
         if (seq[r] >= n_seq) throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " names a sequence that is not below n_seq " + std::to_string(n_seq));
@@ -1570,32 +1608,255 @@ extern "C" pgx_status pgx_read_walk_arrays(int device, const uint64_t *seq_offse
     }
     if (n_reads >= PLACE_LAUNCH_ITEMS / PGX_WALK_FILL_LANES) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_reads) + " reads exceed one launch");
     use_device(device);
-    struct WalkInput { // device copies of the input, the image + the stage's buffers, released on every way out
-        DevBuf seq_off, marks, bits, dir, nodes, counts, seq, ts, te;
+    struct WalkInput : WalkTables { // device copies of the input, the image + the stage's buffers, released on every way out
+        DevBuf seq, ts, te;
         WalkWork w;
-        ~WalkInput() { release_all({&seq_off, &marks, &bits, &dir, &nodes, &counts, &seq, &ts, &te}); w.release(); }
+        ~WalkInput() { release_all({&seq, &ts, &te}); w.release(); }
     } k;
     hipStream_t s = nullptr;
-    const uint64_t n_blocks = n_text / PGX_WALK_BLOCK_BITS + 1, n_words = n_blocks * PGX_WALK_BLOCK_WORDS;
-    upload(k.seq_off, seq_offsets, (n_seq + 1) * 8);
-    upload(k.marks, marks.data(), V * 8);
-    upload(k.nodes, visit_nodes, V * 8);
     upload(k.seq, seq, n_reads * 4);
     upload(k.ts, text_start, n_reads * 8);
     upload(k.te, text_end, n_reads * 8);
-    k.bits.ensure(n_words * 8); k.dir.ensure((n_blocks + 1) * 8);
-    HIPCHECK(hipMemsetAsync(k.bits.p, 0, n_words * 8, s));
-    if (V) {
-        hipLaunchKernelGGL(pgx_walk_set_kernel, dim3((unsigned)std::min<uint64_t>((V + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint64_t *)k.marks.as<uint64_t>(), V, k.bits.as<uint32_t>());
-        HIPCHECK(hipGetLastError());
-    }
-    walk_directory(k.bits.as<uint64_t>(), n_blocks, k.counts, k.dir.as<uint64_t>(), k.w.scan_tmp, s);
-    const PgxWalkImage img{k.bits.as<uint64_t>(), k.dir.as<uint64_t>(), k.nodes.as<uint64_t>(), n_text, n_words, n_blocks, V};
+    const PgxWalkImage img = k.build(seq_offsets, n_seq, marks, visit_nodes, s);
     walk_core(k.w, img, k.seq_off.as<uint64_t>(), 0u, n_seq, nullptr, (const uint32_t *)k.seq.as<uint32_t>(), (const uint64_t *)k.ts.as<uint64_t>(),
               (const uint64_t *)k.te.as<uint64_t>(), n_reads, flags, s);
     if (want_steps && k.w.n_steps > steps_cap)
         throw Error(PGX_ERR_NOMEM, who + ": the list holds " + std::to_string(k.w.n_steps) + " steps, steps_cap is " + std::to_string(steps_cap));
     download_result(k.w.result(), out, step_offsets, steps, s);
+    HIPCHECK(hipStreamSynchronize(s));
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+// ------------------------------------------------------------------------------------------
+// read mapq (pgx_mapq_kernels.hip; the definitions: include/pgx.h "read mapq")
+static const uint32_t MAPQ_FLAGS = PGX_MAPQ_PAIRED;
+
+static void mapq_check_args(const std::string &who, uint32_t scale, uint32_t slack, uint32_t max_extra, uint32_t flags) {
+    if (flags & ~MAPQ_FLAGS) throw Error(PGX_ERR_ARG, who + ": unknown flag");
+    if (scale < 1 || scale > PGX_MAPQ_MAX_SCALE) throw Error(PGX_ERR_ARG, who + ": scale " + std::to_string(scale) + " is outside 1 .. " + std::to_string(PGX_MAPQ_MAX_SCALE));
+    if (slack > PGX_MAPQ_MAX_SLACK) throw Error(PGX_ERR_ARG, who + ": slack " + std::to_string(slack) + " exceeds " + std::to_string(PGX_MAPQ_MAX_SLACK));
+    if (max_extra > PGX_MAPQ_MAX_EXTRA) throw Error(PGX_ERR_ARG, who + ": max_extra " + std::to_string(max_extra) + " exceeds " + std::to_string(PGX_MAPQ_MAX_EXTRA));
+}
+
+// log2 of the lanes a read (a pair under PAIRED) takes: the power of two >= max_entries, and >= PGX_MAPQ_LANES (tests; 1 .. 64, read per call).  Results never
+// depend on it.  Refuses the reads one launch cannot hold.
+static uint32_t mapq_lane_shift(uint64_t n_units, uint64_t max_entries, const std::string &who) {
+    uint64_t want = std::max<uint64_t>(max_entries, 1);
+    if (const char *e = std::getenv("PGX_MAPQ_LANES")) {
+        const long v = std::strtol(e, nullptr, 10);
+        if (v >= 1 && v <= 64) want = std::max<uint64_t>(want, (uint64_t)v);
+    }
+    uint32_t sh = 0;
+    while ((1ull << sh) < want) sh++;
+    if (n_units >= (PLACE_LAUNCH_ITEMS >> sh)) throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_units) + " reads at " + std::to_string(1u << sh) + " lanes a read exceed one launch");
+    return sh;
+}
+
+// The hot kernel on device arrays, enqueued on s: `a` says where the entries lie (out, counters and g_shift are put in here) -> w.recs, w.ctr.  No read has
+// more than max_entries <= 64 entries.  Nothing is read back.
+static void mapq_core(MapqWork &w, PgxMapqArgs a, uint64_t max_entries, bool paired, hipStream_t s, const std::string &who) {
+    const uint64_t n = a.n_reads, n_units = paired ? n / 2 : n;
+    a.g_shift = mapq_lane_shift(n_units, max_entries, who);
+    w.recs.ensure((n ? n : 1) * sizeof(pgx_read_mapq));
+    w.ctr.ensure(32);
+    HIPCHECK(hipMemsetAsync(w.ctr.p, 0, 32, s));
+    a.out = w.recs.as<pgx_read_mapq>();
+    a.counters = w.ctr.as<unsigned long long>();
+    if (n_units) {
+        const dim3 grid(grid_for(n_units, PGX_MAPQ_THREADS >> a.g_shift)), block(PGX_MAPQ_THREADS);
+        if (paired) hipLaunchKernelGGL(pgx_mapq_kernel<true>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(pgx_mapq_kernel<false>, grid, block, 0, s, a);
+        HIPCHECK(hipGetLastError());
+    }
+    w.n_reads = n;
+}
+
+extern "C" pgx_status pgx_batch_read_mapq(pgx_batch *b, uint32_t scale, uint32_t slack, uint32_t max_extra, uint32_t flags, void *stream) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_batch_read_mapq");
+    checked_device_count();
+    const std::string who = "pgx_batch_read_mapq";
+    if (!b) throw Error(PGX_ERR_ARG, who + ": null batch");
+    // (the verify, rescue, mates and place results are only read.  What is refused leaves an earlier mapq result as it was: every refusal but one comes
+    // before anything of the stage is touched, and the last one -- too many extras for one launch -- comes behind the count pass, which has then written
+    // the stage's scratch (count, more, extra_off) and started the timer, and nothing of the result: its records, counters and header stay valid)
+    mapq_check_args(who, scale, slack, max_extra, flags);
+    const bool paired = (flags & PGX_MAPQ_PAIRED) != 0;
+    if (!b->ran) throw Error(PGX_ERR_ARG, who + ": batch has not been run");
+    VerifyWork &vw = b->vw;
+    if (!vw.valid || vw.n_reads != b->n_reads) throw Error(PGX_ERR_ARG, who + ": needs a completed pgx_batch_read_verify(PGX_VERIFY_LIST), the batch has no verify result");
+    if (!(vw.flags & PGX_VERIFY_LIST))
+        throw Error(PGX_ERR_ARG, who + ": needs a verify result made with PGX_VERIFY_LIST, the last pgx_batch_read_verify ran with flags " + std::to_string(vw.flags));
+    PlaceWork &pw = b->pw;
+    if (max_extra > 0) {
+        if (!pw.valid || pw.n_reads != b->n_reads) throw Error(PGX_ERR_ARG, who + ": max_extra " + std::to_string(max_extra) + " needs a completed pgx_batch_read_place(PGX_PLACE_LIST), the batch has no place result");
+        if (!(pw.flags & PGX_PLACE_LIST))
+            throw Error(PGX_ERR_ARG, who + ": max_extra " + std::to_string(max_extra) + " needs a place result made with PGX_PLACE_LIST, the last pgx_batch_read_place ran without it");
+    }
+    const uint64_t n = b->n_reads;
+    const MatesWork &mw = b->mw;
+    if (paired) {
+        if (!mw.valid || mw.n_pairs != n / 2) throw Error(PGX_ERR_ARG, who + ": PGX_MAPQ_PAIRED needs a completed pgx_batch_read_mates, the batch has no mates result");
+        if (mw.verify_gen != vw.gen) throw Error(PGX_ERR_ARG, who + ": PGX_MAPQ_PAIRED needs a mates result made on the current verify result, the batch's was made on an earlier one");
+        if (n & 1) throw Error(PGX_ERR_ARG, who + ": " + std::to_string(n) + " reads, an odd number: reads 2k and 2k + 1 are the mates of pair k");
+    }
+    const uint64_t max_entries = std::min<uint64_t>((uint64_t)vw.max_list + max_extra, PGX_MAPQ_MAX_ENTRIES);
+    (void)mapq_lane_shift(paired ? n / 2 : n, max_entries, who);
+    use_device(b->device);
+    pgx_device_image *d = device_image(b->h, b->device);
+    ensure_walk(b->h, d); // (throws before anything of the batch changes)
+    hipStream_t s = batch_stream(b, stream);
+    MapqWork &w = b->qw;
+    w.timer.begin(b->timed, s);
+    // the extras: counted, scanned, filled, verified by verify's own kernel on a list of their own
+    uint64_t n_extras = 0;
+    if (max_extra > 0 && n) {
+        w.count.ensure(n * 8); w.more.ensure(n * 4); w.extra_off.ensure((n + 1) * 8);
+        hipLaunchKernelGGL(pgx_mapq_choose_extras_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const pgx_read_place *)pw.recs.as<pgx_read_place>(),
+                           (const uint64_t *)pw.place_off.as<uint64_t>(), (const pgx_placement *)pw.places.as<pgx_placement>(), (const uint64_t *)vw.cand_off.as<uint64_t>(), n, max_extra,
+                           w.count.as<uint64_t>(), w.more.as<uint32_t>(), (const uint64_t *)nullptr, (uint32_t *)nullptr, (int64_t *)nullptr);
+        HIPCHECK(hipGetLastError());
+        scan_excl(1, w.count.p, n, 0, w.extra_off.as<uint64_t>(), w.scan_tmp, s);
+        n_extras = read_u64(w.extra_off.as<uint64_t>() + n, s);
+        if (n_extras >= PLACE_LAUNCH_ITEMS) // (the last refusal, mid-pipeline: see above)
+            throw Error(PGX_ERR_UNSUPPORTED, who + ": " + std::to_string(n_extras) + " extras exceed one launch; lower max_extra");
+    }
+    w.valid = false; // (behind the last refusal)
+    if (n_extras) {
+        w.cand_seq.ensure(n_extras * 4); w.cand_diag.ensure(n_extras * 8); w.cand_read.ensure(n_extras * 8); w.extras.ensure(n_extras * sizeof(pgx_read_verify));
+        hipLaunchKernelGGL(pgx_mapq_choose_extras_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const pgx_read_place *)pw.recs.as<pgx_read_place>(),
+                           (const uint64_t *)pw.place_off.as<uint64_t>(), (const pgx_placement *)pw.places.as<pgx_placement>(), (const uint64_t *)vw.cand_off.as<uint64_t>(), n, max_extra,
+                           w.count.as<uint64_t>(), w.more.as<uint32_t>(), (const uint64_t *)w.extra_off.as<uint64_t>(), w.cand_seq.as<uint32_t>(), w.cand_diag.as<int64_t>());
+        hipLaunchKernelGGL(pgx_verify_owner_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, (const uint64_t *)w.extra_off.as<uint64_t>(), n, n_extras, w.cand_read.as<uint64_t>());
+        hipLaunchKernelGGL(pgx_verify_kernel, dim3(grid_for(n_extras, PGX_VERIFY_THREADS)), dim3(PGX_VERIFY_THREADS), 0, s, (const uint32_t *)d->text4.as<uint32_t>(),
+                           (const uint64_t *)d->text_seq_start.as<uint64_t>(), 1u, (const uint32_t *)vw.rcode.as<uint32_t>(), (const uint64_t *)b->offsets.as<uint64_t>(),
+                           (const uint64_t *)w.extra_off.as<uint64_t>(), (const uint64_t *)w.cand_read.as<uint64_t>(), (const uint32_t *)w.cand_seq.as<uint32_t>(),
+                           (const int64_t *)w.cand_diag.as<int64_t>(), n_extras, vw.penalty, w.extras.as<pgx_read_verify>());
+        HIPCHECK(hipGetLastError());
+    }
+    PgxMapqArgs a{};
+    a.walk = d->walk;
+    a.seq_start = d->text_seq_start.as<uint64_t>(); a.endmark = 1u;
+    a.off_a = vw.cand_off.as<uint64_t>(); a.recs_a = vw.cands.as<pgx_read_verify>();
+    if (max_extra > 0 && n) { a.off_b = w.extra_off.as<uint64_t>(); a.recs_b = w.extras.as<pgx_read_verify>(); a.more = w.more.as<uint32_t>(); }
+    a.winners = vw.recs.as<pgx_read_verify>();
+    // the rescue records that go with a merged list are those of the call that merged it: pgx_batch_read_rescue refuses any further call on a merged list,
+    // with or without MERGE, so no later rescue result can stand in their place until the next verify call clears `merged`
+    if (vw.merged && b->rw.valid && (b->rw.flags & PGX_RESCUE_MERGE) && b->rw.n_reads == n) a.rescue = b->rw.recs.as<pgx_read_rescue>();
+    if (paired) { a.frag_min = mw.frag_min; a.frag_max = mw.frag_max; a.penalty = mw.penalty; }
+    a.n_reads = n; a.scale = scale; a.slack = slack; a.max_cand = vw.max_cand;
+    mapq_core(w, a, max_entries, paired, s, who);
+    w.ms = w.timer.end(s);
+    read_scalars(w.counters, w.ctr.p, 32, s); // (waits for the kernel: the call is complete on return)
+    w.scale = scale; w.slack = slack; w.max_extra = max_extra; w.flags = flags; w.n_extras = n_extras;
+    w.valid = true;
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+static void mapqs_header(const pgx_batch *b, pgx_read_mapqs *out) {
+    const MapqWork &w = b->qw;
+    std::memset(out, 0, sizeof *out);
+    out->n_reads = w.n_reads;
+    out->n_has = w.counters[0]; out->n_unique = w.counters[1]; out->n_capped = w.counters[2]; out->sum_mapq = w.counters[3];
+    out->n_extras = w.n_extras;
+    out->scale = w.scale; out->slack = w.slack; out->max_extra = w.max_extra; out->flags = w.flags;
+    out->ms_mapq = w.ms;
+}
+
+extern "C" pgx_status pgx_batch_device_mapqs(pgx_batch *b, pgx_read_mapqs *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->qw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_device_mapqs: batch has no mapq result");
+    mapqs_header(b, out);
+    out->records = b->qw.recs.as<pgx_read_mapq>();
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_batch_mapqs(pgx_batch *b, pgx_read_mapqs *out) {
+    PGX_GUARD_BEGIN
+    if (!b || !out || !b->qw.valid) throw Error(PGX_ERR_ARG, "pgx_batch_mapqs: batch has no mapq result");
+    use_device(b->device);
+    MapqWork &w = b->qw;
+    HostBuf none_off, none_items; // (the result has no list)
+    download_pinned(b, StageResult{w.n_reads, w.recs.p, sizeof(pgx_read_mapq), false, nullptr, 0, nullptr, 0}, w.h_recs, none_off, none_items);
+    mapqs_header(b, out);
+    out->records = w.h_recs.as<pgx_read_mapq>();
+    return PGX_OK;
+    PGX_GUARD_END
+}
+
+extern "C" pgx_status pgx_read_mapq_arrays(int device, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
+                                           const uint32_t *visit_length, uint64_t n_reads, const uint64_t *entry_offsets, const pgx_read_verify *entries,
+                                           const uint32_t *chosen, const pgx_read_rescue *rescue, int64_t frag_min, int64_t frag_max, uint32_t penalty,
+                                           const uint32_t *list_len, uint32_t scale, uint32_t slack, uint32_t flags, pgx_read_mapq *out) {
+    PGX_GUARD_BEGIN
+    RoctxRange range("pgx_read_mapq_arrays");
+    checked_device_count();
+    const std::string who = "pgx_read_mapq_arrays";
+    mapq_check_args(who, scale, slack, 0u, flags);
+    const bool paired = (flags & PGX_MAPQ_PAIRED) != 0;
+    if (!seq_offsets || !visit_offsets || !entry_offsets || (n_reads && (!out || !chosen))) throw Error(PGX_ERR_ARG, who + ": null argument");
+    // what pgx_read_walk_arrays refuses of the tables
+    const std::vector<uint64_t> marks = walk_table_marks(who, seq_offsets, n_seq, visit_offsets, visit_nodes, visit_length);
+    // what pgx_read_mates_arrays refuses
+    if (n_seq >= (1ull << 32) - 1) throw Error(PGX_ERR_ARG, who + ": n_seq " + std::to_string(n_seq) + " does not fit a record's seq");
+    if (paired) {
+        mates_check_args(who, frag_min, frag_max, 0u);
+        if (n_seq & 1) throw Error(PGX_ERR_ARG, who + ": n_seq " + std::to_string(n_seq) + " is odd: sequences 2p and 2p + 1 are twins");
+        if (const uint64_t bad = first_untwinned(seq_offsets, n_seq); bad != ~0ull)
+            throw Error(PGX_ERR_ARG, who + ": sequences " + std::to_string(2 * bad) + " and " + std::to_string(2 * bad + 1) + " (p = " + std::to_string(bad) + ") have the lengths " +
+                                         std::to_string(seq_offsets[2 * bad + 1] - seq_offsets[2 * bad]) + " and " + std::to_string(seq_offsets[2 * bad + 2] - seq_offsets[2 * bad + 1]) +
+                                         ": twins have one length");
+    }
+    check_offsets(who, entry_offsets, n_reads, "entry_offsets", "read");
+    const uint64_t n_entries = entry_offsets[n_reads];
+    if (n_entries && !entries) throw Error(PGX_ERR_ARG, who + ": null argument");
+    uint64_t max_entries = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint64_t c = entry_offsets[r + 1] - entry_offsets[r], nl = list_len ? list_len[r] : c;
+        if (c > PGX_MAPQ_MAX_ENTRIES) throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " has " + std::to_string(c) + " entries, more than " + std::to_string(PGX_MAPQ_MAX_ENTRIES));
+        if (nl > c) throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " has list_len " + std::to_string(nl) + ", above its " + std::to_string(c) + " entries");
+        if (chosen[r] != PGX_MAPQ_NO_CHOSEN && chosen[r] >= nl)
+            throw Error(PGX_ERR_ARG, who + ": read " + std::to_string(r) + " has chosen " + std::to_string(chosen[r]) + ", not below its list_len " + std::to_string(nl));
+        max_entries = std::max(max_entries, c);
+        for (uint64_t i = entry_offsets[r]; i < entry_offsets[r + 1]; i++) {
+            const pgx_read_verify &e = entries[i];
+            const std::string which = "entry " + std::to_string(i - entry_offsets[r]) + " of read " + std::to_string(r);
+            if (e.seq >= n_seq) throw Error(PGX_ERR_ARG, who + ": " + which + " has seq " + std::to_string(e.seq) + ", not below n_seq " + std::to_string(n_seq));
+            const int64_t ls = (int64_t)(seq_offsets[(uint64_t)e.seq + 1] - seq_offsets[e.seq]), lim = 1ll << 62;
+            if (e.diag <= -lim || e.diag >= lim) throw Error(PGX_ERR_ARG, who + ": " + which + " has diag " + std::to_string(e.diag) + ", not inside +-2^62");
+            if (e.span_hi > e.span_lo && (e.diag + (int64_t)e.span_lo < 0 || e.diag + (int64_t)e.span_hi > ls))
+                throw Error(PGX_ERR_ARG, who + ": " + which + " has the span [" + std::to_string(e.span_lo) + ", " + std::to_string(e.span_hi) + ") at diag " + std::to_string(e.diag) +
+                                             ", its sequence has " + std::to_string(ls) + " symbols");
+        }
+    }
+    if (paired && (n_reads & 1)) throw Error(PGX_ERR_ARG, who + ": n_reads " + std::to_string(n_reads) + " is odd: reads 2k and 2k + 1 are the mates of pair k");
+    (void)mapq_lane_shift(paired ? n_reads / 2 : n_reads, max_entries, who);
+    use_device(device);
+    struct MapqInput : WalkTables { // device copies of the input, the image + the stage's buffers, released on every way out
+        DevBuf entry_off, entries, chosen, list_len, rescue;
+        MapqWork w;
+        ~MapqInput() { release_all({&entry_off, &entries, &chosen, &list_len, &rescue}); w.release(); }
+    } k;
+    hipStream_t s = nullptr;
+    upload(k.entry_off, entry_offsets, (n_reads + 1) * 8);
+    upload(k.entries, entries, n_entries * sizeof(pgx_read_verify));
+    upload(k.chosen, chosen, n_reads * 4);
+    if (list_len) upload(k.list_len, list_len, n_reads * 4);
+    if (rescue) upload(k.rescue, rescue, n_reads * sizeof(pgx_read_rescue));
+    PgxMapqArgs a{};
+    a.walk = k.build(seq_offsets, n_seq, marks, visit_nodes, s);
+    a.seq_start = k.seq_off.as<uint64_t>(); a.endmark = 0u;
+    a.off_a = k.entry_off.as<uint64_t>(); a.recs_a = k.entries.as<pgx_read_verify>();
+    a.list_len = list_len ? k.list_len.as<uint32_t>() : nullptr;
+    a.chosen = k.chosen.as<uint32_t>();
+    a.rescue = rescue ? k.rescue.as<pgx_read_rescue>() : nullptr;
+    a.frag_min = frag_min; a.frag_max = frag_max; a.penalty = penalty;
+    a.n_reads = n_reads; a.scale = scale; a.slack = slack;
+    mapq_core(k.w, a, max_entries, paired, s, who);
+    if (n_reads) HIPCHECK(hipMemcpyAsync(out, k.w.recs.p, n_reads * sizeof(pgx_read_mapq), hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     return PGX_OK;
     PGX_GUARD_END

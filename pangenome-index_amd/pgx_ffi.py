@@ -151,6 +151,19 @@ class ReadMatesResult(C.Structure):  # pgx_read_mates_result: a host pointer (pg
                 ("flags", u32), ("penalty", u32), ("pairs", p), ("ms_mates", C.c_float), ("reserved", u32)]
 
 
+MAPQ_PAIRED = 4  # pgx_batch_read_mapq / pgx_read_mapq_arrays flag, and a bit of a record's flags
+MAPQ_HAS, MAPQ_LOCUS, MAPQ_RESCUED, MAPQ_CAPPED, MAPQ_OUTSCORED = 1, 2, 8, 16, 32  # bits of a record's flags
+MAPQ_MAX_ENTRIES, MAPQ_MAX_SCALE, MAPQ_MAX_SLACK, MAPQ_MAX_EXTRA, MAPQ_NO_CHOSEN = 64, 16, 1024, 63, 0xFFFFFFFF
+MAPQ_DTYPE = np.dtype([("mapq", "<u4"), ("flags", "<u4"), ("n_entries", "<u4"), ("n_loci", "<u4"), ("n_with", "<u4"), ("n_competing", "<u4"), ("best_other", "<u4"),
+                       ("excess", "<u4")])  # pgx_read_mapq, 32 bytes
+assert MAPQ_DTYPE.itemsize == 32
+
+
+class ReadMapqs(C.Structure):  # pgx_read_mapqs: a host pointer (pgx_batch_mapqs) or a device pointer (pgx_batch_device_mapqs)
+    _fields_ = [("n_reads", u64), ("n_has", u64), ("n_unique", u64), ("n_capped", u64), ("sum_mapq", u64), ("n_extras", u64), ("scale", u32), ("slack", u32),
+                ("max_extra", u32), ("flags", u32), ("records", p), ("ms_mapq", C.c_float), ("reserved", u32)]
+
+
 RESCUE_MERGE = 1  # pgx_batch_read_rescue / pgx_read_rescue_arrays flag
 RESCUE_TARGET, RESCUE_RESCUED, RESCUE_FULL = 1, 2, 4  # bits of a record's flags
 RESCUE_MAX_ANCHORS, RESCUE_MAX_WINDOW = 8, 65536
@@ -349,6 +362,10 @@ def lib():
     L.pgx_batch_mated.argtypes = [p, C.POINTER(ReadMatesResult)]
     L.pgx_batch_device_mated.argtypes = [p, C.POINTER(ReadMatesResult)]
     L.pgx_read_mates_arrays.argtypes = [C.c_int, p, u64, u64, p, p, C.c_int64, C.c_int64, u32, u32, p, p]
+    L.pgx_batch_read_mapq.argtypes = [p, u32, u32, u32, u32, p]
+    L.pgx_batch_mapqs.argtypes = [p, C.POINTER(ReadMapqs)]
+    L.pgx_batch_device_mapqs.argtypes = [p, C.POINTER(ReadMapqs)]
+    L.pgx_read_mapq_arrays.argtypes = [C.c_int, p, u64, p, p, p, u64, p, p, p, p, C.c_int64, C.c_int64, u32, p, u32, u32, u32, p]
     L.pgx_batch_read_rescue.argtypes = [p, C.c_int64, C.c_int64, u32, u32, u32, p]
     L.pgx_batch_rescued.argtypes = [p, C.POINTER(ReadRescueResult)]
     L.pgx_batch_device_rescued.argtypes = [p, C.POINTER(ReadRescueResult)]
@@ -1104,6 +1121,33 @@ def read_mates_arrays(device, seq_lengths, cand_offsets, cands, frag_min, frag_m
     return res
 
 
+def read_mapq_arrays(device, seq_offsets, visit_offsets, visit_nodes, visit_length, entry_offsets, entries, chosen, rescue=None, frag_min=0, frag_max=0, penalty=0,
+                     list_len=None, scale=2, slack=8, flags=0, n_reads=None, out=None):
+    """pgx_read_mapq_arrays: the mapq kernel on stated tables (the path tables of read_walk_arrays; the entries of read r at [entry_offsets[r],
+    entry_offsets[r + 1]) of entries VERIFY_DTYPE; chosen uint32[n_reads], MAPQ_NO_CHOSEN for none; rescue RESCUE_DTYPE[n_reads] or None; list_len
+    uint32[n_reads] or None: every entry is a list candidate): MAPQ_DTYPE[n_reads].  n_reads: default len(entry_offsets) - 1; out: the array to write into"""
+    seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+    visit_offsets = np.ascontiguousarray(visit_offsets, dtype=np.uint64)
+    visit_nodes = np.ascontiguousarray(visit_nodes, dtype=np.uint64)
+    visit_length = np.ascontiguousarray(visit_length, dtype=np.uint32)
+    entry_offsets = np.ascontiguousarray(entry_offsets, dtype=np.uint64)
+    entries = np.ascontiguousarray(entries, dtype=VERIFY_DTYPE)
+    chosen = np.ascontiguousarray(chosen, dtype=np.uint32)
+    rescue = None if rescue is None else np.ascontiguousarray(rescue, dtype=RESCUE_DTYPE)
+    list_len = None if list_len is None else np.ascontiguousarray(list_len, dtype=np.uint32)
+    n = len(entry_offsets) - 1 if n_reads is None else int(n_reads)
+    if len(chosen) != n or (rescue is not None and len(rescue) != n) or (list_len is not None and len(list_len) != n):
+        raise ValueError("read_mapq_arrays: chosen, rescue and list_len must have an entry per read")
+    if len(visit_offsets) != len(seq_offsets):
+        raise ValueError("read_mapq_arrays: visit_offsets must have len(seq_offsets) entries")
+    res = np.zeros(n, dtype=MAPQ_DTYPE) if out is None else out
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().pgx_read_mapq_arrays(device, seq_offsets.ctypes.data, len(seq_offsets) - 1, visit_offsets.ctypes.data, visit_nodes.ctypes.data, visit_length.ctypes.data, n,
+                                      entry_offsets.ctypes.data, entries.ctypes.data, chosen.ctypes.data, ptr(rescue), frag_min, frag_max, penalty, ptr(list_len), scale, slack,
+                                      flags, res.ctypes.data))
+    return res
+
+
 def read_align_arrays(device, text, seq_offsets, reads, read_offsets, cand_seq, cand_diag, band=8, flags=0, ops_cap=None, out=None):
     """pgx_read_align_arrays: the align kernels on host arrays (text, seq_offsets, reads, read_offsets as in read_verify_arrays; one candidate per
     read, cand_seq uint32[n_reads] with NO_SEQUENCE 0xFFFFFFFF for none, cand_diag int64[n_reads]): dict(reads ALIGN_DTYPE[n_reads], and with
@@ -1565,6 +1609,33 @@ class Batch:
         r, out = self._mated(self.L.pgx_batch_device_mated)
         out["device"] = True
         out["pairs"] = DeviceArray(r.pairs, (out["n_pairs"], 8), self)
+        return out
+
+    def read_mapq(self, scale=2, slack=8, max_extra=16, flags=0, stream=None):
+        """pgx_batch_read_mapq on the list and the winners of the last read_verify (made with VERIFY_LIST; max_extra > 0: and the places of a read_place
+        with PLACE_LIST; MAPQ_PAIRED: and the last read_mates), then mapqs()"""
+        _check(self.L.pgx_batch_read_mapq(self.b, scale, slack, max_extra, flags, stream))
+        return self.mapqs()
+
+    def _mapqs(self, fn):
+        r = ReadMapqs()
+        _check(fn(self.b, C.byref(r)))
+        return r, dict(n_reads=int(r.n_reads), n_has=int(r.n_has), n_unique=int(r.n_unique), n_capped=int(r.n_capped), sum_mapq=int(r.sum_mapq), n_extras=int(r.n_extras),
+                       scale=int(r.scale), slack=int(r.slack), max_extra=int(r.max_extra), flags=int(r.flags), ms_mapq=float(r.ms_mapq))
+
+    def mapqs(self):
+        """the last mapq result: records MAPQ_DTYPE[n_reads], with n_reads, the four counters, n_extras, the parameters of the call and ms_mapq"""
+        r, out = self._mapqs(self.L.pgx_batch_mapqs)
+        k = out["n_reads"]
+        out["records"] = np.frombuffer((C.c_char * (k * 32)).from_address(r.records), dtype=MAPQ_DTYPE).copy() if k else np.zeros(0, MAPQ_DTYPE)
+        return out
+
+    def device_mapqs(self):
+        """the same with records as a device array (valid until the next run / upload / read_verify / read_rescue / read_mates / read_mapq / free):
+        int64[n_reads, 4], the 32-byte records as words"""
+        r, out = self._mapqs(self.L.pgx_batch_device_mapqs)
+        out["device"] = True
+        out["records"] = DeviceArray(r.records, (out["n_reads"], 4), self)
         return out
 
     def read_align(self, band=8, flags=0, stream=None):

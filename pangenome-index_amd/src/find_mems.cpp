@@ -35,7 +35,11 @@
 //                 --rescue (with --paired: pgx_batch_read_rescue with PGX_RESCUE_MERGE between verify and mates, under the bounds of --frag-min /
 //                 --frag-max: a read without a placement near its placed mate is searched for on every diagonal of the window the mate names, and
 //                 what is found joins its candidates, so that mates, --verify, --align and --gaf see it), --rescue-min S (default min_mem_length),
-//                 --rescue-anchors R (1 .. 8, default 2), --rescued FILE (one line per read)
+//                 --rescue-anchors R (1 .. 8, default 2), --rescued FILE (one line per read),
+//                 --mapq (with --gaf or --mapq-file: pgx_batch_read_mapq behind verify, and behind rescue and mates under --paired, where it takes the
+//                 paired scores; place and verify run with their lists, --verify-max defaults to 16; column 12 of a GAF line whose read has steps is the
+//                 read's mapping quality), --mapq-scale D (1 .. 16, default 2), --mapq-slack K (0 .. 1024, default 8), --mapq-extra X (0 .. 63, default
+//                 16), --mapq-file FILE (one line per read)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -171,6 +175,7 @@ struct Done {
     std::string gaf; // --gaf: the lines of this batch
     std::string mates; // --mates: the lines of this batch's pairs
     std::string rescued; // --rescued: the lines of this batch
+    std::string mapqs;   // --mapq-file: the lines of this batch
     std::string error;
 };
 
@@ -381,6 +386,21 @@ static void format_rescued(const pgx_read_rescue *recs, size_t n, uint64_t first
     out.resize((size_t)(p - &out[0]));
 }
 
+// --mapq-file: the lines of reads [0, n) of a batch whose first read is first_seq, appended to out
+static const char MAPQ_HEADER[] = "#read\tmapq\tentries\tloci\twith\tcompeting\tbest_other\texcess\tflags\n";
+static void format_mapqs(const pgx_read_mapq *recs, size_t n, uint64_t first_seq, std::string &out) {
+    out.resize(n * (9 * 21));
+    char *p = &out[0];
+    for (size_t k = 0; k < n; k++) {
+        const pgx_read_mapq &x = recs[k];
+        p = put_u64(p, first_seq + k + 1);
+        const uint32_t f[8] = {x.mapq, x.n_entries, x.n_loci, x.n_with, x.n_competing, x.best_other, x.excess, x.flags};
+        for (uint32_t v : f) { *p++ = '\t'; p = put_u64(p, v); }
+        *p++ = '\n';
+    }
+    out.resize((size_t)(p - &out[0]));
+}
+
 // --align: the lines of reads [0, n) of a batch, appended to out; seq, start, end and cigar print as * when the read has no candidate
 static const char ALIGN_HEADER[] = "#read\tseq\tstart\tend\tclip_lo\tclip_hi\tedits\tmatches\tmismatches\tins\tdel\tband_hit\tcigar\n";
 static void format_aligns(const pgx_read_align *recs, const uint64_t *op_off, const uint32_t *ops, size_t n, uint64_t first_seq, std::string &out) {
@@ -408,8 +428,9 @@ static void format_aligns(const pgx_read_align *recs, const uint64_t *op_off, co
 
 // --gaf: one GAF line per read of a batch, appended to out, from the align records with their operations and the walk records with their steps; len[i] =
 // bytes of read i.  A read without steps prints its number, its length, * in columns 3 to 11 and 255.  The S operations stay out of cg:Z: columns 3 and 4 state them.
+// Column 12 of a read with steps is 255, "missing", or under --mapq (mapqs != nullptr) the read's mapping quality.
 static void format_gaf(const pgx_read_align *recs, const uint64_t *op_off, const uint32_t *ops, const pgx_read_walk *walks, const uint64_t *step_off, const uint64_t *steps,
-                       const uint64_t *read_off, size_t n, uint64_t first_seq, std::string &out) {
+                       const uint64_t *read_off, const pgx_read_mapq *mapqs, size_t n, uint64_t first_seq, std::string &out) {
     out.resize(n * (13 * 21 + 40) + (size_t)(op_off[n] - op_off[0]) * 11 + (size_t)(step_off[n] - step_off[0]) * 21);
     char *p = &out[0];
     for (size_t i = 0; i < n; i++) {
@@ -429,7 +450,8 @@ static void format_gaf(const pgx_read_align *recs, const uint64_t *op_off, const
         for (uint64_t o = step_off[i]; o < step_off[i + 1]; o++) { *p++ = (steps[o] & 1) ? '<' : '>'; p = put_u64(p, steps[o] >> 1); }
         const uint64_t f[5] = {w.path_len, w.path_start, w.path_end, x.n_match, (uint64_t)x.n_match + x.n_mismatch + x.n_ins + x.n_del};
         for (uint64_t v : f) { *p++ = '\t'; p = put_u64(p, v); }
-        p = put_str(p, "\t255\tNM:i:"); p = put_u64(p, x.edits);
+        *p++ = '\t'; p = put_u64(p, mapqs ? mapqs[i].mapq : 255u);
+        p = put_str(p, "\tNM:i:"); p = put_u64(p, x.edits);
         p = put_str(p, "\ths:i:"); p = put_u64(p, x.seq);
         p = put_str(p, "\tho:i:"); p = put_u64(p, x.text_start);
         p = put_str(p, "\tcg:Z:");
@@ -455,7 +477,8 @@ static int usage() {
                  " [--align FILE [--align-band W (0 .. 31)] [--align-only (not with --locate)]]"
                  " [--gaf FILE [--gaf-only (not with --locate)]]"
                  " [--paired [--frag-min A] [--frag-max B] [--mates-penalty U] [--mates FILE [--mates-only (not with --locate)]]"
-                 " [--rescue [--rescue-min S] [--rescue-anchors R (1 .. 8)] [--rescued FILE]]]" << std::endl;
+                 " [--rescue [--rescue-min S] [--rescue-anchors R (1 .. 8)] [--rescued FILE]]]"
+                 " [--mapq (with --gaf or --mapq-file) [--mapq-scale D (1 .. 16)] [--mapq-slack K (0 .. 1024)] [--mapq-extra X (0 .. 63)] [--mapq-file FILE]]" << std::endl;
     return EXIT_FAILURE;
 }
 
@@ -497,6 +520,10 @@ int main(int argc, char **argv) {
     std::string rescued_file;   // --rescued: the rescue records of every batch go to this file
     uint64_t rescue_min = 0, rescue_anchors = 2;
     bool rescue_opt_given = false, rescue_min_given = false;
+    bool mapq = false;          // --mapq: pgx_batch_read_mapq behind verify (and rescue and mates); column 12 of the GAF lines
+    std::string mapq_file;      // --mapq-file: the mapq records of every batch go to this file
+    uint32_t mapq_scale = 2, mapq_slack = 8, mapq_extra = 16;
+    bool mapq_opt_given = false;
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -635,8 +662,25 @@ int main(int argc, char **argv) {
             rescue_opt_given = true;
             if (is_min) rescue_min_given = true;
         }
+        else if (a == "--mapq") mapq = true;
+        else if (a == "--mapq-file") { mapq_file = next(); if (mapq_file.empty()) { std::cerr << "--mapq-file: a file name" << std::endl; return EXIT_FAILURE; } }
+        else if (a == "--mapq-scale" || a == "--mapq-slack" || a == "--mapq-extra") {
+            const unsigned long long lo = a == "--mapq-scale" ? 1 : 0, hi = a == "--mapq-scale" ? PGX_MAPQ_MAX_SCALE : (a == "--mapq-slack" ? PGX_MAPQ_MAX_SLACK : PGX_MAPQ_MAX_EXTRA);
+            const std::string v = next();
+            char *endp = nullptr;
+            errno = 0;
+            const unsigned long long k = v.empty() || v[0] == '-' ? ~0ull : std::strtoull(v.c_str(), &endp, 10);
+            if (!endp || *endp || errno || k < lo || k > hi) {
+                std::cerr << a << ": a number in " << lo << " .. " << hi << std::endl;
+                return EXIT_FAILURE;
+            }
+            (a == "--mapq-scale" ? mapq_scale : (a == "--mapq-slack" ? mapq_slack : mapq_extra)) = (uint32_t)k;
+            mapq_opt_given = true;
+        }
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
+    if ((mapq_opt_given || !mapq_file.empty()) && !mapq) return usage(); // (the mapq options belong to --mapq ...
+    if (mapq && gaf_file.empty() && mapq_file.empty()) return usage();   // ... and --mapq to an output that shows it)
     if (rescue && !paired) return usage();                                     // (the rescue options belong to --paired ...
     if ((!rescued_file.empty() || rescue_opt_given) && !rescue) return usage(); // ... and its own to --rescue)
     if (rescue && !rescue_min_given) rescue_min = mem_length ? std::min<uint64_t>(mem_length, 0xFFFFFFFFull) : 1; // (no less evidence than a placed read: a MEM of that length)
@@ -648,13 +692,13 @@ int main(int argc, char **argv) {
     if (mates_only && mates_file.empty()) return usage();
     if (mates_only && locate_mode) { std::cerr << "--mates-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if (paired && frag_min > frag_max) { std::cerr << "--frag-min " << frag_min << " exceeds --frag-max " << frag_max << std::endl; return EXIT_FAILURE; }
-    if (paired && !verify_max_given) verify_max = 16; // (a pair chooses among candidates: one a read leaves it nothing to choose)
+    if ((paired || mapq) && !verify_max_given) verify_max = 16; // (a pair chooses among candidates, a quality counts them: one a read leaves nothing to choose or count)
     if (paired && !mates_penalty_given) mates_penalty = 2ull * (verify_penalty + 1); // two substitutions' worth of seg_score: each costs a match and P
     if ((hits_max_given || hits_only) && hits_file.empty()) return usage();
     if (hits_only && locate_mode) { std::cerr << "--hits-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if ((place_max_given || place_only) && place_file.empty()) return usage();
     if (place_only && locate_mode) { std::cerr << "--place-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
-    if ((verify_only && verify_file.empty()) || (verify_opt_given && verify_file.empty() && align_file.empty() && gaf_file.empty() && !paired)) return usage();
+    if ((verify_only && verify_file.empty()) || (verify_opt_given && verify_file.empty() && align_file.empty() && gaf_file.empty() && !paired && !mapq)) return usage();
     if (verify_only && locate_mode) { std::cerr << "--verify-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if ((align_only && align_file.empty()) || (align_band_given && align_file.empty() && gaf_file.empty())) return usage();
     if (gaf_only && gaf_file.empty()) return usage();
@@ -662,10 +706,11 @@ int main(int argc, char **argv) {
     if (align_only && locate_mode) { std::cerr << "--align-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     const bool want_hits = !hits_file.empty(), want_places = !place_file.empty(), want_verify = !verify_file.empty(), want_align = !align_file.empty();
     const bool want_gaf = !gaf_file.empty(), run_align = want_align || want_gaf; // (--gaf runs the align stage itself)
-    const bool want_mates = !mates_file.empty(), want_rescued = !rescued_file.empty();
-    const bool run_verify = want_verify || run_align || paired; // (--align runs the verify stage itself; --paired elects its winners)
-    const uint32_t place_flags = run_verify && (verify_max > 1 || paired) ? PGX_PLACE_LIST : 0u; // (the candidates beyond the first come from the list)
-    const uint32_t verify_flags = paired ? PGX_VERIFY_LIST : 0u;                                 // (the mates stage reads the candidates of both mates)
+    const bool want_mates = !mates_file.empty(), want_rescued = !rescued_file.empty(), want_mapqs = !mapq_file.empty();
+    const bool run_verify = want_verify || run_align || paired || mapq; // (--align runs the verify stage itself; --paired elects its winners; --mapq reads its list)
+    const uint32_t place_flags = run_verify && (verify_max > 1 || paired || mapq) ? PGX_PLACE_LIST : 0u; // (the candidates beyond the first, and the extras of --mapq, come from the list)
+    const uint32_t verify_flags = paired || mapq ? PGX_VERIFY_LIST : 0u;                                 // (the mates and the mapq stage read the candidates)
+    const uint32_t mapq_flags = paired ? PGX_MAPQ_PAIRED : 0u;
     const bool no_text = hits_only || place_only || verify_only || align_only || gaf_only || mates_only; // (either one: no tag stage, no download of result arrays, stdout empty)
     if (batch_reads == 0) batch_reads = 1;
     if (locate_max && !locate_mode) { std::cerr << "--locate-max needs --locate" << std::endl; return EXIT_FAILURE; }
@@ -679,8 +724,8 @@ int main(int argc, char **argv) {
         if (!rin) { std::cerr << "Cannot open r-index: " << r_index_file << std::endl; std::exit(EXIT_FAILURE); } // :30
     }
     const bool from_image = is_image_file(r_index_file.c_str());
-    // --gaf with "-" for the tags of a .ri: the index opens without tags and the walk stage's own refusal ends the run below, before any batch
-    const bool gaf_no_tags = !from_image && !gaf_file.empty() && tag_array_index == "-";
+    // --gaf or --mapq with "-" for the tags of a .ri: the index opens without tags and the walk image's own refusal ends the run below, before any batch
+    const bool gaf_no_tags = !from_image && (!gaf_file.empty() || mapq) && tag_array_index == "-";
     if (!from_image && !gaf_no_tags) {
         std::ifstream tin(tag_array_index, std::ios::binary);
         if (!tin) { std::cerr << "Cannot open tag array: " << tag_array_index << std::endl; std::exit(EXIT_FAILURE); }
@@ -747,7 +792,7 @@ int main(int argc, char **argv) {
         std::fwrite(PLACE_HEADER, 1, sizeof PLACE_HEADER - 1, place_fp);
     }
     // --verify: the same question for the text image (what --place asks, and a collection of 2^32 - 2^20 symbols or more)
-    std::FILE *verify_fp = nullptr, *align_fp = nullptr, *gaf_fp = nullptr, *mates_fp = nullptr, *rescued_fp = nullptr;
+    std::FILE *verify_fp = nullptr, *align_fp = nullptr, *gaf_fp = nullptr, *mates_fp = nullptr, *rescued_fp = nullptr, *mapq_fp = nullptr;
     if (run_verify) {
         static const uint8_t probe_read[4] = {'A', 'C', 'G', 'T'};
         static const uint64_t probe_offs[2] = {0, 4};
@@ -772,12 +817,13 @@ int main(int argc, char **argv) {
             }
             if (st == PGX_OK && run_align) st = pgx_batch_read_align(pb, align_band, PGX_ALIGN_CIGAR, nullptr);
             if (st == PGX_OK && want_gaf) st = pgx_batch_read_walk(pb, PGX_WALK_STEPS, nullptr); // (the walk image: an index without tags ends here)
+            if (st == PGX_OK && mapq) st = pgx_batch_read_mapq(pb, mapq_scale, mapq_slack, mapq_extra, 0u, nullptr); // (the same image; a probe of one read is no pair)
             if (st != PGX_OK && !twin_refused) msg = pgx_last_error();
             pgx_batch_free(pb);
         }
         if (st != PGX_OK) {
             std::cerr << msg
-                      << (st != PGX_ERR_UNSUPPORTED || twin_refused ? "" : (want_verify ? " (find_mems --verify)" : (want_align ? " (find_mems --align)" : (want_gaf ? " (find_mems --gaf)" : " (find_mems --paired)"))))
+                      << (st != PGX_ERR_UNSUPPORTED || twin_refused ? "" : (want_verify ? " (find_mems --verify)" : (want_align ? " (find_mems --align)" : (want_gaf ? " (find_mems --gaf)" : (mapq ? " (find_mems --mapq)" : " (find_mems --paired)")))))
                       << std::endl;
             if (hits_fp) std::fclose(hits_fp);
             if (place_fp) std::fclose(place_fp);
@@ -806,6 +852,11 @@ int main(int argc, char **argv) {
             rescued_fp = std::fopen(rescued_file.c_str(), "wb");
             if (!rescued_fp) { std::cerr << "Cannot open rescued file: " << rescued_file << std::endl; return EXIT_FAILURE; }
             std::fwrite(RESCUED_HEADER, 1, sizeof RESCUED_HEADER - 1, rescued_fp);
+        }
+        if (want_mapqs) {
+            mapq_fp = std::fopen(mapq_file.c_str(), "wb");
+            if (!mapq_fp) { std::cerr << "Cannot open mapq file: " << mapq_file << std::endl; return EXIT_FAILURE; }
+            std::fwrite(MAPQ_HEADER, 1, sizeof MAPQ_HEADER - 1, mapq_fp);
         }
     }
 
@@ -1108,6 +1159,7 @@ int main(int argc, char **argv) {
             }
             std::vector<pgx_read_mates> mate_recs;    // --mates: the 64-byte records of the batch's pairs
             std::vector<pgx_read_rescue> rescue_recs; // --rescued: the 64-byte records of the batch's reads
+            std::vector<pgx_read_mapq> mapq_recs;     // --mapq: the 32-byte records of the batch's reads
             std::vector<pgx_read_verify> verify_recs; // --verify: the 64-byte records, at the candidates of the place stage above
             if (st == PGX_OK && run_verify) {
                 st = pgx_batch_read_verify(b, verify_max, verify_penalty, verify_flags, nullptr);
@@ -1122,6 +1174,12 @@ int main(int argc, char **argv) {
                     pgx_read_mates_result rm;
                     if (st == PGX_OK && want_mates) st = pgx_batch_mated(b, &rm);
                     if (st == PGX_OK && want_mates) mate_recs.assign(rm.pairs, rm.pairs + rm.n_pairs);
+                }
+                if (st == PGX_OK && mapq) { // behind the election: the quality of the winners that --gaf reports
+                    st = pgx_batch_read_mapq(b, mapq_scale, mapq_slack, mapq_extra, mapq_flags, nullptr);
+                    pgx_read_mapqs rq;
+                    if (st == PGX_OK) st = pgx_batch_mapqs(b, &rq);
+                    if (st == PGX_OK) mapq_recs.assign(rq.records, rq.records + rq.n_reads);
                 }
                 pgx_read_verifies rv;
                 if (st == PGX_OK && want_verify) st = pgx_batch_verified(b, &rv);
@@ -1202,9 +1260,10 @@ int main(int argc, char **argv) {
                 if (want_verify) format_verifies(verify_recs.data(), verify_recs.size(), j->first_seq, d->verifies);
                 if (want_mates) format_mates(mate_recs.data(), mate_recs.size(), j->first_seq, d->mates);
                 if (want_rescued) format_rescued(rescue_recs.data(), rescue_recs.size(), j->first_seq, d->rescued);
+                if (want_mapqs) format_mapqs(mapq_recs.data(), mapq_recs.size(), j->first_seq, d->mapqs);
                 if (want_gaf && !walk_read_off.empty())
                     format_gaf(align_recs.data(), align_op_off.data(), align_ops.data(), walk_recs.data(), walk_step_off.data(), walk_steps.data(), walk_read_off.data(),
-                               walk_recs.size(), j->first_seq, d->gaf);
+                               mapq ? mapq_recs.data() : nullptr, walk_recs.size(), j->first_seq, d->gaf);
                 if (want_align && !align_op_off.empty()) format_aligns(align_recs.data(), align_op_off.data(), align_ops.data(), align_recs.size(), j->first_seq, d->aligns);
                 if (format_device && !no_text) {
                     // the text of the batch from the device, handed to the writer where it is
@@ -1309,6 +1368,7 @@ int main(int argc, char **argv) {
         if (gaf_fp && !d->gaf.empty()) std::fwrite(d->gaf.data(), 1, d->gaf.size(), gaf_fp);
         if (mates_fp && !d->mates.empty()) std::fwrite(d->mates.data(), 1, d->mates.size(), mates_fp);
         if (rescued_fp && !d->rescued.empty()) std::fwrite(d->rescued.data(), 1, d->rescued.size(), rescued_fp);
+        if (mapq_fp && !d->mapqs.empty()) std::fwrite(d->mapqs.data(), 1, d->mapqs.size(), mapq_fp);
         ns_write += now_ns() - tw0;
         total_mem_time += d->mem_s;
         total_tag_time += d->tag_s;
@@ -1337,6 +1397,7 @@ int main(int argc, char **argv) {
     if (gaf_fp && (std::fclose(gaf_fp) != 0) && error.empty()) error = "Cannot write gaf file: " + gaf_file;
     if (mates_fp && (std::fclose(mates_fp) != 0) && error.empty()) error = "Cannot write mates file: " + mates_file;
     if (rescued_fp && (std::fclose(rescued_fp) != 0) && error.empty()) error = "Cannot write rescued file: " + rescued_file;
+    if (mapq_fp && (std::fclose(mapq_fp) != 0) && error.empty()) error = "Cannot write mapq file: " + mapq_file;
     if (!error.empty()) {
         std::cerr << error << std::endl;
         return EXIT_FAILURE;
