@@ -1316,6 +1316,79 @@ pgx_status pgx_read_mapq_arrays(int device, const uint64_t *seq_offsets, uint64_
                                 const uint32_t *chosen, const pgx_read_rescue *rescue, int64_t frag_min, int64_t frag_max, uint32_t penalty,
                                 const uint32_t *list_len, uint32_t scale, uint32_t slack, uint32_t flags, pgx_read_mapq *out);
 
+/* ---- read pack: how many reads cover every base of every node, accumulated over batches on the device ---------------------------------
+ * Every stage above returns per-read records of one batch.  This one aggregates: a vector the size of the graph that stays on the device over a
+ * whole run and comes down once.  It reads what pgx_batch_read_align left on the device (records and CIGAR operations), the WALK image and,
+ * with a filter, the mapq records; no GAF line is written or parsed.
+ *
+ * DEFINITIONS.
+ *   graph coordinates   The WALK image's visits are node << 1 | rev; visit k covers [m_k, m_k+1) cut at its sequence's end.  len[id] is the
+ *                length of any visit of node id; every visit of one id must have the same length, else PGX_ERR_FORMAT "the tags do not
+ *                describe whole-node paths", naming the smallest such id (a visit of more than 1024 symbols counts as such an id).  Ids that no
+ *                visit names have len = 0; max_id is the largest id visited; n_nodes = max_id + 1 (0 without a visit).  base[id] is the exclusive
+ *                prefix sum of len over 0 .. max_id and G = base[max_id + 1].  Graph base (id, o), o counted in the node's forward orientation,
+ *                is g = base[id] + o.  A text position p inside visit k at distance d = p - m_k maps to o = d when rev = 0 and to
+ *                o = len - 1 - d when rev = 1.  The table is dense in the id: no sort is needed, and max_id + 2 > 2^32 is PGX_ERR_UNSUPPORTED.
+ *   a read is counted   iff its align record has seq != PGX_NO_SEQUENCE and text_end > text_start and it passes the filter: min_mapq == 0, or its
+ *                pgx_read_mapq.mapq >= min_mapq.  (pgx_read_pack_arrays has no text_end: there it is text_start plus the text its
+ *                operations consume, and keep[r] != 0 is the filter.)
+ *   what it adds        its CIGAR is walked in read order with t = text_start: S and I consume no text; D consumes text and adds nothing; = and X
+ *                consume text and add 1 to the coverage of every graph base under the positions they consume.  t ends on text_end.
+ *   coverage            u32 per graph base, summed over every counted read of every added batch.  Sums are modulo 2^32: a base with more than
+ *                2^32 - 1 reads is out of scope.
+ *   summary             for every id with len > 0: covered = bases with coverage > 0, sum (u64), max.  Ids with len = 0 have all three 0.
+ *   counters            reads counted; reads filtered out (placed, with text_end > text_start, and refused by the filter); bases added (the
+ *                summed lengths of the = and X operations of the counted reads, which is sum(cov) while no base wraps).
+ * The device keeps a difference array in the text image's coordinates (n + 1 i32, wrap-around arithmetic): a read adds +1 / -1 at the two ends
+ * of every stretch of matched text, and pgx_pack_finish folds it once -- prefix sums per tile, every covered text position projected onto its
+ * graph base -- and zeroes it.  Integer adds commute: the result depends on nothing but the set of counted reads, not on lane counts, streams,
+ * the order of the batches or how the reads are cut into batches.
+ * Device memory of a pack: 4 (n + 1) + 4 G + 12 (max_id + 2) bytes, and 16 (max_id + 1) more for the summary.
+ * pgx_pack_create returns PGX_ERR_NOMEM with the bytes needed (G bounded by n, the summary included) and the bytes free before any of these
+ * is allocated. */
+typedef struct pgx_pack pgx_pack;
+typedef struct {
+    uint64_t n_nodes;               /* max_id + 1 */
+    uint64_t n_bases;               /* G */
+    uint64_t n_text;                /* n: the text image's positions (tdiff holds n + 1) */
+    uint64_t reads_counted, reads_filtered, bases_added; /* over every pgx_pack_add so far, summed on the device */
+    uint64_t n_projected;           /* text positions the folds so far projected onto the graph */
+    const uint64_t *node_base;      /* n_nodes + 1 */
+    const uint32_t *node_length;    /* n_nodes */
+    const uint32_t *cov;            /* n_bases */
+    const uint32_t *covered;        /* n_nodes */
+    const uint64_t *sum;            /* n_nodes */
+    const uint32_t *max;            /* n_nodes */
+    double ms_add_total;            /* device time of the pgx_pack_add calls on batches run with PGX_RUN_TIMING, summed */
+    float ms_fold;                  /* device time of the last fold and summary */
+    float ms_table;                 /* device time of the node table's build in pgx_pack_create (the WALK image's build is not in it) */
+} pgx_pack_result;
+/* A pack of index h on one device.  Builds the WALK image on first use (every refusal of pgx_batch_read_walk carries over) and the node table. */
+pgx_status pgx_pack_create(pgx_index *h, int device, pgx_pack **out);
+void pgx_pack_free(pgx_pack *p);
+/* Adds the reads of batch b.  Needs this run's align result made with PGX_ALIGN_CIGAR, on the pack's index and device, and with min_mapq > 0
+ * this run's mapq result.  PGX_ERR_ARG with nothing added, naming what was found: no such result, another index or device, min_mapq > 60, an
+ * unknown flag (there are none: flags must be 0).  Runs on `stream` (NULL = the batch's own), complete on return.  May be called from several
+ * threads at once on different batches.  It changes nothing in the batch. */
+pgx_status pgx_pack_add(pgx_pack *p, pgx_batch *b, uint32_t min_mapq, uint32_t flags, void *stream);
+/* Folds what was added and downloads the result into pinned buffers owned by the pack (valid until the next finish or the free).  After the
+ * fold the difference array is all zero and cov holds the total: finish may be called again and returns the same vector, and add may continue
+ * after it.  Must not run concurrently with pgx_pack_add or another finish on the same pack. */
+pgx_status pgx_pack_finish(pgx_pack *p, pgx_pack_result *out);
+/* The result of the last pgx_pack_finish as device pointers.  PGX_ERR_ARG when there was none. */
+pgx_status pgx_pack_device_result(pgx_pack *p, pgx_pack_result *out);
+/* The same kernels on stated tables: the path tables of pgx_read_walk_arrays; read r lies on sequence seq[r] (PGX_NO_SEQUENCE: none) from
+ * text_start[r] with the operations ops[op_offsets[r] .. op_offsets[r + 1]) (length << 4 | op, the codes of pgx_read_align); keep (NULL: every
+ * read) is the filter.  *n_nodes and *n_bases are written first; node_base takes n_nodes + 1 entries, node_length / covered / sum / max n_nodes
+ * each when nodes_cap >= n_nodes, cov n_bases when cov_cap >= n_bases: PGX_ERR_NOMEM with the needed counts otherwise, nothing else written.
+ * counters takes the three counters.  PGX_ERR_ARG with nothing written, the first offender named: the argument checks of pgx_read_walk_arrays,
+ * an operation code that is none of I D S = X, a seq that is neither below n_seq nor PGX_NO_SEQUENCE, a text_start behind its sequence, a
+ * CIGAR whose text length leaves its sequence.  PGX_ERR_FORMAT for two visits of one id with different lengths.  PGX_ERR_NO_DEVICE without a GPU. */
+pgx_status pgx_read_pack_arrays(int device, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
+                                const uint32_t *visit_length, uint64_t n_reads, const uint32_t *seq, const uint64_t *text_start, const uint64_t *op_offsets,
+                                const uint32_t *ops, const uint8_t *keep, uint64_t *n_nodes, uint64_t *n_bases, uint64_t *node_base, uint32_t *node_length,
+                                uint32_t *covered, uint64_t *sum, uint32_t *max, uint64_t nodes_cap, uint32_t *cov, uint64_t cov_cap, uint64_t *counters);
+
 /* ---- compact result: the result of a run as a byte stream, encoded on the device, expanded on the host ---------------------
  * What pgx_batch_result downloads is six dense uint64 arrays (8 bytes per read, 48 per MEM, 8 per graph position), nearly all of
  * them zero bits.  The compact form carries the same values and is expanded to the same pgx_result; only it crosses the link.

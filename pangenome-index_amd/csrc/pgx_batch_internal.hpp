@@ -1,7 +1,9 @@
 // pgx_batch_internal.hpp -- what the units of the batch share and nobody else needs (pgx_batch.hip, pgx_batch_forms.hip, pgx_batch_locate.hip,
-// pgx_read_stages.hip): the pgx_batch object, the work buffers of its result forms, of locate and of the read stages, and the glue around a stage call
+// pgx_read_stages.hip, pgx_pack.hip): the pgx_batch object, the work buffers of its result forms, of locate and of the read stages, and the glue around a stage call
 // (its stream, its timer, the download of its result).  Nothing here is part of the C ABI, and nothing is exported from libpgx.so.
 #pragma once
+
+#include <string>
 
 #include "pgx_runtime_internal.hpp"
 
@@ -302,5 +304,34 @@ inline void download_pinned(pgx_batch *b, const StageResult &r, HostBuf &recs, H
     download_result(r, recs.p, off.p, items.p, b->own);
     HIPCHECK(hipStreamSynchronize(b->own));
 }
+
+// pgx_read_stages.hip: what the _arrays entry points share with pgx_pack.hip
+size_t free_device_memory();
+// what they ask of an offsets array of k items (o[k] is read)
+void check_offsets(const std::string &who, const uint64_t *o, uint64_t k, const char *name, const char *item);
+// what those that take path tables (walk, mapq, pack) ask of them, and the text position of every visit
+std::vector<uint64_t> walk_table_marks(const std::string &who, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
+                                       const uint32_t *visit_length);
+
+// the WALK image of stated path tables on the device (null stream), released on every way out
+struct WalkTables {
+    DevBuf seq_off, marks, bits, dir, nodes, counts, scan_tmp;
+    ~WalkTables() { release_all({&seq_off, &marks, &bits, &dir, &nodes, &counts, &scan_tmp}); }
+    PgxWalkImage build(const uint64_t *seq_offsets, uint64_t n_seq, const std::vector<uint64_t> &m, const uint64_t *visit_nodes, hipStream_t s) {
+        const uint64_t n_text = seq_offsets[n_seq], V = m.size();
+        const uint64_t n_blocks = n_text / PGX_WALK_BLOCK_BITS + 1, n_words = n_blocks * PGX_WALK_BLOCK_WORDS;
+        upload(seq_off, seq_offsets, (n_seq + 1) * 8);
+        upload(marks, m.data(), V * 8);
+        upload(nodes, visit_nodes, V * 8);
+        bits.ensure(n_words * 8); dir.ensure((n_blocks + 1) * 8);
+        HIPCHECK(hipMemsetAsync(bits.p, 0, n_words * 8, s));
+        if (V) {
+            hipLaunchKernelGGL(pgx_walk_set_kernel, dim3((unsigned)std::min<uint64_t>((V + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint64_t *)marks.as<uint64_t>(), V, bits.as<uint32_t>());
+            HIPCHECK(hipGetLastError());
+        }
+        walk_directory(bits.as<uint64_t>(), n_blocks, counts, dir.as<uint64_t>(), scan_tmp, s);
+        return PgxWalkImage{bits.as<uint64_t>(), dir.as<uint64_t>(), nodes.as<uint64_t>(), n_text, n_words, n_blocks, V};
+    }
+};
 
 #pragma GCC visibility pop

@@ -530,6 +530,32 @@ __global__ void pgx_mapq_choose_extras_kernel(const pgx_read_place *recs, const 
 template <bool PAIRED>
 __global__ void pgx_mapq_kernel(PgxMapqArgs a);
 
+// ---- pgx_pack_kernels.hip: read pack (pgx_pack_add, pgx_pack_finish, pgx_read_pack_arrays)
+#define PGX_PACK_THREADS 256
+#define PGX_PACK_NODE_LANES 16u // lanes that summarise one node (pgx_pack_summary_kernel)
+// the node table: len[id] (0: no visit names the id) and base[id], the exclusive prefix sum of len; n_nodes = max_id + 1
+struct PgxPackTable {
+    const uint32_t *len;
+    const uint64_t *base; // n_nodes + 1
+    uint64_t n_nodes;
+};
+__global__ void pgx_pack_max_id_kernel(const uint64_t *nodes, uint64_t n_visits, unsigned long long *max_id);
+// a thread a word of marks: every visit's length into len_min / len_max of its id; a visit longer than PGX_WALK_MAX_VISIT: atomicMin of its id into too_long
+__global__ void pgx_pack_visit_len_kernel(PgxWalkImage w, const uint64_t *seq_start, uint64_t n_seq, uint32_t endmark, uint64_t n_nodes, uint32_t *len_min, uint32_t *len_max,
+                                          unsigned long long *bad, unsigned long long *too_long);
+// len_min -> len in place (0 for an id without a visit); an id with len_min != len_max: atomicMin into bad
+__global__ void pgx_pack_node_len_kernel(uint32_t *len_min, const uint32_t *len_max, uint64_t n_nodes, unsigned long long *bad);
+// a lane a read: recs + mapqs (the batch) or seq / text_start / keep (arrays; mapqs == NULL); counters: reads counted, reads filtered, bases added
+__global__ void pgx_pack_add_kernel(const pgx_read_align *recs, const uint32_t *seq, const uint64_t *text_start, const uint64_t *op_off, const uint32_t *ops,
+                                    const pgx_read_mapq *mapqs, const uint8_t *keep, uint32_t min_mapq, uint64_t n_reads, const uint64_t *seq_start, uint64_t n_seq,
+                                    uint64_t n, int *tdiff, unsigned long long *counters);
+// a workgroup a tile of PGX_SCAN_BLOCK_ITEMS entries of tdiff (n1 = n + 1 entries): its sum, sign-extended
+__global__ void pgx_pack_tile_sum_kernel(const int *tdiff, uint64_t n1, uint64_t *tile_sums);
+// the same tiles: tdiff -> text coverage, every covered position projected onto cov, the tile zeroed; *projected += the positions projected
+__global__ void pgx_pack_fold_kernel(int *tdiff, uint64_t n1, const uint64_t *tile_off, PgxWalkImage w, PgxPackTable t, uint32_t *cov, unsigned long long *projected);
+// PGX_PACK_NODE_LANES lanes a node
+__global__ void pgx_pack_summary_kernel(PgxPackTable t, const uint32_t *cov, uint32_t *covered, uint64_t *sum, uint32_t *max);
+
 // literal count image: COMPAT count_encoded / LF_encoded on an encoded index without N, block by block as the
 // reference's rankAt_encoded (src/r-index.cpp:570-590) sees it -- true cumulative counts, run scan one varint late
 struct PgxLitImage {

@@ -10,14 +10,14 @@
 // reads, MEMs, keys or candidates one launch takes at a thread an item or fewer: a grid holds fewer than 2^32 threads, and a larger one would lose items without an error
 static const uint64_t PLACE_LAUNCH_ITEMS = 1ull << 31;
 
-static size_t free_device_memory() {
+size_t free_device_memory() {
     size_t mem_free = 0, mem_total = 0;
     if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); mem_free = 1ull << 30; }
     return mem_free;
 }
 
 // what the _arrays entry points ask of an offsets array of k items (o[k] is read)
-static void check_offsets(const std::string &who, const uint64_t *o, uint64_t k, const char *name, const char *item) {
+void check_offsets(const std::string &who, const uint64_t *o, uint64_t k, const char *name, const char *item) {
     if (o[0] != 0) throw Error(PGX_ERR_ARG, who + ": " + name + " must start at 0");
     for (uint64_t i = 0; i < k; i++)
         if (o[i] > o[i + 1]) throw Error(PGX_ERR_ARG, who + ": " + name + " decrease at " + item + " " + std::to_string(i));
@@ -1540,7 +1540,7 @@ extern "C" pgx_status pgx_batch_walked(pgx_batch *b, pgx_read_walks *out) {
 
 // What the _arrays entry points that take path tables (walk, mapq) ask of them, and the text position of every visit: sequence q is seq_offsets[q] ..
 // seq_offsets[q + 1] and consists of the visits [visit_offsets[q], visit_offsets[q + 1]).
-static std::vector<uint64_t> walk_table_marks(const std::string &who, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
+std::vector<uint64_t> walk_table_marks(const std::string &who, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
                                               const uint32_t *visit_length) {
     check_offsets(who, seq_offsets, n_seq, "seq_offsets", "sequence");
     check_offsets(who, visit_offsets, n_seq, "visit_offsets", "sequence");
@@ -1563,28 +1563,7 @@ static std::vector<uint64_t> walk_table_marks(const std::string &who, const uint
     return marks;
 }
 
-// the WALK image of stated path tables on the device (null stream), released on every way out
-namespace {
-struct WalkTables {
-    DevBuf seq_off, marks, bits, dir, nodes, counts, scan_tmp;
-    ~WalkTables() { release_all({&seq_off, &marks, &bits, &dir, &nodes, &counts, &scan_tmp}); }
-    PgxWalkImage build(const uint64_t *seq_offsets, uint64_t n_seq, const std::vector<uint64_t> &m, const uint64_t *visit_nodes, hipStream_t s) {
-        const uint64_t n_text = seq_offsets[n_seq], V = m.size();
-        const uint64_t n_blocks = n_text / PGX_WALK_BLOCK_BITS + 1, n_words = n_blocks * PGX_WALK_BLOCK_WORDS;
-        upload(seq_off, seq_offsets, (n_seq + 1) * 8);
-        upload(marks, m.data(), V * 8);
-        upload(nodes, visit_nodes, V * 8);
-        bits.ensure(n_words * 8); dir.ensure((n_blocks + 1) * 8);
-        HIPCHECK(hipMemsetAsync(bits.p, 0, n_words * 8, s));
-        if (V) {
-            hipLaunchKernelGGL(pgx_walk_set_kernel, dim3((unsigned)std::min<uint64_t>((V + 255) / 256, 1u << 20)), dim3(256), 0, s, (const uint64_t *)marks.as<uint64_t>(), V, bits.as<uint32_t>());
-            HIPCHECK(hipGetLastError());
-        }
-        walk_directory(bits.as<uint64_t>(), n_blocks, counts, dir.as<uint64_t>(), scan_tmp, s);
-        return PgxWalkImage{bits.as<uint64_t>(), dir.as<uint64_t>(), nodes.as<uint64_t>(), n_text, n_words, n_blocks, V};
-    }
-};
-} // namespace
+// (the WALK image of stated path tables, WalkTables: pgx_batch_internal.hpp)
 
 extern "C" pgx_status pgx_read_walk_arrays(int device, const uint64_t *seq_offsets, uint64_t n_seq, const uint64_t *visit_offsets, const uint64_t *visit_nodes,
                                            const uint32_t *visit_length, uint64_t n_reads, const uint32_t *seq, const uint64_t *text_start, const uint64_t *text_end,

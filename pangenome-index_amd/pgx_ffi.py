@@ -205,6 +205,12 @@ class ReadWalks(C.Structure):  # pgx_read_walks: host pointers (pgx_batch_walked
                 ("reserved2", u32)]
 
 
+class PackResult(C.Structure):  # pgx_pack_result: host pointers (pgx_pack_finish) or device pointers (pgx_pack_device_result)
+    _fields_ = [("n_nodes", u64), ("n_bases", u64), ("n_text", u64), ("reads_counted", u64), ("reads_filtered", u64), ("bases_added", u64), ("n_projected", u64),
+                ("node_base", p), ("node_length", p), ("cov", p), ("covered", p), ("sum", p), ("max", p), ("ms_add_total", C.c_double), ("ms_fold", C.c_float),
+                ("ms_table", C.c_float)]
+
+
 class DeviceArray:
     """a device buffer owned by a batch, exposed through __cuda_array_interface__ (zero copy: torch.as_tensor(a, device="cuda"));
     64-bit unsigned values are presented as int64"""
@@ -375,6 +381,13 @@ def lib():
     L.pgx_batch_device_walked.argtypes = [p, C.POINTER(ReadWalks)]
     L.pgx_index_paths.argtypes = [p, C.c_int, p, u64, p, p, u64]
     L.pgx_read_walk_arrays.argtypes = [C.c_int, p, u64, p, p, p, u64, p, p, p, u32, p, p, p, u64]
+    L.pgx_pack_create.argtypes = [p, C.c_int, C.POINTER(p)]
+    L.pgx_pack_free.argtypes = [p]
+    L.pgx_pack_free.restype = None
+    L.pgx_pack_add.argtypes = [p, p, u32, u32, p]
+    L.pgx_pack_finish.argtypes = [p, C.POINTER(PackResult)]
+    L.pgx_pack_device_result.argtypes = [p, C.POINTER(PackResult)]
+    L.pgx_read_pack_arrays.argtypes = [C.c_int, p, u64, p, p, p, u64, p, p, p, p, p, p, p, p, p, p, p, p, u64, p, u64, p]
     L.pgx_batch_result_compact.argtypes = [p, C.POINTER(CompactResult)]
     L.pgx_compact_expand.argtypes = [C.POINTER(CompactResult), u64, u64, p, p, p, p, p]
     L.pgx_compact_bound.argtypes = [u64, u64, u64, u32]
@@ -1213,6 +1226,90 @@ def read_walk_arrays(device, seq_offsets, visit_offsets, visit_nodes, visit_leng
     if lst:
         res["steps"] = res["steps"][: int(res["step_offsets"][-1])]
     return res
+
+
+def read_pack_arrays(device, seq_offsets, visit_offsets, visit_nodes, visit_length, seq, text_start, op_offsets, ops, keep=None, nodes_cap=None, cov_cap=None, out=None):
+    """pgx_read_pack_arrays: the pack kernels on stated path tables (those of read_walk_arrays); read r lies on sequence seq[r] (NO_SEQUENCE for none)
+    from text_start[r] with the operations ops[op_offsets[r] : op_offsets[r + 1]] (uint32, length << 4 | op); keep uint8[n_reads] or None.
+    dict(n_nodes, n_bases, node_base uint64[n_nodes + 1], node_length uint32, cov uint32[n_bases], covered uint32, sum uint64, max uint32,
+    reads_counted, reads_filtered, bases_added).  nodes_cap / cov_cap: the capacities handed to the library (default: what these tables need);
+    out: a dict of arrays to write into (tests)"""
+    seq_offsets = np.ascontiguousarray(seq_offsets, dtype=np.uint64)
+    visit_offsets = np.ascontiguousarray(visit_offsets, dtype=np.uint64)
+    visit_nodes = np.ascontiguousarray(visit_nodes, dtype=np.uint64)
+    visit_length = np.ascontiguousarray(visit_length, dtype=np.uint32)
+    seq = np.ascontiguousarray(seq, dtype=np.uint32)
+    text_start = np.ascontiguousarray(text_start, dtype=np.uint64)
+    op_offsets = np.ascontiguousarray(op_offsets, dtype=np.uint64)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    keep = None if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
+    n, n_seq = len(seq), len(seq_offsets) - 1
+    if len(text_start) != n or len(op_offsets) != n + 1 or (keep is not None and len(keep) != n) or len(visit_offsets) != n_seq + 1 or len(visit_nodes) != len(visit_length):
+        raise ValueError("read_pack_arrays: array lengths disagree")
+    ncap = (int(visit_nodes.max() >> np.uint64(1)) + 1 if len(visit_nodes) else 0) if nodes_cap is None else int(nodes_cap)
+    ccap = int(visit_length.astype(np.uint64).sum()) if cov_cap is None else int(cov_cap)  # (G is at most the text)
+    res = dict(out) if out else {}
+    for name, shape, dt in (("node_base", ncap + 1, np.uint64), ("node_length", max(ncap, 1), np.uint32), ("covered", max(ncap, 1), np.uint32), ("sum", max(ncap, 1), np.uint64),
+                            ("max", max(ncap, 1), np.uint32), ("cov", max(ccap, 1), np.uint32), ("counters", 3, np.uint64)):
+        if name not in res:
+            res[name] = np.zeros(shape, dtype=dt)
+    nn, nb = u64(0), u64(0)
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(lib().pgx_read_pack_arrays(device, seq_offsets.ctypes.data, n_seq, visit_offsets.ctypes.data, visit_nodes.ctypes.data, visit_length.ctypes.data, n, seq.ctypes.data,
+                                      text_start.ctypes.data, op_offsets.ctypes.data, ops.ctypes.data, ptr(keep), C.addressof(nn), C.addressof(nb), ptr(res["node_base"]),
+                                      ptr(res["node_length"]), ptr(res["covered"]), ptr(res["sum"]), ptr(res["max"]), ncap, ptr(res["cov"]), ccap, ptr(res["counters"])))
+    k, g = int(nn.value), int(nb.value)
+    c = res.pop("counters")
+    res.update(n_nodes=k, n_bases=g, node_base=res["node_base"][: k + 1], node_length=res["node_length"][:k], covered=res["covered"][:k], sum=res["sum"][:k], max=res["max"][:k],
+               cov=res["cov"][:g], reads_counted=int(c[0]), reads_filtered=int(c[1]), bases_added=int(c[2]))
+    return res
+
+
+class Pack:
+    """pgx_pack: the coverage of every graph base, accumulated over the batches added to it (one index, one device)"""
+
+    def __init__(self, index, device=0):
+        self.L = lib()
+        self.index = index  # keeps the index alive
+        self.device = device
+        self.p = p()
+        _check(self.L.pgx_pack_create(index.h, device, C.byref(self.p)))
+
+    def add(self, batch, min_mapq=0, flags=0, stream=None):
+        """pgx_pack_add: the reads of the batch's align result (made with ALIGN_CIGAR); min_mapq > 0 reads its mapq result too"""
+        _check(self.L.pgx_pack_add(self.p, batch.b if batch is not None else None, min_mapq, flags, stream))
+
+    def _result(self, fn):
+        r = PackResult()
+        _check(fn(self.p, C.byref(r)))
+        return r, dict(n_nodes=int(r.n_nodes), n_bases=int(r.n_bases), n_text=int(r.n_text), reads_counted=int(r.reads_counted), reads_filtered=int(r.reads_filtered),
+                       bases_added=int(r.bases_added), n_projected=int(r.n_projected), ms_add_total=float(r.ms_add_total), ms_fold=float(r.ms_fold), ms_table=float(r.ms_table))
+
+    def finish(self):
+        """pgx_pack_finish as numpy arrays: node_base uint64[n_nodes + 1], node_length uint32[n_nodes], cov uint32[n_bases], covered uint32, sum uint64 and
+        max uint32 per node, with n_nodes, n_bases, n_text, the counters and the times"""
+        r, out = self._result(self.L.pgx_pack_finish)
+        k, g = out["n_nodes"], out["n_bases"]
+        view = lambda ptr, n, dt: np.frombuffer((C.c_char * (n * np.dtype(dt).itemsize)).from_address(ptr), dtype=dt).copy() if n else np.zeros(0, dt)
+        out.update(node_base=view(r.node_base, k + 1, np.uint64), node_length=view(r.node_length, k, np.uint32), cov=view(r.cov, g, np.uint32),
+                   covered=view(r.covered, k, np.uint32), sum=view(r.sum, k, np.uint64), max=view(r.max, k, np.uint32))
+        return out
+
+    def device_result(self):
+        """the last finish as device arrays (valid until the next finish / close)"""
+        r, out = self._result(self.L.pgx_pack_device_result)
+        k, g = out["n_nodes"], out["n_bases"]
+        out.update(device=True, node_base=DeviceArray(r.node_base, (k + 1,), self), node_length=DeviceArray(r.node_length, (k,), self, "<u4"),
+                   cov=DeviceArray(r.cov, (g,), self, "<u4"), covered=DeviceArray(r.covered, (k,), self, "<u4"), sum=DeviceArray(r.sum, (k,), self),
+                   max=DeviceArray(r.max, (k,), self, "<u4"))
+        return out
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.L.pgx_pack_free(self.p)
+            self.p = None
+
+    __del__ = close
 
 
 def find_mems_sharded(index, devices, reads_cat, offsets, min_len, min_occ, tags=False):

@@ -40,6 +40,11 @@
 //                 paired scores; place and verify run with their lists, --verify-max defaults to 16; column 12 of a GAF line whose read has steps is the
 //                 read's mapping quality), --mapq-scale D (1 .. 16, default 2), --mapq-slack K (0 .. 1024, default 8), --mapq-extra X (0 .. 63, default
 //                 16), --mapq-file FILE (one line per read)
+//                 --pack FILE (written once at the end: per node of the graph how many reads cover its bases, pgx_pack; runs the place, verify and align
+//                 stages itself when they are not requested, align with its CIGAR list, and no walk stage; one pack per device, every worker adds its
+//                 finished batch, the vectors of several devices are summed on the host; stdout and stderr stay as they are), --pack-bases FILE2 (one
+//                 line per covered base), --pack-min-mapq Q (1 .. 60, with --mapq, which --pack satisfies as --gaf does: reads below Q are not
+//                 counted), --pack-only (no MEM text, like --gaf-only)
 // The tag file may be either query format; the reference's find_mems only loads the sdsl-compact one.
 //
 // The per-read loop of the reference (find_mems.cpp:94-139) becomes a pipeline: one reader thread cuts the reads file into
@@ -466,6 +471,56 @@ static void format_gaf(const pgx_read_align *recs, const uint64_t *op_off, const
     out.resize((size_t)(p - &out[0]));
 }
 
+// --pack: every device's pack finished, the vectors summed (modulo 2^32, like the device's own sums), the summary recomputed from the sum, the two
+// files written.  Returns the error, or an empty string.
+static std::string write_packs(const std::map<int, pgx_pack *> &packs, const std::string &file, const std::string &bases_file) {
+    std::vector<uint32_t> cov, len;
+    std::vector<uint64_t> base;
+    for (const auto &kv : packs) {
+        pgx_pack_result r;
+        if (pgx_pack_finish(kv.second, &r) != PGX_OK) return pgx_last_error();
+        if (base.empty()) {
+            base.assign(r.node_base, r.node_base + r.n_nodes + 1);
+            len.assign(r.node_length, r.node_length + r.n_nodes);
+            cov.assign(r.cov, r.cov + r.n_bases);
+        } else {
+            if (r.n_nodes + 1 != base.size() || r.n_bases != cov.size()) return "find_mems --pack: the packs of two devices describe different graphs";
+            for (uint64_t g = 0; g < r.n_bases; g++) cov[g] += r.cov[g];
+        }
+    }
+    // the node file is a line a node and is built in memory; the base file is a line a covered base and is streamed through its FILE's buffer
+    std::FILE *bfp = nullptr;
+    if (!bases_file.empty()) {
+        bfp = std::fopen(bases_file.c_str(), "wb");
+        if (!bfp) return "Cannot open pack-bases file: " + bases_file;
+        std::fputs("#node\toffset\tcoverage\n", bfp);
+    }
+    std::string out = "#node\tlength\tcovered\tsum\tmax\n";
+    char line[128];
+    for (size_t id = 0; id < len.size(); id++) {
+        if (!len[id]) continue;
+        uint64_t covered = 0, sum = 0;
+        uint32_t mx = 0;
+        for (uint32_t o = 0; o < len[id]; o++) {
+            const uint32_t c = cov[base[id] + o];
+            if (!c) continue;
+            covered++; sum += c; mx = std::max(mx, c);
+            if (bfp) std::fprintf(bfp, "%zu\t%u\t%u\n", id, o, c);
+        }
+        std::snprintf(line, sizeof line, "%zu\t%u\t%llu\t%llu\t%u\n", id, len[id], (unsigned long long)covered, (unsigned long long)sum, mx);
+        out += line;
+    }
+    if (bfp) {
+        const bool bad = std::ferror(bfp) != 0;
+        if ((std::fclose(bfp) != 0) || bad) return "Cannot write pack-bases file: " + bases_file;
+    }
+    std::FILE *fp = std::fopen(file.c_str(), "wb");
+    if (!fp) return "Cannot open pack file: " + file;
+    const bool ok = std::fwrite(out.data(), 1, out.size(), fp) == out.size();
+    if ((std::fclose(fp) != 0) || !ok) return "Cannot write pack file: " + file;
+    return "";
+}
+
 static int usage() {
     std::cerr << "usage: find_mems <r_index.ri> <tags> <reads.txt> <min_mem_length> <min_occ>"
                  " [--device N | --gpus N | --devices a,b,..] [--streams W] [--mode compat|strict] [--batch N]"
@@ -478,7 +533,8 @@ static int usage() {
                  " [--gaf FILE [--gaf-only (not with --locate)]]"
                  " [--paired [--frag-min A] [--frag-max B] [--mates-penalty U] [--mates FILE [--mates-only (not with --locate)]]"
                  " [--rescue [--rescue-min S] [--rescue-anchors R (1 .. 8)] [--rescued FILE]]]"
-                 " [--mapq (with --gaf or --mapq-file) [--mapq-scale D (1 .. 16)] [--mapq-slack K (0 .. 1024)] [--mapq-extra X (0 .. 63)] [--mapq-file FILE]]" << std::endl;
+                 " [--mapq (with --gaf or --mapq-file) [--mapq-scale D (1 .. 16)] [--mapq-slack K (0 .. 1024)] [--mapq-extra X (0 .. 63)] [--mapq-file FILE]]"
+                 " [--pack FILE [--pack-bases FILE2] [--pack-min-mapq Q (1 .. 60, with --mapq)] [--pack-only (not with --locate)]]" << std::endl;
     return EXIT_FAILURE;
 }
 
@@ -524,6 +580,10 @@ int main(int argc, char **argv) {
     std::string mapq_file;      // --mapq-file: the mapq records of every batch go to this file
     uint32_t mapq_scale = 2, mapq_slack = 8, mapq_extra = 16;
     bool mapq_opt_given = false;
+    std::string pack_file;      // --pack: the per-node coverage summary, written once at the end
+    std::string pack_bases_file; // --pack-bases: one line per covered base
+    uint32_t pack_min_mapq = 0;
+    bool pack_min_mapq_given = false, pack_only = false;
     int first_opt = 6;
     // find_mems_chunked.cpp:15-28 takes an optional sixth positional (chunk_size_mb of its memory-mapped loader): accepted, unused
     if (argc > 6 && argv[6][0] >= '0' && argv[6][0] <= '9') first_opt = 7;
@@ -663,6 +723,17 @@ int main(int argc, char **argv) {
             if (is_min) rescue_min_given = true;
         }
         else if (a == "--mapq") mapq = true;
+        else if (a == "--pack") { pack_file = next(); if (pack_file.empty()) { std::cerr << "--pack: a file name" << std::endl; return EXIT_FAILURE; } }
+        else if (a == "--pack-bases") { pack_bases_file = next(); if (pack_bases_file.empty()) { std::cerr << "--pack-bases: a file name" << std::endl; return EXIT_FAILURE; } }
+        else if (a == "--pack-only") pack_only = true;
+        else if (a == "--pack-min-mapq") {
+            const std::string v = next();
+            char *end = nullptr;
+            const unsigned long long k = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || *end || v[0] == '-' || k < 1 || k > 60) { std::cerr << "--pack-min-mapq: an integer 1 .. 60, got '" << v << "'" << std::endl; return EXIT_FAILURE; }
+            pack_min_mapq = (uint32_t)k;
+            pack_min_mapq_given = true;
+        }
         else if (a == "--mapq-file") { mapq_file = next(); if (mapq_file.empty()) { std::cerr << "--mapq-file: a file name" << std::endl; return EXIT_FAILURE; } }
         else if (a == "--mapq-scale" || a == "--mapq-slack" || a == "--mapq-extra") {
             const unsigned long long lo = a == "--mapq-scale" ? 1 : 0, hi = a == "--mapq-scale" ? PGX_MAPQ_MAX_SCALE : (a == "--mapq-slack" ? PGX_MAPQ_MAX_SLACK : PGX_MAPQ_MAX_EXTRA);
@@ -680,7 +751,10 @@ int main(int argc, char **argv) {
         else { std::cerr << "unknown option " << a << std::endl; return EXIT_FAILURE; }
     }
     if ((mapq_opt_given || !mapq_file.empty()) && !mapq) return usage(); // (the mapq options belong to --mapq ...
-    if (mapq && gaf_file.empty() && mapq_file.empty()) return usage();   // ... and --mapq to an output that shows it)
+    if (mapq && gaf_file.empty() && mapq_file.empty() && pack_file.empty()) return usage(); // ... and --mapq to an output that shows or uses it)
+    if ((!pack_bases_file.empty() || pack_min_mapq_given || pack_only) && pack_file.empty()) return usage(); // (the pack options belong to --pack)
+    if (pack_min_mapq_given && !mapq) return usage();                                                        // (a filter on qualities needs them)
+    if (pack_only && locate_mode) { std::cerr << "--pack-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if (rescue && !paired) return usage();                                     // (the rescue options belong to --paired ...
     if ((!rescued_file.empty() || rescue_opt_given) && !rescue) return usage(); // ... and its own to --rescue)
     if (rescue && !rescue_min_given) rescue_min = mem_length ? std::min<uint64_t>(mem_length, 0xFFFFFFFFull) : 1; // (no less evidence than a placed read: a MEM of that length)
@@ -698,20 +772,21 @@ int main(int argc, char **argv) {
     if (hits_only && locate_mode) { std::cerr << "--hits-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if ((place_max_given || place_only) && place_file.empty()) return usage();
     if (place_only && locate_mode) { std::cerr << "--place-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
-    if ((verify_only && verify_file.empty()) || (verify_opt_given && verify_file.empty() && align_file.empty() && gaf_file.empty() && !paired && !mapq)) return usage();
+    if ((verify_only && verify_file.empty()) || (verify_opt_given && verify_file.empty() && align_file.empty() && gaf_file.empty() && pack_file.empty() && !paired && !mapq)) return usage();
     if (verify_only && locate_mode) { std::cerr << "--verify-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
-    if ((align_only && align_file.empty()) || (align_band_given && align_file.empty() && gaf_file.empty())) return usage();
+    if ((align_only && align_file.empty()) || (align_band_given && align_file.empty() && gaf_file.empty() && pack_file.empty())) return usage();
     if (gaf_only && gaf_file.empty()) return usage();
     if (gaf_only && locate_mode) { std::cerr << "--gaf-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     if (align_only && locate_mode) { std::cerr << "--align-only makes no MEM text: it does not go with --locate" << std::endl; return EXIT_FAILURE; }
     const bool want_hits = !hits_file.empty(), want_places = !place_file.empty(), want_verify = !verify_file.empty(), want_align = !align_file.empty();
-    const bool want_gaf = !gaf_file.empty(), run_align = want_align || want_gaf; // (--gaf runs the align stage itself)
+    const bool want_gaf = !gaf_file.empty(), want_pack = !pack_file.empty();
+    const bool run_align = want_align || want_gaf || want_pack; // (--gaf and --pack run the align stage themselves)
     const bool want_mates = !mates_file.empty(), want_rescued = !rescued_file.empty(), want_mapqs = !mapq_file.empty();
     const bool run_verify = want_verify || run_align || paired || mapq; // (--align runs the verify stage itself; --paired elects its winners; --mapq reads its list)
     const uint32_t place_flags = run_verify && (verify_max > 1 || paired || mapq) ? PGX_PLACE_LIST : 0u; // (the candidates beyond the first, and the extras of --mapq, come from the list)
     const uint32_t verify_flags = paired || mapq ? PGX_VERIFY_LIST : 0u;                                 // (the mates and the mapq stage read the candidates)
     const uint32_t mapq_flags = paired ? PGX_MAPQ_PAIRED : 0u;
-    const bool no_text = hits_only || place_only || verify_only || align_only || gaf_only || mates_only; // (either one: no tag stage, no download of result arrays, stdout empty)
+    const bool no_text = hits_only || place_only || verify_only || align_only || gaf_only || mates_only || pack_only; // (either one: no tag stage, no download of result arrays, stdout empty)
     if (batch_reads == 0) batch_reads = 1;
     if (locate_max && !locate_mode) { std::cerr << "--locate-max needs --locate" << std::endl; return EXIT_FAILURE; }
 
@@ -725,7 +800,7 @@ int main(int argc, char **argv) {
     }
     const bool from_image = is_image_file(r_index_file.c_str());
     // --gaf or --mapq with "-" for the tags of a .ri: the index opens without tags and the walk image's own refusal ends the run below, before any batch
-    const bool gaf_no_tags = !from_image && (!gaf_file.empty() || mapq) && tag_array_index == "-";
+    const bool gaf_no_tags = !from_image && (!gaf_file.empty() || mapq || want_pack) && tag_array_index == "-";
     if (!from_image && !gaf_no_tags) {
         std::ifstream tin(tag_array_index, std::ios::binary);
         if (!tin) { std::cerr << "Cannot open tag array: " << tag_array_index << std::endl; std::exit(EXIT_FAILURE); }
@@ -793,6 +868,8 @@ int main(int argc, char **argv) {
     }
     // --verify: the same question for the text image (what --place asks, and a collection of 2^32 - 2^20 symbols or more)
     std::FILE *verify_fp = nullptr, *align_fp = nullptr, *gaf_fp = nullptr, *mates_fp = nullptr, *rescued_fp = nullptr, *mapq_fp = nullptr;
+    std::map<int, pgx_pack *> packs; // --pack: one per distinct device, made here (the walk image: an index without tags ends the run before any batch)
+    auto free_packs = [&]() { for (auto &kv : packs) pgx_pack_free(kv.second); packs.clear(); };
     if (run_verify) {
         static const uint8_t probe_read[4] = {'A', 'C', 'G', 'T'};
         static const uint64_t probe_offs[2] = {0, 4};
@@ -818,15 +895,21 @@ int main(int argc, char **argv) {
             if (st == PGX_OK && run_align) st = pgx_batch_read_align(pb, align_band, PGX_ALIGN_CIGAR, nullptr);
             if (st == PGX_OK && want_gaf) st = pgx_batch_read_walk(pb, PGX_WALK_STEPS, nullptr); // (the walk image: an index without tags ends here)
             if (st == PGX_OK && mapq) st = pgx_batch_read_mapq(pb, mapq_scale, mapq_slack, mapq_extra, 0u, nullptr); // (the same image; a probe of one read is no pair)
+            if (st == PGX_OK && want_pack && !packs.count(devices[i])) {
+                pgx_pack *pk = nullptr;
+                st = pgx_pack_create(h, devices[i], &pk);
+                if (st == PGX_OK) packs[devices[i]] = pk;
+            }
             if (st != PGX_OK && !twin_refused) msg = pgx_last_error();
             pgx_batch_free(pb);
         }
         if (st != PGX_OK) {
             std::cerr << msg
-                      << (st != PGX_ERR_UNSUPPORTED || twin_refused ? "" : (want_verify ? " (find_mems --verify)" : (want_align ? " (find_mems --align)" : (want_gaf ? " (find_mems --gaf)" : (mapq ? " (find_mems --mapq)" : " (find_mems --paired)")))))
+                      << (st != PGX_ERR_UNSUPPORTED || twin_refused ? "" : (want_verify ? " (find_mems --verify)" : (want_align ? " (find_mems --align)" : (want_gaf ? " (find_mems --gaf)" : (mapq ? " (find_mems --mapq)" : (want_pack ? " (find_mems --pack)" : " (find_mems --paired)"))))))
                       << std::endl;
             if (hits_fp) std::fclose(hits_fp);
             if (place_fp) std::fclose(place_fp);
+            free_packs();
             return EXIT_FAILURE;
         }
         if (want_verify) {
@@ -1191,13 +1274,15 @@ int main(int argc, char **argv) {
             if (st == PGX_OK && run_align) {
                 st = pgx_batch_read_align(b, align_band, PGX_ALIGN_CIGAR, nullptr);
                 pgx_read_aligns ra;
-                if (st == PGX_OK) st = pgx_batch_aligned(b, &ra);
-                if (st == PGX_OK) {
+                const bool down = want_align || want_gaf; // (--pack reads the result where it lies)
+                if (st == PGX_OK && down) st = pgx_batch_aligned(b, &ra);
+                if (st == PGX_OK && down) {
                     align_recs.assign(ra.reads, ra.reads + ra.n_reads);
                     align_op_off.assign(ra.op_offsets, ra.op_offsets + ra.n_reads + 1);
                     align_ops.assign(ra.ops, ra.ops + ra.n_ops);
                 }
             }
+            if (st == PGX_OK && want_pack) st = pgx_pack_add(packs.at(device), b, pack_min_mapq, 0u, nullptr); // (behind the election and the qualities: the winners)
             std::vector<pgx_read_walk> walk_recs; // --gaf: the 32-byte records and the steps, along the stretches of the align stage above; the reads' lengths
             std::vector<uint64_t> walk_step_off, walk_steps, walk_read_off;
             if (st == PGX_OK && want_gaf) {
@@ -1398,6 +1483,8 @@ int main(int argc, char **argv) {
     if (mates_fp && (std::fclose(mates_fp) != 0) && error.empty()) error = "Cannot write mates file: " + mates_file;
     if (rescued_fp && (std::fclose(rescued_fp) != 0) && error.empty()) error = "Cannot write rescued file: " + rescued_file;
     if (mapq_fp && (std::fclose(mapq_fp) != 0) && error.empty()) error = "Cannot write mapq file: " + mapq_file;
+    if (want_pack && error.empty()) error = write_packs(packs, pack_file, pack_bases_file);
+    free_packs();
     if (!error.empty()) {
         std::cerr << error << std::endl;
         return EXIT_FAILURE;
